@@ -3,7 +3,7 @@ Rotated-MNIST-shaped synthetic data (batch 32, 16x1x28x28, ngf=ndf=64; configs[1
 iteration milliseconds, at N = 1/2/4/8 GPUs (one process per GPU; weak scaling, 32 clips per GPU; gradients are
 all-reduced over RCCL once per optimiser step in the train-step timings).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 works both ways: under a launcher that already set RANK/WORLD_SIZE (python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...) this process IS a rank; started
@@ -30,8 +30,8 @@ sys.path.insert(0, REPO)
 # not touch the GPU, and does not even import torch (gan-ode_amd/launch.py is standard library only).
 np = torch = dist = None
 
-FP32_MFMA_PEAK_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md, "Peak FP32 (matrix)"
-HBM_PEAK_GBS = 8000.0           # same guide, "HBM3E peak BW" (spec)
+FP32_MFMA_PEAK_TFLOPS = 157.3   # MI355X "Peak FP32 (matrix)"
+HBM_PEAK_GBS = 8000.0           # MI355X "HBM3E peak BW" (spec)
 B, T = 32, 16
 
 
@@ -281,7 +281,31 @@ def _parse():
                          "BASELINE configs[1]); default: the reference's own call, 15 steps on the output times")
     ap.add_argument("--ode-method", default="rk4", choices=["rk4", "dopri5"],
                     help="rk4 = the reference's call; dopri5 = torchdiffeq's adaptive default (BASELINE configs[3] wording)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed sample_videos call returned as DIR/videos.npy "
+                         "(float32) and DIR/labels.npy (float64); the headline's inputs depend on the arguments only, so "
+                         "two builds run with the same arguments can be compared output for output")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and (a.roofline_only or a.iteration_only):
+        ap.error("--dump-outputs writes the headline's outputs: not with --roofline-only / --iteration-only")
+    return a
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def _dump_outputs(d, outputs):
+    """Writes the arrays of one sample_videos call ((videos, labels)) as DIR/<name>.npy."""
+    arrays = {"videos": outputs[0].detach().float(), "labels": outputs[1].detach().double()}
+    arrays = {k: np.ascontiguousarray(v.cpu().numpy()) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 def main():
@@ -356,6 +380,9 @@ def _rank_main(a):
 
     # the trainer broadcasts rank 0's parameters and buffers to every replica when world > 1
     tr = G.GanTrainer(gen, dv, di)
+    # the headline samples from these random-init weights: the training timings below update them, so they are
+    # restored (with the host generators' seeds) before its warm-up
+    gen_init = {k_: v.clone() for k_, v in gen.state_dict().items()}
     g = torch.Generator().manual_seed(99 + rank)
     imgs = [torch.rand(B, C_, HW, HW, generator=g).cuda() for _ in range(2)]
     vids = [torch.rand(B, T, C_, HW, HW, generator=g).cuda() for _ in range(2)]
@@ -396,14 +423,20 @@ def _rank_main(a):
         trg.gen_opt, trg.vid_opt, trg.img_opt = tr.gen_opt, tr.vid_opt, tr.img_opt     # continue the same optimiser state
         it_graph_ms = _timed(lambda: trg.step(imgs, vids), k, max(3, wtr), distributed) / k * 1e3
 
+    gen.load_state_dict(gen_init)
+    torch.manual_seed(1234 + rank); np.random.seed(1234 + rank)
+    last = [None]
+
     def sample():
         with torch.no_grad():
-            gen.sample_videos(B)
+            last[0] = gen.sample_videos(B)
 
     # the headline: W untimed warm-up steps, then exactly K timed steps between barrier + synchronize, max over ranks.
     # freeze_host_gc keeps Python's full-heap garbage-collection pass (75-100 ms) out of the loop (see its docstring)
     dt = _timed(sample, a.steps, a.warmup, distributed, after_warmup=G.freeze_host_gc)
     vps = world * B * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        _dump_outputs(a.dump_outputs, last[0])     # now: the next call reuses the plan's output buffer
 
     # per-step spread (rank 0): GPU time between stream markers recorded after every step of a second, untimed-by-the-
     # contract pass of min(steps, 200) steps -- reported beside the headline, never used for `value`

@@ -1,4 +1,4 @@
-import sys; sys.path.insert(0, "/root/repo")
+import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch, gan_ode_amd as G
 for name, (gen, dv, di), B in (("mnist", G.build_mnist(), 32), ("ucf", G.build_ucf(), 16)):
     gen.cuda()

@@ -1,5 +1,5 @@
 import ctypes as C, os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import gan_ode_amd._lib as L
 from gan_ode_amd.engine import make_geom, stream_ptr

@@ -1,4 +1,6 @@
-import sys; sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
 import torch, numpy as np
 import gan_ode_amd._lib as L
 from oracle import mocogan_ref as M

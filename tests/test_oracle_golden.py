@@ -1,6 +1,7 @@
 """CPU: the oracle restatement (oracle/mocogan_ref.py + oracle/ode_ref.py) against fixtures produced by the
 reference's own classes (oracle/make_goldens.py).  Tolerance: the two run the same stock torch CPU kernels in the
-same order, so agreement is expected to ~1e-6 relative; 1e-5 is asserted (north_star's bar is 1e-4)."""
+same order, so agreement is expected to ~1e-6 relative; 1e-5 is asserted (north_star's bar is 1e-4).  On another CPU
+those kernels may sum in another order: the training-step fixture then allows a few sign flips of Adam's first steps."""
 import numpy as np
 import pytest
 import torch
@@ -92,14 +93,21 @@ def test_train_step_fixture(tag, build, iters):
         seed_all(s + 1 + it)
         losses = M.train_step(gen, dv, di, opts, imgs, vids)
         assert np.allclose([float(v) for v in losses], g["losses"][it], rtol=2e-5, atol=0)
-    for m, p in ((gen, "gen"), (dv, "vid"), (di, "img")):
+    lr = opts[0].param_groups[0]["lr"]
+    for m, p, steps in ((gen, "gen", iters), (dv, "vid", 2 * iters), (di, "img", 2 * iters)):
         for k, v in m.state_dict().items():
             ref = g[f"w1/{p}/{k}"]
             if v.dtype == torch.int64:
                 assert int(v) == int(ref), k
             else:
-                # Adam's first steps move every weight by ~lr regardless of gradient scale: compare absolutely
-                assert float((v - torch.from_numpy(ref)).abs().max()) < 2e-5, (p, k)
+                # Adam's first steps move every weight by ~lr regardless of gradient scale: compare absolutely.  On a
+                # CPU whose kernels sum in another order than the fixture's, an entry whose gradient is within fp32
+                # rounding of zero may take the other sign (up to 2 lr per optimiser step off): a few such entries are
+                # allowed, every other entry must match to 2e-5
+                d = (v - torch.from_numpy(ref)).abs()
+                off = int((d >= 2e-5).sum())
+                assert off <= max(1, 1e-3 * d.numel()), (p, k, off, d.numel())
+                assert float(d.max()) < 2 * lr * steps + 2e-5, (p, k, float(d.max()))
     gen.eval()
     seed_all(s + 50)
     with torch.no_grad():
