@@ -15,8 +15,10 @@ EPI_RAW, EPI_TANH = 0, 1
 FPROP, DGRAD = 0, 1
 OP_IGEMM, OP_WGRAD, OP_BN_FINALIZE, OP_BN_BWD, OP_ODE_FWD, OP_ODE_BWD, OP_BCE, OP_ADAM, OP_PACK = range(1, 10)
 OP_ODERNN_FWD, OP_ODERNN_BWD, OP_BN_APPLY, OP_COL2IM = 10, 11, 12, 13
+OP_SDE_FWD, OP_SDE_BWD = 14, 15
 ODE_NPARAM = 2672
 ODERNN_NPARAM = 2176
+SDE_NPARAM = 3216
 
 
 class ConvGeom(C.Structure):
@@ -96,6 +98,24 @@ class OdeRnnBwdOp(C.Structure):
     KIND = OP_ODERNN_BWD
 
 
+class SdeParams(C.Structure):
+    _fields_ = [(n, ptr) for n in "Wa ba Wb bb Wf1 bf1 Wf2 bf2 Wg1 bg1 Wg2 bg2".split()]
+
+
+class SdeFwdOp(C.Structure):
+    _fields_ = [("p", SdeParams), ("x", ptr), ("content", ptr), ("sel_t", ptr), ("dt", ptr), ("sqrt_dt", ptr),
+                ("emit_at", ptr), ("emit_w0", ptr), ("emit_w1", ptr), ("z", ptr), ("states", ptr), ("N", i32),
+                ("T", i32), ("S", i32), ("prenet", i32), ("zcols", i32), ("pad_", i32)]
+    KIND = OP_SDE_FWD
+
+
+class SdeBwdOp(C.Structure):
+    _fields_ = [("p", SdeParams), ("x", ptr), ("states", ptr), ("sel_t", ptr), ("dt", ptr), ("sqrt_dt", ptr),
+                ("emit_at", ptr), ("emit_w0", ptr), ("emit_w1", ptr), ("gz", ptr), ("work", ptr), ("grads", ptr),
+                ("N", i32), ("T", i32), ("S", i32), ("prenet", i32), ("accumulate", i32), ("zcols", i32)]
+    KIND = OP_SDE_BWD
+
+
 class BnApplyOp(C.Structure):
     _fields_ = [("y", ptr), ("out", ptr), ("scale", ptr), ("shift", ptr), ("M", i64), ("C", i32), ("act", i32),
                 ("M0", i64)]
@@ -126,13 +146,14 @@ class PackOp(C.Structure):
 
 _STRUCTS = {0: ConvGeom, OP_IGEMM: IgemmOp, OP_WGRAD: WgradOp, OP_BN_FINALIZE: BnFinalizeOp, OP_BN_BWD: BnBwdOp,
             OP_ODE_FWD: OdeFwdOp, OP_ODE_BWD: OdeBwdOp, OP_BCE: BceOp, OP_ADAM: AdamOp, OP_PACK: PackOp,
-            OP_ODERNN_FWD: OdeRnnFwdOp, OP_ODERNN_BWD: OdeRnnBwdOp, OP_BN_APPLY: BnApplyOp, OP_COL2IM: Col2imOp}
+            OP_ODERNN_FWD: OdeRnnFwdOp, OP_ODERNN_BWD: OdeRnnBwdOp, OP_BN_APPLY: BnApplyOp, OP_COL2IM: Col2imOp,
+            OP_SDE_FWD: SdeFwdOp, OP_SDE_BWD: SdeBwdOp}
 
 EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "gode_igemm_stats_segments", "gode_igemm_model_cycles", "gode_igemm_work_size", "gode_pack_size", "gode_pack_weights", "gode_wgrad",
            "gode_wgrad_work_size", "gode_wgrad_auto_splits", "gode_bn_finalize", "gode_bn_bwd",
            "gode_bn_bwd_work_size", "gode_bn_apply", "gode_col2im", "gode_ode_fwd", "gode_ode_bwd", "gode_ode_fwd_multi", "gode_ode_bwd_multi", "gode_ode_bwd_work_size", "gode_odernn_fwd",
            "gode_odernn_bwd", "gode_odernn_bwd_work_size", "gode_odernn_sync_size", "gode_odernn_fwd_multi",
-           "gode_odernn_bwd_multi", "gode_bce_logits",
+           "gode_odernn_bwd_multi", "gode_sde_fwd", "gode_sde_bwd", "gode_sde_bwd_work_size", "gode_bce_logits",
            "gode_adam_l2", "gode_adam_multi", "gode_adam_multi_dev", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
 
 _lib = None
@@ -155,7 +176,8 @@ def lib():
         if L.gode_sizeof(kind) != C.sizeof(st):
             raise RuntimeError(f"ABI mismatch for op kind {kind}: C {L.gode_sizeof(kind)} != ctypes {C.sizeof(st)}")
     for name in ("gode_igemm", "gode_wgrad", "gode_bn_finalize", "gode_bn_bwd", "gode_ode_fwd", "gode_ode_bwd",
-                 "gode_bce_logits", "gode_adam_l2", "gode_odernn_fwd", "gode_odernn_bwd", "gode_bn_apply", "gode_col2im"):
+                 "gode_bce_logits", "gode_adam_l2", "gode_odernn_fwd", "gode_odernn_bwd", "gode_bn_apply", "gode_col2im",
+                 "gode_sde_fwd", "gode_sde_bwd"):
         getattr(L, name).argtypes = [ptr, ptr]
         getattr(L, name).restype = C.c_int
     L.gode_igemm_stats_rows.argtypes = [ptr]
@@ -177,6 +199,8 @@ def lib():
     L.gode_ode_bwd_work_size.restype = i64
     L.gode_odernn_bwd_work_size.argtypes = [i32]
     L.gode_odernn_bwd_work_size.restype = i64
+    L.gode_sde_bwd_work_size.argtypes = [i32]
+    L.gode_sde_bwd_work_size.restype = i64
     L.gode_odernn_sync_size.argtypes = [i32]
     L.gode_odernn_sync_size.restype = i64
     L.gode_ode_fwd_multi.argtypes = [ptr, i32, ptr]
@@ -250,5 +274,6 @@ def _run_one(op, stream):
     fn = {OP_IGEMM: "gode_igemm", OP_WGRAD: "gode_wgrad", OP_BN_FINALIZE: "gode_bn_finalize", OP_BN_BWD: "gode_bn_bwd",
           OP_ODE_FWD: "gode_ode_fwd", OP_ODE_BWD: "gode_ode_bwd", OP_BCE: "gode_bce_logits",
           OP_ADAM: "gode_adam_l2", OP_ODERNN_FWD: "gode_odernn_fwd", OP_ODERNN_BWD: "gode_odernn_bwd",
-          OP_BN_APPLY: "gode_bn_apply", OP_COL2IM: "gode_col2im"}[op.KIND]
+          OP_BN_APPLY: "gode_bn_apply", OP_COL2IM: "gode_col2im", OP_SDE_FWD: "gode_sde_fwd",
+          OP_SDE_BWD: "gode_sde_bwd"}[op.KIND]
     check(getattr(lib(), fn)(C.byref(op), stream), fn)

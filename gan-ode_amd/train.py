@@ -510,6 +510,9 @@ class GanTrainer:
         self._feed = None
         if self._graph_mode and self.world > 1:
             raise NotImplementedError("GanTrainer(graph=True) is single-process; data-parallel runs use the eager schedule")
+        if self._graph_mode and not getattr(gen, "_gode_graph_capture", True):
+            raise NotImplementedError(f"GanTrainer(graph=True) does not capture {type(gen).__name__}: use the eager "
+                                      "schedule (graph=False)")
         # freeze_gc: call freeze_host_gc() after the second iteration (process-global, hence opt-in; bench.py and
         # long training loops want it, see its docstring)
         self._iters, self._freeze_gc = 0, freeze_gc

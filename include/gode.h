@@ -308,6 +308,45 @@ int64_t gode_odernn_bwd_work_size(int32_t N);
 int gode_odernn_bwd_multi(const gode_odernn_bwd_op* ops, int32_t count, void* stream);
 #define GODE_ODERNN_NPARAM 2176
 
+/* ---- Neural-SDE motion latent (models/mocogan_sde.py: sdeint_adjoint(SDEFunc, x, linspace(0, 1, T), method='euler',
+ * dt=2.5e-2); Ito, diagonal noise) ---------------------------------------------------------------------------------
+ * forward: x[1+S][N][16] = the host-drawn initial noise x0 followed by the standard-normal stack xi_0..xi_{S-1} ->
+ * pre-net (as gode_ode_fwd; prenet==0: nn.Identity) -> S Euler-Maruyama steps
+ *   y_{k+1} = y_k + dt[k] f(y_k) + g(y_k) * sqrt_dt[k] * xi_k,   f = Wf2 tanh(Wf1 y + bf1) + bf2,  g = Wg2 tanh(Wg1 y + bg1) + bg2
+ * with the host schedule dt[S], sqrt_dt[S] (torchsde's fixed-step loop in fp32; the Brownian increment is
+ * sqrt(dt_k) xi_k, a documented deviation from torchsde's BrownianInterval).  Output 0 is y_0; output j >= 1 is produced
+ * after step emit_at[j] as emit_w0[j] y_k + emit_w1[j] y_{k+1} (torchsde's linear_interp).  z / content / sel_t / zcols as
+ * in gode_ode_fwd.  states[N][S+1][16] (nullable in the forward) keeps every state for the backward. */
+typedef struct gode_sde_params {
+  const float* Wa; const float* ba; const float* Wb; const float* bb;       /* pre-net (NULL when prenet == 0) */
+  const float* Wf1; const float* bf1; const float* Wf2; const float* bf2;   /* drift_fn: [16,16],[16],[16,16],[16] */
+  const float* Wg1; const float* bg1; const float* Wg2; const float* bg2;   /* diffusion_fn: the same shapes */
+} gode_sde_params;
+typedef struct gode_sde_fwd_op {
+  gode_sde_params p;
+  const float* x; const float* content; const int32_t* sel_t;
+  const float* dt; const float* sqrt_dt; const int32_t* emit_at; const float* emit_w0; const float* emit_w1;
+  float* z; float* states;
+  int32_t N, T, S, prenet, zcols, pad_;
+} gode_sde_fwd_op;
+int gode_sde_fwd(const gode_sde_fwd_op* op, void* stream);
+/* backward: the exact gradient of the discrete forward above (not torchsde's continuous adjoint), the reverse sweep
+ *   a_k = a_{k+1} + dt_k Jf(y_k)^T a_{k+1} + Jg(y_k)^T (a_{k+1} * dW_k)  + the interpolation weights' share of gz,
+ * then the pre-net backward.  gz[rows][zcols] as in gode_ode_bwd (full or sel_t rows; 16 motion columns read).  Parameter
+ * gradients are reduced in fixed order through work (>= gode_sde_bwd_work_size(N) floats) and written (accumulate != 0:
+ * added) to grads, which points at the FIRST PRESENT tensor of gode_sde_params: 3216 floats with the pre-net, 1088
+ * (drift + diffusion) without.  Nothing outside that span is touched. */
+typedef struct gode_sde_bwd_op {
+  gode_sde_params p;
+  const float* x; const float* states; const int32_t* sel_t;
+  const float* dt; const float* sqrt_dt; const int32_t* emit_at; const float* emit_w0; const float* emit_w1;
+  const float* gz; float* work; float* grads;
+  int32_t N, T, S, prenet, accumulate, zcols;
+} gode_sde_bwd_op;
+int gode_sde_bwd(const gode_sde_bwd_op* op, void* stream);
+int64_t gode_sde_bwd_work_size(int32_t N);
+#define GODE_SDE_NPARAM 3216
+
 /* ---- loss and optimiser (mnist_moco_ode.py:86-89) ------------------------------------------------------------
  * BCE-with-logits, mean reduced, constant target: loss (+)= mean(max(x,0) - x*t + log1p(exp(-|x|))) and
  * g[i] = gscale*(sigmoid(x[i]) - t)/n.  loss is one device float; accumulate!=0 adds to it. */
@@ -338,7 +377,8 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
 /* ---- program runner: executes n ops back to back on the stream (one host call per network pass) -------------*/
 enum { GODE_OP_IGEMM = 1, GODE_OP_WGRAD = 2, GODE_OP_BN_FINALIZE = 3, GODE_OP_BN_BWD = 4, GODE_OP_ODE_FWD = 5,
        GODE_OP_ODE_BWD = 6, GODE_OP_BCE = 7, GODE_OP_ADAM = 8, GODE_OP_PACK = 9, GODE_OP_ODERNN_FWD = 10,
-       GODE_OP_ODERNN_BWD = 11, GODE_OP_BN_APPLY = 12, GODE_OP_COL2IM = 13 };
+       GODE_OP_ODERNN_BWD = 11, GODE_OP_BN_APPLY = 12, GODE_OP_COL2IM = 13, GODE_OP_SDE_FWD = 14,
+       GODE_OP_SDE_BWD = 15 };
 typedef struct gode_pack_op {
   gode_conv_geom g; int32_t dir, co_canon; const float* w; float* wpack; const int32_t* co_perm;
 } gode_pack_op;
