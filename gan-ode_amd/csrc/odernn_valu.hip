@@ -1199,7 +1199,9 @@ __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_bwd_valu_kernel(const O
     if (e < TH_N) put(DP_W1 + e, (wg == 0 && steps >= 0) ? S.gt[k] : 0.f);     // TH_* order == W1, b1, W2, b2
   }
   if (!a.prenet) {
-    for (int k = threadIdx.x; k < DP_W1; k += RV_THREADS) put(k, 0.f);
+    // no pre-net: [0, DP_W1) of grads is not the caller's memory (gode.h) -- only a work row gets its zeros
+    if (!J.direct)
+      for (int k = threadIdx.x; k < DP_W1; k += RV_THREADS) put(k, 0.f);
     return;
   }
   // ---- pre-net backward; adj = dL/d(pre-net output).  With one (trajectory, feature) value per lane the batch sums of
@@ -1243,10 +1245,11 @@ __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_bwd_valu_kernel(const O
   }
 }
 
-// rows of `work` (ops sharing a grads pointer, in array order) -> grads, fixed order; row length 2,672
-struct OdeRowsArgs { const float* work[RV_MAX_JOBS]; int32_t rows[RV_MAX_JOBS]; int32_t count, accumulate; float* grads; };
+// rows of `work` (ops sharing a grads pointer, in array order) -> grads, fixed order; row length 2,672.  Entries below
+// `first` are not touched (DP_W1 when none of the ops has a pre-net: that block of grads is then not the caller's)
+struct OdeRowsArgs { const float* work[RV_MAX_JOBS]; int32_t rows[RV_MAX_JOBS]; int32_t count, accumulate, first; float* grads; };
 __global__ void __launch_bounds__(256) ode_rows_kernel(const OdeRowsArgs A) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
+  const int k = A.first + blockIdx.x * 256 + threadIdx.x;
   if (k >= GODE_ODE_NPARAM) return;
   float s = 0.f;
   for (int j = 0; j < A.count; ++j)
@@ -1319,11 +1322,14 @@ static int ode5_bwd_launch(const gode_ode_bwd_op* ops, int count, hipStream_t st
   for (int k = 0; k < count; ++k) {
     if (done[k]) continue;
     OdeRowsArgs A;
-    A.count = 0; A.grads = ops[k].grads; A.accumulate = ops[k].accumulate;
+    A.count = 0; A.grads = ops[k].grads; A.accumulate = ops[k].accumulate; A.first = DP_W1;
     for (int j = k; j < count; ++j) {
-      if (!done[j] && ops[j].grads == ops[k].grads) { A.work[A.count] = ops[j].work; A.rows[A.count] = J.nblk[j]; A.count += 1; done[j] = true; }
+      if (!done[j] && ops[j].grads == ops[k].grads) {
+        A.work[A.count] = ops[j].work; A.rows[A.count] = J.nblk[j]; A.count += 1; done[j] = true;
+        if (ops[j].prenet) A.first = 0;
+      }
     }
-    hipLaunchKernelGGL(ode_rows_kernel, dim3((GODE_ODE_NPARAM + 255) / 256), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(ode_rows_kernel, dim3((GODE_ODE_NPARAM - A.first + 255) / 256), dim3(256), 0, st, A);
     GODE_LAUNCH_CHECK();
   }
   return 0;

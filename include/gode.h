@@ -229,7 +229,9 @@ int gode_ode_fwd_multi(const gode_ode_fwd_op* ops, int32_t count, void* stream);
  * (y, a, g_theta), y reset to the stored trajectory, a += upstream grad) followed by the pre-net backward.
  * gz[rows][zcols]: gradient wrt the latent rows (only the 16 motion columns are read).  Parameter gradients are
  * reduced deterministically through work (>= gode_ode_bwd_work_size floats) and written (accumulate!=0: added) to
- * grads, laid out as the 8 tensors of gode_ode_params in order (2672 floats). */
+ * grads, laid out as the 8 tensors of gode_ode_params in order (2672 floats).  prenet == 0: the first 2128 floats of
+ * grads (the pre-net block) are neither read nor written, on every path (rk4 and dopri5, single and _multi calls) --
+ * grads may point 2128 floats before a region that holds only the ODEFunc block. */
 typedef struct gode_ode_bwd_op {
   gode_ode_params p;
   const float* x; const float* traj; const float* dt; const int32_t* sel_t; const float* gz;
