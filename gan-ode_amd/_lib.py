@@ -16,9 +16,12 @@ FPROP, DGRAD = 0, 1
 OP_IGEMM, OP_WGRAD, OP_BN_FINALIZE, OP_BN_BWD, OP_ODE_FWD, OP_ODE_BWD, OP_BCE, OP_ADAM, OP_PACK = range(1, 10)
 OP_ODERNN_FWD, OP_ODERNN_BWD, OP_BN_APPLY, OP_COL2IM = 10, 11, 12, 13
 OP_SDE_FWD, OP_SDE_BWD = 14, 15
+OP_CDE_FWD, OP_CDE_BWD = 16, 17
 ODE_NPARAM = 2672
 ODERNN_NPARAM = 2176
 SDE_NPARAM = 3216
+CDE_NPARAM = 7536
+CDE_MAX_N = 4096
 
 
 class ConvGeom(C.Structure):
@@ -116,6 +119,24 @@ class SdeBwdOp(C.Structure):
     KIND = OP_SDE_BWD
 
 
+class CdeParams(C.Structure):
+    _fields_ = [(n, ptr) for n in "Wa ba Wb bb W1 b1 W2 b2".split()]
+
+
+class CdeFwdOp(C.Structure):
+    _fields_ = [("p", CdeParams), ("x", ptr), ("tslope", ptr), ("content", ptr), ("sel_t", ptr), ("z", ptr),
+                ("states", ptr), ("sched", ptr), ("counts", ptr), ("sync", ptr), ("N", i32), ("T", i32),
+                ("S_cap", i32), ("zcols", i32), ("rtol", f32), ("atol", f32)]
+    KIND = OP_CDE_FWD
+
+
+class CdeBwdOp(C.Structure):
+    _fields_ = [("p", CdeParams), ("x", ptr), ("tslope", ptr), ("sel_t", ptr), ("states", ptr), ("sched", ptr),
+                ("counts", ptr), ("gz", ptr), ("work", ptr), ("grads", ptr), ("N", i32), ("T", i32), ("S_cap", i32),
+                ("accumulate", i32), ("zcols", i32), ("pad_", i32)]
+    KIND = OP_CDE_BWD
+
+
 class BnApplyOp(C.Structure):
     _fields_ = [("y", ptr), ("out", ptr), ("scale", ptr), ("shift", ptr), ("M", i64), ("C", i32), ("act", i32),
                 ("M0", i64)]
@@ -147,13 +168,13 @@ class PackOp(C.Structure):
 _STRUCTS = {0: ConvGeom, OP_IGEMM: IgemmOp, OP_WGRAD: WgradOp, OP_BN_FINALIZE: BnFinalizeOp, OP_BN_BWD: BnBwdOp,
             OP_ODE_FWD: OdeFwdOp, OP_ODE_BWD: OdeBwdOp, OP_BCE: BceOp, OP_ADAM: AdamOp, OP_PACK: PackOp,
             OP_ODERNN_FWD: OdeRnnFwdOp, OP_ODERNN_BWD: OdeRnnBwdOp, OP_BN_APPLY: BnApplyOp, OP_COL2IM: Col2imOp,
-            OP_SDE_FWD: SdeFwdOp, OP_SDE_BWD: SdeBwdOp}
+            OP_SDE_FWD: SdeFwdOp, OP_SDE_BWD: SdeBwdOp, OP_CDE_FWD: CdeFwdOp, OP_CDE_BWD: CdeBwdOp}
 
 EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "gode_igemm_stats_segments", "gode_igemm_model_cycles", "gode_igemm_work_size", "gode_pack_size", "gode_pack_weights", "gode_wgrad",
            "gode_wgrad_work_size", "gode_wgrad_auto_splits", "gode_bn_finalize", "gode_bn_bwd",
            "gode_bn_bwd_work_size", "gode_bn_apply", "gode_col2im", "gode_ode_fwd", "gode_ode_bwd", "gode_ode_fwd_multi", "gode_ode_bwd_multi", "gode_ode_bwd_work_size", "gode_odernn_fwd",
            "gode_odernn_bwd", "gode_odernn_bwd_work_size", "gode_odernn_sync_size", "gode_odernn_fwd_multi",
-           "gode_odernn_bwd_multi", "gode_sde_fwd", "gode_sde_bwd", "gode_sde_bwd_work_size", "gode_bce_logits",
+           "gode_odernn_bwd_multi", "gode_sde_fwd", "gode_sde_bwd", "gode_sde_bwd_work_size", "gode_cde_fwd", "gode_cde_bwd", "gode_cde_sync_size", "gode_cde_state_size", "gode_cde_bwd_work_size", "gode_bce_logits",
            "gode_adam_l2", "gode_adam_multi", "gode_adam_multi_dev", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
 
 _lib = None
@@ -177,7 +198,7 @@ def lib():
             raise RuntimeError(f"ABI mismatch for op kind {kind}: C {L.gode_sizeof(kind)} != ctypes {C.sizeof(st)}")
     for name in ("gode_igemm", "gode_wgrad", "gode_bn_finalize", "gode_bn_bwd", "gode_ode_fwd", "gode_ode_bwd",
                  "gode_bce_logits", "gode_adam_l2", "gode_odernn_fwd", "gode_odernn_bwd", "gode_bn_apply", "gode_col2im",
-                 "gode_sde_fwd", "gode_sde_bwd"):
+                 "gode_sde_fwd", "gode_sde_bwd", "gode_cde_fwd", "gode_cde_bwd"):
         getattr(L, name).argtypes = [ptr, ptr]
         getattr(L, name).restype = C.c_int
     L.gode_igemm_stats_rows.argtypes = [ptr]
@@ -201,6 +222,11 @@ def lib():
     L.gode_odernn_bwd_work_size.restype = i64
     L.gode_sde_bwd_work_size.argtypes = [i32]
     L.gode_sde_bwd_work_size.restype = i64
+    for name in ("gode_cde_sync_size", "gode_cde_bwd_work_size"):
+        getattr(L, name).argtypes = [i32]
+        getattr(L, name).restype = i64
+    L.gode_cde_state_size.argtypes = [i32, i32]
+    L.gode_cde_state_size.restype = i64
     L.gode_odernn_sync_size.argtypes = [i32]
     L.gode_odernn_sync_size.restype = i64
     L.gode_ode_fwd_multi.argtypes = [ptr, i32, ptr]
@@ -275,5 +301,5 @@ def _run_one(op, stream):
           OP_ODE_FWD: "gode_ode_fwd", OP_ODE_BWD: "gode_ode_bwd", OP_BCE: "gode_bce_logits",
           OP_ADAM: "gode_adam_l2", OP_ODERNN_FWD: "gode_odernn_fwd", OP_ODERNN_BWD: "gode_odernn_bwd",
           OP_BN_APPLY: "gode_bn_apply", OP_COL2IM: "gode_col2im", OP_SDE_FWD: "gode_sde_fwd",
-          OP_SDE_BWD: "gode_sde_bwd"}[op.KIND]
+          OP_SDE_BWD: "gode_sde_bwd", OP_CDE_FWD: "gode_cde_fwd", OP_CDE_BWD: "gode_cde_bwd"}[op.KIND]
     check(getattr(lib(), fn)(C.byref(op), stream), fn)

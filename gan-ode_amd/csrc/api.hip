@@ -21,6 +21,8 @@ extern "C" int gode_sizeof(int kind) {
     case GODE_OP_COL2IM: return (int)sizeof(gode_col2im_op);
     case GODE_OP_SDE_FWD: return (int)sizeof(gode_sde_fwd_op);
     case GODE_OP_SDE_BWD: return (int)sizeof(gode_sde_bwd_op);
+    case GODE_OP_CDE_FWD: return (int)sizeof(gode_cde_fwd_op);
+    case GODE_OP_CDE_BWD: return (int)sizeof(gode_cde_bwd_op);
   }
   return GODE_E_KIND;
 }
@@ -48,6 +50,8 @@ extern "C" int gode_run(const int32_t* kinds, const void* const* ops, int32_t n,
       case GODE_OP_COL2IM: rc = gode_col2im((const gode_col2im_op*)ops[i], stream); break;
       case GODE_OP_SDE_FWD: rc = gode_sde_fwd((const gode_sde_fwd_op*)ops[i], stream); break;
       case GODE_OP_SDE_BWD: rc = gode_sde_bwd((const gode_sde_bwd_op*)ops[i], stream); break;
+      case GODE_OP_CDE_FWD: rc = gode_cde_fwd((const gode_cde_fwd_op*)ops[i], stream); break;
+      case GODE_OP_CDE_BWD: rc = gode_cde_bwd((const gode_cde_bwd_op*)ops[i], stream); break;
       case GODE_OP_PACK: {
         // every run of consecutive pack ops goes out as one launch per 8 panels
         int j = i;

@@ -1428,6 +1428,236 @@ class VideoGeneratorSDE(VideoGeneratorMNIST):
         return _SdeLatentFn.apply(self, x, num_samples, T, *sde)
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# Neural-CDE motion latent (models/mocogan_cde.py)
+# ------------------------------------------------------------------------------------------------------------------
+class CDEFunc(nn.Module):
+    """The CDE vector field z -> tanh(linear2(relu(linear1(z)))).view(hidden, input) (models/mocogan_cde.py:13-29),
+    Linear(16, 128) and Linear(128, 32) for the reference's call.  Evaluated inside the fused CDE kernels; calling it
+    directly is not part of the hot path."""
+
+    def __init__(self, dim, dim_hidden):
+        super().__init__()
+        self.input_dim = dim
+        self.hidden_dim = dim_hidden
+        self.linear1 = nn.Linear(dim_hidden, 128)
+        self.linear2 = nn.Linear(128, dim * dim_hidden)
+
+    def forward(self, t, z):
+        raise RuntimeError("CDEFunc is evaluated inside libgode's fused CDE kernels (gode_cde_fwd/bwd)")
+
+
+def cde_time_slopes(T):
+    """The time channel's per-interval slopes: the fp32 differences of linspace(0, 1, T) (the knots torchcde's spline
+    interpolates; the spline's own knots are at t = 0, 1, ..., T-1, so these are its derivatives)."""
+    tt = torch.linspace(0, 1, T).float()
+    return tt[1:] - tt[:-1]
+
+
+_CDE_GRAD_OFFS = [(0, 128, (64, 2)), (128, 64, (64,)), (192, 1024, (16, 64)), (1216, 16, (16,)),
+                  (1232, 2048, (128, 16)), (3280, 128, (128,)), (3408, 4096, (32, 128)), (7504, 32, (32,))]
+
+
+class _CdeGenPlan(_GenPlan):
+    """Neural-CDE latent (gode_cde_fwd/bwd) + decoder.  x_host carries the noise channel's knots [n, T]."""
+
+    def __init__(self, gen, n_traj, T, select, zbuf=None):
+        if n_traj > L.CDE_MAX_N:
+            raise ValueError(f"{type(gen).__name__}: {n_traj} trajectories in one solve; the whole-batch error norm of "
+                             f"gode_cde_fwd needs all workgroups co-resident, at most {L.CDE_MAX_N} trajectories")
+        super().__init__(gen, n_traj, T, select, zbuf=zbuf)
+        self._cde_alloc()
+
+    def _cde_alloc(self):
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.S_cap = int(self.gen.cde_max_steps)
+        self.tslope = cde_time_slopes(self.T).to(self.device)
+        self.states = torch.empty(self.n, self.S_cap + 1, 16, **f32)      # the state at every accepted step
+        self.sched = torch.zeros(2 * self.S_cap, dtype=torch.float64, device=self.device)
+        self.counts = torch.zeros(2, dtype=torch.int32, device=self.device)
+        ns = L.lib().gode_cde_sync_size(self.n)
+        self.sync = torch.zeros(ns, dtype=torch.int32, device=self.device) if ns else None
+        self.cde_work = torch.empty(L.lib().gode_cde_bwd_work_size(self.n), **f32)
+        self.last_counts = None
+
+    def _x_shape(self, n_traj, T):
+        return (n_traj, T)
+
+    def _cde_params(self):
+        g = self.gen
+        f, fn = g.f, g.ode_fn
+        return (f[0].weight, f[0].bias, f[2].weight, f[2].bias, fn.linear1.weight, fn.linear1.bias,
+                fn.linear2.weight, fn.linear2.bias)
+
+    def _programs(self):
+        ps = self._cde_params()
+        key = tuple(dptr(p) for p in ps) + (self.gen.cde_rtol, self.gen.cde_atol)
+        if key != self._ode_ptrs:
+            self._ode_ptrs = key
+            zbuf = getattr(self, "_zbuf", None)
+            zbuf = self.stack.x_in if zbuf is None else zbuf
+            common = dict(p=L.CdeParams(*key[:8]), x=dptr(self.x), tslope=dptr(self.tslope), sel_t=dptr(self.sel),
+                          states=dptr(self.states), sched=dptr(self.sched), counts=dptr(self.counts), N=self.n,
+                          T=self.T, S_cap=self.S_cap, zcols=getattr(self, "_zcols", Z_COLS))
+            self.fwd_op = L.CdeFwdOp(content=dptr(self.content), z=dptr(zbuf), sync=dptr(self.sync),
+                                     rtol=float(self.gen.cde_rtol), atol=float(self.gen.cde_atol), **common)
+            self.bwd_op = L.CdeBwdOp(gz=None, work=dptr(self.cde_work), grads=None, accumulate=0, **common)
+            self.fwd_prog = L.Program([self.fwd_op])
+
+    def check_solve(self):
+        """Reads the solve's {accepted, trials} (a host synchronisation with the current stream) and raises when the
+        kernel stopped early: more than cde_max_steps accepted steps, the trial limit or a step-size underflow."""
+        c = self.counts.cpu().tolist()
+        self.last_counts = c
+        if c[0] < 0:
+            raise RuntimeError(f"{type(self.gen).__name__}: the dopri5 CDE solve stopped after {-c[0] - 1} accepted steps "
+                               f"({c[1]} trials): more than cde_max_steps = {self.S_cap} accepted steps, or the step "
+                               "size underflowed; raise cde_max_steps or loosen cde_rtol / cde_atol")
+        return c
+
+    def forward(self, x_host, content_host, sel_host, training, keep):
+        if x_host is None:                     # prefetched (checked by _launch_latents)
+            return super().forward(None, content_host, sel_host, training, keep)
+        self.stage_inputs(x_host, content_host, sel_host)
+        self.fwd_prog.run(stream_ptr())
+        self.check_solve()
+        out = self.stack.forward(training)
+        self.busy = keep
+        return out
+
+    def latent_backward(self, gz_ptr, arena, keep):
+        """As _GenPlan.latent_backward: f's and CDEFunc's 8 tensors, contiguous in the kernel's order."""
+        self.bwd_op.gz = gz_ptr
+        if arena is not None:
+            tgt = [arena.target(q) for q in self._cde_params()]
+            base, acc = tgt[0]
+            self.bwd_op.grads = base.data_ptr()
+            self.bwd_op.accumulate = 1 if acc else 0
+            L.run_one(self.bwd_op, stream_ptr())
+            return None
+        grads = torch.empty(L.CDE_NPARAM, dtype=torch.float32, device=self.device)
+        self.bwd_op.grads = grads.data_ptr()
+        self.bwd_op.accumulate = 0
+        L.run_one(self.bwd_op, stream_ptr())
+        return [grads[o:o + k].view(shp) for o, k, shp in _CDE_GRAD_OFFS]
+
+
+class _CdeLatentFn(torch.autograd.Function):
+    """VideoGeneratorCDE.sample_z_m as its own autograd node: gode_cde_fwd alone, latent rows [N*T, 16] (row n*T + t,
+    the reference's z_T.reshape(-1, T) order); backward = gode_cde_bwd."""
+
+    @staticmethod
+    def forward(ctx, gen, x_host, n, T, *params):
+        dev = gen.main[0].weight.device
+        lp = _CdeGenPlan.__new__(_CdeGenPlan)          # only the latent half of a plan: no decoder buffers
+        lp.gen, lp.n, lp.T, lp.select, lp.device = gen, n, T, False, dev
+        lp.x = x_host.to(dev).contiguous()               # [n, T]
+        lp.content, lp.sel = None, None
+        lp._cde_alloc()
+        lp._zbuf, lp._zcols = torch.empty(n * T, 16, dtype=torch.float32, device=dev), 16
+        lp._ode_ptrs = None
+        lp._programs()
+        lp.fwd_prog.run(stream_ptr())
+        lp.check_solve()
+        ctx.lp = lp
+        return lp._zbuf
+
+    @staticmethod
+    def backward(ctx, gout):
+        lp = ctx.lp
+        g = gout.contiguous()
+        grads = lp.latent_backward(g.data_ptr(), None, g)
+        return (None, None, None, None, *grads)
+
+
+class VideoGeneratorCDE(VideoGeneratorMNIST):
+    """The class mnist_moco_cde.py:6 imports (models/mocogan_cde.py:32-84): the MNIST generator whose motion latent is
+    the Neural CDE dz = F(z) dX, X the backward-difference Hermite cubic spline of [linspace(0, 1, T), x] (x = the
+    [n, 16] motion noise, one knot per frame, so video_len must equal dim_z_motion), z0 = f([0, x_0]), solved by
+    torchdiffeq's dopri5 (rtol cde_rtol = 1e-4, atol cde_atol = 1e-6: torchcde's defaults) with dense output at
+    t = 0..T-1.  Deviations ("Neural-CDE motion latent"): x is drawn on the global torch CPU generator (the
+    reference's device generator cannot be reproduced); sample_images integrates only the selected trajectories, so
+    its whole-batch error norm runs over those (as VideoGenerator.sample_images with ode_method="dopri5"); and the
+    gradient is the exact gradient of the discrete forward instead of torchdiffeq's continuous adjoint.
+    RNG order: sample_videos(n): content (NumPy), x = randn(n, 16); sample_images(n): content and x of all n*T*2
+    trajectories, then np.random.choice.  Dead parameters (never used by sample_z_m, no gradient): recurrent.*,
+    linear.*."""
+
+    _plan_cls = _CdeGenPlan
+    _gode_graph_capture = False     # GanTrainer(graph=True) refuses this generator (not captured / verified)
+    cde_rtol, cde_atol = 1e-4, 1e-6
+    cde_max_steps = 512             # accepted-step capacity of a solve's stored schedule and states
+
+    def __init__(self, n_channels, dim_z_content, dim_z_category, dim_z_motion, video_length, ode_fn=CDEFunc,
+                 cde_input_dim=2, dim_hidden=None, linear=True, ngf=64):
+        self._cde_args = (cde_input_dim, dim_hidden)
+        super().__init__(n_channels, dim_z_content, dim_z_category, dim_z_motion, video_length, ode_fn=ode_fn,
+                         dim_hidden=None, linear=linear, ngf=ngf)
+
+    def _init_ode_parts(self, ode_fn, dim_hidden, linear, dim_z, ngf):
+        cde_input_dim, dim_hidden = self._cde_args
+        del self._cde_args
+        if cde_input_dim != 2:
+            raise NotImplementedError(f"cde_input_dim={cde_input_dim}: the path of models/mocogan_cde.py is [time, noise] "
+                                      "(2 channels), the only one libgode's fused CDE kernels integrate")
+        if dim_hidden not in (None, 16):
+            raise NotImplementedError(f"dim_hidden={dim_hidden}: libgode's fused CDE kernels are specialised for the "
+                                      "16-dimensional state of mnist_moco_cde.py (dim_hidden=None -> dim_z_motion=16)")
+        if not (isinstance(ode_fn, type) and issubclass(ode_fn, CDEFunc)):
+            raise NotImplementedError("ode_fn must be gan_ode_amd's CDEFunc (models/mocogan_cde.py:13-29): the vector "
+                                      "field is evaluated inside the fused HIP kernels, an arbitrary Python callable cannot be")
+        # construction order == the reference's: VideoGeneratorMNIST with its defaults (ODEFunc(16, 16), the 28x28
+        # `main`, `linear`), then the CDEFunc, `linear` again and the pre-net `f`
+        super()._init_ode_parts(ODEFunc, None, True, dim_z, ngf)
+        fn = ode_fn(dim=cde_input_dim, dim_hidden=dim_hidden if dim_hidden else self.dim_z_motion)
+        l1, l2 = getattr(fn, "linear1", None), getattr(fn, "linear2", None)
+        if not (isinstance(l1, nn.Linear) and isinstance(l2, nn.Linear) and tuple(l1.weight.shape) == (128, 16)
+                and l1.bias is not None and tuple(l2.weight.shape) == (32, 128) and l2.bias is not None):
+            raise NotImplementedError("ode_fn must hold linear1 = Linear(16, 128) and linear2 = Linear(128, 32)")
+        self.ode_fn = fn
+        self.linear = self._make_prenet(linear)
+        d = self.dim_z_motion
+        self.f = nn.Sequential(nn.Linear(cde_input_dim, 64), nn.LeakyReLU(0.2), nn.Linear(64, d), nn.LeakyReLU(0.2))
+
+    def _param_list(self):
+        dec = []
+        for p in self._decoder_params():
+            dec.append(p.weight)
+            if p.gamma is not None:
+                dec += [p.gamma, p.beta]
+        fn = self.ode_fn
+        cde = [self.f[0].weight, self.f[0].bias, self.f[2].weight, self.f[2].bias, fn.linear1.weight, fn.linear1.bias,
+               fn.linear2.weight, fn.linear2.bias]
+        return dec, cde
+
+    def _check_len(self, T):
+        if T != self.dim_z_motion:
+            raise ValueError(f"video_len={T}: models/mocogan_cde.py views the [n, {self.dim_z_motion}] motion noise as "
+                             f"[n, video_len, 1], which needs video_len == dim_z_motion ({self.dim_z_motion})")
+
+    def _host_inputs(self, select, num_samples, T):
+        self._check_len(T)
+        return super()._host_inputs(select, num_samples, T)
+
+    def _launch_latents(self, plans):
+        st = stream_ptr()
+        for p in plans:
+            p.fwd_prog.run(st)
+        for p in plans:
+            p.check_solve()
+
+    def sample_z_m(self, num_samples, video_len=None):
+        """models/mocogan_cde.py:60-84 -> [N*T, 16], row n*T + t: one gode_cde_fwd launch, differentiable
+        (gode_cde_bwd).  sample_videos()/sample_images() fuse the same launch with the content broadcast and the
+        decoder; this method is the reference's public surface (and what the inherited sample_z_video calls)."""
+        T = video_len if video_len is not None else self.video_length
+        self._check_len(T)
+        _require_gpu(self.main[0].weight, type(self).__name__)
+        x = self._draw_motion(num_samples, T)
+        _, cde = self._param_list()
+        return _CdeLatentFn.apply(self, x, num_samples, T, *cde)
+
+
 # ==================================================================================================================
 # discriminators
 # ==================================================================================================================

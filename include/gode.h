@@ -349,6 +349,52 @@ int gode_sde_bwd(const gode_sde_bwd_op* op, void* stream);
 int64_t gode_sde_bwd_work_size(int32_t N);
 #define GODE_SDE_NPARAM 3216
 
+/* ---- Neural-CDE motion latent (models/mocogan_cde.py: torchcde.cdeint(X, f([0, x_0]), CDEFunc, t=arange(T)) on the
+ * backward-difference Hermite cubic spline of the path [linspace(0, 1, T), x]; dopri5, rtol/atol from the caller) -----
+ * forward, ONE launch: z0 = f([tt_0, x_0]) (Linear(2,64) -> LReLU -> Linear(64,16) -> LReLU), then dopri5 on
+ *   dz/dt = tanh(W2 relu(W1 z + b1) + b2).view(16, 2) @ dX/dt(t)
+ * with torchdiffeq's controller (_select_initial_step, safety 0.9, ifactor 10, dfactor 0.2, exponent -1/5), the RMS error
+ * norm over ALL N*16 values of the call (workgroups exchange partial sums through `sync`, fixed order: bit-identical
+ * decisions) and the 4th-order dense output at t = 0..T-1, written into z (content / sel_t / zcols as in gode_ode_fwd).
+ * The clock and the step size are fp64, the state fp32.  x[N][T]: the noise channel's knots; tslope[T-1]: the time
+ * channel's per-interval slopes (fp32 differences of linspace(0, 1, T)).  Recorded for the backward: states[N][S_cap+1][16]
+ * (the state at the start of every accepted step, then the final one), sched[2][S_cap] (fp64: t_k, then h_k; one schedule
+ * for the whole batch) and counts[2] = {accepted, trials}.  More than S_cap accepted steps, a trial limit or a step-size
+ * underflow stop the solve cleanly: counts[0] = -(accepted) - 1, nothing is written past the buffers.
+ * 2 <= T <= 16, 1 <= N <= GODE_CDE_MAX_N (all workgroups must be co-resident). */
+typedef struct gode_cde_params {
+  const float* Wa; const float* ba; const float* Wb; const float* bb;   /* f: Linear(2,64) [64,2],[64]; Linear(64,16) [16,64],[16] */
+  const float* W1; const float* b1; const float* W2; const float* b2;   /* CDEFunc: linear1 [128,16],[128]; linear2 [32,128],[32] */
+} gode_cde_params;
+typedef struct gode_cde_fwd_op {
+  gode_cde_params p;
+  const float* x; const float* tslope; const float* content; const int32_t* sel_t;
+  float* z; float* states; double* sched; int32_t* counts;
+  int32_t* sync;    /* N > 16: >= gode_cde_sync_size(N) words (zeroed by the call); may be NULL for N <= 16 */
+  int32_t N, T, S_cap, zcols;
+  float rtol, atol;
+} gode_cde_fwd_op;
+int gode_cde_fwd(const gode_cde_fwd_op* op, void* stream);
+int64_t gode_cde_sync_size(int32_t N);
+int64_t gode_cde_state_size(int32_t N, int32_t S_cap);   /* floats of states */
+/* backward: the exact gradient of the discrete forward above (step sizes held constant; not torchdiffeq's continuous
+ * adjoint): for every accepted step in reverse, the 7 stages are recomputed from the stored state and back-propagated,
+ * with the dense-output interpolant's share of gz and, at the end, the pre-net.  gz[rows][zcols] as in gode_ode_bwd.
+ * The parameter sums are reduced in fixed order through work (>= gode_cde_bwd_work_size(N) floats) and written
+ * (accumulate != 0: added) to grads[GODE_CDE_NPARAM] = Wa, ba, Wb, bb, W1, b1, W2, b2; nothing outside it is touched.
+ * counts is the forward's (read on the device; a failed forward leaves grads untouched). */
+typedef struct gode_cde_bwd_op {
+  gode_cde_params p;
+  const float* x; const float* tslope; const int32_t* sel_t;
+  const float* states; const double* sched; const int32_t* counts;
+  const float* gz; float* work; float* grads;
+  int32_t N, T, S_cap, accumulate, zcols, pad_;
+} gode_cde_bwd_op;
+int gode_cde_bwd(const gode_cde_bwd_op* op, void* stream);
+int64_t gode_cde_bwd_work_size(int32_t N);
+#define GODE_CDE_NPARAM 7536
+#define GODE_CDE_MAX_N 4096
+
 /* ---- loss and optimiser (mnist_moco_ode.py:86-89) ------------------------------------------------------------
  * BCE-with-logits, mean reduced, constant target: loss (+)= mean(max(x,0) - x*t + log1p(exp(-|x|))) and
  * g[i] = gscale*(sigmoid(x[i]) - t)/n.  loss is one device float; accumulate!=0 adds to it. */
@@ -380,7 +426,7 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
 enum { GODE_OP_IGEMM = 1, GODE_OP_WGRAD = 2, GODE_OP_BN_FINALIZE = 3, GODE_OP_BN_BWD = 4, GODE_OP_ODE_FWD = 5,
        GODE_OP_ODE_BWD = 6, GODE_OP_BCE = 7, GODE_OP_ADAM = 8, GODE_OP_PACK = 9, GODE_OP_ODERNN_FWD = 10,
        GODE_OP_ODERNN_BWD = 11, GODE_OP_BN_APPLY = 12, GODE_OP_COL2IM = 13, GODE_OP_SDE_FWD = 14,
-       GODE_OP_SDE_BWD = 15 };
+       GODE_OP_SDE_BWD = 15, GODE_OP_CDE_FWD = 16, GODE_OP_CDE_BWD = 17 };
 typedef struct gode_pack_op {
   gode_conv_geom g; int32_t dir, co_canon; const float* w; float* wpack; const int32_t* co_perm;
 } gode_pack_op;
