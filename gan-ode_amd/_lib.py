@@ -17,6 +17,8 @@ OP_IGEMM, OP_WGRAD, OP_BN_FINALIZE, OP_BN_BWD, OP_ODE_FWD, OP_ODE_BWD, OP_BCE, O
 OP_ODERNN_FWD, OP_ODERNN_BWD, OP_BN_APPLY, OP_COL2IM = 10, 11, 12, 13
 OP_SDE_FWD, OP_SDE_BWD = 14, 15
 OP_CDE_FWD, OP_CDE_BWD = 16, 17
+OP_WGAN = 18
+REC_ADAM_NOISE = -1          # gode_sizeof index of the gode_adam_noise_tensor table record
 ODE_NPARAM = 2672
 ODERNN_NPARAM = 2176
 SDE_NPARAM = 3216
@@ -154,6 +156,16 @@ class BceOp(C.Structure):
     KIND = OP_BCE
 
 
+class WganOp(C.Structure):
+    _fields_ = [("fake", ptr), ("real", ptr), ("grad_fake", ptr), ("grad_real", ptr), ("loss", ptr), ("n", i64),
+                ("sign", f32), ("gscale", f32), ("reduction", i32), ("accumulate", i32)]
+    KIND = OP_WGAN
+
+
+class AdamNoiseTensor(C.Structure):
+    _fields_ = [("p", ptr), ("g", ptr), ("m", ptr), ("v", ptr), ("n", i64), ("noise_off", i64)]
+
+
 class AdamOp(C.Structure):
     _fields_ = [("p", ptr), ("g", ptr), ("m", ptr), ("v", ptr), ("n", i64), ("lr", f32), ("beta1", f32),
                 ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("gscale", f32), ("step", i32), ("pad_", i32)]
@@ -168,14 +180,16 @@ class PackOp(C.Structure):
 _STRUCTS = {0: ConvGeom, OP_IGEMM: IgemmOp, OP_WGRAD: WgradOp, OP_BN_FINALIZE: BnFinalizeOp, OP_BN_BWD: BnBwdOp,
             OP_ODE_FWD: OdeFwdOp, OP_ODE_BWD: OdeBwdOp, OP_BCE: BceOp, OP_ADAM: AdamOp, OP_PACK: PackOp,
             OP_ODERNN_FWD: OdeRnnFwdOp, OP_ODERNN_BWD: OdeRnnBwdOp, OP_BN_APPLY: BnApplyOp, OP_COL2IM: Col2imOp,
-            OP_SDE_FWD: SdeFwdOp, OP_SDE_BWD: SdeBwdOp, OP_CDE_FWD: CdeFwdOp, OP_CDE_BWD: CdeBwdOp}
+            OP_SDE_FWD: SdeFwdOp, OP_SDE_BWD: SdeBwdOp, OP_CDE_FWD: CdeFwdOp, OP_CDE_BWD: CdeBwdOp, OP_WGAN: WganOp,
+            REC_ADAM_NOISE: AdamNoiseTensor}
 
 EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "gode_igemm_stats_segments", "gode_igemm_model_cycles", "gode_igemm_work_size", "gode_pack_size", "gode_pack_weights", "gode_wgrad",
            "gode_wgrad_work_size", "gode_wgrad_auto_splits", "gode_bn_finalize", "gode_bn_bwd",
            "gode_bn_bwd_work_size", "gode_bn_apply", "gode_col2im", "gode_ode_fwd", "gode_ode_bwd", "gode_ode_fwd_multi", "gode_ode_bwd_multi", "gode_ode_bwd_work_size", "gode_odernn_fwd",
            "gode_odernn_bwd", "gode_odernn_bwd_work_size", "gode_odernn_sync_size", "gode_odernn_fwd_multi",
            "gode_odernn_bwd_multi", "gode_sde_fwd", "gode_sde_bwd", "gode_sde_bwd_work_size", "gode_cde_fwd", "gode_cde_bwd", "gode_cde_sync_size", "gode_cde_state_size", "gode_cde_bwd_work_size", "gode_bce_logits",
-           "gode_adam_l2", "gode_adam_multi", "gode_adam_multi_dev", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
+           "gode_wgan_logits", "gode_adam_l2", "gode_adam_multi", "gode_adam_multi_dev", "gode_adam_noise_multi",
+           "gode_adam_noise_multi_dev", "gode_param_noise", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
 
 _lib = None
 
@@ -198,7 +212,7 @@ def lib():
             raise RuntimeError(f"ABI mismatch for op kind {kind}: C {L.gode_sizeof(kind)} != ctypes {C.sizeof(st)}")
     for name in ("gode_igemm", "gode_wgrad", "gode_bn_finalize", "gode_bn_bwd", "gode_ode_fwd", "gode_ode_bwd",
                  "gode_bce_logits", "gode_adam_l2", "gode_odernn_fwd", "gode_odernn_bwd", "gode_bn_apply", "gode_col2im",
-                 "gode_sde_fwd", "gode_sde_bwd", "gode_cde_fwd", "gode_cde_bwd"):
+                 "gode_sde_fwd", "gode_sde_bwd", "gode_cde_fwd", "gode_cde_bwd", "gode_wgan_logits"):
         getattr(L, name).argtypes = [ptr, ptr]
         getattr(L, name).restype = C.c_int
     L.gode_igemm_stats_rows.argtypes = [ptr]
@@ -236,6 +250,10 @@ def lib():
     L.gode_scale.argtypes = [ptr, ptr, i64, f32, C.c_int, ptr]
     L.gode_adam_multi.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, f32, i32, ptr]
     L.gode_adam_multi_dev.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, ptr, ptr]
+    u32, u64 = C.c_uint32, C.c_uint64
+    L.gode_adam_noise_multi.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, f32, i32, u64, u32, u32, f32, ptr]
+    L.gode_adam_noise_multi_dev.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, ptr, u64, u32, f32, ptr]
+    L.gode_param_noise.argtypes = [ptr, i64, u64, u32, u32, i64, f32, i32, ptr]
     L.gode_run.argtypes = [ptr, ptr, i32, ptr]
     _lib = L
     return L
@@ -301,5 +319,6 @@ def _run_one(op, stream):
           OP_ODE_FWD: "gode_ode_fwd", OP_ODE_BWD: "gode_ode_bwd", OP_BCE: "gode_bce_logits",
           OP_ADAM: "gode_adam_l2", OP_ODERNN_FWD: "gode_odernn_fwd", OP_ODERNN_BWD: "gode_odernn_bwd",
           OP_BN_APPLY: "gode_bn_apply", OP_COL2IM: "gode_col2im", OP_SDE_FWD: "gode_sde_fwd",
-          OP_SDE_BWD: "gode_sde_bwd", OP_CDE_FWD: "gode_cde_fwd", OP_CDE_BWD: "gode_cde_bwd"}[op.KIND]
+          OP_SDE_BWD: "gode_sde_bwd", OP_CDE_FWD: "gode_cde_fwd", OP_CDE_BWD: "gode_cde_bwd",
+          OP_WGAN: "gode_wgan_logits"}[op.KIND]
     check(getattr(lib(), fn)(C.byref(op), stream), fn)

@@ -6,6 +6,7 @@ extern "C" int gode_version(void) { return GODE_VERSION; }
 extern "C" int gode_sizeof(int kind) {
   switch (kind) {
     case 0: return (int)sizeof(gode_conv_geom);
+    case -1: return (int)sizeof(gode_adam_noise_tensor);
     case GODE_OP_IGEMM: return (int)sizeof(gode_igemm_op);
     case GODE_OP_WGRAD: return (int)sizeof(gode_wgrad_op);
     case GODE_OP_BN_FINALIZE: return (int)sizeof(gode_bn_finalize_op);
@@ -23,6 +24,7 @@ extern "C" int gode_sizeof(int kind) {
     case GODE_OP_SDE_BWD: return (int)sizeof(gode_sde_bwd_op);
     case GODE_OP_CDE_FWD: return (int)sizeof(gode_cde_fwd_op);
     case GODE_OP_CDE_BWD: return (int)sizeof(gode_cde_bwd_op);
+    case GODE_OP_WGAN: return (int)sizeof(gode_wgan_op);
   }
   return GODE_E_KIND;
 }
@@ -52,6 +54,7 @@ extern "C" int gode_run(const int32_t* kinds, const void* const* ops, int32_t n,
       case GODE_OP_SDE_BWD: rc = gode_sde_bwd((const gode_sde_bwd_op*)ops[i], stream); break;
       case GODE_OP_CDE_FWD: rc = gode_cde_fwd((const gode_cde_fwd_op*)ops[i], stream); break;
       case GODE_OP_CDE_BWD: rc = gode_cde_bwd((const gode_cde_bwd_op*)ops[i], stream); break;
+      case GODE_OP_WGAN: rc = gode_wgan_logits((const gode_wgan_op*)ops[i], stream); break;
       case GODE_OP_PACK: {
         // every run of consecutive pack ops goes out as one launch per 8 panels
         int j = i;

@@ -512,6 +512,39 @@ extern "C" int gode_bce_logits(const gode_bce_op* op, void* stream) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Wasserstein loss (torchgan: generator -reduce(fgz), discriminator reduce(fgz - fx)), same single-block pattern
+__global__ void __launch_bounds__(256) wgan_kernel(const gode_wgan_op a) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  const float gv = a.sign * (a.reduction ? a.gscale : a.gscale / (float)a.n);
+  for (int64_t i = tid; i < a.n; i += 256) {
+    const float d = a.real ? a.fake[i] - a.real[i] : a.fake[i];
+    s += (double)d;
+    if (a.grad_fake) a.grad_fake[i] = gv;
+    if (a.grad_real) a.grad_real[i] = -gv;
+  }
+  red[tid] = s;
+  __syncthreads();
+  for (int k = 128; k > 0; k >>= 1) {
+    if (tid < k) red[tid] += red[tid + k];
+    __syncthreads();
+  }
+  if (tid == 0 && a.loss) {
+    const float v = a.sign * (float)(a.reduction ? red[0] : red[0] / (double)a.n);
+    *a.loss = a.accumulate ? *a.loss + v : v;
+  }
+}
+
+extern "C" int gode_wgan_logits(const gode_wgan_op* op, void* stream) {
+  if (!op || !op->fake || op->n <= 0 || (op->reduction != 0 && op->reduction != 1) || (op->grad_real && !op->real))
+    return GODE_E_ARG;
+  hipLaunchKernelGGL(wgan_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *op);
+  GODE_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Adam with L2-coupled weight decay (operation order of torch.optim.Adam's single-tensor path)
 __global__ void __launch_bounds__(256) adam_kernel(float* p, const float* g, float* m, float* v, int64_t n, float b1,
                                                    float b2, float eps, float wd, float gscale, float step_size,
@@ -618,6 +651,165 @@ __global__ void __launch_bounds__(256) scale_kernel(float* out, const float* a, 
 extern "C" int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulate, void* stream) {
   if (!out || !a || n <= 0) return GODE_E_ARG;
   hipLaunchKernelGGL(scale_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, out, a, n, alpha, accumulate);
+  GODE_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Parameter noise (add_noise: p += randn_like(p) * sigma after the optimiser step), fused into Adam.  The stream is a
+// function of (seed, stream, step, element index in the param group) alone -- see gode.h -- so the grid, the float4 path
+// and the arena layout do not change a single value.  One Philox4x32-10 call feeds the four elements of one float4:
+// ~100 integer ops + two log / sqrt / sincospi per 4 elements, well under the ~175 VALU ops per element that Adam's
+// 28 B of HBM traffic per parameter leaves at 6.3 TB/s.
+struct NoiseArgs { uint32_t k0, k1, stream, step; float sigma; };
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+}
+__device__ __forceinline__ void philox_quad(uint64_t quad, const NoiseArgs& a, uint32_t c[4]) {
+  c[0] = (uint32_t)quad; c[1] = a.step; c[2] = a.stream; c[3] = (uint32_t)(quad >> 32);
+  philox4x32_10(c, a.k0, a.k1);
+}
+// 23 bits per uniform: (k + 0.5) * 2^-23 is exact in fp32 and lies in (0, 1)
+__device__ __forceinline__ float noise_uniform(uint32_t x) { return ((float)(x >> 9) + 0.5f) * 0x1p-23f; }
+__device__ __forceinline__ f32x4 box_muller4(const uint32_t c[4]) {
+  const float r0 = sqrtf(-2.f * logf(noise_uniform(c[0]))), r2 = sqrtf(-2.f * logf(noise_uniform(c[2])));
+  float s1, c1, s3, c3;
+  sincospif(2.f * noise_uniform(c[1]), &s1, &c1);      // sin / cos of 2 pi u: u in revolutions, no range reduction
+  sincospif(2.f * noise_uniform(c[3]), &s3, &c3);
+  f32x4 z;
+  z[0] = r0 * c1; z[1] = r0 * s1; z[2] = r2 * c3; z[3] = r2 * s3;
+  return z;
+}
+// p + fp32(z * sigma), each operation rounded on its own: the library builds with -ffp-contract=fast, which fuses across
+// pragmas and __fmul_rn / __fadd_rn alike, and a fused multiply-add here would differ from the reference's
+// randn_like(p) * sigma followed by add_.  The empty asm statement makes the product opaque to the combiner (no code).
+__device__ __forceinline__ float noise_scale(float z, float sigma) {
+  float t = z * sigma;
+  __asm__("" : "+v"(t));
+  return t;
+}
+__device__ __forceinline__ float noise_add(float p, float z, float sigma) { return p + noise_scale(z, sigma); }
+__device__ __forceinline__ float noise_elem(uint64_t e, const NoiseArgs& a) {
+  uint32_t c[4];
+  philox_quad(e >> 2, a, c);
+  const f32x4 z = box_muller4(c);
+  const int l = (int)(e & 3);
+  return l == 0 ? z[0] : l == 1 ? z[1] : l == 2 ? z[2] : z[3];
+}
+
+__device__ __forceinline__ void adam_noise_tensor(const gode_adam_noise_tensor& t, float b1, float b2, float eps, float wd,
+                                                  float gscale, float step_size, float bc2_sqrt, const NoiseArgs& na) {
+  const bool adam = t.g != nullptr;          // uniform per block (one tensor per blockIdx.y)
+  const bool vec = (((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 15) == 0 && (t.noise_off & 3) == 0;
+  const int64_t n4 = vec ? t.n >> 2 : 0;
+  const uint64_t q0 = (uint64_t)t.noise_off >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    f32x4 p = reinterpret_cast<const f32x4*>(t.p)[i];
+    if (adam) {
+      f32x4 m = reinterpret_cast<const f32x4*>(t.m)[i], v = reinterpret_cast<const f32x4*>(t.v)[i];
+      const f32x4 g = reinterpret_cast<const f32x4*>(t.g)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = p[e], me = m[e], ve = v[e];
+        adam_elem(pe, g[e], me, ve, b1, b2, eps, wd, gscale, step_size, bc2_sqrt);
+        p[e] = pe; m[e] = me; v[e] = ve;
+      }
+      reinterpret_cast<f32x4*>(t.m)[i] = m; reinterpret_cast<f32x4*>(t.v)[i] = v;
+    }
+    uint32_t c[4];
+    philox_quad(q0 + (uint64_t)i, na, c);
+    const f32x4 z = box_muller4(c);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) p[e] = noise_add(p[e], z[e], na.sigma);
+    reinterpret_cast<f32x4*>(t.p)[i] = p;
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < t.n; i += (int64_t)gridDim.x * 256) {
+    float p = t.p[i];
+    if (adam) {
+      float m = t.m[i], v = t.v[i];
+      adam_elem(p, t.g[i], m, v, b1, b2, eps, wd, gscale, step_size, bc2_sqrt);
+      t.m[i] = m; t.v[i] = v;
+    }
+    t.p[i] = noise_add(p, noise_elem((uint64_t)t.noise_off + (uint64_t)i, na), na.sigma);
+  }
+}
+static NoiseArgs make_noise_args(uint64_t seed, uint32_t stream, uint32_t step, float sigma) {
+  NoiseArgs a; a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.stream = stream; a.step = step; a.sigma = sigma;
+  return a;
+}
+
+__global__ void __launch_bounds__(256) adam_noise_multi_kernel(const gode_adam_noise_tensor* table, float b1, float b2,
+                                                               float eps, float wd, float gscale, float step_size,
+                                                               float bc2_sqrt, NoiseArgs na) {
+  adam_noise_tensor(table[blockIdx.y], b1, b2, eps, wd, gscale, step_size, bc2_sqrt, na);
+}
+
+extern "C" int gode_adam_noise_multi(const gode_adam_noise_tensor* table, int32_t count, int64_t max_n, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, float gscale, int32_t step,
+                                     uint64_t seed, uint32_t noise_stream, uint32_t noise_step, float sigma, void* stream) {
+  if (!table || count <= 0 || max_n <= 0 || step < 1) return GODE_E_ARG;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  const int bx = adam_blocks(max_n);
+  hipLaunchKernelGGL(adam_noise_multi_kernel, dim3(bx, count), dim3(256), 0, (hipStream_t)stream, table, beta1, beta2,
+                     eps, weight_decay, gscale, (float)((double)lr / bc1), (float)sqrt(bc2),
+                     make_noise_args(seed, noise_stream, noise_step, sigma));
+  GODE_LAUNCH_CHECK();
+  return 0;
+}
+
+// coef[0], coef[1]: Adam's step-dependent coefficients as in adam_multi_dev_kernel; coef[2]: the noise step, raw 32 bits
+__global__ void __launch_bounds__(256) adam_noise_multi_dev_kernel(const gode_adam_noise_tensor* table, float b1, float b2,
+                                                                   float eps, float wd, float gscale, const float* coef,
+                                                                   NoiseArgs na) {
+  na.step = __float_as_uint(coef[2]);
+  adam_noise_tensor(table[blockIdx.y], b1, b2, eps, wd, gscale, coef[0], coef[1], na);
+}
+
+extern "C" int gode_adam_noise_multi_dev(const gode_adam_noise_tensor* table, int32_t count, int64_t max_n, float beta1,
+                                         float beta2, float eps, float weight_decay, float gscale, const float* coef,
+                                         uint64_t seed, uint32_t noise_stream, float sigma, void* stream) {
+  if (!table || count <= 0 || max_n <= 0 || !coef) return GODE_E_ARG;
+  const int bx = adam_blocks(max_n);
+  hipLaunchKernelGGL(adam_noise_multi_dev_kernel, dim3(bx, count), dim3(256), 0, (hipStream_t)stream, table, beta1, beta2,
+                     eps, weight_decay, gscale, coef, make_noise_args(seed, noise_stream, 0, sigma));
+  GODE_LAUNCH_CHECK();
+  return 0;
+}
+
+// The stream on its own: one thread per Philox quad overlapping [noise_off, noise_off + n), any offset and length
+__global__ void __launch_bounds__(256) param_noise_kernel(float* out, int64_t n, int64_t noise_off, NoiseArgs na, int mode) {
+  const uint64_t q_lo = (uint64_t)noise_off >> 2, q_hi = ((uint64_t)noise_off + (uint64_t)n - 1) >> 2;
+  for (uint64_t q = q_lo + (uint64_t)blockIdx.x * 256 + threadIdx.x; q <= q_hi; q += (uint64_t)gridDim.x * 256) {
+    uint32_t c[4];
+    philox_quad(q, na, c);
+    f32x4 z;
+    if (mode != 2) z = box_muller4(c);
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+      const int64_t i = (int64_t)(q * 4 + l) - noise_off;
+      if (i < 0 || i >= n) continue;
+      if (mode == 2) out[i] = __uint_as_float(c[l]);
+      else if (mode == 1) out[i] = noise_add(out[i], z[l], na.sigma);
+      else out[i] = noise_scale(z[l], na.sigma);
+    }
+  }
+}
+
+extern "C" int gode_param_noise(float* out, int64_t n, uint64_t seed, uint32_t noise_stream, uint32_t noise_step,
+                                int64_t noise_off, float sigma, int32_t accumulate, void* stream) {
+  if (!out || n <= 0 || noise_off < 0 || accumulate < 0 || accumulate > 2) return GODE_E_ARG;
+  const int64_t quads = (((noise_off + n - 1) >> 2) - (noise_off >> 2)) + 1;
+  const int64_t b = (quads + 255) / 256;
+  hipLaunchKernelGGL(param_noise_kernel, dim3((unsigned)(b > 4096 ? 4096 : b)), dim3(256), 0, (hipStream_t)stream, out, n,
+                     noise_off, make_noise_args(seed, noise_stream, noise_step, sigma), (int)accumulate);
   GODE_LAUNCH_CHECK();
   return 0;
 }

@@ -153,6 +153,127 @@ def bce_with_logits_pair(logits_a, target_a: float, logits_b, target_b: float) -
     return _BceConstFn.apply(logits_a, target_a, logits_b, target_b)
 
 
+# Wasserstein loss (torchgan.losses, mnist_moco_ode_wgan.py:13,97-98): generator -reduce(fgz), discriminator
+# reduce(fgz - fx), no clipping, no gradient penalty.  The terms of one loss accumulate into one device scalar.
+_REDUCTIONS = {"mean": 0, "sum": 1}
+
+
+class _WganFn(torch.autograd.Function):
+    """sum_k sign_k * reduce(fake_k [- real_k]) in one autograd node.  terms: per term (sign, layout) with layout 1 (one
+    tensor: fake), 2 (two tensors: real, fake) or 0 (one joint [real; fake] tensor); xs holds the tensors in order."""
+
+    @staticmethod
+    def forward(ctx, reduction, terms, *xs):
+        red = _REDUCTIONS[reduction]
+        loss = torch.empty((), dtype=torch.float32, device=xs[0].device)
+        st = stream_ptr()
+        grads, j = [], 0
+        for k, (sign, layout) in enumerate(terms):
+            if layout == 0:
+                x = xs[j].contiguous()
+                g = torch.empty_like(x)
+                n = x.numel() // 2
+                op = L.WganOp(real=x.data_ptr(), fake=x.data_ptr() + 4 * n, grad_real=g.data_ptr(),
+                              grad_fake=g.data_ptr() + 4 * n, n=n)
+                grads.append(g)
+                j += 1
+            elif layout == 1:
+                x = xs[j].contiguous()
+                g = torch.empty_like(x)
+                op = L.WganOp(fake=x.data_ptr(), grad_fake=g.data_ptr(), n=x.numel())
+                grads.append(g)
+                j += 1
+            else:
+                r, f = xs[j].contiguous(), xs[j + 1].contiguous()
+                gr, gf = torch.empty_like(r), torch.empty_like(f)
+                op = L.WganOp(real=r.data_ptr(), fake=f.data_ptr(), grad_real=gr.data_ptr(), grad_fake=gf.data_ptr(),
+                              n=f.numel())
+                grads += [gr, gf]
+                j += 2
+            op.loss, op.sign, op.gscale, op.reduction, op.accumulate = loss.data_ptr(), float(sign), 1.0, red, 1 if k else 0
+            L.run_one(op, st)
+        ctx.save_for_backward(*grads)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        return (None, None) + tuple(_scaled(g, gout) for g in ctx.saved_tensors)
+
+
+def _wgan_check(*xs):
+    for x in xs:
+        if not x.is_cuda:
+            raise RuntimeError("the Wasserstein losses run only on the GPU through libgode.so")
+
+
+def wasserstein_generator_loss(fgz: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
+    """torchgan's wasserstein_generator_loss: reduce(-fgz)."""
+    _wgan_check(fgz)
+    return _WganFn.apply(reduction, ((-1.0, 1),), fgz)
+
+
+def wasserstein_generator_loss_pair(fgz_a: torch.Tensor, fgz_b: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
+    """wasserstein_generator_loss(a) + wasserstein_generator_loss(b) as one node (each term reduced on its own, the two
+    added in fp32: mnist_moco_ode_wgan.py:174)."""
+    _wgan_check(fgz_a, fgz_b)
+    return _WganFn.apply(reduction, ((-1.0, 1), (-1.0, 1)), fgz_a, fgz_b)
+
+
+def wasserstein_discriminator_loss(fx: torch.Tensor, fgz: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
+    """torchgan's wasserstein_discriminator_loss: reduce(fgz - fx), the difference taken per element."""
+    _wgan_check(fx, fgz)
+    if fx.shape != fgz.shape:
+        raise RuntimeError(f"wasserstein_discriminator_loss: fx {tuple(fx.shape)} and fgz {tuple(fgz.shape)} differ in shape")
+    return _WganFn.apply(reduction, ((1.0, 2),), fx, fgz)
+
+
+def wasserstein_discriminator_loss_halves(joint: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
+    """wasserstein_discriminator_loss(x[:B], x[B:]) on the joint [real; fake] output of forward_pair_joint."""
+    _wgan_check(joint)
+    if joint.shape[0] % 2:
+        raise RuntimeError("wasserstein_discriminator_loss_halves: a tensor with an even leading dimension is expected")
+    return _WganFn.apply(reduction, ((1.0, 0),), joint)
+
+
+def _wgan_args(reduction, override_train_ops, clip=None):
+    if reduction == "none":
+        raise ValueError("reduction='none' is not supported: the loss kernel reduces on the device (use 'mean' or 'sum')")
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"reduction must be 'mean' or 'sum', got {reduction!r}")
+    if override_train_ops is not None:
+        raise ValueError("override_train_ops is not supported: train with GanTrainer(loss='wasserstein') or a loop of "
+                         "your own")
+    if clip is not None:
+        raise ValueError("weight clipping (clip=...) is not supported; the reference trains without it")
+
+
+class WassersteinGeneratorLoss(torch.nn.Module):
+    """torchgan.losses.WassersteinGeneratorLoss drop-in (constructor and forward signatures): -reduce(fgz)."""
+
+    def __init__(self, reduction="mean", override_train_ops=None):
+        super().__init__()
+        _wgan_args(reduction, override_train_ops)
+        self.reduction = reduction
+        self.override_train_ops = None
+
+    def forward(self, fgz):
+        return wasserstein_generator_loss(fgz, self.reduction)
+
+
+class WassersteinDiscriminatorLoss(torch.nn.Module):
+    """torchgan.losses.WassersteinDiscriminatorLoss drop-in (constructor and forward signatures): reduce(fgz - fx)."""
+
+    def __init__(self, reduction="mean", clip=None, override_train_ops=None):
+        super().__init__()
+        _wgan_args(reduction, override_train_ops, clip)
+        self.reduction = reduction
+        self.clip = None
+        self.override_train_ops = None
+
+    def forward(self, fx, fgz):
+        return wasserstein_discriminator_loss(fx, fgz, self.reduction)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # optimiser
 # ------------------------------------------------------------------------------------------------------------------
@@ -161,12 +282,50 @@ class FusedAdam(torch.optim.Optimizer):
     are skipped -- the generator's dead GRU cell, models/mocogan.py:198) on libgode's Adam kernel.  state_dict()
     uses torch.optim.Adam's keys (step / exp_avg / exp_avg_sq) so checkpoints interchange."""
 
-    def __init__(self, params, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=1e-5):
+    def __init__(self, params, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=1e-5, noise_sigma=0.0, noise_seed=None,
+                 noise_stream=0):
         # the extra keys are torch.optim.Adam's remaining hyper-parameters at their defaults, carried so that a
         # state_dict saved here loads into torch.optim.Adam and vice versa (mnist_moco_ode.py:92-103,175-190)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       maximize=False, foreach=None, capturable=False, differentiable=False,
                                       fused=None, decoupled_weight_decay=False))
+        # noise_sigma > 0: add_noise of mnist_moco_ode_noise.py / _wgan.py (p += randn_like(p) * sigma on EVERY parameter,
+        # gradient or not, right after the update) fused into the Adam launch.  The normals come from libgode's
+        # counter-based stream (gode.h: Philox4x32-10 keyed by noise_seed, counter (element quad, noise step,
+        # noise_stream)), not torch's generator (DESIGN section 10).  The noise step counter and the stream parameters
+        # live in each param group, so state_dict() / load_state_dict() resume the same stream.
+        sigma = float(noise_sigma)
+        if not (sigma >= 0.0 and sigma != float("inf")):
+            raise ValueError(f"noise_sigma must be a finite number >= 0, got {noise_sigma!r}")
+        if noise_seed is not None and (isinstance(noise_seed, bool) or not isinstance(noise_seed, int)):
+            raise TypeError(f"noise_seed must be an int or None, got {type(noise_seed).__name__}")
+        if isinstance(noise_stream, bool) or not isinstance(noise_stream, int) or not 0 <= noise_stream < 1 << 32:
+            raise ValueError(f"noise_stream must be an int in [0, 2**32), got {noise_stream!r}")
+        self._noise_defaults = None
+        if sigma > 0.0:
+            seed = torch.initial_seed() if noise_seed is None else noise_seed
+            self._noise_defaults = dict(noise_sigma=sigma, noise_seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        noise_stream=int(noise_stream), noise_step=0)
+            self._fill_noise_keys()
+
+    def _fill_noise_keys(self):
+        for group in self.param_groups:
+            for k, v in self._noise_defaults.items():
+                group.setdefault(k, v)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        if self._noise_defaults is not None:      # a state saved without noise (stock torch.optim.Adam): stream from step 0
+            self._fill_noise_keys()
+
+    @staticmethod
+    def noise_offsets(params):
+        """noise_off of every tensor of a param group (gode.h): the running sum of roundup4(numel) in group order."""
+        offs, off = [], 0
+        for p in params:
+            offs.append(off)
+            off += (p.numel() + 3) // 4 * 4
+        return offs
 
     @staticmethod
     def step_coefficients(lr, beta1, beta2, step):
@@ -187,6 +346,9 @@ class FusedAdam(torch.optim.Optimizer):
         import numpy as np
         lib = L.lib()
         for gi, group in enumerate(self.param_groups):
+            if group.get("noise_sigma", 0.0) > 0.0:
+                self._noisy_step(gi, group, grads, gscale, feed)
+                continue
             b1, b2 = group["betas"]
             rows, keep, step, max_n, dev = [], [], None, 0, None
             for p in group["params"]:
@@ -256,13 +418,98 @@ class FusedAdam(torch.optim.Optimizer):
                 self._keep = keep
         return None
 
+    def _noisy_step(self, gi, group, grads, gscale, feed):
+        """One Adam + parameter-noise step of a param group: every parameter gets its noise exactly once -- those with a
+        gradient as Adam + noise rows, those without (the generator's dead GRU cell) as noise-only rows of the same
+        launch (gode_adam_noise_multi), those on a different Adam step count through gode_adam_l2 + gode_param_noise."""
+        import numpy as np
+        lib = L.lib()
+        b1, b2 = group["betas"]
+        group["noise_step"] += 1
+        nstep, seed, nstream, sigma = group["noise_step"], group["noise_seed"], group["noise_stream"], group["noise_sigma"]
+        base = sum(sum((p.numel() + 3) // 4 * 4 for p in g["params"]) for g in self.param_groups[:gi])
+        rows, keep, step, max_n, dev = [], [], None, 0, None
+        for p, off in zip(group["params"], self.noise_offsets(group["params"])):
+            off += base
+            if not p.is_cuda:
+                raise RuntimeError("FusedAdam runs only on the GPU through libgode.so")
+            g = grads.get(p) if grads is not None else p.grad
+            if g is None:
+                rows.append((p.data_ptr(), 0, 0, 0, p.numel(), off))        # noise-only row
+            else:
+                if not g.is_contiguous():
+                    g = g.contiguous()
+                st = self.state[p]
+                if not st:
+                    st["step"] = torch.tensor(0.0)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["step"] += 1
+                s_now = int(st["step"].item())
+                if step is None:
+                    step = s_now
+                if s_now != step:       # parameters on different step counts: one Adam launch and one noise launch each
+                    if feed is not None:
+                        raise RuntimeError("graph capture needs all parameters of a group on the same Adam step")
+                    L.run_one(L.AdamOp(p=p.data_ptr(), g=g.data_ptr(), m=st["exp_avg"].data_ptr(),
+                                       v=st["exp_avg_sq"].data_ptr(), n=p.numel(), lr=group["lr"], beta1=b1, beta2=b2,
+                                       eps=group["eps"], weight_decay=group["weight_decay"], gscale=gscale,
+                                       step=s_now), stream_ptr())
+                    L.call("param_noise", lambda p=p, off=off: L.check(
+                        lib.gode_param_noise(p.data_ptr(), p.numel(), seed, nstream, nstep, off, sigma, 1, stream_ptr()),
+                        "gode_param_noise"))
+                else:
+                    rows.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                                 p.numel(), off))
+                keep.append(g)
+            max_n = max(max_n, p.numel())
+            p._gode_ver = getattr(p, "_gode_ver", 0) + 1     # updated through a raw pointer: bump our own version
+            dev = p.device
+        if not rows:
+            return
+        step = step if step is not None else max(1, self.current_step(gi))   # (noise-only launch: coefficients unused)
+        tbl = getattr(self, "_tables", None)
+        if tbl is None:
+            tbl = self._tables = {}
+        n = len(rows)
+        ent = tbl.get(id(group))
+        key = tuple(rows)
+        if ent is None or ent.get("key") != key:
+            if feed is not None:
+                raise RuntimeError("graph capture: the Adam pointer table must exist already (run eager iterations first)")
+            if ent is None or tuple(ent["host"].shape) != (n, 6):
+                ent = tbl[id(group)] = dict(host=torch.empty((n, 6), dtype=torch.int64).pin_memory(),
+                                            dev=torch.empty((n, 6), dtype=torch.int64, device=dev), ev=None)
+            if ent["ev"] is not None:
+                ent["ev"].synchronize()
+            ent["key"] = key
+            ent["host"].copy_(torch.from_numpy(np.asarray(rows, dtype=np.int64)))
+            ent["dev"].copy_(ent["host"], non_blocking=True)
+            if ent["ev"] is None:
+                ent["ev"] = torch.cuda.Event()
+            ent["ev"].record()
+        if feed is not None:
+            coef = feed.adam_slot(self, gi, group["lr"], b1, b2, step, noise_step=nstep)
+            L.call("adam_noise_multi", lambda: L.check(
+                lib.gode_adam_noise_multi_dev(ent["dev"].data_ptr(), n, max_n, b1, b2, group["eps"], group["weight_decay"],
+                                              gscale, coef, seed, nstream, sigma, stream_ptr()), "gode_adam_noise_multi_dev"))
+        else:
+            L.call("adam_noise_multi", lambda: L.check(
+                lib.gode_adam_noise_multi(ent["dev"].data_ptr(), n, max_n, group["lr"], b1, b2, group["eps"],
+                                          group["weight_decay"], gscale, step, seed, nstream, nstep, sigma, stream_ptr()),
+                "gode_adam_noise_multi"))
+        self._keep = keep
+
     def advance_steps(self, group_index=0):
         """Host-side bookkeeping of one optimiser step that a replayed graph performed on the device: the `step`
-        entries of the state (checkpoints, the next coefficient upload) move on by one."""
+        entries of the state (checkpoints, the next coefficient upload) move on by one, and so does the noise step."""
         for p in self.param_groups[group_index]["params"]:
             st = self.state.get(p)
             if st:
                 st["step"] += 1
+        group = self.param_groups[group_index]
+        if group.get("noise_sigma", 0.0) > 0.0:
+            group["noise_step"] += 1
 
     def current_step(self, group_index=0):
         for p in self.param_groups[group_index]["params"]:
@@ -305,12 +552,15 @@ class HostFeed:
         self.script.append(("noise", gen, select, num_samples, T, off, nfloats))
         return self.pinned[self.parity][off:off + nfloats], self.dev[off:off + nfloats]
 
-    def adam_slot(self, opt, group_index, lr, b1, b2, step):
+    def adam_slot(self, opt, group_index, lr, b1, b2, step, noise_step=None):
+        """Adam's two step coefficients; with noise_step, the parameter-noise step counter follows as a raw 32-bit word."""
         assert self.recording
-        off = self._reserve(2)
-        self.script.append(("adam", opt, group_index, lr, b1, b2, off))
+        off = self._reserve(2 if noise_step is None else 3)
+        self.script.append(("adam", opt, group_index, lr, b1, b2, off, noise_step is not None))
         c = FusedAdam.step_coefficients(lr, b1, b2, step)
         self.pinned[self.parity][off], self.pinned[self.parity][off + 1] = c[0], c[1]
+        if noise_step is not None:
+            self.pinned[self.parity][off:off + 4].view(torch.int32)[2] = int(noise_step)
         return self.dev[off:off + 2].data_ptr()
 
     # -- replay ----------------------------------------------------------------------------------------------------
@@ -329,10 +579,12 @@ class HostFeed:
                 _, gen, select, num_samples, T, off, nfloats = ent
                 gen._fill_host_inputs(buf[off:off + nfloats], select, num_samples, T)
             else:
-                _, opt, gi, lr, b1, b2, off = ent
+                _, opt, gi, lr, b1, b2, off, noisy = ent
                 opt.advance_steps(gi)
                 c = FusedAdam.step_coefficients(lr, b1, b2, opt.current_step(gi))
                 buf[off], buf[off + 1] = c[0], c[1]
+                if noisy:
+                    buf[off:off + 4].view(torch.int32)[2] = int(opt.param_groups[gi]["noise_step"])
 
     def upload(self):
         """One H2D copy of the used part of the block on the current stream (ordered before the replay that reads it,
@@ -457,13 +709,33 @@ class GanTrainer:
     def __init__(self, gen, dis_vid, dis_img, lr=2e-4, betas=(0.5, 0.999), weight_decay=1e-5, d_iters=2,
                  process_group=None, freeze_d_in_g_step=True, freeze_gc=False, direct_grads=True, sync_replicas=True,
                  overlap_image_d=True, graph=False, pair_d_passes=True, prefetch_latents=True, overlap_allreduce=True,
-                 joint_generator_passes=True):
+                 joint_generator_passes=True, loss="bce", param_noise=0.0, noise_seed=None):
         self.gen, self.dis_vid, self.dis_img = gen, dis_vid, dis_img
-        mk = lambda m: FusedAdam(m.parameters(), lr=lr, betas=betas, weight_decay=weight_decay)  # noqa: E731
-        self.gen_opt, self.vid_opt, self.img_opt = mk(gen), mk(dis_vid), mk(dis_img)
+        # loss: "bce" (mnist_moco_ode.py) or "wasserstein" (torchgan's losses, mnist_moco_ode_wgan.py: D minimises
+        # mean(D(fake) - D(real)), G minimises -mean(D(fake)); no clipping, no gradient penalty)
+        if loss not in ("bce", "wasserstein"):
+            raise ValueError(f"GanTrainer(loss=...) must be 'bce' or 'wasserstein', got {loss!r}")
+        self.loss = loss
+        self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
+        # param_noise > 0: add_noise(model.parameters(), param_noise) after every optimiser step (mnist_moco_ode_noise.py
+        # sigma 1e-5, mnist_moco_ode_wgan.py 1e-4), fused into the Adam launch; streams gen 0, dis_vid 1, dis_img 2 of
+        # noise_seed (default torch.initial_seed(): nothing is drawn from the CPU generator, whose stream feeds the latent
+        # noise in the reference's order).  Replicas take rank 0's seed.
+        noise = float(param_noise)
+        if noise > 0.0:
+            if noise_seed is None:
+                noise_seed = torch.initial_seed()
+            if self.world > 1 and sync_replicas:
+                dev = next(gen.parameters()).device
+                t = torch.tensor([noise_seed & 0xFFFFFFFF, (noise_seed >> 32) & 0xFFFFFFFF], dtype=torch.int64, device=dev)
+                dist.broadcast(t, src=0, group=process_group)
+                noise_seed = int(t[0]) | (int(t[1]) << 32)
+        self.param_noise, self.noise_seed = noise, (noise_seed if noise > 0.0 else None)
+        mk = lambda m, k: FusedAdam(m.parameters(), lr=lr, betas=betas, weight_decay=weight_decay,  # noqa: E731
+                                    noise_sigma=noise, noise_seed=self.noise_seed, noise_stream=k)
+        self.gen_opt, self.vid_opt, self.img_opt = mk(gen, 0), mk(dis_vid, 1), mk(dis_img, 2)
         self.d_iters, self.group = d_iters, process_group
         self.freeze_d = freeze_d_in_g_step
-        self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         if self.world > 1 and sync_replicas:
             self.broadcast_state()
         self.buckets = {id(m): GradBucket(list(m.parameters())) for m in (gen, dis_vid, dis_img)}
@@ -633,6 +905,17 @@ class GanTrainer:
         else:
             opt.step(gscale=gscale)
 
+    def _d_loss(self, pr, pf):
+        if self.loss == "wasserstein":
+            return wasserstein_discriminator_loss(pr, pf)
+        return bce_with_logits_pair(pr, 1.0, pf, 0.0)
+
+    def _d_loss_joint(self, joint):
+        """the discriminator loss on the [real; fake] output of forward_pair_joint"""
+        if self.loss == "wasserstein":
+            return wasserstein_discriminator_loss_halves(joint)
+        return bce_with_logits_halves(joint, 1.0, 0.0)
+
     @staticmethod
     def _mean(losses):
         if len(losses) == 1:
@@ -670,10 +953,10 @@ class GanTrainer:
                 fake.record_stream(side)
             with on_side():
                 if self.pair_d:
-                    loss = bce_with_logits_halves(self.dis_img.forward_pair_joint(x, fake), 1.0, 0.0)
+                    loss = self._d_loss_joint(self.dis_img.forward_pair_joint(x, fake))
                 else:
                     pf, _ = self.dis_img(fake)
-                    loss = bce_with_logits_pair(pr, 1.0, pf, 0.0)
+                    loss = self._d_loss(pr, pf)
                 loss.backward(gradient=unit_grad(loss.device))
             losses.append(loss.detach())
         with on_side():
@@ -717,10 +1000,10 @@ class GanTrainer:
                 self._begin(self.dis_vid, self.vid_opt)
                 begun = True
             if self.pair_d:
-                loss = bce_with_logits_halves(self.dis_vid.forward_pair_joint(real, fake), 1.0, 0.0)
+                loss = self._d_loss_joint(self.dis_vid.forward_pair_joint(real, fake))
             else:
                 pf, _ = self.dis_vid(fake)
-                loss = bce_with_logits_pair(pr, 1.0, pf, 0.0)
+                loss = self._d_loss(pr, pf)
             loss.backward(gradient=unit_grad(loss.device))
             losses.append(loss.detach())
         self._opt_step(self.dis_vid, self.vid_opt, len(shards))
@@ -771,7 +1054,10 @@ class GanTrainer:
                 else:
                     pv, _ = self.dis_vid(fake_vid)
                     pi, _ = self.dis_img(fake_img)
-                loss = bce_with_logits_pair(pv, 1.0, pi, 1.0)
+                if self.loss == "wasserstein":
+                    loss = wasserstein_generator_loss_pair(pi, pv)      # image term first (mnist_moco_ode_wgan.py:174)
+                else:
+                    loss = bce_with_logits_pair(pv, 1.0, pi, 1.0)
                 if batch_adj:      # the video and the image path: two latent adjoints, one launch
                     self.gen._adjoint_batch = dict(expect=2, ops=[], keep=[])
                 if early_ar and shards == 1:

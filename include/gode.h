@@ -419,6 +419,44 @@ int gode_adam_multi(const gode_adam_tensor* table, int32_t count, int64_t max_n,
 int gode_adam_multi_dev(const gode_adam_tensor* table, int32_t count, int64_t max_n, float beta1, float beta2, float eps,
                         float weight_decay, float gscale, const float* coef, void* stream);
 
+/* ---- Wasserstein loss (torchgan.losses.WassersteinGeneratorLoss / WassersteinDiscriminatorLoss, reduction "mean" or
+ * "sum", no clipping; mnist_moco_ode_wgan.py:97-98,138,159,174) ----------------------------------------------------
+ *   real == NULL: loss (+)= sign * reduce(fake)            (generator: sign = -1)
+ *   real != NULL: loss (+)= sign * reduce(fake - real)     (discriminator: sign = +1; the difference is taken per element)
+ * reduce = mean (reduction 0) or sum (1), summed in double in one workgroup.  Gradients (each nullable):
+ * grad_fake[i] = sign * (gscale / n) (sum: sign * gscale), grad_real[i] = -grad_fake[i].  A joint [real; fake] tensor of
+ * 2n elements is passed as real = x, fake = x + n.  loss is one device float; accumulate != 0 adds to it. */
+typedef struct gode_wgan_op {
+  const float* fake; const float* real; float* grad_fake; float* grad_real; float* loss; int64_t n;
+  float sign, gscale; int32_t reduction, accumulate;
+} gode_wgan_op;
+int gode_wgan_logits(const gode_wgan_op* op, void* stream);
+
+/* ---- parameter noise (add_noise of mnist_moco_ode_noise.py / mnist_moco_ode_wgan.py: p += randn_like(p) * sigma after
+ * every optimiser step) ------------------------------------------------------------------------------------------------
+ * The stream: element e of a param group (e = noise_off + local index; noise_off of tensor k is the sum of
+ * roundup4(numel) over the tensors before it) takes output lane e & 3 of Philox4x32-10 with key (seed_lo, seed_hi) and
+ * counter (e >> 2 low word, step, stream, e >> 2 high word); each output word x becomes u = ((x >> 9) + 0.5) * 2^-23
+ * (exact in fp32, never 0 or 1), Box-Muller maps (u0, u1) -> (r cos 2 pi u1, r sin 2 pi u1), r = sqrt(-2 ln u0), and (u2, u3)
+ * alike.  Independent of the grid, the vector width and the arena layout.  The update is t = fp32(n * sigma),
+ * p = fp32(p + t): two roundings, no FMA, as the reference's two torch ops.
+ *
+ * Adam + noise on `count` tensors in ONE launch: rows with g == NULL are noise-only (no Adam update; m and v are neither
+ * read nor written and may be NULL).  The noise is added after the Adam update of the row. */
+typedef struct gode_adam_noise_tensor { float* p; const float* g; float* m; float* v; int64_t n; int64_t noise_off; } gode_adam_noise_tensor;
+int gode_adam_noise_multi(const gode_adam_noise_tensor* table, int32_t count, int64_t max_n, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, float gscale, int32_t step, uint64_t seed,
+                          uint32_t noise_stream, uint32_t noise_step, float sigma, void* stream);
+/* the same with coef[0], coef[1] as in gode_adam_multi_dev and the noise step read as the raw 32-bit word coef[2] (a graph
+ * replay advances it with the Adam coefficients) */
+int gode_adam_noise_multi_dev(const gode_adam_noise_tensor* table, int32_t count, int64_t max_n, float beta1, float beta2,
+                              float eps, float weight_decay, float gscale, const float* coef, uint64_t seed,
+                              uint32_t noise_stream, float sigma, void* stream);
+/* the stream alone over elements [noise_off, noise_off + n): accumulate 0: out[i] = n_e * sigma; 1: out[i] = out[i] + n_e * sigma
+ * (the rounding above); 2: out[i] receives the raw Philox word of element e (bit pattern, for tests) */
+int gode_param_noise(float* out, int64_t n, uint64_t seed, uint32_t noise_stream, uint32_t noise_step, int64_t noise_off,
+                     float sigma, int32_t accumulate, void* stream);
+
 /* out[i] = a[i]*alpha (+ out[i] if accumulate); small utility for gradient bucket handling */
 int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulate, void* stream);
 
@@ -426,14 +464,15 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
 enum { GODE_OP_IGEMM = 1, GODE_OP_WGRAD = 2, GODE_OP_BN_FINALIZE = 3, GODE_OP_BN_BWD = 4, GODE_OP_ODE_FWD = 5,
        GODE_OP_ODE_BWD = 6, GODE_OP_BCE = 7, GODE_OP_ADAM = 8, GODE_OP_PACK = 9, GODE_OP_ODERNN_FWD = 10,
        GODE_OP_ODERNN_BWD = 11, GODE_OP_BN_APPLY = 12, GODE_OP_COL2IM = 13, GODE_OP_SDE_FWD = 14,
-       GODE_OP_SDE_BWD = 15, GODE_OP_CDE_FWD = 16, GODE_OP_CDE_BWD = 17 };
+       GODE_OP_SDE_BWD = 15, GODE_OP_CDE_FWD = 16, GODE_OP_CDE_BWD = 17, GODE_OP_WGAN = 18 };
 typedef struct gode_pack_op {
   gode_conv_geom g; int32_t dir, co_canon; const float* w; float* wpack; const int32_t* co_perm;
 } gode_pack_op;
 int gode_run(const int32_t* kinds, const void* const* ops, int32_t n, void* stream);
 
 int gode_version(void);
-/* size of every op struct as compiled, so the ctypes mirror can assert it matches (index = GODE_OP_*) */
+/* size of every op struct as compiled, so the ctypes mirror can assert it matches (index = GODE_OP_*; -1: the
+ * gode_adam_noise_tensor table record) */
 int gode_sizeof(int kind);
 
 #ifdef __cplusplus

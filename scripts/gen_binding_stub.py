@@ -63,7 +63,7 @@ KIND_STRUCT = {"GODE_OP_IGEMM": "gode_igemm_op", "GODE_OP_WGRAD": "gode_wgrad_op
                "GODE_OP_ODERNN_BWD": "gode_odernn_bwd_op", "GODE_OP_BN_APPLY": "gode_bn_apply_op",
                "GODE_OP_COL2IM": "gode_col2im_op", "GODE_OP_SDE_FWD": "gode_sde_fwd_op",
                "GODE_OP_SDE_BWD": "gode_sde_bwd_op", "GODE_OP_CDE_FWD": "gode_cde_fwd_op",
-               "GODE_OP_CDE_BWD": "gode_cde_bwd_op"}
+               "GODE_OP_CDE_BWD": "gode_cde_bwd_op", "GODE_OP_WGAN": "gode_wgan_op"}
 
 
 def generate():
@@ -86,7 +86,7 @@ def generate():
             row += item + ", "
         rows.append(row.rstrip(", ") + "]")
         lines += rows + [""]
-    lines.append("KINDS = {0: gode_conv_geom, " + ", ".join(f"{v}: {KIND_STRUCT[k]}" for k, v in kinds) + "}")
+    lines.append("KINDS = {0: gode_conv_geom, -1: gode_adam_noise_tensor, " + ", ".join(f"{v}: {KIND_STRUCT[k]}" for k, v in kinds) + "}")
     lines += ["", "",
               "def load(path=\"gan-ode_amd/lib/libgode.so\"):",
               "    lib = C.CDLL(path)",
@@ -94,7 +94,8 @@ def generate():
               "    for kind, st in KINDS.items():            # the mirror must match the compiled ABI, field for field",
               "        assert lib.gode_sizeof(kind) == C.sizeof(st), (kind, st.__name__)",
               "    for fn in (\"gode_igemm\", \"gode_wgrad\", \"gode_bn_finalize\", \"gode_bn_bwd\", \"gode_bn_apply\", \"gode_col2im\", \"gode_ode_fwd\",",
-              "               \"gode_ode_bwd\", \"gode_odernn_fwd\", \"gode_odernn_bwd\", \"gode_bce_logits\", \"gode_adam_l2\"):",
+              "               \"gode_ode_bwd\", \"gode_odernn_fwd\", \"gode_odernn_bwd\", \"gode_bce_logits\", \"gode_wgan_logits\",",
+              "               \"gode_adam_l2\"):",
               "        getattr(lib, fn).argtypes = [ptr, ptr]          # (const op struct*, hipStream_t)",
               "        getattr(lib, fn).restype = C.c_int              # 0 ok, <0 GODE_E_*, >0 hipError_t",
               "    return lib"]
