@@ -6,7 +6,7 @@ anything does, and there is no fallback path.
 """
 from . import _lib
 from .modules import (CDEFunc, Noise, ODEFunc, PatchImageDiscriminator, SDEFunc, VideoDiscriminator, VideoGenerator,
-                      VideoGeneratorCDE, VideoGeneratorMNIST, VideoGeneratorMNISTODE, VideoGeneratorMNISTODERNN,
+                      VideoGeneratorCDE, VideoGeneratorGRU, VideoGeneratorMNIST, VideoGeneratorMNISTODE, VideoGeneratorMNISTODERNN,
                       VideoGeneratorSDE)
 from .train import (FusedAdam, GanTrainer, WassersteinDiscriminatorLoss, WassersteinGeneratorLoss, bce_with_logits_const,
                     bce_with_logits_halves, bce_with_logits_pair, build_mnist, build_ucf, freeze_host_gc, host_cpu_quota,
@@ -14,7 +14,7 @@ from .train import (FusedAdam, GanTrainer, WassersteinDiscriminatorLoss, Wassers
                     wasserstein_discriminator_loss_halves, wasserstein_generator_loss, wasserstein_generator_loss_pair)
 
 __all__ = ["Noise", "ODEFunc", "PatchImageDiscriminator", "VideoDiscriminator", "VideoGenerator",
-           "VideoGeneratorMNIST", "VideoGeneratorMNISTODE", "VideoGeneratorMNISTODERNN", "SDEFunc", "VideoGeneratorSDE", "CDEFunc", "VideoGeneratorCDE", "FusedAdam", "GanTrainer", "bce_with_logits_const",
+           "VideoGeneratorMNIST", "VideoGeneratorMNISTODE", "VideoGeneratorMNISTODERNN", "SDEFunc", "VideoGeneratorSDE", "CDEFunc", "VideoGeneratorCDE", "VideoGeneratorGRU", "FusedAdam", "GanTrainer", "bce_with_logits_const",
            "bce_with_logits_pair", "bce_with_logits_halves", "WassersteinGeneratorLoss", "WassersteinDiscriminatorLoss",
            "wasserstein_generator_loss", "wasserstein_generator_loss_pair", "wasserstein_discriminator_loss",
            "wasserstein_discriminator_loss_halves", "unit_grad", "build_mnist", "build_ucf", "train_step", "host_cpu_quota", "limit_host_threads", "freeze_host_gc", "_lib"]

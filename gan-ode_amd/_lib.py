@@ -18,12 +18,14 @@ OP_ODERNN_FWD, OP_ODERNN_BWD, OP_BN_APPLY, OP_COL2IM = 10, 11, 12, 13
 OP_SDE_FWD, OP_SDE_BWD = 14, 15
 OP_CDE_FWD, OP_CDE_BWD = 16, 17
 OP_WGAN = 18
+OP_GRU_FWD, OP_GRU_BWD = 19, 20
 REC_ADAM_NOISE = -1          # gode_sizeof index of the gode_adam_noise_tensor table record
 ODE_NPARAM = 2672
 ODERNN_NPARAM = 2176
 SDE_NPARAM = 3216
 CDE_NPARAM = 7536
 CDE_MAX_N = 4096
+GRU_NPARAM = 1632
 
 
 class ConvGeom(C.Structure):
@@ -139,6 +141,22 @@ class CdeBwdOp(C.Structure):
     KIND = OP_CDE_BWD
 
 
+class GruParams(C.Structure):
+    _fields_ = [(n, ptr) for n in "Wih Whh bih bhh".split()]
+
+
+class GruFwdOp(C.Structure):
+    _fields_ = [("p", GruParams), ("noise", ptr), ("content", ptr), ("sel_t", ptr), ("z", ptr), ("hs", ptr), ("N", i32),
+                ("T", i32), ("zcols", i32), ("pad_", i32)]
+    KIND = OP_GRU_FWD
+
+
+class GruBwdOp(C.Structure):
+    _fields_ = [("p", GruParams), ("noise", ptr), ("hs", ptr), ("sel_t", ptr), ("gz", ptr), ("work", ptr), ("grads", ptr),
+                ("N", i32), ("T", i32), ("accumulate", i32), ("zcols", i32)]
+    KIND = OP_GRU_BWD
+
+
 class BnApplyOp(C.Structure):
     _fields_ = [("y", ptr), ("out", ptr), ("scale", ptr), ("shift", ptr), ("M", i64), ("C", i32), ("act", i32),
                 ("M0", i64)]
@@ -181,13 +199,14 @@ _STRUCTS = {0: ConvGeom, OP_IGEMM: IgemmOp, OP_WGRAD: WgradOp, OP_BN_FINALIZE: B
             OP_ODE_FWD: OdeFwdOp, OP_ODE_BWD: OdeBwdOp, OP_BCE: BceOp, OP_ADAM: AdamOp, OP_PACK: PackOp,
             OP_ODERNN_FWD: OdeRnnFwdOp, OP_ODERNN_BWD: OdeRnnBwdOp, OP_BN_APPLY: BnApplyOp, OP_COL2IM: Col2imOp,
             OP_SDE_FWD: SdeFwdOp, OP_SDE_BWD: SdeBwdOp, OP_CDE_FWD: CdeFwdOp, OP_CDE_BWD: CdeBwdOp, OP_WGAN: WganOp,
-            REC_ADAM_NOISE: AdamNoiseTensor}
+            OP_GRU_FWD: GruFwdOp, OP_GRU_BWD: GruBwdOp, REC_ADAM_NOISE: AdamNoiseTensor}
 
 EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "gode_igemm_stats_segments", "gode_igemm_model_cycles", "gode_igemm_work_size", "gode_pack_size", "gode_pack_weights", "gode_wgrad",
            "gode_wgrad_work_size", "gode_wgrad_auto_splits", "gode_bn_finalize", "gode_bn_bwd",
            "gode_bn_bwd_work_size", "gode_bn_apply", "gode_col2im", "gode_ode_fwd", "gode_ode_bwd", "gode_ode_fwd_multi", "gode_ode_bwd_multi", "gode_ode_bwd_work_size", "gode_odernn_fwd",
            "gode_odernn_bwd", "gode_odernn_bwd_work_size", "gode_odernn_sync_size", "gode_odernn_fwd_multi",
-           "gode_odernn_bwd_multi", "gode_sde_fwd", "gode_sde_bwd", "gode_sde_bwd_work_size", "gode_cde_fwd", "gode_cde_bwd", "gode_cde_sync_size", "gode_cde_state_size", "gode_cde_bwd_work_size", "gode_bce_logits",
+           "gode_odernn_bwd_multi", "gode_sde_fwd", "gode_sde_bwd", "gode_sde_bwd_work_size", "gode_cde_fwd", "gode_cde_bwd", "gode_cde_sync_size", "gode_cde_state_size", "gode_cde_bwd_work_size", "gode_gru_fwd", "gode_gru_bwd", "gode_gru_fwd_multi",
+           "gode_gru_bwd_multi", "gode_gru_bwd_work_size", "gode_bce_logits",
            "gode_wgan_logits", "gode_adam_l2", "gode_adam_multi", "gode_adam_multi_dev", "gode_adam_noise_multi",
            "gode_adam_noise_multi_dev", "gode_param_noise", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
 
@@ -212,7 +231,8 @@ def lib():
             raise RuntimeError(f"ABI mismatch for op kind {kind}: C {L.gode_sizeof(kind)} != ctypes {C.sizeof(st)}")
     for name in ("gode_igemm", "gode_wgrad", "gode_bn_finalize", "gode_bn_bwd", "gode_ode_fwd", "gode_ode_bwd",
                  "gode_bce_logits", "gode_adam_l2", "gode_odernn_fwd", "gode_odernn_bwd", "gode_bn_apply", "gode_col2im",
-                 "gode_sde_fwd", "gode_sde_bwd", "gode_cde_fwd", "gode_cde_bwd", "gode_wgan_logits"):
+                 "gode_sde_fwd", "gode_sde_bwd", "gode_cde_fwd", "gode_cde_bwd", "gode_wgan_logits", "gode_gru_fwd",
+                 "gode_gru_bwd"):
         getattr(L, name).argtypes = [ptr, ptr]
         getattr(L, name).restype = C.c_int
     L.gode_igemm_stats_rows.argtypes = [ptr]
@@ -247,6 +267,10 @@ def lib():
     L.gode_ode_bwd_multi.argtypes = [ptr, i32, ptr]
     L.gode_odernn_fwd_multi.argtypes = [ptr, i32, ptr]
     L.gode_odernn_bwd_multi.argtypes = [ptr, i32, ptr]
+    L.gode_gru_fwd_multi.argtypes = [ptr, i32, ptr]
+    L.gode_gru_bwd_multi.argtypes = [ptr, i32, ptr]
+    L.gode_gru_bwd_work_size.argtypes = [i32]
+    L.gode_gru_bwd_work_size.restype = i64
     L.gode_scale.argtypes = [ptr, ptr, i64, f32, C.c_int, ptr]
     L.gode_adam_multi.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, f32, i32, ptr]
     L.gode_adam_multi_dev.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, ptr, ptr]
@@ -320,5 +344,5 @@ def _run_one(op, stream):
           OP_ADAM: "gode_adam_l2", OP_ODERNN_FWD: "gode_odernn_fwd", OP_ODERNN_BWD: "gode_odernn_bwd",
           OP_BN_APPLY: "gode_bn_apply", OP_COL2IM: "gode_col2im", OP_SDE_FWD: "gode_sde_fwd",
           OP_SDE_BWD: "gode_sde_bwd", OP_CDE_FWD: "gode_cde_fwd", OP_CDE_BWD: "gode_cde_bwd",
-          OP_WGAN: "gode_wgan_logits"}[op.KIND]
+          OP_WGAN: "gode_wgan_logits", OP_GRU_FWD: "gode_gru_fwd", OP_GRU_BWD: "gode_gru_bwd"}[op.KIND]
     check(getattr(lib(), fn)(C.byref(op), stream), fn)

@@ -1152,6 +1152,183 @@ class VideoGeneratorMNISTODERNN(VideoGeneratorMNIST):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# GRU motion latent: the original MoCoGAN generator (models/mocogan.py:185-301)
+# ------------------------------------------------------------------------------------------------------------------
+class _GruGenPlan(_GenPlan):
+    """GRU latent (gode_gru_fwd/bwd) + decoder.  x_host carries the noise stack [T+1, n, 16] (h_0, e_0 .. e_{T-1})."""
+
+    def __init__(self, gen, n_traj, T, select, zbuf=None):
+        super().__init__(gen, n_traj, T, select, zbuf=zbuf)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.noise = self.x        # [T+1, n, 16], staged by the base class
+        self.hs = torch.empty(n_traj, T + 1, 16, **f32)                  # every h_t, kept for the backward
+        self.gru_work = torch.empty(L.lib().gode_gru_bwd_work_size(n_traj), **f32)
+
+    @staticmethod
+    def _x_shape(n_traj, T):
+        return (T + 1, n_traj, 16)
+
+    def _gru_params(self):
+        r = self.gen.recurrent
+        return (r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh)
+
+    def _programs(self):
+        ptrs = tuple(dptr(p) for p in self._gru_params())
+        if ptrs != self._ode_ptrs:
+            self._ode_ptrs = ptrs
+            op = L.GruParams(*ptrs)
+            zbuf = self.stack.x_in if self.stack is not None else self._zbuf
+            self.fwd_op = L.GruFwdOp(p=op, noise=dptr(self.noise), content=dptr(self.content), sel_t=dptr(self.sel),
+                                     z=dptr(zbuf), hs=dptr(self.hs), N=self.n, T=self.T, zcols=Z_COLS)
+            self.bwd_op = L.GruBwdOp(p=op, noise=dptr(self.noise), hs=dptr(self.hs), sel_t=dptr(self.sel), gz=None,
+                                     work=dptr(self.gru_work), grads=None, N=self.n, T=self.T, accumulate=0, zcols=Z_COLS)
+            self.fwd_prog = L.Program([self.fwd_op])
+
+    def latent_backward(self, gz_ptr, arena, keep):
+        self.bwd_op.gz = gz_ptr
+        if arena is not None:
+            # the 1632 GRU gradients go straight into the trainer's arena: the four tensors are its tail, contiguous in
+            # the kernel's output order (VideoGeneratorGRU._arena_tail)
+            tgt = [arena.target(q) for q in self._gru_params()]       # (every tensor: marks its .grad as written)
+            base, acc = tgt[0]
+            self.bwd_op.grads = base.data_ptr()
+            self.bwd_op.accumulate = 1 if acc else 0
+            batch = getattr(self.gen, "_adjoint_batch", None)
+            if batch is not None:
+                # video + image path of the G step: their BPTT passes go out as ONE launch (VideoGeneratorGRU.flush_adjoints)
+                batch["ops"].append(self.bwd_op)
+                batch["keep"].append(keep)
+                if len(batch["ops"]) >= batch["expect"]:
+                    self.gen.flush_adjoints()
+            else:
+                L.run_one(self.bwd_op, stream_ptr())
+            return None
+        grads = torch.empty(L.GRU_NPARAM, dtype=torch.float32, device=self.device)
+        self.bwd_op.grads = grads.data_ptr()
+        self.bwd_op.accumulate = 0
+        L.run_one(self.bwd_op, stream_ptr())
+        return [grads[o:o + n].view(shp) for o, n, shp in _GRU_GRAD_OFFS]
+
+
+_GRU_GRAD_OFFS = [(0, 768, (48, 16)), (768, 768, (48, 16)), (1536, 48, (48,)), (1584, 48, (48,))]
+
+
+class _GruLatentFn(torch.autograd.Function):
+    """VideoGeneratorGRU.sample_z_m as its own autograd node: gode_gru_fwd alone (latent rows [N*T, 16], row n*T + t =
+    h_{t+1}), backward = gode_gru_bwd (BPTT)."""
+
+    @staticmethod
+    def forward(ctx, gen, noise_host, n, T, *params):
+        dev = gen.main[0].weight.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        noise = noise_host.to(dev)                                    # [T+1, n, 16]: h_0, e_0 .. e_{T-1}
+        hs = torch.empty(n, T + 1, 16, **f32)
+        z = torch.empty(n * T, 16, **f32)
+        prm = L.GruParams(*[dptr(p) for p in params])
+        fop = L.GruFwdOp(p=prm, noise=dptr(noise), content=None, sel_t=None, z=dptr(z), hs=dptr(hs), N=n, T=T, zcols=16)
+        L.run_one(fop, stream_ptr())
+        ctx.keep = (noise, hs, n, T, [p.detach() for p in params])
+        return z
+
+    @staticmethod
+    def backward(ctx, gout):
+        noise, hs, n, T, params = ctx.keep
+        dev = noise.device
+        g = gout.contiguous()
+        grads = torch.empty(L.GRU_NPARAM, dtype=torch.float32, device=dev)
+        work = torch.empty(L.lib().gode_gru_bwd_work_size(n), dtype=torch.float32, device=dev)
+        prm = L.GruParams(*[dptr(p) for p in params])
+        bop = L.GruBwdOp(p=prm, noise=dptr(noise), hs=dptr(hs), sel_t=None, gz=dptr(g), work=dptr(work),
+                         grads=dptr(grads), N=n, T=T, accumulate=0, zcols=16)
+        L.run_one(bop, stream_ptr())
+        return (None, None, None, None, *[grads[o:o + k].view(shp) for o, k, shp in _GRU_GRAD_OFFS])
+
+
+class VideoGeneratorGRU(VideoGenerator):
+    """The original MoCoGAN generator (models/mocogan.py:185-301; `from models.mocogan import VideoGenerator` resolves
+    here): the motion latent is a GRUCell(16, 16) driven by fresh noise every frame, h_{t+1} = GRUCell(e_t, h_t), latent
+    row n*T + t = h_{t+1}; the 64x64 decoder is the one the UCF ODE generator inherits.  The module holds exactly
+    `recurrent` and `main`, built in the reference's order (same seeded weights and state_dict).
+    Deviation: h_0 and the e_t are drawn on the global torch CPU generator in the reference's order (content (NumPy),
+    then h_0, e_0 .. e_{T-1}, each a FloatTensor(n, 16).normal_()) and copied to the device; the reference draws them on
+    the device generator on a GPU (models/mocogan.py:297-301), which cannot be reproduced bit for bit."""
+
+    _plan_cls = _GruGenPlan
+    _gode_graph_capture = False     # GanTrainer(graph=True) refuses this generator (not captured / verified)
+
+    def __init__(self, n_channels, dim_z_content, dim_z_category, dim_z_motion, video_length, ngf=64):
+        if dim_z_category != 0:
+            raise NotImplementedError("categorical latents are not implemented (dim_z_category=0: no reference script "
+                                      "uses them)")
+        if dim_z_motion != 16 or dim_z_content != 50:
+            raise NotImplementedError("libgode's fused GRU kernels are specialised for dim_z_motion=16, "
+                                      "dim_z_content=50 (the reference scripts' latent sizes)")
+        super().__init__(n_channels, dim_z_content, dim_z_category, dim_z_motion, video_length, ngf=ngf)
+
+    def _init_ode_parts(self, ode_fn, dim_hidden, linear, dim_z, ngf):
+        pass                        # recurrent + main only, as the reference's class
+
+    def _param_list(self):
+        dec = []
+        for p in self._decoder_params():
+            dec.append(p.weight)
+            if p.gamma is not None:
+                dec += [p.gamma, p.beta]
+        r = self.recurrent
+        return dec, [r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh]
+
+    def _draw(self, num_samples, video_len):
+        """content (NumPy) first, then h_0 and one e_t per frame (models/mocogan.py:252,297-301) as ONE normal_() over
+        the reused [T+1, n, 16] host stack: torch's CPU normal_ draws the uniforms in order and transforms them in blocks
+        of 16, so with rows of n*16 values this is bitwise the T+1 separate FloatTensor(n, 16).normal_() calls of the
+        reference (tests/test_host_gru.py pins it) for a third of the host time -- sample_images draws n*T*2 trajectories."""
+        content = np.random.normal(0, 1, (num_samples, self.dim_z_content)).astype(np.float32)
+        key = (num_samples, video_len)
+        buf = self.__dict__.setdefault("_noise_bufs", {}).get(key)
+        if buf is None:
+            buf = self._noise_bufs[key] = torch.empty(video_len + 1, num_samples, self.dim_z_motion)
+        buf.normal_()
+        return torch.from_numpy(content), buf
+
+    _take_trajectories = staticmethod(VideoGeneratorMNISTODERNN._take_trajectories)
+
+    def _draw_motion(self, num_samples, T):
+        """h_0 and one e_t per frame -> [T+1, n, 16] (see _draw)"""
+        return torch.empty(T + 1, num_samples, self.dim_z_motion).normal_()
+
+    def _launch_latents(self, plans):
+        """All prefetched GRU chains in one launch (<= 8 per launch)."""
+        st = stream_ptr()
+        for k in range(0, len(plans), 8):
+            chunk = plans[k:k + 8]
+            arr = (L.GruFwdOp * len(chunk))(*[p.fwd_op for p in chunk])
+            L.call("gru_fwd_multi", lambda: L.check(L.lib().gode_gru_fwd_multi(arr, len(chunk), st), "gode_gru_fwd_multi"))
+
+    def flush_adjoints(self):
+        """Launch the BPTT passes collected during a backward pass (the video and the image path of the G step)."""
+        batch = getattr(self, "_adjoint_batch", None)
+        if not batch or not batch["ops"]:
+            return
+        ops = batch["ops"]
+        st = stream_ptr()
+        for k in range(0, len(ops), 8):
+            chunk = ops[k:k + 8]
+            arr = (L.GruBwdOp * len(chunk))(*chunk)
+            L.call("gru_bwd_multi", lambda: L.check(L.lib().gode_gru_bwd_multi(arr, len(chunk), st), "gode_gru_bwd_multi"))
+        batch["ops"], batch["keep"] = [], []
+
+    def sample_z_m(self, num_samples, video_len=None):
+        """models/mocogan.py:217-229 -> [N*T, 16], row n*T + t = h_{t+1}: one gode_gru_fwd launch, differentiable
+        (gode_gru_bwd).  sample_videos()/sample_images() fuse the same launch with the content broadcast and the decoder;
+        this method is the reference's public surface (and what the inherited sample_z_video calls)."""
+        T = video_len if video_len is not None else self.video_length
+        _require_gpu(self.main[0].weight, type(self).__name__)
+        noise = self._draw_motion(num_samples, T)
+        _, rnn = self._param_list()
+        return _GruLatentFn.apply(self, noise, num_samples, T, *rnn)
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Neural-SDE motion latent (models/mocogan_sde.py)
 # ------------------------------------------------------------------------------------------------------------------
 class SDEFunc(nn.Module):

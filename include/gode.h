@@ -395,6 +395,42 @@ int64_t gode_cde_bwd_work_size(int32_t N);
 #define GODE_CDE_NPARAM 7536
 #define GODE_CDE_MAX_N 4096
 
+/* ---- GRU motion latent (models/mocogan.py:217-229: MoCoGAN's VideoGenerator.sample_z_m) ---------------------------
+ * h_0 ~ N(0,1); for t < T: h_{t+1} = GRUCell(e_t, h_t) (torch's definition, gate order r, z, n); latent row t = h_{t+1}.
+ * noise[T+1][N][16] = h_0, e_0..e_{T-1} drawn on the host.  z / content / sel_t / zcols as in gode_ode_fwd (content NULL:
+ * only the 16 motion columns of each row are written, zcols >= 16).  hs[N][T+1][16] (nullable) keeps every h_t for the
+ * backward.  Trajectories are independent: any N >= 1, T >= 1. */
+typedef struct gode_gru_params {
+  const float* Wih; const float* Whh; const float* bih; const float* bhh;   /* GRUCell(16,16): [48,16]x2, [48]x2 */
+} gode_gru_params;
+typedef struct gode_gru_fwd_op {
+  gode_gru_params p;
+  const float* noise; const float* content; const int32_t* sel_t;
+  float* z; float* hs;
+  int32_t N, T, zcols, pad_;
+} gode_gru_fwd_op;
+int gode_gru_fwd(const gode_gru_fwd_op* op, void* stream);
+/* `count` (<= 8) independent chains in ONE launch (one training iteration's prefetched latents; ops: HOST array) */
+int gode_gru_fwd_multi(const gode_gru_fwd_op* ops, int32_t count, void* stream);
+/* backward: backpropagation through time from gz[rows][zcols] (the decoder's input gradient, full or sel_t rows as in
+ * gode_ode_bwd; 16 motion columns read), gates recomputed from hs and noise.  No gradient for the noise.  The parameter
+ * sums are reduced in fixed order (trajectories within a workgroup, then workgroups in order through work, >=
+ * gode_gru_bwd_work_size(N) floats, one buffer per op) and written (accumulate != 0: added) to
+ * grads[GODE_GRU_NPARAM] = Wih, Whh, bih, bhh; nothing outside it is touched. */
+typedef struct gode_gru_bwd_op {
+  gode_gru_params p;
+  const float* noise; const float* hs; const int32_t* sel_t; const float* gz;
+  float* work; float* grads;
+  int32_t N, T, accumulate, zcols;
+} gode_gru_bwd_op;
+int gode_gru_bwd(const gode_gru_bwd_op* op, void* stream);
+int64_t gode_gru_bwd_work_size(int32_t N);
+/* the BPTT of `count` (<= 8) chains (the video and the image path of one generator step) in one launch; ops sharing a
+ * grads pointer are applied in array order, each op's rows reduced into its own partial first and stored / added under
+ * its own accumulate flag: bit-identical to the same ops launched one by one */
+int gode_gru_bwd_multi(const gode_gru_bwd_op* ops, int32_t count, void* stream);
+#define GODE_GRU_NPARAM 1632
+
 /* ---- loss and optimiser (mnist_moco_ode.py:86-89) ------------------------------------------------------------
  * BCE-with-logits, mean reduced, constant target: loss (+)= mean(max(x,0) - x*t + log1p(exp(-|x|))) and
  * g[i] = gscale*(sigmoid(x[i]) - t)/n.  loss is one device float; accumulate!=0 adds to it. */
@@ -464,7 +500,8 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
 enum { GODE_OP_IGEMM = 1, GODE_OP_WGRAD = 2, GODE_OP_BN_FINALIZE = 3, GODE_OP_BN_BWD = 4, GODE_OP_ODE_FWD = 5,
        GODE_OP_ODE_BWD = 6, GODE_OP_BCE = 7, GODE_OP_ADAM = 8, GODE_OP_PACK = 9, GODE_OP_ODERNN_FWD = 10,
        GODE_OP_ODERNN_BWD = 11, GODE_OP_BN_APPLY = 12, GODE_OP_COL2IM = 13, GODE_OP_SDE_FWD = 14,
-       GODE_OP_SDE_BWD = 15, GODE_OP_CDE_FWD = 16, GODE_OP_CDE_BWD = 17, GODE_OP_WGAN = 18 };
+       GODE_OP_SDE_BWD = 15, GODE_OP_CDE_FWD = 16, GODE_OP_CDE_BWD = 17, GODE_OP_WGAN = 18,
+       GODE_OP_GRU_FWD = 19, GODE_OP_GRU_BWD = 20 };
 typedef struct gode_pack_op {
   gode_conv_geom g; int32_t dir, co_canon; const float* w; float* wpack; const int32_t* co_perm;
 } gode_pack_op;
