@@ -19,6 +19,7 @@ OP_SDE_FWD, OP_SDE_BWD = 14, 15
 OP_CDE_FWD, OP_CDE_BWD = 16, 17
 OP_WGAN = 18
 OP_GRU_FWD, OP_GRU_BWD = 19, 20
+OP_DNOISE = 21
 REC_ADAM_NOISE = -1          # gode_sizeof index of the gode_adam_noise_tensor table record
 ODE_NPARAM = 2672
 ODERNN_NPARAM = 2176
@@ -163,6 +164,13 @@ class BnApplyOp(C.Structure):
     KIND = OP_BN_APPLY
 
 
+class DnoiseOp(C.Structure):
+    _fields_ = [("x", ptr), ("out", ptr), ("scale", ptr), ("shift", ptr), ("call_dev", ptr), ("M", i64), ("C", i32),
+                ("act", i32), ("M0", i64), ("e_off", i64), ("xs", i64 * 5), ("N", i32), ("D", i32), ("H", i32), ("W", i32),
+                ("seed", i64), ("stream", i32), ("layer", i32), ("call", i32), ("sigma", f32)]
+    KIND = OP_DNOISE
+
+
 class Col2imOp(C.Structure):
     _fields_ = [("cols", ptr), ("out", ptr)] + [(n, i32) for n in "N Hi Wi Ho Wo C kh kw sh sw ph pw epilogue pad_ Di Do kd sd pd pad2_".split()]
     KIND = OP_COL2IM
@@ -199,7 +207,7 @@ _STRUCTS = {0: ConvGeom, OP_IGEMM: IgemmOp, OP_WGRAD: WgradOp, OP_BN_FINALIZE: B
             OP_ODE_FWD: OdeFwdOp, OP_ODE_BWD: OdeBwdOp, OP_BCE: BceOp, OP_ADAM: AdamOp, OP_PACK: PackOp,
             OP_ODERNN_FWD: OdeRnnFwdOp, OP_ODERNN_BWD: OdeRnnBwdOp, OP_BN_APPLY: BnApplyOp, OP_COL2IM: Col2imOp,
             OP_SDE_FWD: SdeFwdOp, OP_SDE_BWD: SdeBwdOp, OP_CDE_FWD: CdeFwdOp, OP_CDE_BWD: CdeBwdOp, OP_WGAN: WganOp,
-            OP_GRU_FWD: GruFwdOp, OP_GRU_BWD: GruBwdOp, REC_ADAM_NOISE: AdamNoiseTensor}
+            OP_GRU_FWD: GruFwdOp, OP_GRU_BWD: GruBwdOp, OP_DNOISE: DnoiseOp, REC_ADAM_NOISE: AdamNoiseTensor}
 
 EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "gode_igemm_stats_segments", "gode_igemm_model_cycles", "gode_igemm_work_size", "gode_pack_size", "gode_pack_weights", "gode_wgrad",
            "gode_wgrad_work_size", "gode_wgrad_auto_splits", "gode_bn_finalize", "gode_bn_bwd",
@@ -208,7 +216,7 @@ EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "god
            "gode_odernn_bwd_multi", "gode_sde_fwd", "gode_sde_bwd", "gode_sde_bwd_work_size", "gode_cde_fwd", "gode_cde_bwd", "gode_cde_sync_size", "gode_cde_state_size", "gode_cde_bwd_work_size", "gode_gru_fwd", "gode_gru_bwd", "gode_gru_fwd_multi",
            "gode_gru_bwd_multi", "gode_gru_bwd_work_size", "gode_bce_logits",
            "gode_wgan_logits", "gode_adam_l2", "gode_adam_multi", "gode_adam_multi_dev", "gode_adam_noise_multi",
-           "gode_adam_noise_multi_dev", "gode_param_noise", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
+           "gode_adam_noise_multi_dev", "gode_param_noise", "gode_dnoise", "gode_dnoise_normals", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
 
 _lib = None
 
@@ -232,7 +240,7 @@ def lib():
     for name in ("gode_igemm", "gode_wgrad", "gode_bn_finalize", "gode_bn_bwd", "gode_ode_fwd", "gode_ode_bwd",
                  "gode_bce_logits", "gode_adam_l2", "gode_odernn_fwd", "gode_odernn_bwd", "gode_bn_apply", "gode_col2im",
                  "gode_sde_fwd", "gode_sde_bwd", "gode_cde_fwd", "gode_cde_bwd", "gode_wgan_logits", "gode_gru_fwd",
-                 "gode_gru_bwd"):
+                 "gode_gru_bwd", "gode_dnoise"):
         getattr(L, name).argtypes = [ptr, ptr]
         getattr(L, name).restype = C.c_int
     L.gode_igemm_stats_rows.argtypes = [ptr]
@@ -278,6 +286,7 @@ def lib():
     L.gode_adam_noise_multi.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, f32, i32, u64, u32, u32, f32, ptr]
     L.gode_adam_noise_multi_dev.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, ptr, u64, u32, f32, ptr]
     L.gode_param_noise.argtypes = [ptr, i64, u64, u32, u32, i64, f32, i32, ptr]
+    L.gode_dnoise_normals.argtypes = [ptr, i64, u64, u32, u32, u32, i64, i32, ptr]
     L.gode_run.argtypes = [ptr, ptr, i32, ptr]
     _lib = L
     return L
@@ -344,5 +353,6 @@ def _run_one(op, stream):
           OP_ADAM: "gode_adam_l2", OP_ODERNN_FWD: "gode_odernn_fwd", OP_ODERNN_BWD: "gode_odernn_bwd",
           OP_BN_APPLY: "gode_bn_apply", OP_COL2IM: "gode_col2im", OP_SDE_FWD: "gode_sde_fwd",
           OP_SDE_BWD: "gode_sde_bwd", OP_CDE_FWD: "gode_cde_fwd", OP_CDE_BWD: "gode_cde_bwd",
-          OP_WGAN: "gode_wgan_logits", OP_GRU_FWD: "gode_gru_fwd", OP_GRU_BWD: "gode_gru_bwd"}[op.KIND]
+          OP_WGAN: "gode_wgan_logits", OP_GRU_FWD: "gode_gru_fwd", OP_GRU_BWD: "gode_gru_bwd",
+          OP_DNOISE: "gode_dnoise"}[op.KIND]
     check(getattr(lib(), fn)(C.byref(op), stream), fn)

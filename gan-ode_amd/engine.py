@@ -46,6 +46,7 @@ class LayerSpec:
     has_bn: bool
     epilogue: int = L.EPI_RAW    # only the last layer: tanh
     co_perm: Optional[torch.Tensor] = None  # int32 device tensor (generator layer 0)
+    noise: bool = False          # instance noise on this layer's INPUT (Noise(use_noise=True) in front of the conv)
 
     def out_dims(self):
         g = self.geom
@@ -113,6 +114,12 @@ class ConvStack:
                                                      or specs[0].geom.N % 2)):
             raise ValueError("grouped ConvStack: two groups, Conv stack, caller-owned input, no BatchNorm on layer 0")
         self.nl = len(specs)
+        # instance noise (LayerSpec.noise): the GEMM and the weight gradient of a noised layer read a noisy copy of its input
+        # -- layer 0: a plan-owned channels-last copy of the caller's tensor; layer l >= 1: the activated copy a[l-1], which
+        # is then always materialised.  BatchNorm / activation backward keep reading the raw y[l-1] (gode_dnoise_op).
+        self.noisy = any(s.noise for s in specs)
+        if self.noisy and (owns_input or self.split):
+            raise ValueError("instance noise: caller-owned input, no split stack")
         self.momentum, self.eps = momentum, eps
         self.busy = False
         self.generation = 0      # bumped by every forward; an autograd node checks it before using the plan's buffers
@@ -123,6 +130,7 @@ class ConvStack:
         lib = L.lib()
         f32 = dict(dtype=torch.float32, device=device)
         self.x_in = torch.zeros(specs[0].in_dims(), **f32) if owns_input else None
+        self.x0n = torch.empty(specs[0].in_dims(), **f32) if specs[0].noise else None
         # raw outputs of all but the last layer are plan-owned; the last is allocated per call
         self.y = [torch.empty(s.out_dims(), **f32) for s in specs[:-1]]
         # activated copies a[l] = act(BN(y[l])) for layers whose consumer is a heavy GEMM (see gode_bn_apply)
@@ -224,6 +232,8 @@ class ConvStack:
         """Materialise act(BN(y[l])) when the consuming layer l+1 is a heavy vector-path GEMM."""
         if l + 1 >= len(self.specs):
             return False
+        if self.specs[l + 1].noise:
+            return True
         prod, cons = self.specs[l], self.specs[l + 1]
         C_out = prod.out_dims()[4]
         g = cons.geom
@@ -272,7 +282,7 @@ class ConvStack:
     def _in_src(self, l):
         """Tensor the consumer layer l reads (activated copy if materialised, else the raw producer output)."""
         if l == 0:
-            return self.x_in
+            return self.x0n if self.x0n is not None else self.x_in
         return self.a[l - 1] if self.a[l - 1] is not None else self.y[l - 1]
 
     def _in_xform(self, l):
@@ -346,6 +356,17 @@ class ConvStack:
         patch = {}
         lib = L.lib()
         G2 = self.groups == 2
+        noise = patch["noise"] = []      # [(DnoiseOp, elements per sample, call offset, caller input index or None)]
+        if self.x0n is not None:
+            # layer 0: the noisy channels-last copy of each caller tensor (the second group's draws call + 1)
+            n0, d0, h0, w0, c0 = self.specs[0].in_dims()
+            ng = 2 if G2 else 1
+            per = d0 * h0 * w0 * c0
+            for k in range(ng):
+                op = L.DnoiseOp(x=None, out=self.x0n.data_ptr() + 4 * k * (n0 // ng) * per, M=(n0 // ng) * d0 * h0 * w0,
+                                C=c0, act=L.ACT_NONE, N=n0 // ng, D=d0, H=h0, W=w0, layer=0)
+                noise.append((op, per, k, k))
+                ops.append(op)
         for l, (s, p) in enumerate(zip(self.specs, self.params)):
             packs.append((l, s.fwd_dir, L.PackOp(g=s.geom, dir=s.fwd_dir, co_canon=0, w=dptr(p.weight),
                                                  wpack=dptr(self.wpack_f[l]), co_perm=dptr(s.co_perm))))
@@ -357,15 +378,19 @@ class ConvStack:
                 half = self.y[0].numel() // 2
                 pair = []
                 for k in range(2):
-                    o = L.IgemmOp(g=hg, dir=s.fwd_dir, act=act, epilogue=s.epilogue, tile=0, src=None,
+                    o = L.IgemmOp(g=hg, dir=s.fwd_dir, act=act, epilogue=s.epilogue, tile=0,
+                                  src=None if self.x0n is None else self.x0n.data_ptr() + 4 * (self.x0n.numel() // 2) * k,
                                   wpack=dptr(self.wpack_f[l]), out=self.y[0].data_ptr() + 4 * half * k)
                     pair.append(o)
                     ops.append(o)
                 patch["first"], patch["first2"] = pair
                 if self.a[0] is not None:          # activated copy for a heavy consumer (no BatchNorm on layer 0)
                     d = s.out_dims()
-                    ops.append(L.BnApplyOp(y=dptr(self.y[0]), out=dptr(self.a[0]), scale=None, shift=None,
-                                           M=d[0] * d[1] * d[2] * d[3], C=d[4], act=s.act))
+                    if self.specs[1].noise:
+                        ops.append(self._noise_op(noise, 0, None, None, M0=d[0] * d[1] * d[2] * d[3] // 2))
+                    else:
+                        ops.append(L.BnApplyOp(y=dptr(self.y[0]), out=dptr(self.a[0]), scale=None, shift=None,
+                                               M=d[0] * d[1] * d[2] * d[3], C=d[4], act=s.act))
                 continue
             hg = self._head_as_gemm(l)
             if hg is not None:
@@ -454,14 +479,44 @@ class ConvStack:
                 d = s.out_dims()
                 M = d[0] * d[1] * d[2] * d[3]
                 M0 = M // 2 if (G2 and s.has_bn) else ((M // d[0]) * self.split if (self.split and s.has_bn) else 0)
+                if self.specs[l + 1].noise:
+                    # (a paired pass draws the second group's noise with call + 1 whether or not the layer has BatchNorm)
+                    ops.append(self._noise_op(noise, l, dptr(self.scale[l]), dptr(self.shift[l]), M // 2 if G2 else 0))
+                    continue
                 ops.append(L.BnApplyOp(y=dptr(self.y[l]), out=dptr(self.a[l]), scale=dptr(self.scale[l]),
                                        shift=dptr(self.shift[l]), M=M, C=d[4], act=s.act, M0=M0))
         patch["packs"] = packs
         self._attach_work([op for op in ops if isinstance(op, L.IgemmOp)])
         return L.Program(ops), patch
 
+    def _noise_op(self, noise, l, scale, shift, M0):
+        """act(BN(y[l])) + noise -> a[l], the input of the noised layer l + 1 (registered in the program's noise list)."""
+        d = self.specs[l].out_dims()
+        op = L.DnoiseOp(x=dptr(self.y[l]), out=dptr(self.a[l]), scale=scale, shift=shift, M=d[0] * d[1] * d[2] * d[3],
+                        C=d[4], act=self.specs[l].act, M0=M0, layer=l + 1)
+        noise.append((op, d[1] * d[2] * d[3] * d[4], 0, None))
+        return op
+
+    @staticmethod
+    def _patch_noise(patch, noise, inputs):
+        """noise: dict(seed, stream, sigma, call, call_dev, sample_offset) -- see modules._DiscBase._noise_args."""
+        seed = int(noise["seed"]) & 0xFFFFFFFFFFFFFFFF
+        seed = seed - (1 << 64) if seed >= 1 << 63 else seed
+        dev = noise.get("call_dev")
+        base = 0 if dev else int(noise["call"])
+        for op, per, add, k in patch["noise"]:
+            op.seed, op.stream, op.sigma = seed, int(noise["stream"]), float(noise["sigma"])
+            c = (base + add) & 0xFFFFFFFF                 # (a uint32 in an int32 field)
+            op.call_dev, op.call = dev, c - (1 << 32) if c >= 1 << 31 else c
+            op.e_off = int(noise.get("sample_offset", 0)) * per
+            if k is not None:
+                x, xs = inputs[k]
+                op.x = x.data_ptr()
+                for i in range(5):
+                    op.xs[i] = int(xs[i])
+
     def forward(self, training: bool, x: Optional[torch.Tensor] = None, x_strides=None, pre_ops_program=None,
-                x2: Optional[torch.Tensor] = None, x2_strides=None):
+                x2: Optional[torch.Tensor] = None, x2_strides=None, noise=None):
         """Runs the stack.  x (+ element strides {N,D,H,W,C}) is required when the plan does not own its input; a
         grouped stack takes the second group's tensor as x2.  Returns the freshly allocated last-layer output
         [N,D,H,W,C] (grouped: N = both groups, first group first)."""
@@ -469,23 +524,29 @@ class ConvStack:
         if training not in self._fwd:
             self._fwd[training] = self._build_fwd(training)
         prog, patch = self._fwd[training]
+        if self.noisy:
+            if noise is None:
+                raise RuntimeError("this plan applies instance noise: forward() needs its noise arguments")
+            self._patch_noise(patch, noise, [(x, x_strides), (x2, x2_strides)])
         out = torch.empty(self.out_dims, dtype=torch.float32, device=self.device)
         patch["last"].out = out.data_ptr()
         if "last2" in patch:
             patch["last2"][0].out = out.data_ptr() + patch["last2"][1]
-        if self.x_in is None:
+        if self.x_in is None and self.x0n is None:
             first = patch["first"]
             first.src = x.data_ptr()
             for i in range(5):
                 first.gs[i] = int(x_strides[i])
+        if self.x_in is None:
             # aliases WITHOUT autograd history: the plan must not keep the caller's graph (or, below, its own autograd
             # node, which holds the plan's lease) alive
             self._x_user, self._x_strides = x.detach(), tuple(int(v) for v in x_strides)
             if self.groups == 2:
-                second = patch["first2"]
-                second.src = x2.data_ptr()
-                for i in range(5):
-                    second.gs[i] = int(x2_strides[i])
+                if self.x0n is None:
+                    second = patch["first2"]
+                    second.src = x2.data_ptr()
+                    for i in range(5):
+                        second.gs[i] = int(x2_strides[i])
                 self._x2_user, self._x2_strides = x2.detach(), tuple(int(v) for v in x2_strides)
         st = stream_ptr()
         self._run_stale_packs(patch["packs"], st)
@@ -538,7 +599,8 @@ class ConvStack:
                 half = self.g[0].numel() // 2
                 pair = []
                 for k in range(2):
-                    pair.append(L.WgradOp(g=hg, act=act, xform_on_y=0, splits=0, accumulate=0, x=None,
+                    pair.append(L.WgradOp(g=hg, act=act, xform_on_y=0, splits=0, accumulate=0,
+                                          x=None if self.x0n is None else self.x0n.data_ptr() + 4 * (self.x0n.numel() // 2) * k,
                                           y=self.g[0].data_ptr() + 4 * half * k, scale=dptr(sc), shift=dptr(sh)))
                 if need_param_grad:
                     for k, wk in enumerate(pair):
@@ -697,7 +759,7 @@ class ConvStack:
         main.wait_stream(side)
 
     def _patch_user_input(self, patch):
-        if self.x_in is None and "wgrad0" in patch:
+        if self.x_in is None and self.x0n is None and "wgrad0" in patch:
             if self.specs[0].fwd_dir != L.FPROP:
                 raise RuntimeError("caller-owned input is only supported for Conv (FPROP) stacks")
             srcs = [(patch["wgrad0"], self._x_user, self._x_strides)]

@@ -12,6 +12,7 @@ through the HIP kernels and raises if the tensors are not on the GPU or libgode.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import numpy as np
@@ -1838,23 +1839,60 @@ class VideoGeneratorCDE(VideoGeneratorMNIST):
 # ==================================================================================================================
 # discriminators
 # ==================================================================================================================
+def _noise_sigma(use_noise, sigma):
+    """The reference takes any sigma and fails deep in forward (None * tensor); here a bad one is refused up front."""
+    if not use_noise:
+        return sigma
+    if sigma is None or isinstance(sigma, bool):
+        raise ValueError(f"use_noise=True needs a finite noise sigma >= 0, got {sigma!r}")
+    try:
+        s = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"use_noise=True needs a finite noise sigma >= 0, got {sigma!r}") from None
+    if not math.isfinite(s) or s < 0.0:
+        raise ValueError(f"use_noise=True needs a finite noise sigma >= 0, got {sigma!r}")
+    return s
+
+
+def dnoise_normals(n, seed, stream, layer, call, offset=0, device="cuda", raw=False):
+    """The instance-noise stream of gode.h alone: z of elements [offset, offset + n) for (seed, stream,
+    layer, call) as a float32 device tensor (raw=True: the Philox words, as int32)."""
+    out = torch.empty(int(n), dtype=torch.float32, device=device)
+    L.check(L.lib().gode_dnoise_normals(out.data_ptr(), int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(layer),
+                                        int(call) & 0xFFFFFFFF, int(offset), 1 if raw else 0, stream_ptr()),
+            "gode_dnoise_normals")
+    return out.view(torch.int32) if raw else out
+
+
 class Noise(nn.Module):
-    """Identity when use_noise is False, which is always the case in stage 3 (models/mocogan.py:20-29)."""
+    """models/mocogan.py:20-29: x + sigma * N(0, 1) when use_noise (train and eval mode alike, gradient the identity), else
+    the identity.  The discriminators never call these modules: their plans apply the noise (gode_dnoise_op).  A standalone
+    Noise(True, sigma) on a device tensor draws from the same stream with its own seed (torch.initial_seed() at
+    construction), stream 0, layer 0 and call counter, over the tensor's channels-last element order."""
 
     def __init__(self, use_noise, sigma=0.2):
         super().__init__()
-        if use_noise:
-            raise NotImplementedError("use_noise=True is never used by the stage-3 scripts")
-        self.use_noise, self.sigma = use_noise, sigma
+        self.use_noise, self.sigma = use_noise, _noise_sigma(use_noise, sigma)
+        self.noise_seed, self.noise_stream, self.noise_call = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, 0, 0
 
     def forward(self, x):
-        return x
+        if not self.use_noise:
+            return x
+        _require_gpu(x, "Noise input")
+        if x.dtype != torch.float32 or x.dim() < 2:
+            raise RuntimeError("Noise: fp32 input [N, C, ...] expected")
+        perm = (0,) + tuple(range(2, x.dim())) + (1,)
+        shape = tuple(x.shape[i] for i in perm)
+        z = dnoise_normals(x.numel(), self.noise_seed, self.noise_stream, 0, self.noise_call, device=x.device)
+        self.noise_call += 1
+        inv = [perm.index(i) for i in range(x.dim())]
+        return x + z.view(shape).permute(*inv) * self.sigma      # fp32(x + fp32(sigma * z)): two roundings, as gode.h
 
 
 class _DiscFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, plan, strides, training, keep, arena, x, *params):
-        out = plan.forward(training, x=x, x_strides=strides)
+    def forward(ctx, plan, strides, training, keep, arena, noise, x, *params):
+        out = plan.forward(training, x=x, x_strides=strides, noise=noise)
         plan.busy = keep
         ctx.plan = plan
         ctx.lease = _Lease(plan)
@@ -1866,8 +1904,8 @@ class _DiscFn(torch.autograd.Function):
     def backward(ctx, gout):
         plan = ctx.plan
         ctx.lease.check("discriminator")
-        need_x = ctx.needs_input_grad[5]
-        need_p = any(ctx.needs_input_grad[6:])
+        need_x = ctx.needs_input_grad[6]
+        need_p = any(ctx.needs_input_grad[7:])
         arena = ctx.arena
         into = None
         if need_p and arena is not None and arena.active:
@@ -1882,19 +1920,19 @@ class _DiscFn(torch.autograd.Function):
         flat, views, g_in = plan.backward(gout, need_input_grad=need_x, need_param_grad=need_p, into=into)
         grads = []
         if into is not None:
-            grads = [None] * (len(ctx.needs_input_grad) - 6)
+            grads = [None] * (len(ctx.needs_input_grad) - 7)
         elif need_p:
             for wv, gv, bv in views:
                 grads.append(wv)
                 if gv is not None:
                     grads += [gv, bv]
         else:
-            grads = [None] * (len(ctx.needs_input_grad) - 6)
+            grads = [None] * (len(ctx.needs_input_grad) - 7)
         gx = None
         if need_x:
             g = g_in                                       # [N, D, H, W, C] channels-last, allocated for this call
             gx = g.permute(0, 4, 1, 2, 3) if len(ctx.x_shape) == 5 else g.squeeze(1).permute(0, 3, 1, 2)
-        return (None, None, None, None, None, gx, *grads)
+        return (None, None, None, None, None, None, gx, *grads)
 
 
 class _DiscPairFn(torch.autograd.Function):
@@ -1902,8 +1940,8 @@ class _DiscPairFn(torch.autograd.Function):
     statistics: returns the joint raw output [2B, Do, Ho, Wo, 1]."""
 
     @staticmethod
-    def forward(ctx, plan, strides1, strides2, training, keep, arena, x1, x2, *params):
-        out = plan.forward(training, x=x1, x_strides=strides1, x2=x2, x2_strides=strides2)
+    def forward(ctx, plan, strides1, strides2, training, keep, arena, noise, x1, x2, *params):
+        out = plan.forward(training, x=x1, x_strides=strides1, x2=x2, x2_strides=strides2, noise=noise)
         plan.busy = keep
         ctx.plan = plan
         ctx.lease = _Lease(plan)
@@ -1914,11 +1952,11 @@ class _DiscPairFn(torch.autograd.Function):
     def backward(ctx, gout):
         plan = ctx.plan
         ctx.lease.check("discriminator (paired pass)")
-        if ctx.needs_input_grad[6] or ctx.needs_input_grad[7]:
+        if ctx.needs_input_grad[7] or ctx.needs_input_grad[8]:
             raise NotImplementedError("the paired discriminator pass is for discriminator updates (detached inputs)")
-        need_p = any(ctx.needs_input_grad[8:])
+        need_p = any(ctx.needs_input_grad[9:])
         arena = ctx.arena
-        nparams = len(ctx.needs_input_grad) - 8
+        nparams = len(ctx.needs_input_grad) - 9
         into = None
         if need_p and arena is not None and arena.active:
             into = []
@@ -1937,7 +1975,7 @@ class _DiscPairFn(torch.autograd.Function):
                 grads.append(wv)
                 if gv is not None:
                     grads += [gv, bv]
-        return (None, None, None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, None, None, *grads)
 
 
 class _DiscBase(nn.Module):
@@ -1949,6 +1987,37 @@ class _DiscBase(nn.Module):
 
     def _specs(self, x_shape):
         raise NotImplementedError
+
+    # -- instance noise -------------------------------------------------------------------------------
+    # Plain attributes, not buffers: the state_dict keys stay the reference's.  noise_seed / noise_stream pick the stream,
+    # _noise_call counts the reference's forward calls (forward: one, forward_pair_joint: two), _noise_sample_offset is the
+    # first global sample of the batch this module sees (data-parallel ranks, virtual-replica shards: GanTrainer sets it).
+    NOISED_LAYERS = ()
+
+    def _init_noise(self, use_noise, noise_sigma, stream):
+        self.use_noise = bool(use_noise)
+        self.noise_sigma = _noise_sigma(use_noise, noise_sigma)
+        self.noise_seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
+        self.noise_stream = stream
+        self._noise_call, self._noise_sample_offset = 0, 0
+
+    def _noise_active(self):
+        """sigma 0 adds exact zeros: the plan then stays the noise-free one (the call counter still advances)."""
+        return self.use_noise and self.noise_sigma > 0.0
+
+    def _noise_args(self, ncalls):
+        """This call's noise arguments (forward: ncalls 1, forward_pair_joint: 2); advances the call counter.  Inside a graph
+        capture the base call is read from the HostFeed, which rewrites it before every replay."""
+        if not self.use_noise:
+            return None
+        call = self._noise_call
+        self._noise_call = (call + ncalls) & 0xFFFFFFFF
+        if not self._noise_active():
+            return None
+        feed = getattr(self, "_feed", None)
+        dev = feed.dnoise_slot(self, call, ncalls) if (feed is not None and feed.recording) else None
+        return dict(seed=self.noise_seed, stream=self.noise_stream, sigma=self.noise_sigma, call=call, call_dev=dev,
+                    sample_offset=self._noise_sample_offset)
 
     def _layer_params(self):
         out = []
@@ -1984,7 +2053,7 @@ class _DiscBase(nn.Module):
             strides = (x.stride(0), x.stride(2), x.stride(3), x.stride(4), x.stride(1))
         else:
             strides = (x.stride(0), 0, x.stride(2), x.stride(3), x.stride(1))
-        key = tuple(x.shape)
+        key = tuple(x.shape) + (("noise",) if self._noise_active() else ())
         plan = self._pool.get(key, lambda: ConvStack(self._specs(x.shape), self._layer_params(),
                                                      self.main[1].weight.device, owns_input=False,
                                                      pack_cache=self._pool.pack_cache, two_lane_backward=self.two_lane_backward))
@@ -1994,7 +2063,8 @@ class _DiscBase(nn.Module):
             if p.gamma is not None:
                 params += [p.gamma, p.beta]
         keep = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-        out = _DiscFn.apply(plan, strides, self.training, keep, getattr(self, "_gode_arena", None), x, *params)      # [B, Do, Ho, Wo, 1]
+        noise = self._noise_args(1)
+        out = _DiscFn.apply(plan, strides, self.training, keep, getattr(self, "_gode_arena", None), noise, x, *params)      # [B, Do, Ho, Wo, 1]
         h = out.permute(0, 4, 1, 2, 3)
         if input.dim() == 4:
             h = h.squeeze(2)       # (a squeeze, not h[:, :, 0]: select's backward allocates a zero tensor and copies)
@@ -2023,7 +2093,7 @@ class _DiscBase(nn.Module):
         if first.requires_grad or second.requires_grad:
             raise RuntimeError("paired pass: inputs must be detached (it is the discriminator-update pass)")
         joint_shape = (2 * first.shape[0],) + tuple(first.shape[1:])
-        key = ("pair",) + tuple(first.shape)
+        key = ("pair",) + tuple(first.shape) + (("noise",) if self._noise_active() else ())
         plan = self._pool.get(key, lambda: ConvStack(self._specs(joint_shape), self._layer_params(),
                                                      self.main[1].weight.device, owns_input=False,
                                                      pack_cache=self._pool.pack_cache, groups=2,
@@ -2034,8 +2104,9 @@ class _DiscBase(nn.Module):
             if p.gamma is not None:
                 params += [p.gamma, p.beta]
         keep = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        noise = self._noise_args(2)
         return _DiscPairFn.apply(plan, self._strides5(first), self._strides5(second), self.training, keep,
-                                 getattr(self, "_gode_arena", None), first, second, *params)
+                                 getattr(self, "_gode_arena", None), noise, first, second, *params)
 
     def forward_pair(self, first, second):
         """-> ((logits_first, None), (logits_second, None)) with forward()'s shapes."""
@@ -2053,9 +2124,12 @@ class _DiscBase(nn.Module):
 class PatchImageDiscriminator(_DiscBase):
     """models/mocogan.py:66-93: Conv2d k4 s2 p1 x4 (C->ndf->2ndf->4ndf->1), BN on layers 2-3, LeakyReLU(0.2)."""
 
+    NOISED_LAYERS = (0, 1, 2, 3)        # every convolution's input, the head's included (models/mocogan.py:72-89)
+
     def __init__(self, n_channels, ndf=64, use_noise=False, noise_sigma=None):
         super().__init__()
-        self.use_noise, self.n_channels, self.ndf = use_noise, n_channels, ndf
+        self._init_noise(use_noise, noise_sigma, stream=2)
+        self.n_channels, self.ndf = n_channels, ndf
         self.main = nn.Sequential(
             Noise(use_noise, sigma=noise_sigma), nn.Conv2d(n_channels, ndf, 4, 2, 1, bias=False),
             nn.LeakyReLU(0.2, inplace=True),
@@ -2074,7 +2148,8 @@ class PatchImageDiscriminator(_DiscBase):
         for i in range(4):
             Ho, Wo = conv_out(H, 4, 2, 1), conv_out(W, 4, 2, 1)
             specs.append(LayerSpec(make_geom(B, chans[i], chans[i + 1], (1, H, W), (1, Ho, Wo), (1, 4, 4), (1, 2, 2),
-                                             (0, 1, 1)), L.FPROP, L.ACT_LRELU if i < 3 else L.ACT_NONE, i in (1, 2)))
+                                             (0, 1, 1)), L.FPROP, L.ACT_LRELU if i < 3 else L.ACT_NONE, i in (1, 2),
+                                   noise=self._noise_active() and i in self.NOISED_LAYERS))
             H, W = Ho, Wo
         return specs
 
@@ -2082,12 +2157,15 @@ class PatchImageDiscriminator(_DiscBase):
 class VideoDiscriminator(_DiscBase):
     """models/mocogan.py:129-164: Conv3d ksize^3, stride (1,2,2), pad (0,1,1) x4 + a final ksize^3 s1 p0 conv."""
 
+    NOISED_LAYERS = (0, 1, 2, 3)        # the final ndf*8 -> 1 convolution has no Noise in front (models/mocogan.py:138-159)
+
     def __init__(self, n_channels, n_output_neurons=1, bn_use_gamma=True, use_noise=False, noise_sigma=None, ndf=64,
                  ksize=4):
         super().__init__()
         if n_output_neurons != 1:
             raise NotImplementedError("n_output_neurons != 1 is only used by the categorical discriminator")
-        self.n_channels, self.n_output_neurons, self.use_noise = n_channels, n_output_neurons, use_noise
+        self._init_noise(use_noise, noise_sigma, stream=1)
+        self.n_channels, self.n_output_neurons = n_channels, n_output_neurons
         self.bn_use_gamma, self.ndf, self.ksize = bn_use_gamma, ndf, ksize
         st, pd = (1, 2, 2), (0, 1, 1)
         self.main = nn.Sequential(
@@ -2110,7 +2188,8 @@ class VideoDiscriminator(_DiscBase):
         for i in range(4):
             Do, Ho, Wo = conv_out(D, k, 1, 0), conv_out(H, k, 2, 1), conv_out(W, k, 2, 1)
             specs.append(LayerSpec(make_geom(B, chans[i], chans[i + 1], (D, H, W), (Do, Ho, Wo), (k, k, k), (1, 2, 2),
-                                             (0, 1, 1)), L.FPROP, L.ACT_LRELU, i > 0))
+                                             (0, 1, 1)), L.FPROP, L.ACT_LRELU, i > 0,
+                                   noise=self._noise_active() and i in self.NOISED_LAYERS))
             D, H, W = Do, Ho, Wo
         Do, Ho, Wo = conv_out(D, k, 1, 0), conv_out(H, k, 1, 0), conv_out(W, k, 1, 0)
         specs.append(LayerSpec(make_geom(B, chans[4], 1, (D, H, W), (Do, Ho, Wo), (k, k, k), (1, 1, 1), (0, 0, 0)),

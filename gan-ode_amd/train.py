@@ -563,6 +563,15 @@ class HostFeed:
             self.pinned[self.parity][off:off + 4].view(torch.int32)[2] = int(noise_step)
         return self.dev[off:off + 2].data_ptr()
 
+    def dnoise_slot(self, model, call, ncalls):
+        """A discriminator's instance-noise call index (raw 32 bits) for one captured forward; every replay writes the
+        module's current counter and advances it by the forward's `ncalls`, as an eager forward does."""
+        assert self.recording
+        off = self._reserve(1)
+        self.script.append(("dnoise", model, off, ncalls))
+        self.pinned[self.parity][off:off + 4].view(torch.int32)[0] = int(call) - (1 << 32) if call >= 1 << 31 else int(call)
+        return self.dev[off:off + 1].data_ptr()
+
     # -- replay ----------------------------------------------------------------------------------------------------
     def begin(self):
         """Next pinned buffer (waits until the upload that last used it has been consumed)."""
@@ -578,6 +587,11 @@ class HostFeed:
             if ent[0] == "noise":
                 _, gen, select, num_samples, T, off, nfloats = ent
                 gen._fill_host_inputs(buf[off:off + nfloats], select, num_samples, T)
+            elif ent[0] == "dnoise":
+                _, model, off, ncalls = ent
+                call = model._noise_call
+                buf[off:off + 4].view(torch.int32)[0] = call - (1 << 32) if call >= 1 << 31 else call
+                model._noise_call = (call + ncalls) & 0xFFFFFFFF
             else:
                 _, opt, gi, lr, b1, b2, off, noisy = ent
                 opt.advance_steps(gi)
@@ -679,16 +693,18 @@ class GradArena:
 # ------------------------------------------------------------------------------------------------------------------
 # the iteration
 # ------------------------------------------------------------------------------------------------------------------
-def build_mnist(ngf=64, ndf=64):
-    """The three networks of mnist_moco_ode.py:75-78."""
-    return VideoGeneratorMNISTODE(1, 50, 0, 16, 16, ngf=ngf), VideoDiscriminator(1, ksize=2, ndf=ndf), \
-        PatchImageDiscriminator(1, ndf=ndf)
+def build_mnist(ngf=64, ndf=64, use_noise=False, noise_sigma=None):
+    """The three networks of mnist_moco_ode.py:75-78 (use_noise / noise_sigma: the discriminators' instance noise)."""
+    return VideoGeneratorMNISTODE(1, 50, 0, 16, 16, ngf=ngf), \
+        VideoDiscriminator(1, ksize=2, ndf=ndf, use_noise=use_noise, noise_sigma=noise_sigma), \
+        PatchImageDiscriminator(1, ndf=ndf, use_noise=use_noise, noise_sigma=noise_sigma)
 
 
-def build_ucf(ngf=64, ndf=64):
+def build_ucf(ngf=64, ndf=64, use_noise=False, noise_sigma=None):
     """ucf_moco_ode.py:77-80 with dim_hidden=16 (the shipped call omits it and raises)."""
-    return VideoGenerator(3, 50, 0, 16, 16, dim_hidden=16, ngf=ngf), VideoDiscriminator(3, ndf=ndf), \
-        PatchImageDiscriminator(3, ndf=ndf)
+    return VideoGenerator(3, 50, 0, 16, 16, dim_hidden=16, ngf=ngf), \
+        VideoDiscriminator(3, ndf=ndf, use_noise=use_noise, noise_sigma=noise_sigma), \
+        PatchImageDiscriminator(3, ndf=ndf, use_noise=use_noise, noise_sigma=noise_sigma)
 
 
 def _shards(x):
@@ -717,6 +733,20 @@ class GanTrainer:
             raise ValueError(f"GanTrainer(loss=...) must be 'bce' or 'wasserstein', got {loss!r}")
         self.loss = loss
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0
+        # discriminator instance noise (VideoDiscriminator / PatchImageDiscriminator(use_noise=True)): noise_seed, when given,
+        # keys both discriminators' streams (default: each module's torch.initial_seed() at construction).  Replicas take
+        # rank 0's seeds; each replica and virtual-replica shard draws the noise of its own samples (_noise_shard).
+        dnoise = [m for m in (dis_vid, dis_img) if getattr(m, "use_noise", False)]
+        if noise_seed is not None:
+            for m in dnoise:
+                m.noise_seed = int(noise_seed) & 0xFFFFFFFFFFFFFFFF
+        if dnoise and self.world > 1 and sync_replicas:
+            dev = next(gen.parameters()).device
+            t = torch.tensor([[m.noise_seed & 0xFFFFFFFF, m.noise_seed >> 32] for m in dnoise], dtype=torch.int64, device=dev)
+            dist.broadcast(t, src=0, group=process_group)
+            for m, (lo, hi) in zip(dnoise, t.tolist()):
+                m.noise_seed = int(lo) | (int(hi) << 32)
         # param_noise > 0: add_noise(model.parameters(), param_noise) after every optimiser step (mnist_moco_ode_noise.py
         # sigma 1e-5, mnist_moco_ode_wgan.py 1e-4), fused into the Adam launch; streams gen 0, dis_vid 1, dis_img 2 of
         # noise_seed (default torch.initial_seed(): nothing is drawn from the CPU generator, whose stream feeds the latent
@@ -922,6 +952,13 @@ class GanTrainer:
             return losses[0]
         return torch.stack(losses).mean()
 
+    def _noise_shard(self, model, k, B, nsh, call0):
+        """Instance noise of shard k of nsh (batch B each): the shards of one step share the call index call0 and draw the
+        noise of their own samples -- the offset is the shard's first sample in the global batch."""
+        if getattr(model, "use_noise", False):
+            model._noise_call = call0
+            model._noise_sample_offset = (self.rank * nsh + k) * B
+
     def d_image_step(self, real_img, _join=True, _defer=False, _pair_videos=0):
         """mnist_moco_ode.py:115-131.  real_img: [B,C,H,W], or a list of such shards (virtual replicas).
         _pair_videos (step() only): the batch size of the d_video_step that follows -- its fake videos are generated here,
@@ -936,8 +973,10 @@ class GanTrainer:
         with on_side():
             self._begin(self.dis_img, self.img_opt)
         losses = []
-        for x in shards:
+        call0 = getattr(self.dis_img, "_noise_call", 0)
+        for k, x in enumerate(shards):
             B = x.shape[0]
+            self._noise_shard(self.dis_img, k, B, len(shards), call0)
             if not self.pair_d:
                 with on_side():
                     pr, _ = self.dis_img(x)
@@ -979,8 +1018,10 @@ class GanTrainer:
         shards = _shards(real_vid)
         losses = []
         begun = False
-        for x in shards:
+        call0 = getattr(self.dis_vid, "_noise_call", 0)
+        for k, x in enumerate(shards):
             B = x.shape[0]
+            self._noise_shard(self.dis_vid, k, B, len(shards), call0)
             real = x.transpose(1, 2)                            # [B,T,C,H,W] -> [B,C,T,H,W] view, read in place
             if not self.pair_d and not begun:
                 self._begin(self.dis_vid, self.vid_opt)
@@ -1032,7 +1073,10 @@ class GanTrainer:
         early_ar = self.world > 1 and self.overlap_ar and id(self.gen) in self.arenas
         try:
             joint = shards == 1 and self._can_pair(B, B, False)
-            for _ in range(shards):
+            calls0 = [getattr(m, "_noise_call", 0) for m in (self.dis_vid, self.dis_img)]
+            for k in range(shards):
+                for m, c0 in zip((self.dis_vid, self.dis_img), calls0):
+                    self._noise_shard(m, k, B, shards, c0)
                 if joint:          # both calls' rows in one decoder pass (two BatchNorm batches)
                     (fake_vid, _), (fake_img, _) = self.gen.sample_pair(B, B)
                 else:
@@ -1176,6 +1220,7 @@ class GanTrainer:
             m.invalidate_packs()
         feed = self._feed = HostFeed(dev)
         self.gen._feed = feed
+        self.dis_vid._feed = self.dis_img._feed = feed      # (instance noise: the call index of every captured forward)
         for o in (self.gen_opt, self.vid_opt, self.img_opt):
             o._feed = feed
         graph = torch.cuda.CUDAGraph()

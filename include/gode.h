@@ -493,6 +493,35 @@ int gode_adam_noise_multi_dev(const gode_adam_noise_tensor* table, int32_t count
 int gode_param_noise(float* out, int64_t n, uint64_t seed, uint32_t noise_stream, uint32_t noise_step, int64_t noise_off,
                      float sigma, int32_t accumulate, void* stream);
 
+/* ---- discriminator instance noise (Noise(use_noise=True, sigma) of models/mocogan.py:20-29: x + sigma * N(0, 1) in front of
+ * the discriminators' convolutions, train and eval mode alike) ----------------------------------------------------------
+ * The stream: element e of a noised tensor is its flat channels-last index ([N][D][H][W][C], C fastest) plus e_off (the
+ * shard's first global sample times D*H*W*C).  It takes lane e & 3 of Philox4x32-10 with key (seed lo, seed hi) and counter
+ * (q low word, call, 0x80000000 | stream << 8 | layer, q high word), q = e >> 2; uniforms and Box-Muller as the parameter
+ * noise above (the tag bit keeps the two families of streams disjoint).  The noisy value is fp32(a + fp32(sigma * z)), no
+ * FMA, where a is bit for bit what the noise-free path feeds the convolution.
+ * Two modes, one struct:
+ *  - gather (N > 0, layer 0): x is the caller's [N][D][H][W][C] tensor read through element strides xs {N, D, H, W, C};
+ *    out[N*D*H*W][C] receives the channels-last noisy copy (a = x);
+ *  - apply (N == 0, layers >= 1): x is a raw output y[M][C] (C % 4 == 0); a = act(y * scale[c] + shift[c]) exactly as
+ *    gode_bn_apply (scale == NULL: act(y)); M0 > 0: rows >= M0 are the second group of a paired pass -- scale + C /
+ *    shift + C, call + 1, and e restarts at e_off.
+ * call = (call_dev ? call_dev[0] : 0) + call: a launch captured in a graph reads its base call from device memory, which
+ * the host rewrites before every replay.  stream < 2^23, layer < 256. */
+typedef struct gode_dnoise_op {
+  const float* x; float* out; const float* scale; const float* shift; const int32_t* call_dev;
+  int64_t M; int32_t C, act;
+  int64_t M0, e_off;
+  int64_t xs[5];
+  int32_t N, D, H, W;
+  int64_t seed;
+  int32_t stream, layer, call; float sigma;
+} gode_dnoise_op;
+int gode_dnoise(const gode_dnoise_op* op, void* stream);
+/* the stream alone: out[i] = z of element e_off + i for i < n (raw != 0: the raw Philox word of that element, bit pattern) */
+int gode_dnoise_normals(float* out, int64_t n, uint64_t seed, uint32_t noise_stream, uint32_t layer, uint32_t call,
+                        int64_t e_off, int32_t raw, void* stream);
+
 /* out[i] = a[i]*alpha (+ out[i] if accumulate); small utility for gradient bucket handling */
 int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulate, void* stream);
 
@@ -501,7 +530,7 @@ enum { GODE_OP_IGEMM = 1, GODE_OP_WGRAD = 2, GODE_OP_BN_FINALIZE = 3, GODE_OP_BN
        GODE_OP_ODE_BWD = 6, GODE_OP_BCE = 7, GODE_OP_ADAM = 8, GODE_OP_PACK = 9, GODE_OP_ODERNN_FWD = 10,
        GODE_OP_ODERNN_BWD = 11, GODE_OP_BN_APPLY = 12, GODE_OP_COL2IM = 13, GODE_OP_SDE_FWD = 14,
        GODE_OP_SDE_BWD = 15, GODE_OP_CDE_FWD = 16, GODE_OP_CDE_BWD = 17, GODE_OP_WGAN = 18,
-       GODE_OP_GRU_FWD = 19, GODE_OP_GRU_BWD = 20 };
+       GODE_OP_GRU_FWD = 19, GODE_OP_GRU_BWD = 20, GODE_OP_DNOISE = 21 };
 typedef struct gode_pack_op {
   gode_conv_geom g; int32_t dir, co_canon; const float* w; float* wpack; const int32_t* co_perm;
 } gode_pack_op;
