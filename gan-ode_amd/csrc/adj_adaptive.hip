@@ -16,13 +16,9 @@
 // images are combined through LDS for the norm, and only accepted steps are added to the state.
 #include <stdlib.h>
 #include "ode_common.h"
+#include "dopri5.h"
 
 #define ADJ_BLOCK 64
-#define TH_W1 0
-#define TH_B1 256
-#define TH_W2 272
-#define TH_B2 528
-#define TH_N 544
 
 struct Th { f32x4 W1, W2, b1, b2; };   // one wave's share: W* in MFMA D layout (lane (j, g) reg r = [4g + r][j]), b* per lane
 __device__ __forceinline__ Th th_zero() { return Th{zero4(), zero4(), zero4(), zero4()}; }
@@ -169,29 +165,29 @@ struct AdjSolver {
       const float dt = (float)dtd;
       f32x4 k2y, k2a, k3y, k3a, k4y, k4a, k5y, k5a, k6y, k6a, k7y, k7a;
       Th X, S = th_zero(), E = th_zero(), M = th_zero(), X7;
-      th_axpy(S, 35.f / 384.f, X1); th_axpy(E, 35.f / 384.f - 1951.f / 21600.f, X1); th_axpy(M, 6025192743.f / 30085553152.f / 2.f, X1);
-      eval(y0 + dt * (0.2f * k1y), a0 + dt * (0.2f * k1a), k2y, k2a, X, false);      // stage 2 has zero weight in S, E, M
-      eval(y0 + dt * ((3.f / 40.f) * k1y + (9.f / 40.f) * k2y), a0 + dt * ((3.f / 40.f) * k1a + (9.f / 40.f) * k2a), k3y, k3a, X, true);
-      th_axpy(S, 500.f / 1113.f, X); th_axpy(E, 500.f / 1113.f - 22642.f / 50085.f, X); th_axpy(M, 51252292925.f / 65400821598.f / 2.f, X);
-      eval(y0 + dt * ((44.f / 45.f) * k1y + (-56.f / 15.f) * k2y + (32.f / 9.f) * k3y),
-           a0 + dt * ((44.f / 45.f) * k1a + (-56.f / 15.f) * k2a + (32.f / 9.f) * k3a), k4y, k4a, X, true);
-      th_axpy(S, 125.f / 192.f, X); th_axpy(E, 125.f / 192.f - 451.f / 720.f, X); th_axpy(M, -2691868925.f / 45128329728.f / 2.f, X);
-      eval(y0 + dt * ((19372.f / 6561.f) * k1y + (-25360.f / 2187.f) * k2y + (64448.f / 6561.f) * k3y + (-212.f / 729.f) * k4y),
-           a0 + dt * ((19372.f / 6561.f) * k1a + (-25360.f / 2187.f) * k2a + (64448.f / 6561.f) * k3a + (-212.f / 729.f) * k4a),
+      th_axpy(S, DP5_B1, X1); th_axpy(E, DP5_E1, X1); th_axpy(M, DP5_C1, X1);
+      eval(y0 + dt * (DP5_A21 * k1y), a0 + dt * (DP5_A21 * k1a), k2y, k2a, X, false);      // stage 2 has zero weight in S, E, M
+      eval(y0 + dt * (DP5_A31 * k1y + DP5_A32 * k2y), a0 + dt * (DP5_A31 * k1a + DP5_A32 * k2a), k3y, k3a, X, true);
+      th_axpy(S, DP5_B3, X); th_axpy(E, DP5_E3, X); th_axpy(M, DP5_C3, X);
+      eval(y0 + dt * (DP5_A41 * k1y + DP5_A42 * k2y + DP5_A43 * k3y),
+           a0 + dt * (DP5_A41 * k1a + DP5_A42 * k2a + DP5_A43 * k3a), k4y, k4a, X, true);
+      th_axpy(S, DP5_B4, X); th_axpy(E, DP5_E4, X); th_axpy(M, DP5_C4, X);
+      eval(y0 + dt * (DP5_A51 * k1y + DP5_A52 * k2y + DP5_A53 * k3y + DP5_A54 * k4y),
+           a0 + dt * (DP5_A51 * k1a + DP5_A52 * k2a + DP5_A53 * k3a + DP5_A54 * k4a),
            k5y, k5a, X, true);
-      th_axpy(S, -2187.f / 6784.f, X); th_axpy(E, -2187.f / 6784.f + 12231.f / 42400.f, X); th_axpy(M, 187940372067.f / 1594534317056.f / 2.f, X);
-      eval(y0 + dt * ((9017.f / 3168.f) * k1y + (-355.f / 33.f) * k2y + (46732.f / 5247.f) * k3y + (49.f / 176.f) * k4y + (-5103.f / 18656.f) * k5y),
-           a0 + dt * ((9017.f / 3168.f) * k1a + (-355.f / 33.f) * k2a + (46732.f / 5247.f) * k3a + (49.f / 176.f) * k4a + (-5103.f / 18656.f) * k5a),
+      th_axpy(S, DP5_B5, X); th_axpy(E, DP5_E5, X); th_axpy(M, DP5_C5, X);
+      eval(y0 + dt * (DP5_A61 * k1y + DP5_A62 * k2y + DP5_A63 * k3y + DP5_A64 * k4y + DP5_A65 * k5y),
+           a0 + dt * (DP5_A61 * k1a + DP5_A62 * k2a + DP5_A63 * k3a + DP5_A64 * k4a + DP5_A65 * k5a),
            k6y, k6a, X, true);
-      th_axpy(S, 11.f / 84.f, X); th_axpy(E, 11.f / 84.f - 649.f / 6300.f, X); th_axpy(M, -1776094331.f / 19743644256.f / 2.f, X);
-      const f32x4 y1 = y0 + dt * ((35.f / 384.f) * k1y + (500.f / 1113.f) * k3y + (125.f / 192.f) * k4y + (-2187.f / 6784.f) * k5y + (11.f / 84.f) * k6y);
-      const f32x4 a1 = a0 + dt * ((35.f / 384.f) * k1a + (500.f / 1113.f) * k3a + (125.f / 192.f) * k4a + (-2187.f / 6784.f) * k5a + (11.f / 84.f) * k6a);
+      th_axpy(S, DP5_B6, X); th_axpy(E, DP5_E6, X); th_axpy(M, DP5_C6, X);
+      const f32x4 y1 = y0 + dt * (DP5_B1 * k1y + DP5_B3 * k3y + DP5_B4 * k4y + DP5_B5 * k5y + DP5_B6 * k6y);
+      const f32x4 a1 = a0 + dt * (DP5_B1 * k1a + DP5_B3 * k3a + DP5_B4 * k4a + DP5_B5 * k5a + DP5_B6 * k6a);
       eval(y1, a1, k7y, k7a, X7, true);
-      th_axpy(E, -1.f / 60.f, X7); th_axpy(M, 11237099.f / 235043384.f / 2.f, X7);
-      const f32x4 erry = dt * ((35.f / 384.f - 1951.f / 21600.f) * k1y + (500.f / 1113.f - 22642.f / 50085.f) * k3y + (125.f / 192.f - 451.f / 720.f) * k4y +
-                               (-2187.f / 6784.f + 12231.f / 42400.f) * k5y + (11.f / 84.f - 649.f / 6300.f) * k6y + (-1.f / 60.f) * k7y);
-      const f32x4 erra = dt * ((35.f / 384.f - 1951.f / 21600.f) * k1a + (500.f / 1113.f - 22642.f / 50085.f) * k3a + (125.f / 192.f - 451.f / 720.f) * k4a +
-                               (-2187.f / 6784.f + 12231.f / 42400.f) * k5a + (11.f / 84.f - 649.f / 6300.f) * k6a + (-1.f / 60.f) * k7a);
+      th_axpy(E, DP5_E7, X7); th_axpy(M, DP5_C7, X7);
+      const f32x4 erry = dt * (DP5_E1 * k1y + DP5_E3 * k3y + DP5_E4 * k4y +
+                               DP5_E5 * k5y + DP5_E6 * k6y + DP5_E7 * k7y);
+      const f32x4 erra = dt * (DP5_E1 * k1a + DP5_E3 * k3a + DP5_E4 * k4a +
+                               DP5_E5 * k5a + DP5_E6 * k6a + DP5_E7 * k7a);
       const Th Sd = th_scale(dt, S), Ed = th_scale(dt, E);
       put_image(0, Ed);
       put_image(1, Sd);
@@ -207,9 +203,9 @@ struct AdjSolver {
         if (last) {
           // 4th-order interpolant through (z0, z_mid, z1, f0, f1); abscissa from the fp32-rounded times as torchdiffeq
           const float x = ((float)tau1 - (float)tcur) / ((float)(tcur + dtd) - (float)tcur);
-          const f32x4 amid = a0 + dt * ((6025192743.f / 30085553152.f / 2.f) * k1a + (51252292925.f / 65400821598.f / 2.f) * k3a +
-                                        (-2691868925.f / 45128329728.f / 2.f) * k4a + (187940372067.f / 1594534317056.f / 2.f) * k5a +
-                                        (-1776094331.f / 19743644256.f / 2.f) * k6a + (11237099.f / 235043384.f / 2.f) * k7a);
+          const f32x4 amid = a0 + dt * (DP5_C1 * k1a + DP5_C3 * k3a +
+                                        DP5_C4 * k4a + DP5_C5 * k5a +
+                                        DP5_C6 * k6a + DP5_C7 * k7a);
           const f32x4 ca = 2.f * dt * (k7a - k1a) - 8.f * (a1 + a0) + 16.f * amid;
           const f32x4 cb = dt * (5.f * k1a - 3.f * k7a) + 18.f * a0 + 14.f * a1 - 32.f * amid;
           const f32x4 cc = dt * (k7a - 4.f * k1a) - 11.f * a0 - 5.f * a1 + 16.f * amid;
@@ -245,14 +241,6 @@ struct AdjSolver {
 };
 
 #define RNN_NPARAM 2176
-#define RO_W1 0
-#define RO_B1 256
-#define RO_W2 272
-#define RO_B2 528
-#define RO_WIH 544
-#define RO_WHH 1312
-#define RO_BIH 2080
-#define RO_BHH 2128
 
 // ODE-RNN backward with the adaptive adjoint: per frame GRU backward, then ONE adjoint call over [1, 0] (its theta state
 // starts at zero, as each odeint_adjoint call's does).  One partial row of `work` per wave (16 trajectories).
@@ -377,14 +365,6 @@ int gode_launch_odernn_bwd_adaptive(const gode_odernn_bwd_op* op, hipStream_t st
 // Plain Neural-ODE generator solved with dopri5 (gode_ode_bwd_op.method == 1): ONE adjoint call over the T output
 // times -- the theta state is carried across the output intervals, the solver is restarted on every interval
 // (oracle/ode_ref.py:_Adjoint.backward) -- followed by the pre-net backward of ode_bwd_kernel.
-#define OFF_WA 0
-#define OFF_BA 1024
-#define OFF_WB 1088
-#define OFF_BB 2112
-#define OFF_W1 2128
-#define OFF_B1 2384
-#define OFF_W2 2400
-#define OFF_B2 2656
 __global__ void __launch_bounds__(ADJ_BLOCK * 4) ode_dopri5_bwd_kernel(const gode_ode_bwd_op a) {
   __shared__ AdjLds lds;
   AdjSolver S;

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "ode_common.h"
 #include "valu_common.h"
+#include "dopri5.h"
 
 // parameter block (gode_cde_params order; the layout of `grads`)
 #define CP_WA 0
@@ -42,59 +43,7 @@ static_assert(CP_B2 + 32 == GODE_CDE_NPARAM, "CDE parameter block");
 #define CB_W1T 40          // m = 40 + m:                     lane j, rot r -> W1[16m + src r][j]
 #define CDE_WG 16          // trajectories per workgroup
 #define CDE_MAX_TRIALS 100000
-#define XS_VALS 2
-#define XS_HDR 16
-
-// ---- dopri5 tableau (torchdiffeq's Dormand-Prince-Shampine) ----------------------------------------------------------
-#define A21 (1.f / 5.f)
-#define A31 (3.f / 40.f)
-#define A32 (9.f / 40.f)
-#define A41 (44.f / 45.f)
-#define A42 (-56.f / 15.f)
-#define A43 (32.f / 9.f)
-#define A51 (19372.f / 6561.f)
-#define A52 (-25360.f / 2187.f)
-#define A53 (64448.f / 6561.f)
-#define A54 (-212.f / 729.f)
-#define A61 (9017.f / 3168.f)
-#define A62 (-355.f / 33.f)
-#define A63 (46732.f / 5247.f)
-#define A64 (49.f / 176.f)
-#define A65 (-5103.f / 18656.f)
-#define B1 (35.f / 384.f)
-#define B3 (500.f / 1113.f)
-#define B4 (125.f / 192.f)
-#define B5 (-2187.f / 6784.f)
-#define B6 (11.f / 84.f)
-#define E1 (35.f / 384.f - 1951.f / 21600.f)
-#define E3 (500.f / 1113.f - 22642.f / 50085.f)
-#define E4 (125.f / 192.f - 451.f / 720.f)
-#define E5 (-2187.f / 6784.f + 12231.f / 42400.f)
-#define E6 (11.f / 84.f - 649.f / 6300.f)
-#define E7 (-1.f / 60.f)
-#define C1 (6025192743.f / 30085553152.f / 2.f)
-#define C3 (51252292925.f / 65400821598.f / 2.f)
-#define C4 (-2691868925.f / 45128329728.f / 2.f)
-#define C5 (187940372067.f / 1594534317056.f / 2.f)
-#define C6 (-1776094331.f / 19743644256.f / 2.f)
-#define C7 (11237099.f / 235043384.f / 2.f)
-
-__device__ __forceinline__ float cde_pow(float x, float p) { return __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(x)); }
-// torchdiffeq _optimal_step_size (order 5): safety 0.9, ifactor 10, dfactor 0.2; a step with ratio < 1 never shrinks
-__device__ __forceinline__ float cde_step_factor(float ratio) {
-  if (ratio == 0.f) return 10.f;
-  const float f = 0.9f * cde_pow(ratio, -0.2f);
-  return fminf(10.f, fmaxf(f, ratio < 1.f ? 1.f : 0.2f));
-}
-// weights of the 4th-order interpolant (torchdiffeq _interp_fit / _interp_eval) at abscissa x:
-//   y(x) = y0 + wS (y1 - y0) + wM (ymid - y0) + dt (w1 f0 + w7 f1)
-__device__ __forceinline__ void cde_interp_weights(float x, float& wS, float& wM, float& w1c, float& w7c) {
-  const float x2 = x * x, x3 = x2 * x, x4 = x3 * x;
-  wS = -8.f * x4 + 14.f * x3 - 5.f * x2;
-  wM = 16.f * x4 - 32.f * x3 + 16.f * x2;
-  w1c = -2.f * x4 + 5.f * x3 - 4.f * x2 + x;
-  w7c = 2.f * x4 - 3.f * x3 + x2;
-}
+#define XS_VALS 2           // floats per exchange slot
 
 // ---- LDS image shared by both kernels ----------------------------------------------------------------------------------
 struct CdeLds {
@@ -209,79 +158,8 @@ __device__ __forceinline__ float cde_prenet(const CdeLds& S, float t0, float x0,
   return lrelu1(acc);
 }
 
-// ---- whole-batch sums (as odernn_valu.hip's batch_sum, for a 4-wave workgroup) -----------------------------------------
-struct CdeRed {
-  float red[2][4][XS_VALS];
-  float bc[2][XS_VALS];
-  int dead;
-};
-struct CdeSync { int* counter; float* slots; int nwg, wg, seq; };
-
-template <int K>
-__device__ __forceinline__ void cde_batch_sum(float* v, CdeRed& R, int& par, CdeSync& X) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) R.red[par][wave][k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = (R.red[par][0][k] + R.red[par][1][k]) + (R.red[par][2][k] + R.red[par][3][k]);
-  if (X.nwg > 1) {
-    float* slot = X.slots + (size_t)(X.seq & 1) * X.nwg * XS_VALS;
-    if (wave == 0) {
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) __hip_atomic_store(&slot[X.wg * XS_VALS + k], v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(X.counter, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        const int target = (X.seq + 1) * X.nwg;
-        int spins = 0;
-        while (__hip_atomic_load(X.counter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) {
-          __builtin_amdgcn_s_sleep(2);
-          if (++spins > (1 << 20)) { R.dead = 1; break; }     // a workgroup of the call never arrived: give up, report
-        }
-      }
-      float t[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) t[k] = 0.f;
-      for (int w = lane; w < X.nwg; w += 64) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) t[k] += __hip_atomic_load(&slot[w * XS_VALS + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-#pragma unroll
-      for (int k = 0; k < K; ++k) t[k] = wave_sum(t[k]);
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) R.bc[par][k] = t[k];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = R.bc[par][k];
-    X.seq += 1;
-  }
-  par ^= 1;
-}
-
-// content columns 16..65 + zero pad (as sde_valu.hip)
-__device__ __forceinline__ void cde_broadcast_content(const gode_cde_fwd_op& a, int n0) {
-  const int rows_per = a.sel_t ? 1 : a.T;
-  const int q4 = (a.zcols - 16) >> 2;
-  const int total4 = CDE_WG * rows_per * q4;
-  for (int k = threadIdx.x; k < total4; k += 256) {
-    const int rr = k / q4, q = k - rr * q4;
-    const int ns = rr / rows_per, tt = rr - ns * rows_per;
-    if (n0 + ns < a.N) {
-      const float* c = a.content + (int64_t)(n0 + ns) * 50 + 4 * q;
-      f32x4 v = zero4();
-      if (q < 12) v = f32x4{c[0], c[1], c[2], c[3]};
-      else if (q == 12) v = f32x4{c[0], c[1], 0.f, 0.f};
-      *reinterpret_cast<f32x4*>(a.z + ((int64_t)(n0 + ns) * rows_per + tt) * a.zcols + 16 + 4 * q) = v;
-    }
-  }
-}
+// whole-batch sums: 4 waves, the per-wave partials added pairwise
+typedef RedLds<4, XS_VALS, true> CdeRed;
 
 // =====================================================================================================================
 __global__ void __launch_bounds__(256) cde_fwd_kernel(const gode_cde_fwd_op a) {
@@ -295,7 +173,7 @@ __global__ void __launch_bounds__(256) cde_fwd_kernel(const gode_cde_fwd_op a) {
   const int T = a.T;
   const float inv_count = 1.f / ((float)a.N * 16.f);
   const float rtol = a.rtol, atol = a.atol;
-  CdeSync X;
+  XSync X;
   X.nwg = gridDim.x; X.wg = wg; X.seq = 0; X.counter = a.sync;
   X.slots = a.sync ? reinterpret_cast<float*>(a.sync) + XS_HDR : nullptr;
   int par = 0;
@@ -305,7 +183,7 @@ __global__ void __launch_bounds__(256) cde_fwd_kernel(const gode_cde_fwd_op a) {
   probe_sources(i, src);
   cde_stage_blocks(a.p, Wp, CB_W2T, src);
   cde_stage_small(a.p, a.x, a.tslope, a.N, T, n0, S);        // (ends with a barrier)
-  if (a.content) cde_broadcast_content(a, n0);               // stores only
+  if (a.content) broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, n0, CDE_WG, threadIdx.x, 256);
 
   const int tsel = (a.sel_t && valid) ? a.sel_t[n] : -1;
   auto emit = [&](int t, float v) {
@@ -332,15 +210,15 @@ __global__ void __launch_bounds__(256) cde_fwd_kernel(const gode_cde_fwd_op a) {
   {   // torchdiffeq _select_initial_step (order 4)
     const float sc = atol + fabsf(y0) * rtol;
     float v[2] = {valid ? (y0 / sc) * (y0 / sc) : 0.f, valid ? (k1 / sc) * (k1 / sc) : 0.f};
-    cde_batch_sum<2>(v, R, par, X);
+    batch_sum<2>(v, R, par, X);
     const float d0 = sqrtf(v[0] * inv_count), d1 = sqrtf(v[1] * inv_count);
     const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
     const float f1 = f(tcur + (double)h0, fmaf(h0, k1, y0));
     const float df = (f1 - k1) / sc;
     float w[1] = {valid ? df * df : 0.f};
-    cde_batch_sum<1>(w, R, par, X);
+    batch_sum<1>(w, R, par, X);
     const float d2 = sqrtf(w[0] * inv_count) / h0;
-    const float hh = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : cde_pow(0.01f / fmaxf(d1, d2), 0.2f);
+    const float hh = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : fast_pow(0.01f / fmaxf(d1, d2), 0.2f);
     dtd = (double)fminf(100.f * h0, hh);
   }
 
@@ -349,18 +227,18 @@ __global__ void __launch_bounds__(256) cde_fwd_kernel(const gode_cde_fwd_op a) {
   while (jo < T) {
     if (R.dead || trials >= CDE_MAX_TRIALS || !(tcur + dtd > tcur)) { failed = true; break; }
     const float dt = (float)dtd;
-    const float k2 = f(tcur + 0.2 * dtd, fmaf(dt, A21 * k1, y0));
-    const float k3 = f(tcur + 0.3 * dtd, fmaf(dt, A31 * k1 + A32 * k2, y0));
-    const float k4 = f(tcur + 0.8 * dtd, fmaf(dt, A41 * k1 + A42 * k2 + A43 * k3, y0));
-    const float k5 = f(tcur + (8.0 / 9.0) * dtd, fmaf(dt, A51 * k1 + A52 * k2 + A53 * k3 + A54 * k4, y0));
-    const float k6 = f(tcur + dtd, fmaf(dt, A61 * k1 + A62 * k2 + A63 * k3 + A64 * k4 + A65 * k5, y0));
-    const float y1 = fmaf(dt, B1 * k1 + B3 * k3 + B4 * k4 + B5 * k5 + B6 * k6, y0);
+    const float k2 = f(tcur + 0.2 * dtd, fmaf(dt, DP5_A21 * k1, y0));
+    const float k3 = f(tcur + 0.3 * dtd, fmaf(dt, DP5_A31 * k1 + DP5_A32 * k2, y0));
+    const float k4 = f(tcur + 0.8 * dtd, fmaf(dt, DP5_A41 * k1 + DP5_A42 * k2 + DP5_A43 * k3, y0));
+    const float k5 = f(tcur + (8.0 / 9.0) * dtd, fmaf(dt, DP5_A51 * k1 + DP5_A52 * k2 + DP5_A53 * k3 + DP5_A54 * k4, y0));
+    const float k6 = f(tcur + dtd, fmaf(dt, DP5_A61 * k1 + DP5_A62 * k2 + DP5_A63 * k3 + DP5_A64 * k4 + DP5_A65 * k5, y0));
+    const float y1 = fmaf(dt, DP5_B1 * k1 + DP5_B3 * k3 + DP5_B4 * k4 + DP5_B5 * k5 + DP5_B6 * k6, y0);
     const float k7 = f(tcur + dtd, y1);
-    const float err = dt * (E1 * k1 + E3 * k3 + E4 * k4 + E5 * k5 + E6 * k6 + E7 * k7);
+    const float err = dt * (DP5_E1 * k1 + DP5_E3 * k3 + DP5_E4 * k4 + DP5_E5 * k5 + DP5_E6 * k6 + DP5_E7 * k7);
     const float tol = atol + rtol * fmaxf(fabsf(y0), fabsf(y1));
     const float rr = err / tol;
     float v[1] = {valid ? rr * rr : 0.f};
-    cde_batch_sum<1>(v, R, par, X);
+    batch_sum<1>(v, R, par, X);
     const float ratio = sqrtf(v[0] * inv_count);
     ++trials;
     if (ratio <= 1.f) {
@@ -372,15 +250,15 @@ __global__ void __launch_bounds__(256) cde_fwd_kernel(const gode_cde_fwd_op a) {
       while (jo < T && (double)jo <= t1) {
         const float x = ((float)jo - (float)tcur) / ((float)t1 - (float)tcur);
         float wS, wM, w1c, w7c;
-        cde_interp_weights(x, wS, wM, w1c, w7c);
-        const float ym = fmaf(dt, C1 * k1 + C3 * k3 + C4 * k4 + C5 * k5 + C6 * k6 + C7 * k7, y0);
+        interp_weights(x, wS, wM, w1c, w7c);
+        const float ym = fmaf(dt, DP5_C1 * k1 + DP5_C3 * k3 + DP5_C4 * k4 + DP5_C5 * k5 + DP5_C6 * k6 + DP5_C7 * k7, y0);
         emit(jo, y0 + wS * (y1 - y0) + wM * (ym - y0) + dt * (w1c * k1 + w7c * k7));
         ++jo;
       }
       ++accepted;
       tcur = t1; y0 = y1; k1 = k7;
     }
-    dtd *= (double)cde_step_factor(ratio);
+    dtd *= (double)step_factor(ratio);
   }
   if (wg == 0 && threadIdx.x == 0) { a.counts[0] = failed ? -accepted - 1 : accepted; a.counts[1] = trials; }
 }
@@ -502,24 +380,24 @@ __global__ void __launch_bounds__(256) cde_bwd_kernel(const gode_cde_bwd_op a) {
     const float y0 = stp ? stp[(int64_t)s * 16] : 0.f;
     // recompute the stages
     const float k1 = f(t0, y0);
-    const float z2 = fmaf(dt, A21 * k1, y0);
+    const float z2 = fmaf(dt, DP5_A21 * k1, y0);
     const float k2 = f(t0 + 0.2 * hd, z2);
-    const float z3 = fmaf(dt, A31 * k1 + A32 * k2, y0);
+    const float z3 = fmaf(dt, DP5_A31 * k1 + DP5_A32 * k2, y0);
     const float k3 = f(t0 + 0.3 * hd, z3);
-    const float z4 = fmaf(dt, A41 * k1 + A42 * k2 + A43 * k3, y0);
+    const float z4 = fmaf(dt, DP5_A41 * k1 + DP5_A42 * k2 + DP5_A43 * k3, y0);
     const float k4 = f(t0 + 0.8 * hd, z4);
-    const float z5 = fmaf(dt, A51 * k1 + A52 * k2 + A53 * k3 + A54 * k4, y0);
+    const float z5 = fmaf(dt, DP5_A51 * k1 + DP5_A52 * k2 + DP5_A53 * k3 + DP5_A54 * k4, y0);
     const float k5 = f(t0 + (8.0 / 9.0) * hd, z5);
-    const float z6 = fmaf(dt, A61 * k1 + A62 * k2 + A63 * k3 + A64 * k4 + A65 * k5, y0);
+    const float z6 = fmaf(dt, DP5_A61 * k1 + DP5_A62 * k2 + DP5_A63 * k3 + DP5_A64 * k4 + DP5_A65 * k5, y0);
     const float k6 = f(t0 + hd, z6);
-    const float y1 = fmaf(dt, B1 * k1 + B3 * k3 + B4 * k4 + B5 * k5 + B6 * k6, y0);
+    const float y1 = fmaf(dt, DP5_B1 * k1 + DP5_B3 * k3 + DP5_B4 * k4 + DP5_B5 * k5 + DP5_B6 * k6, y0);
 
     float gy0 = 0.f, gy1 = adj, gk1 = 0.f, gk3 = 0.f, gk4 = 0.f, gk5 = 0.f, gk6 = 0.f, gk7 = 0.f, gym = 0.f;
     bool outs = false;
     while (jhi >= 1 && (double)jhi > t0) {           // outputs read off this step's interpolant (t0 < j <= t1)
       const float x = ((float)jhi - (float)t0) / ((float)t1 - (float)t0);
       float wS, wM, w1c, w7c;
-      cde_interp_weights(x, wS, wM, w1c, w7c);
+      interp_weights(x, wS, wM, w1c, w7c);
       const float g = upstream(jhi);
       gy0 += (1.f - wS - wM) * g;
       gy1 += wS * g;
@@ -529,31 +407,31 @@ __global__ void __launch_bounds__(256) cde_bwd_kernel(const gode_cde_bwd_op a) {
       outs = true;
       --jhi;
     }
-    if (outs) {                      // ym = y0 + dt (C1 k1 + C3 k3 + ... + C7 k7), k7 = f(t1, y1)
+    if (outs) {                      // ym = y0 + dt (DP5_C1 k1 + DP5_C3 k3 + ... + DP5_C7 k7), k7 = f(t1, y1)
       gy0 += gym;
       const float dg = dt * gym;
-      gk1 += C1 * dg; gk3 += C3 * dg; gk4 += C4 * dg; gk5 += C5 * dg; gk6 += C6 * dg; gk7 += C7 * dg;
+      gk1 += DP5_C1 * dg; gk3 += DP5_C3 * dg; gk4 += DP5_C4 * dg; gk5 += DP5_C5 * dg; gk6 += DP5_C6 * dg; gk7 += DP5_C7 * dg;
       gy1 += vjp(t1, y1, gk7);
     }
-    // y1 = y0 + dt (B1 k1 + B3 k3 + ... + B6 k6)
+    // y1 = y0 + dt (DP5_B1 k1 + DP5_B3 k3 + ... + DP5_B6 k6)
     gy0 += gy1;
     const float db = dt * gy1;
-    gk1 += B1 * db; gk3 += B3 * db; gk4 += B4 * db; gk5 += B5 * db; gk6 += B6 * db;
+    gk1 += DP5_B1 * db; gk3 += DP5_B3 * db; gk4 += DP5_B4 * db; gk5 += DP5_B5 * db; gk6 += DP5_B6 * db;
     float gz = vjp(t0 + hd, z6, gk6);
     gy0 += gz; gz *= dt;
-    gk1 += A61 * gz; float gk2 = A62 * gz; gk3 += A63 * gz; gk4 += A64 * gz; gk5 += A65 * gz;
+    gk1 += DP5_A61 * gz; float gk2 = DP5_A62 * gz; gk3 += DP5_A63 * gz; gk4 += DP5_A64 * gz; gk5 += DP5_A65 * gz;
     gz = vjp(t0 + (8.0 / 9.0) * hd, z5, gk5);
     gy0 += gz; gz *= dt;
-    gk1 += A51 * gz; gk2 += A52 * gz; gk3 += A53 * gz; gk4 += A54 * gz;
+    gk1 += DP5_A51 * gz; gk2 += DP5_A52 * gz; gk3 += DP5_A53 * gz; gk4 += DP5_A54 * gz;
     gz = vjp(t0 + 0.8 * hd, z4, gk4);
     gy0 += gz; gz *= dt;
-    gk1 += A41 * gz; gk2 += A42 * gz; gk3 += A43 * gz;
+    gk1 += DP5_A41 * gz; gk2 += DP5_A42 * gz; gk3 += DP5_A43 * gz;
     gz = vjp(t0 + 0.3 * hd, z3, gk3);
     gy0 += gz; gz *= dt;
-    gk1 += A31 * gz; gk2 += A32 * gz;
+    gk1 += DP5_A31 * gz; gk2 += DP5_A32 * gz;
     gz = vjp(t0 + 0.2 * hd, z2, gk2);
     gy0 += gz;
-    gk1 += A21 * dt * gz;
+    gk1 += DP5_A21 * dt * gz;
     gy0 += vjp(t0, y0, gk1);
     adj = gy0;
   }
@@ -603,26 +481,6 @@ __global__ void __launch_bounds__(256) cde_bwd_kernel(const gode_cde_bwd_op a) {
   if ((th & 1) == 0) part[CP_B1 + m1] = gb1;
 }
 
-// second level: grads[k] (+)= sum over the workgroup rows b = 0, stride, 2*stride, ... of work[b][k]
-__global__ void __launch_bounds__(256) cde_bwd_reduce_kernel(const float* work, float* grads, int nblk, int stride,
-                                                             int accumulate, const int32_t* counts) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= GODE_CDE_NPARAM || counts[0] < 0) return;
-  float s = 0.f;
-  for (int b = 0; b < nblk; b += stride) s += work[(int64_t)b * GODE_CDE_NPARAM + k];
-  grads[k] = accumulate ? grads[k] + s : s;
-}
-// many workgroups: chunks of `chunk` consecutive rows summed in place into their first row (fixed order), first
-__global__ void __launch_bounds__(256) cde_bwd_reduce_chunks_kernel(float* work, int nblk, int chunk, const int32_t* counts) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= GODE_CDE_NPARAM || counts[0] < 0) return;
-  const int b0 = blockIdx.y * chunk, b1 = b0 + chunk < nblk ? b0 + chunk : nblk;
-  float s = 0.f;
-#pragma unroll 8
-  for (int b = b0; b < b1; ++b) s += work[(int64_t)b * GODE_CDE_NPARAM + k];
-  work[(int64_t)b0 * GODE_CDE_NPARAM + k] = s;
-}
-
 static bool cde_params_ok(const gode_cde_params& p) {
   return p.Wa && p.ba && p.Wb && p.bb && p.W1 && p.b1 && p.W2 && p.b2;
 }
@@ -666,16 +524,6 @@ extern "C" int gode_cde_bwd(const gode_cde_bwd_op* op, void* stream) {
   const int nblk = (op->N + CDE_WG - 1) / CDE_WG;
   hipLaunchKernelGGL(cde_bwd_kernel, dim3(nblk), dim3(256), 0, st, *op);
   GODE_LAUNCH_CHECK();
-  const int gx = (GODE_CDE_NPARAM + 255) / 256;
-  int stride = 1;
-  if (nblk > 32) {
-    stride = 16;
-    hipLaunchKernelGGL(cde_bwd_reduce_chunks_kernel, dim3(gx, (nblk + stride - 1) / stride), dim3(256), 0, st, op->work,
-                       nblk, stride, op->counts);
-    GODE_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(cde_bwd_reduce_kernel, dim3(gx), dim3(256), 0, st, op->work, op->grads, nblk, stride,
-                     op->accumulate, op->counts);
-  GODE_LAUNCH_CHECK();
-  return 0;
+  // two levels above 32 rows; a failed forward (counts[0] < 0) leaves grads alone
+  return gode_reduce_rows(op->work, op->grads, nblk, GODE_CDE_NPARAM, 0, 0, op->accumulate, op->counts, 32, 16, st);
 }

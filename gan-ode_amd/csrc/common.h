@@ -67,3 +67,39 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
   const uint32_t t = __umulhi(f.mul, n);
   return (t + ((n - t) >> f.sh1)) >> f.sh2;
 }
+
+
+// ---- fixed-order sums of per-workgroup gradient rows (latent_reduce.hip) ---------------------------------------------
+// grads[k - grads_bias] (+)= sum over the nblk rows of work[.][nparam], k in [first, nparam), rows in order.  More than
+// chunk_threshold rows: chunks of `chunk` consecutive rows are first summed in place into their first row, then every
+// chunk-th row is added (both levels in row order).  counts != NULL: nothing is touched when counts[0] < 0.
+int gode_reduce_rows(float* work, float* grads, int nblk, int nparam, int first, int grads_bias, int accumulate,
+                     const int32_t* counts, int chunk_threshold, int chunk, hipStream_t st);
+
+// Multi-solve launches (up to GODE_MAX_JOBS ops): the ops that share a grads pointer form a group, in array order.
+#define GODE_MAX_JOBS 8
+struct RowsArgs {
+  const float* work[GODE_MAX_JOBS]; int32_t rows[GODE_MAX_JOBS]; int32_t accumulate[GODE_MAX_JOBS];
+  int32_t count, nparam, first; float* grads;
+};
+// grads[k] (+)= all rows of the group in order, k in [first, nparam), under the FIRST op's accumulate flag (the later ops of
+// a group add by construction)
+int gode_launch_rows(const RowsArgs& A, hipStream_t st);
+// calls launch(A) once per group with work / rows / accumulate / count / grads filled in; stops at the first non-zero return
+template <class Op, class Launch>
+static inline int gode_for_each_grads_group(const Op* ops, const int32_t* nblk, int count, Launch launch) {
+  bool done[GODE_MAX_JOBS] = {false};
+  for (int k = 0; k < count; ++k) {
+    if (done[k]) continue;
+    RowsArgs A = {};
+    A.grads = ops[k].grads;
+    for (int j = k; j < count; ++j) {
+      if (done[j] || ops[j].grads != A.grads) continue;
+      A.work[A.count] = ops[j].work; A.rows[A.count] = nblk[j]; A.accumulate[A.count] = ops[j].accumulate ? 1 : 0;
+      A.count += 1; done[j] = true;
+    }
+    const int rc = launch(A);
+    if (rc) return rc;
+  }
+  return 0;
+}

@@ -24,7 +24,7 @@
 #define GB_WAVES 8                   // backward: 8 waves, 32 trajectories per workgroup
 #define GB_TRAJ (4 * GB_WAVES)
 #define GB_THREADS (64 * GB_WAVES)
-#define GR_MAX_JOBS 8
+#define GR_MAX_JOBS GODE_MAX_JOBS
 // parameter block == gradient block: Wih [48][16], Whh [48][16], bih [48], bhh [48]
 #define GO_WIH 0
 #define GO_WHH 768
@@ -55,23 +55,7 @@ __global__ void __launch_bounds__(64) gru_fwd_kernel(const GruFwdJobs J) {
   float h = valid ? noise[(int64_t)n * 16 + i] : 0.f;
   float e = valid ? noise[((int64_t)N + n) * 16 + i] : 0.f;
   stage_gru_params(a.p, P, 64);
-  if (a.content) {
-    // content columns 16..65 (the same 50 values on every row of a trajectory) + zero pad: stores only
-    const int rows_per = a.sel_t ? 1 : T;
-    const int q4 = (zcols - 16) >> 2;
-    const int total4 = GF_TRAJ * rows_per * q4;
-    for (int k = lane; k < total4; k += 64) {
-      const int rr = k / q4, q = k - rr * q4;
-      const int ns = rr / rows_per, tt = rr - ns * rows_per;
-      if (n0 + ns < N) {
-        const float* c = a.content + (int64_t)(n0 + ns) * 50 + 4 * q;
-        f32x4 v = zero4();
-        if (q < 12) v = f32x4{c[0], c[1], c[2], c[3]};
-        else if (q == 12) v = f32x4{c[0], c[1], 0.f, 0.f};
-        *reinterpret_cast<f32x4*>(a.z + ((int64_t)(n0 + ns) * rows_per + tt) * zcols + 16 + 4 * q) = v;
-      }
-    }
-  }
+  if (a.content) broadcast_content(a.content, a.z, a.sel_t, N, T, zcols, n0, GF_TRAJ, lane, 64);      // stores only
   int src[16];
   probe_sources(i, src);
   W16 wih[3], whh[3];
@@ -231,10 +215,7 @@ __global__ void __launch_bounds__(GB_THREADS) gru_bwd_kernel(const GruBwdJobs J)
 // rows of `work` -> grads, fixed order.  A group holds the ops of a launch that share a grads pointer, in array order;
 // each op's rows are first summed into its own partial (row order), which is then stored or added under that op's own
 // accumulate flag -- the arithmetic of the same ops launched one by one.
-struct GruRowsArgs {
-  const float* work[GR_MAX_JOBS]; int32_t rows[GR_MAX_JOBS]; int32_t accumulate[GR_MAX_JOBS]; int32_t count; float* grads;
-};
-__global__ void __launch_bounds__(256) gru_bwd_rows_kernel(const GruRowsArgs A) {
+__global__ void __launch_bounds__(256) gru_bwd_rows_kernel(const RowsArgs A) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= GO_N) return;
   float v = A.accumulate[0] ? A.grads[k] : 0.f;
@@ -271,21 +252,11 @@ extern "C" int gode_gru_bwd_multi(const gode_gru_bwd_op* ops, int32_t count, voi
   hipLaunchKernelGGL(gru_bwd_kernel, dim3(grid), dim3(GB_THREADS), 0, st, J);
   GODE_LAUNCH_CHECK();
   if (J.direct) return 0;
-  bool done[GR_MAX_JOBS] = {false};
-  for (int k = 0; k < count; ++k) {
-    if (done[k]) continue;
-    GruRowsArgs A;
-    A.count = 0; A.grads = ops[k].grads;
-    for (int j = k; j < count; ++j) {
-      if (!done[j] && ops[j].grads == ops[k].grads) {
-        A.work[A.count] = ops[j].work; A.rows[A.count] = J.nblk[j]; A.accumulate[A.count] = ops[j].accumulate ? 1 : 0;
-        A.count += 1; done[j] = true;
-      }
-    }
+  return gode_for_each_grads_group(ops, J.nblk, count, [&](const RowsArgs& A) {
     hipLaunchKernelGGL(gru_bwd_rows_kernel, dim3((GO_N + 255) / 256), dim3(256), 0, st, A);
     GODE_LAUNCH_CHECK();
-  }
-  return 0;
+    return 0;
+  });
 }
 
 extern "C" int gode_gru_bwd(const gode_gru_bwd_op* op, void* stream) { return gode_gru_bwd_multi(op, 1, stream); }

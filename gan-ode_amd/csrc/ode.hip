@@ -25,22 +25,7 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(const gode_ode_fwd_op a) {
   const int n0 = blockIdx.x * 16;
   const int T = a.T;
   if (threadIdx.x >= 64) {
-    // content columns 16..65 (the same 50 values on all T rows of a trajectory) + zero pad, one float4 per thread and
-    // turn; rows are 200 B in `content`, so the four values are gathered one by one (L1-resident: 3.2 KB per workgroup)
-    const int rows_per = a.sel_t ? 1 : T;
-    const int q4 = (a.zcols - 16) >> 2;      // float4 chunks of content + pad per latent row
-    const int total4 = 16 * rows_per * q4;
-    for (int i = threadIdx.x - 64; i < total4; i += 192) {
-      const int rr = i / q4, q = i - rr * q4;
-      const int ns = rr / rows_per, tt = rr - ns * rows_per;
-      if (n0 + ns < a.N) {
-        const float* c = a.content + (int64_t)(n0 + ns) * 50 + 4 * q;
-        f32x4 v = zero4();
-        if (q < 12) v = f32x4{c[0], c[1], c[2], c[3]};
-        else if (q == 12) v = f32x4{c[0], c[1], 0.f, 0.f};
-        *reinterpret_cast<f32x4*>(a.z + ((int64_t)(n0 + ns) * rows_per + tt) * a.zcols + 16 + 4 * q) = v;
-      }
-    }
+    broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, n0, 16, threadIdx.x - 64, 192);
     return;
   }
   const int l = threadIdx.x, s = l & 15, g = l >> 4;
@@ -139,14 +124,6 @@ extern "C" int gode_ode_fwd(const gode_ode_fwd_op* op, void* stream) {
 
 // ---------------------------------------------------------------------------------------------------------------
 // adjoint backward
-#define OFF_WA 0
-#define OFF_BA 1024
-#define OFF_WB 1088
-#define OFF_BB 2112
-#define OFF_W1 2128
-#define OFF_B1 2384
-#define OFF_W2 2400
-#define OFF_B2 2656
 __global__ void __launch_bounds__(64) ode_bwd_kernel(const gode_ode_bwd_op a) {
   __shared__ __attribute__((aligned(16))) float tile[4][16 * LDT];
   const int l = threadIdx.x, s = l & 15, g = l >> 4;
@@ -266,30 +243,6 @@ __global__ void __launch_bounds__(64) ode_bwd_kernel(const gode_ode_bwd_op a) {
   }
 }
 
-// `first`: entries below it are not touched (no pre-net: only the ODEFunc block [OFF_W1, NPARAM) exists, and `grads`
-// may then point 2128 floats before a caller-owned region that holds just that block).  Rows b = 0, stride, 2*stride, ...
-__global__ void __launch_bounds__(256) ode_bwd_reduce_kernel(const float* work, float* grads, int nblk, int stride, int accumulate,
-                                                             int first) {
-  const int i = first + blockIdx.x * 256 + threadIdx.x;
-  if (i >= GODE_ODE_NPARAM) return;
-  float s = 0.f;
-  for (int b = 0; b < nblk; b += stride) s += work[(int64_t)b * GODE_ODE_NPARAM + i];
-  grads[i] = accumulate ? grads[i] + s : s;
-}
-// Many workgroups (N >> 1024): a first level sums chunks of `chunk` consecutive partial rows in parallel, in place (the
-// sum of rows [c*chunk, (c+1)*chunk) replaces row c*chunk; a thread only ever touches its own column of its own chunk),
-// the kernel above then adds every chunk-th row.  Fixed order at both levels.  (A single level left 11 workgroups
-// walking 65,536 rows each: 25 of the 28 ms of the N = 2^20 adjoint.)
-__global__ void __launch_bounds__(256) ode_bwd_reduce_chunks_kernel(float* work, int nblk, int chunk, int first) {
-  const int i = first + blockIdx.x * 256 + threadIdx.x;
-  if (i >= GODE_ODE_NPARAM) return;
-  const int b0 = blockIdx.y * chunk, b1 = b0 + chunk < nblk ? b0 + chunk : nblk;
-  float s = 0.f;
-#pragma unroll 8
-  for (int b = b0; b < b1; ++b) s += work[(int64_t)b * GODE_ODE_NPARAM + i];
-  work[(int64_t)b0 * GODE_ODE_NPARAM + i] = s;
-}
-
 extern "C" int64_t gode_ode_bwd_work_size(int32_t N) { return (int64_t)((N + 15) / 16) * GODE_ODE_NPARAM; }
 
 int gode_launch_ode_dopri5_bwd(const gode_ode_bwd_op* op, hipStream_t st);   // adj_adaptive.hip
@@ -326,16 +279,8 @@ extern "C" int gode_ode_bwd(const gode_ode_bwd_op* op, void* stream) {
   return ode_bwd_reduce(op, nblk, st);
 }
 
+// rows of `work` -> grads.  Without the pre-net only the ODEFunc block [OFF_W1, NPARAM) exists (`grads` may then point 2128
+// floats before a caller-owned region that holds just that block); two levels above 128 rows
 static int ode_bwd_reduce(const gode_ode_bwd_op* op, int nblk, hipStream_t st) {
-  const int first = op->prenet ? 0 : OFF_W1;
-  const int gx = (GODE_ODE_NPARAM - first + 255) / 256;
-  int stride = 1;
-  if (nblk > 128) {
-    stride = 64;
-    hipLaunchKernelGGL(ode_bwd_reduce_chunks_kernel, dim3(gx, (nblk + stride - 1) / stride), dim3(256), 0, st, op->work, nblk, stride, first);
-    GODE_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(ode_bwd_reduce_kernel, dim3(gx), dim3(256), 0, st, op->work, op->grads, nblk, stride, op->accumulate, first);
-  GODE_LAUNCH_CHECK();
-  return 0;
+  return gode_reduce_rows(op->work, op->grads, nblk, GODE_ODE_NPARAM, op->prenet ? 0 : OFF_W1, 0, op->accumulate, nullptr, 128, 64, st);
 }

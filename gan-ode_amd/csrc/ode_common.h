@@ -1,7 +1,36 @@
-// ode_common.h -- device helpers shared by ode.hip and odernn.hip: the transposed 16x16 mat-vec batch on
-// v_mfma_f32_16x16x4_f32 (see the header comment of ode.hip for the lane mapping) and the activations.
+// ode_common.h -- device helpers shared by the motion-latent kernels: the transposed 16x16 mat-vec batch on
+// v_mfma_f32_16x16x4_f32 (see the header comment of ode.hip for the lane mapping), the activations, the layout of the
+// gode_ode_params block and the content broadcast.
 #pragma once
 #include "common.h"
+
+// parameter block in gode_ode_params order: the layout of `grads` and of a `work` row of gode_ode_bwd, and of the LDS copy
+// the VALU kernels stage (valu_common.h:stage_ode_params)
+#define OFF_WA 0
+#define OFF_BA 1024
+#define OFF_WB 1088
+#define OFF_BB 2112
+#define OFF_W1 2128
+#define OFF_B1 2384
+#define OFF_W2 2400
+#define OFF_B2 2656
+static_assert(OFF_B2 + 16 == GODE_ODE_NPARAM, "ODE parameter block");
+// ODEFunc block alone (W1, b1, W2, b2): the theta state of the adaptive adjoints
+#define TH_W1 0
+#define TH_B1 256
+#define TH_W2 272
+#define TH_B2 528
+#define TH_N 544
+// gode_odernn_params order: the ODEFunc block, then the GRU cell
+#define RO_W1 0
+#define RO_B1 256
+#define RO_W2 272
+#define RO_B2 528
+#define RO_WIH 544
+#define RO_WHH 1312
+#define RO_BIH 2080
+#define RO_BHH 2128
+static_assert(RO_BHH + 48 == GODE_ODERNN_NPARAM, "ODE-RNN parameter block");
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
@@ -53,4 +82,26 @@ __device__ __forceinline__ f32x4 sum_over_samples(f32x4 v) {
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ f32x4 sigmoid4(const f32x4 u) {
   return f32x4{fast_sigmoid(u[0]), fast_sigmoid(u[1]), fast_sigmoid(u[2]), fast_sigmoid(u[3])};
+}
+
+
+// content columns 16..65 (the same 50 values on every row of a trajectory) + zero pad for the `ntraj` trajectories from n0
+// on, one float4 per thread and turn; thread `tid` of `nthreads`.  Rows are 200 B in `content`, so the four values are
+// gathered one by one (L1-resident).  Stores only: nothing in the caller waits for them.
+__device__ __forceinline__ void broadcast_content(const float* content, float* z, const int32_t* sel_t, int N, int T, int zcols,
+                                                  int n0, int ntraj, int tid, int nthreads) {
+  const int rows_per = sel_t ? 1 : T;
+  const int q4 = (zcols - 16) >> 2;      // float4 chunks of content + pad per latent row
+  const int total4 = ntraj * rows_per * q4;
+  for (int k = tid; k < total4; k += nthreads) {
+    const int rr = k / q4, q = k - rr * q4;
+    const int ns = rr / rows_per, tt = rr - ns * rows_per;
+    if (n0 + ns < N) {
+      const float* c = content + (int64_t)(n0 + ns) * 50 + 4 * q;
+      f32x4 v = zero4();
+      if (q < 12) v = f32x4{c[0], c[1], c[2], c[3]};
+      else if (q == 12) v = f32x4{c[0], c[1], 0.f, 0.f};
+      *reinterpret_cast<f32x4*>(z + ((int64_t)(n0 + ns) * rows_per + tt) * zcols + 16 + 4 * q) = v;
+    }
+  }
 }

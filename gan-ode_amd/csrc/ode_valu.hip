@@ -24,48 +24,6 @@
 #include "ode_common.h"
 #include "valu_common.h"
 
-// All 2,672 parameters (10.7 KB) go to LDS with ONE round of coalesced loads before anything else: the per-lane weight
-// arrangement is then gathered from LDS.  (Gathering it from global memory cost the config-size adjoint launch more
-// than its whole time loop: twelve dependent batches of L2-missing loads in the pre-net backward, 60k of 126k cycles.)
-#define VP_WA 0
-#define VP_BA 1024
-#define VP_WB 1088
-#define VP_BB 2112
-#define VP_W1 2128
-#define VP_B1 2384
-#define VP_W2 2400
-#define VP_B2 2656
-__device__ __forceinline__ void stage_params(const gode_ode_params& p, int prenet, float* lds) {
-  const int t = threadIdx.x;
-  if (prenet) {
-    for (int k = t; k < 1024; k += 256) { lds[VP_WA + k] = p.Wa[k]; lds[VP_WB + k] = p.Wb[k]; }
-    if (t < 64) lds[VP_BA + t] = p.ba[t];
-    if (t < 16) lds[VP_BB + t] = p.bb[t];
-  }
-  lds[VP_W1 + t] = p.W1[t];
-  lds[VP_W2 + t] = p.W2[t];
-  if (t < 16) { lds[VP_B1 + t] = p.b1[t]; lds[VP_B2 + t] = p.b2[t]; }
-  __syncthreads();
-}
-
-// content columns 16..65 (the same 50 values on all T rows of a trajectory) + zero pad: one float4 per thread and turn
-__device__ __forceinline__ void broadcast_content(const gode_ode_fwd_op& a, int n0) {
-  const int rows_per = a.sel_t ? 1 : a.T;
-  const int q4 = (a.zcols - 16) >> 2;
-  const int total4 = 16 * rows_per * q4;
-  for (int k = threadIdx.x; k < total4; k += 256) {
-    const int rr = k / q4, q = k - rr * q4;
-    const int ns = rr / rows_per, tt = rr - ns * rows_per;
-    if (n0 + ns < a.N) {
-      const float* c = a.content + (int64_t)(n0 + ns) * 50 + 4 * q;
-      f32x4 v = zero4();
-      if (q < 12) v = f32x4{c[0], c[1], c[2], c[3]};
-      else if (q == 12) v = f32x4{c[0], c[1], 0.f, 0.f};
-      *reinterpret_cast<f32x4*>(a.z + ((int64_t)(n0 + ns) * rows_per + tt) * a.zcols + 16 + 4 * q) = v;
-    }
-  }
-}
-
 __global__ void __launch_bounds__(256) ode_fwd_valu_kernel(const gode_ode_fwd_op a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, tl = lane >> 4;
@@ -74,28 +32,16 @@ __global__ void __launch_bounds__(256) ode_fwd_valu_kernel(const gode_ode_fwd_op
   const int T = a.T;
   __shared__ float P[GODE_ODE_NPARAM];
   float y = valid ? a.x[n * 16 + i] : 0.f;
-  stage_params(a.p, a.prenet, P);
-  if (a.content) broadcast_content(a, n0);      // stores only; nothing below waits for them
+  stage_ode_params<256>(a.p, a.prenet, P);
+  if (a.content) broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, n0, 16, threadIdx.x, 256);
 
   int src[16];
   probe_sources(i, src);
-  if (a.prenet) {
-    // Linear(16,64) -> LReLU -> Linear(64,16) -> LReLU: the 64 hidden units as four row-resident chunks
-    float acc = P[VP_BB + i];
-#pragma unroll 1
-    for (int m = 0; m < 4; ++m) {
-      W16 wa, wb;
-      load_rows(wa, P + VP_WA, 16, 16 * m, 0, i, src);
-      load_rows(wb, P + VP_WB, 64, 0, 16 * m, i, src);
-      const float h = lrelu1(mv16(wa, y, P[VP_BA + 16 * m + i]));
-      acc = mv16(wb, h, acc);
-    }
-    y = lrelu1(acc);
-  }
+  if (a.prenet) y = prenet_fwd(P, y, i, src);
   W16 w1, w2;
-  load_rows(w1, P + VP_W1, 16, 0, 0, i, src);
-  load_rows(w2, P + VP_W2, 16, 0, 0, i, src);
-  const float b1 = P[VP_B1 + i], b2 = P[VP_B2 + i];
+  load_rows(w1, P + OFF_W1, 16, 0, 0, i, src);
+  load_rows(w2, P + OFF_W2, 16, 0, 0, i, src);
+  const float b1 = P[OFF_B1 + i], b2 = P[OFF_B2 + i];
   auto f = [&](float yy) { return mv16(w2, fast_tanh(mv16(w1, yy, b1)), b2); };
 
   const int tsel = (a.sel_t && valid) ? a.sel_t[n] : -1;
@@ -141,23 +87,7 @@ __global__ void __launch_bounds__(256) ode_fwd_valu_kernel(const gode_ode_fwd_op
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// adjoint backward (same parameter-block offsets as ode.hip / gode_ode_params order)
-#define VOFF_WA 0
-#define VOFF_BA 1024
-#define VOFF_WB 1088
-#define VOFF_BB 2112
-#define VOFF_W1 2128
-#define VOFF_B1 2384
-#define VOFF_W2 2400
-#define VOFF_B2 2656
-
-// sum over the 4 trajectories of a wave (lanes i, i+16, i+32, i+48), result in every lane
-__device__ __forceinline__ float sum_traj(float v) {
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
-
+// adjoint backward
 __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op a) {
   __shared__ float R[4][GODE_ODE_NPARAM];     // per-wave image of the gradient vector (combined once, at the end)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -173,17 +103,17 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
 #endif
 
   __shared__ float P[GODE_ODE_NPARAM];
-  stage_params(a.p, a.prenet, P);
+  stage_ode_params<256>(a.p, a.prenet, P);
   int src[16];
   probe_sources(i, src);
   W16 w1, w2, w1t, w2t, gW1, gW2;
-  load_rows(w1, P + VP_W1, 16, 0, 0, i, src);
-  load_rows(w2, P + VP_W2, 16, 0, 0, i, src);
-  load_cols(w1t, P + VP_W1, 16, 0, 0, i, src);
-  load_cols(w2t, P + VP_W2, 16, 0, 0, i, src);
+  load_rows(w1, P + OFF_W1, 16, 0, 0, i, src);
+  load_rows(w2, P + OFF_W2, 16, 0, 0, i, src);
+  load_cols(w1t, P + OFF_W1, 16, 0, 0, i, src);
+  load_cols(w2t, P + OFF_W2, 16, 0, 0, i, src);
 #pragma unroll
   for (int r = 0; r < 16; ++r) { gW1.w[r] = 0.f; gW2.w[r] = 0.f; }
-  const float b1 = P[VP_B1 + i], b2 = P[VP_B2 + i];
+  const float b1 = P[OFF_B1 + i], b2 = P[OFF_B2 + i];
   float gb1 = 0.f, gb2 = 0.f;
 
   const int tsel = (a.sel_t && valid) ? a.sel_t[n] : -1;
@@ -262,45 +192,45 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
     const float s = sum_traj(v);
     if (tl == 0) R[wave][off + i] = s;
   };
-  put_matrix(gW1, VOFF_W1, 16, 0, 0);
-  put_matrix(gW2, VOFF_W2, 16, 0, 0);
-  put_vector(gb1, VOFF_B1);
-  put_vector(gb2, VOFF_B2);
+  put_matrix(gW1, OFF_W1, 16, 0, 0);
+  put_matrix(gW2, OFF_W2, 16, 0, 0);
+  put_vector(gb1, OFF_B1);
+  put_vector(gb2, OFF_B2);
 
   // ---- pre-net backward; adj = dL/d(pre-net output)
   if (a.prenet) {
     float hpre[4];
-    float acc = P[VP_BB + i];
+    float acc = P[OFF_BB + i];
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       W16 wa, wb;
-      load_rows(wa, P + VP_WA, 16, 16 * m, 0, i, src);
-      load_rows(wb, P + VP_WB, 64, 0, 16 * m, i, src);
-      hpre[m] = mv16(wa, x, P[VP_BA + 16 * m + i]);
+      load_rows(wa, P + OFF_WA, 16, 16 * m, 0, i, src);
+      load_rows(wb, P + OFF_WB, 64, 0, 16 * m, i, src);
+      hpre[m] = mv16(wa, x, P[OFF_BA + 16 * m + i]);
       acc = mv16(wb, lrelu1(hpre[m]), acc);
     }
     const float g0 = acc > 0.f ? adj : 0.2f * adj;
-    put_vector(g0, VOFF_BB);
+    put_vector(g0, OFF_BB);
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       W16 G, wbt;
 #pragma unroll
       for (int r = 0; r < 16; ++r) G.w[r] = 0.f;
       outer16(G, g0, lrelu1(hpre[m]));                       // dWb[i][16m + j] = sum g0_i * lrelu(hpre)_j
-      put_matrix(G, VOFF_WB, 64, 0, 16 * m);
-      load_cols(wbt, P + VP_WB, 64, 0, 16 * m, i, src);      // (Wb chunk)^T
+      put_matrix(G, OFF_WB, 64, 0, 16 * m);
+      load_cols(wbt, P + OFF_WB, 64, 0, 16 * m, i, src);      // (Wb chunk)^T
       const float t = mv16(wbt, g0, 0.f);
       const float gh = hpre[m] > 0.f ? t : 0.2f * t;
-      put_vector(gh, VOFF_BA + 16 * m);
+      put_vector(gh, OFF_BA + 16 * m);
 #pragma unroll
       for (int r = 0; r < 16; ++r) G.w[r] = 0.f;
       outer16(G, gh, x);                                     // dWa[16m + i][j] = sum gh_i * x_j
-      put_matrix(G, VOFF_WA, 16, 16 * m, 0);
+      put_matrix(G, OFF_WA, 16, 16 * m, 0);
     }
   }
   __syncthreads();
   for (int k = threadIdx.x; k < GODE_ODE_NPARAM; k += 256)
-    part[k] = (k < VOFF_W1 && !a.prenet) ? 0.f : (R[0][k] + R[1][k]) + (R[2][k] + R[3][k]);
+    part[k] = (k < OFF_W1 && !a.prenet) ? 0.f : (R[0][k] + R[1][k]) + (R[2][k] + R[3][k]);
 #ifdef GODE_ODE_STAMPS
   st3 = __builtin_amdgcn_s_memtime();
   if (threadIdx.x == 0 && blockIdx.x == 0) {

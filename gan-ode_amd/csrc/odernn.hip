@@ -12,19 +12,12 @@
 //     the default (substeps == 0) integrates the adjoint adaptively with torchdiffeq's mixed norm, as odeint_adjoint does;
 //   * ode_dopri5_fwd_kernel: dopri5 for the plain Neural-ODE generators (gode_ode_fwd_op.method == 1).
 #include "ode_common.h"
+#include "dopri5.h"
 
 // trajectories per workgroup of the forward kernel (4 waves): keeps the kernel inside the register file -- a spilling
 // build needed scratch memory, whose (re)allocation by the runtime stalled the queue for ~75 ms at a time
 #define RNN_BLOCK_SAMPLES 64
 #define RNN_NPARAM 2176
-#define RO_W1 0
-#define RO_B1 256
-#define RO_W2 272
-#define RO_B2 528
-#define RO_WIH 544
-#define RO_WHH 1312
-#define RO_BIH 2080
-#define RO_BHH 2128
 
 // Workgroup sum, every thread gets the total (fixed order).  red[2][...] alternates per call, so ONE barrier per call
 // suffices: a wave can write slot set p again only after passing the barrier of the call in between, which every wave
@@ -91,27 +84,27 @@ __global__ void __launch_bounds__(RNN_BLOCK_SAMPLES * 4) odernn_fwd_kernel(const
     for (; steps < 100000; ++steps) {
       const float dt = (float)dtd;
       const f32x4 k1 = f0;
-      const f32x4 k2 = f(y0 + dt * (0.2f * k1));
-      const f32x4 k3 = f(y0 + dt * ((3.f / 40.f) * k1 + (9.f / 40.f) * k2));
-      const f32x4 k4 = f(y0 + dt * ((44.f / 45.f) * k1 + (-56.f / 15.f) * k2 + (32.f / 9.f) * k3));
-      const f32x4 k5 = f(y0 + dt * ((19372.f / 6561.f) * k1 + (-25360.f / 2187.f) * k2 + (64448.f / 6561.f) * k3 +
-                                    (-212.f / 729.f) * k4));
-      const f32x4 k6 = f(y0 + dt * ((9017.f / 3168.f) * k1 + (-355.f / 33.f) * k2 + (46732.f / 5247.f) * k3 +
-                                    (49.f / 176.f) * k4 + (-5103.f / 18656.f) * k5));
-      const f32x4 y1 = y0 + dt * ((35.f / 384.f) * k1 + (500.f / 1113.f) * k3 + (125.f / 192.f) * k4 +
-                                  (-2187.f / 6784.f) * k5 + (11.f / 84.f) * k6);
+      const f32x4 k2 = f(y0 + dt * (DP5_A21 * k1));
+      const f32x4 k3 = f(y0 + dt * (DP5_A31 * k1 + DP5_A32 * k2));
+      const f32x4 k4 = f(y0 + dt * (DP5_A41 * k1 + DP5_A42 * k2 + DP5_A43 * k3));
+      const f32x4 k5 = f(y0 + dt * (DP5_A51 * k1 + DP5_A52 * k2 + DP5_A53 * k3 +
+                                    DP5_A54 * k4));
+      const f32x4 k6 = f(y0 + dt * (DP5_A61 * k1 + DP5_A62 * k2 + DP5_A63 * k3 +
+                                    DP5_A64 * k4 + DP5_A65 * k5));
+      const f32x4 y1 = y0 + dt * (DP5_B1 * k1 + DP5_B3 * k3 + DP5_B4 * k4 +
+                                  DP5_B5 * k5 + DP5_B6 * k6);
       const f32x4 k7 = f(y1);
-      const f32x4 err = dt * ((35.f / 384.f - 1951.f / 21600.f) * k1 + (500.f / 1113.f - 22642.f / 50085.f) * k3 +
-                              (125.f / 192.f - 451.f / 720.f) * k4 + (-2187.f / 6784.f + 12231.f / 42400.f) * k5 +
-                              (11.f / 84.f - 649.f / 6300.f) * k6 + (-1.f / 60.f) * k7);
+      const f32x4 err = dt * (DP5_E1 * k1 + DP5_E3 * k3 +
+                              DP5_E4 * k4 + DP5_E5 * k5 +
+                              DP5_E6 * k6 + DP5_E7 * k7);
       const f32x4 tol = a.atol + a.rtol * max4(abs4(y0), abs4(y1));
       const float ratio = rms(err / tol);
       const bool accept = ratio <= 1.f;
       if (accept) {
         if (tcur + dtd >= 1.0) {   // dense output (4th-order fit through the mid-point) at t = 1
-          const f32x4 ymid = y0 + dt * ((6025192743.f / 30085553152.f / 2.f) * k1 + (51252292925.f / 65400821598.f / 2.f) * k3 +
-                                        (-2691868925.f / 45128329728.f / 2.f) * k4 + (187940372067.f / 1594534317056.f / 2.f) * k5 +
-                                        (-1776094331.f / 19743644256.f / 2.f) * k6 + (11237099.f / 235043384.f / 2.f) * k7);
+          const f32x4 ymid = y0 + dt * (DP5_C1 * k1 + DP5_C3 * k3 +
+                                        DP5_C4 * k4 + DP5_C5 * k5 +
+                                        DP5_C6 * k6 + DP5_C7 * k7);
           const f32x4 ca = 2.f * dt * (k7 - k1) - 8.f * (y1 + y0) + 16.f * ymid;
           const f32x4 cb = dt * (5.f * k1 - 3.f * k7) + 18.f * y0 + 14.f * y1 - 32.f * ymid;
           const f32x4 cc = dt * (k7 - 4.f * k1) - 11.f * y0 - 5.f * y1 + 16.f * ymid;
@@ -220,25 +213,25 @@ __global__ void __launch_bounds__(RNN_BLOCK_SAMPLES * 4) ode_dopri5_fwd_kernel(c
     while (target > seg1 && steps < 1000000) {
       const float dt = (float)dtd;
       const f32x4 k1 = f0;
-      const f32x4 k2 = f(y0 + dt * (0.2f * k1));
-      const f32x4 k3 = f(y0 + dt * ((3.f / 40.f) * k1 + (9.f / 40.f) * k2));
-      const f32x4 k4 = f(y0 + dt * ((44.f / 45.f) * k1 + (-56.f / 15.f) * k2 + (32.f / 9.f) * k3));
-      const f32x4 k5 = f(y0 + dt * ((19372.f / 6561.f) * k1 + (-25360.f / 2187.f) * k2 + (64448.f / 6561.f) * k3 +
-                                    (-212.f / 729.f) * k4));
-      const f32x4 k6 = f(y0 + dt * ((9017.f / 3168.f) * k1 + (-355.f / 33.f) * k2 + (46732.f / 5247.f) * k3 +
-                                    (49.f / 176.f) * k4 + (-5103.f / 18656.f) * k5));
-      const f32x4 y1 = y0 + dt * ((35.f / 384.f) * k1 + (500.f / 1113.f) * k3 + (125.f / 192.f) * k4 +
-                                  (-2187.f / 6784.f) * k5 + (11.f / 84.f) * k6);
+      const f32x4 k2 = f(y0 + dt * (DP5_A21 * k1));
+      const f32x4 k3 = f(y0 + dt * (DP5_A31 * k1 + DP5_A32 * k2));
+      const f32x4 k4 = f(y0 + dt * (DP5_A41 * k1 + DP5_A42 * k2 + DP5_A43 * k3));
+      const f32x4 k5 = f(y0 + dt * (DP5_A51 * k1 + DP5_A52 * k2 + DP5_A53 * k3 +
+                                    DP5_A54 * k4));
+      const f32x4 k6 = f(y0 + dt * (DP5_A61 * k1 + DP5_A62 * k2 + DP5_A63 * k3 +
+                                    DP5_A64 * k4 + DP5_A65 * k5));
+      const f32x4 y1 = y0 + dt * (DP5_B1 * k1 + DP5_B3 * k3 + DP5_B4 * k4 +
+                                  DP5_B5 * k5 + DP5_B6 * k6);
       const f32x4 k7 = f(y1);
-      const f32x4 err = dt * ((35.f / 384.f - 1951.f / 21600.f) * k1 + (500.f / 1113.f - 22642.f / 50085.f) * k3 +
-                              (125.f / 192.f - 451.f / 720.f) * k4 + (-2187.f / 6784.f + 12231.f / 42400.f) * k5 +
-                              (11.f / 84.f - 649.f / 6300.f) * k6 + (-1.f / 60.f) * k7);
+      const f32x4 err = dt * (DP5_E1 * k1 + DP5_E3 * k3 +
+                              DP5_E4 * k4 + DP5_E5 * k5 +
+                              DP5_E6 * k6 + DP5_E7 * k7);
       const f32x4 tol = atol + rtol * max4(abs4(y0), abs4(y1));
       const float ratio = rms(err / tol);
       if (ratio <= 1.f) {
-        const f32x4 ymid = y0 + dt * ((6025192743.f / 30085553152.f / 2.f) * k1 + (51252292925.f / 65400821598.f / 2.f) * k3 +
-                                      (-2691868925.f / 45128329728.f / 2.f) * k4 + (187940372067.f / 1594534317056.f / 2.f) * k5 +
-                                      (-1776094331.f / 19743644256.f / 2.f) * k6 + (11237099.f / 235043384.f / 2.f) * k7);
+        const f32x4 ymid = y0 + dt * (DP5_C1 * k1 + DP5_C3 * k3 +
+                                      DP5_C4 * k4 + DP5_C5 * k5 +
+                                      DP5_C6 * k6 + DP5_C7 * k7);
         ca = 2.f * dt * (k7 - k1) - 8.f * (y1 + y0) + 16.f * ymid;
         cb = dt * (5.f * k1 - 3.f * k7) + 18.f * y0 + 14.f * y1 - 32.f * ymid;
         cc = dt * (k7 - 4.f * k1) - 11.f * y0 - 5.f * y1 + 16.f * ymid;
@@ -401,14 +394,6 @@ __global__ void __launch_bounds__(64) odernn_bwd_kernel(const gode_odernn_bwd_op
   }
 }
 
-__global__ void __launch_bounds__(256) odernn_bwd_reduce_kernel(const float* work, float* grads, int nblk, int accumulate) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= RNN_NPARAM) return;
-  float sacc = 0.f;
-  for (int b = 0; b < nblk; ++b) sacc += work[(int64_t)b * RNN_NPARAM + i];
-  grads[i] = accumulate ? grads[i] + sacc : sacc;
-}
-
 int gode_launch_odernn_bwd_adaptive(const gode_odernn_bwd_op* op, hipStream_t st);   // adj_adaptive.hip
 
 // substeps > 0: fixed Kutta-3/8 substeps; substeps == 0: the MFMA adaptive adjoint (norm per 64-trajectory workgroup), only
@@ -422,8 +407,5 @@ int gode_launch_odernn_bwd_mfma(const gode_odernn_bwd_op* op, hipStream_t st) {
     hipLaunchKernelGGL(odernn_bwd_kernel, dim3(nblk), dim3(64), 0, st, *op);
     GODE_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(odernn_bwd_reduce_kernel, dim3((RNN_NPARAM + 255) / 256), dim3(256), 0, st, op->work, op->grads, nblk,
-                     op->accumulate);
-  GODE_LAUNCH_CHECK();
-  return 0;
+  return gode_reduce_rows(op->work, op->grads, nblk, RNN_NPARAM, 0, 0, op->accumulate, nullptr, INT32_MAX, 1, st);   // one level
 }

@@ -29,148 +29,25 @@
 #include "common.h"
 #include "ode_common.h"
 #include "valu_common.h"
+#include "dopri5.h"
 
 #ifndef RV_WAVES
 #define RV_WAVES 8                   // (scripts/exp/odernn_waves.sh builds 4 to measure one wave per SIMD)
 #endif
 #define RV_TRAJ (4 * RV_WAVES)
 #define RV_THREADS (64 * RV_WAVES)
-#define RV_MAX_JOBS 8
+#define RV_MAX_JOBS GODE_MAX_JOBS
 #define RV_MAX_WGS (GODE_ODERNN_SYNC_MAX_N / RV_TRAJ)
 #define RV_MAX_TRIALS 20000          // per frame; torchdiffeq's max_num_steps is 2^31 - 1
-#define XS_VALS 8
-#define XS_HDR 16
+#define XS_VALS 8                    // floats per exchange slot of the forward kernels
 
-#define RO_W1 0
-#define RO_B1 256
-#define RO_W2 272
-#define RO_B2 528
-#define RO_WIH 544
-#define RO_WHH 1312
-#define RO_BIH 2080
-#define RO_BHH 2128
 #define RO_N 2176
 #define RP_M 2176
 #define RP_C 2432
 #define RP_N 2448
 
-// ---- dopri5 tableau (torchdiffeq _DORMAND_PRINCE_SHAMPINE_TABLEAU) ---------------------------------------------------
-#define A21 (1.f / 5.f)
-#define A31 (3.f / 40.f)
-#define A32 (9.f / 40.f)
-#define A41 (44.f / 45.f)
-#define A42 (-56.f / 15.f)
-#define A43 (32.f / 9.f)
-#define A51 (19372.f / 6561.f)
-#define A52 (-25360.f / 2187.f)
-#define A53 (64448.f / 6561.f)
-#define A54 (-212.f / 729.f)
-#define A61 (9017.f / 3168.f)
-#define A62 (-355.f / 33.f)
-#define A63 (46732.f / 5247.f)
-#define A64 (49.f / 176.f)
-#define A65 (-5103.f / 18656.f)
-#define B1 (35.f / 384.f)
-#define B3 (500.f / 1113.f)
-#define B4 (125.f / 192.f)
-#define B5 (-2187.f / 6784.f)
-#define B6 (11.f / 84.f)
-#define E1 (35.f / 384.f - 1951.f / 21600.f)
-#define E3 (500.f / 1113.f - 22642.f / 50085.f)
-#define E4 (125.f / 192.f - 451.f / 720.f)
-#define E5 (-2187.f / 6784.f + 12231.f / 42400.f)
-#define E6 (11.f / 84.f - 649.f / 6300.f)
-#define E7 (-1.f / 60.f)
-#define C1 (6025192743.f / 30085553152.f / 2.f)
-#define C3 (51252292925.f / 65400821598.f / 2.f)
-#define C4 (-2691868925.f / 45128329728.f / 2.f)
-#define C5 (187940372067.f / 1594534317056.f / 2.f)
-#define C6 (-1776094331.f / 19743644256.f / 2.f)
-#define C7 (11237099.f / 235043384.f / 2.f)
-
-// x^p through the hardware log2 / exp2 units (1 ulp each): the step-size controller needs 3-4 digits
-__device__ __forceinline__ float fast_pow(float x, float p) { return __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(x)); }
-
-// torchdiffeq _optimal_step_size (order 5): safety 0.9, ifactor 10, dfactor 0.2; a step with ratio < 1 never shrinks
-__device__ __forceinline__ float step_factor(float ratio) {
-  if (ratio == 0.f) return 10.f;
-  const float f = 0.9f * fast_pow(ratio, -0.2f);
-  return fminf(10.f, fmaxf(f, ratio < 1.f ? 1.f : 0.2f));
-}
-// weights of the 4th-order interpolant at abscissa x in terms of (y1 - y0, ymid - y0, dt f0, dt f1)
-__device__ __forceinline__ void interp_weights(float x, float& wS, float& wM, float& w1c, float& w7c) {
-  const float x2 = x * x, x3 = x2 * x, x4 = x3 * x;
-  wS = -8.f * x4 + 14.f * x3 - 5.f * x2;
-  wM = 16.f * x4 - 32.f * x3 + 16.f * x2;
-  w1c = -2.f * x4 + 5.f * x3 - 4.f * x2 + x;
-  w7c = 2.f * x4 - 3.f * x3 + x2;
-}
-
-// ---- whole-batch sums ------------------------------------------------------------------------------------------------
-struct XSync {
-  int* counter;     // sync[0]: arrivals so far, over all exchanges of the launch
-  float* slots;     // sync + XS_HDR: [2][nwg][XS_VALS] partial sums, double-buffered by exchange parity
-  int nwg, wg, seq;
-};
-struct RedLds {
-  float red[2][RV_WAVES][XS_VALS];   // per-wave partials, double-buffered: one barrier per sum
-  float bc[2][XS_VALS];              // cross-workgroup totals broadcast to the workgroup
-  int dead;                          // a spin timed out somewhere: every thread of the workgroup bails out
-};
-
-// v[0..K): per-thread values -> the sums over ALL threads of ALL workgroups of the call, in every thread, fixed order.
-template <int K>
-__device__ __forceinline__ void batch_sum(float* v, RedLds* R, int& par, XSync& X) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) R->red[par][wave][k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < RV_WAVES; ++w) s += R->red[par][w][k];
-    v[k] = s;
-  }
-  if (X.nwg > 1) {
-    float* slot = X.slots + (size_t)(X.seq & 1) * X.nwg * XS_VALS;
-    if (wave == 0) {
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) __hip_atomic_store(&slot[X.wg * XS_VALS + k], v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(X.counter, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        const int target = (X.seq + 1) * X.nwg;
-        int spins = 0;
-        while (__hip_atomic_load(X.counter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) {
-          __builtin_amdgcn_s_sleep(2);
-          if (++spins > (1 << 20)) { R->dead = 1; break; }     // ~seconds: a workgroup of the call never arrived
-        }
-      }
-      float t[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) t[k] = 0.f;
-      for (int w = lane; w < X.nwg; w += 64) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) t[k] += __hip_atomic_load(&slot[w * XS_VALS + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-#pragma unroll
-      for (int k = 0; k < K; ++k) t[k] = wave_sum(t[k]);
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) R->bc[par][k] = t[k];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = R->bc[par][k];
-    X.seq += 1;
-  }
-  par ^= 1;
-}
+// whole-batch sums (valu_common.h:batch_sum): the per-wave partials added one after the other
+typedef RedLds<RV_WAVES, XS_VALS> RnnRed;
 
 // Stage all 2,176 parameters in LDS with one round of coalesced loads, then M = W1 W2 and c = W1 b2 (fp64 accumulation).
 __device__ __forceinline__ void stage_rnn_params(const gode_odernn_params& p, float* P, bool fused) {
@@ -198,29 +75,11 @@ __device__ __forceinline__ void stage_rnn_params(const gode_odernn_params& p, fl
   }
 }
 
-// content columns 16..65 (the same 50 values on all rows of a trajectory) + zero pad for this workgroup's trajectories
-__device__ __forceinline__ void rnn_broadcast_content(const float* content, float* z, const int32_t* sel_t, int N, int T, int zcols, int n0) {
-  const int rows_per = sel_t ? 1 : T;
-  const int q4 = (zcols - 16) >> 2;
-  const int total4 = RV_TRAJ * rows_per * q4;
-  for (int k = threadIdx.x; k < total4; k += RV_THREADS) {
-    const int rr = k / q4, q = k - rr * q4;
-    const int ns = rr / rows_per, tt = rr - ns * rows_per;
-    if (n0 + ns < N) {
-      const float* c = content + (int64_t)(n0 + ns) * 50 + 4 * q;
-      f32x4 v = zero4();
-      if (q < 12) v = f32x4{c[0], c[1], c[2], c[3]};
-      else if (q == 12) v = f32x4{c[0], c[1], 0.f, 0.f};
-      *reinterpret_cast<f32x4*>(z + ((int64_t)(n0 + ns) * rows_per + tt) * zcols + 16 + 4 * q) = v;
-    }
-  }
-}
-
 struct RnnFwdJobs { gode_odernn_fwd_op op[RV_MAX_JOBS]; int32_t nblk[RV_MAX_JOBS]; int32_t count; };
 
 __global__ void __launch_bounds__(RV_THREADS) odernn_fwd_valu_kernel(const RnnFwdJobs J) {
   __shared__ float P[RP_N];
-  __shared__ RedLds R;
+  __shared__ RnnRed R;
   int job = 0, wg = blockIdx.x;
   while (job + 1 < J.count && wg >= J.nblk[job]) { wg -= J.nblk[job]; ++job; }
   const gode_odernn_fwd_op a = J.op[job];
@@ -243,7 +102,7 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_fwd_valu_kernel(const RnnFw
 #endif
   float h = valid ? a.noise[(int64_t)n * 16 + i] : 0.f;
   stage_rnn_params(a.p, P, true);
-  if (a.content) rnn_broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, n0);      // stores only
+  if (a.content) broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, n0, RV_TRAJ, threadIdx.x, RV_THREADS);      // stores only
 
   int src[16];
   probe_sources(i, src);
@@ -282,12 +141,12 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_fwd_valu_kernel(const RnnFw
       const float f0 = mv16c(w2, h1, b2);
       const float sc = atol + fabsf(y0) * rtol;
       float v[2] = {valid ? (y0 / sc) * (y0 / sc) : 0.f, valid ? (f0 / sc) * (f0 / sc) : 0.f};
-      batch_sum<2>(v, &R, par, X);
+      batch_sum<2>(v, R, par, X);
       const float d0 = sqrtf(v[0] * inv_count), d1 = sqrtf(v[1] * inv_count);
       const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
       const float df = mv16c(w2, fast_tanh(fmaf(h0, q1, u0)) - h1, 0.f);          // f(y0 + h0 f0) - f0
       float w[1] = {valid ? (df / sc) * (df / sc) : 0.f};
-      batch_sum<1>(w, &R, par, X);
+      batch_sum<1>(w, R, par, X);
       const float d2 = sqrtf(w[0] * inv_count) / h0;
       const float hh = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : fast_pow(0.01f / fmaxf(d1, d2), 0.2f);
       dtd = (double)fminf(100.f * h0, hh);
@@ -302,24 +161,24 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_fwd_valu_kernel(const RnnFw
       const long long sA = __builtin_amdgcn_s_memtime();
 #endif
       const float dt = (float)dtd;
-      const float h2 = fast_tanh(fmaf(dt * A21, q1, u0));
+      const float h2 = fast_tanh(fmaf(dt * DP5_A21, q1, u0));
       const float q2 = mv16c(Mw, h2, cq);
-      const float h3 = fast_tanh(fmaf(dt, A31 * q1 + A32 * q2, u0));
+      const float h3 = fast_tanh(fmaf(dt, DP5_A31 * q1 + DP5_A32 * q2, u0));
       const float q3 = mv16c(Mw, h3, cq);
-      const float h4 = fast_tanh(fmaf(dt, A41 * q1 + A42 * q2 + A43 * q3, u0));
+      const float h4 = fast_tanh(fmaf(dt, DP5_A41 * q1 + DP5_A42 * q2 + DP5_A43 * q3, u0));
       const float q4 = mv16c(Mw, h4, cq);
-      const float h5 = fast_tanh(fmaf(dt, A51 * q1 + A52 * q2 + A53 * q3 + A54 * q4, u0));
+      const float h5 = fast_tanh(fmaf(dt, DP5_A51 * q1 + DP5_A52 * q2 + DP5_A53 * q3 + DP5_A54 * q4, u0));
       const float q5 = mv16c(Mw, h5, cq);
-      const float h6 = fast_tanh(fmaf(dt, A61 * q1 + A62 * q2 + A63 * q3 + A64 * q4 + A65 * q5, u0));
+      const float h6 = fast_tanh(fmaf(dt, DP5_A61 * q1 + DP5_A62 * q2 + DP5_A63 * q3 + DP5_A64 * q4 + DP5_A65 * q5, u0));
       const float q6 = mv16c(Mw, h6, cq);
-      const float u7 = fmaf(dt, B1 * q1 + B3 * q3 + B4 * q4 + B5 * q5 + B6 * q6, u0);
+      const float u7 = fmaf(dt, DP5_B1 * q1 + DP5_B3 * q3 + DP5_B4 * q4 + DP5_B5 * q5 + DP5_B6 * q6, u0);
       const float h7 = fast_tanh(u7);
 #ifdef GODE_ODE_STAMPS
       asm volatile("" ::"v"(h7));
       const long long sB = __builtin_amdgcn_s_memtime();
 #endif
-      const float Hb = B1 * h1 + B3 * h3 + B4 * h4 + B5 * h5 + B6 * h6;
-      const float He = E1 * h1 + E3 * h3 + E4 * h4 + E5 * h5 + E6 * h6 + E7 * h7;
+      const float Hb = DP5_B1 * h1 + DP5_B3 * h3 + DP5_B4 * h4 + DP5_B5 * h5 + DP5_B6 * h6;
+      const float He = DP5_E1 * h1 + DP5_E3 * h3 + DP5_E4 * h4 + DP5_E5 * h5 + DP5_E6 * h6 + DP5_E7 * h7;
       const float y1 = fmaf(dt, mv16c(w2, Hb, b2), y0);
       const float err = dt * mv16c(w2, He, 0.f);
       const float tol = atol + rtol * fmaxf(fabsf(y0), fabsf(y1));
@@ -330,7 +189,7 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_fwd_valu_kernel(const RnnFw
       asm volatile("" ::"v"(q7), "v"(v[0]));
       const long long sC = __builtin_amdgcn_s_memtime();
 #endif
-      batch_sum<1>(v, &R, par, X);
+      batch_sum<1>(v, R, par, X);
       const float ratio = sqrtf(v[0] * inv_count);
       ++steps;
 #ifdef GODE_ODE_STAMPS
@@ -346,7 +205,7 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_fwd_valu_kernel(const RnnFw
           const float x = (float)((1.0 - tcur) / dtd);
           float wS, wM, w1c, w7c;
           interp_weights(x, wS, wM, w1c, w7c);
-          const float Hm = C1 * h1 + C3 * h3 + C4 * h4 + C5 * h5 + C6 * h6 + C7 * h7;
+          const float Hm = DP5_C1 * h1 + DP5_C3 * h3 + DP5_C4 * h4 + DP5_C5 * h5 + DP5_C6 * h6 + DP5_C7 * h7;
           const float Hx = wS * Hb + wM * Hm + w1c * h1 + w7c * h7;
           yend = fmaf(dt, mv16c(w2, Hx, b2 * (wS + 0.5f * wM + w1c + w7c)), y0);
           break;
@@ -445,11 +304,6 @@ extern "C" int gode_odernn_fwd(const gode_odernn_fwd_op* op, void* stream) { ret
 // the A operand is scaled by the tableau weight), the waves' images meet in LDS once for the norm, and each thread owns
 // two elements of the workgroup total, so the accepted state's total stays in registers.
 // =================================================================================================================
-#define TH_W1 0
-#define TH_B1 256
-#define TH_W2 272
-#define TH_B2 528
-#define TH_N 544
 #define GP_LD 17                     // padded row stride of the GRU matrices in LDS (conflict-free row / column gathers)
 #define GP_WIH 0
 #define GP_WHH (48 * GP_LD)
@@ -471,7 +325,7 @@ struct AdjV {
   int i, tl, wave, lane;
   bool valid;
   AdjLdsV* L;
-  RedLds* R;
+  RnnRed* R;
   XSync X;
   float* xslots;                     // sync + XS_HDR: [2][nwg][XB_VALS]
   int par;
@@ -509,15 +363,6 @@ struct AdjV {
 #pragma unroll
     for (int w = 0; w < RV_WAVES; ++w) t += L->img[w][slot][e];
     return t;
-  }
-  __device__ __forceinline__ void arrive_and_wait() {     // thread 0 only
-    __hip_atomic_fetch_add(X.counter, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    const int target = (X.seq + 1) * X.nwg;
-    int spins = 0;
-    while (__hip_atomic_load(X.counter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) {
-      __builtin_amdgcn_s_sleep(2);
-      if (++spins > (1 << 20)) { R->dead = 1; break; }
-    }
   }
   // torchdiffeq's mixed norm of an augmented vector: its y / a parts per lane (vy, va, already divided by their scale), its
   // theta part as the per-wave images in LDS -- mode 0: slot 0 = V, scale = atol + rtol |G|;  mode 1: slot 0 = E, slot 1 = S,
@@ -561,7 +406,7 @@ struct AdjV {
       }
       if (threadIdx.x == 0) { mine[2 * TH_N] = v[0]; mine[2 * TH_N + 1] = v[1]; }
       __syncthreads();                     // (waits for every thread's stores; thread 0's release then publishes them)
-      if (threadIdx.x == 0) arrive_and_wait();
+      if (threadIdx.x == 0) xs_arrive_and_wait(X, &R->dead);
       __syncthreads();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       float s0 = 0.f, s1 = 0.f;
@@ -632,7 +477,7 @@ struct AdjV {
         if (e < TH_N) slot[(size_t)X.wg * XB_VALS + e] = V[k];
       }
       __syncthreads();
-      if (threadIdx.x == 0) arrive_and_wait();
+      if (threadIdx.x == 0) xs_arrive_and_wait(X, &R->dead);
       __syncthreads();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       V[0] = V[1] = 0.f;
@@ -686,29 +531,29 @@ struct AdjV {
       const float dt = (float)dtd;
       Acc4 S, E, M;
       acc_zero(S); acc_zero(E); acc_zero(M);
-      theta_acc(S, B1, a0, h1, du1, y0); theta_acc(E, E1, a0, h1, du1, y0); theta_acc(M, C1, a0, h1, du1, y0);
+      theta_acc(S, DP5_B1, a0, h1, du1, y0); theta_acc(E, DP5_E1, a0, h1, du1, y0); theta_acc(M, DP5_C1, a0, h1, du1, y0);
       float h, du, ys, as;
-      ys = fmaf(dt * A21, k1y, y0); as = fmaf(dt * A21, k1a, a0);
+      ys = fmaf(dt * DP5_A21, k1y, y0); as = fmaf(dt * DP5_A21, k1a, a0);
       float k2y, k2a; eval(ys, as, k2y, k2a, h, du);                        // stage 2 has zero weight in S, E, M
-      ys = fmaf(dt, A31 * k1y + A32 * k2y, y0); as = fmaf(dt, A31 * k1a + A32 * k2a, a0);
+      ys = fmaf(dt, DP5_A31 * k1y + DP5_A32 * k2y, y0); as = fmaf(dt, DP5_A31 * k1a + DP5_A32 * k2a, a0);
       float k3y, k3a; eval(ys, as, k3y, k3a, h, du);
-      theta_acc(S, B3, as, h, du, ys); theta_acc(E, E3, as, h, du, ys); theta_acc(M, C3, as, h, du, ys);
-      ys = fmaf(dt, A41 * k1y + A42 * k2y + A43 * k3y, y0); as = fmaf(dt, A41 * k1a + A42 * k2a + A43 * k3a, a0);
+      theta_acc(S, DP5_B3, as, h, du, ys); theta_acc(E, DP5_E3, as, h, du, ys); theta_acc(M, DP5_C3, as, h, du, ys);
+      ys = fmaf(dt, DP5_A41 * k1y + DP5_A42 * k2y + DP5_A43 * k3y, y0); as = fmaf(dt, DP5_A41 * k1a + DP5_A42 * k2a + DP5_A43 * k3a, a0);
       float k4y, k4a; eval(ys, as, k4y, k4a, h, du);
-      theta_acc(S, B4, as, h, du, ys); theta_acc(E, E4, as, h, du, ys); theta_acc(M, C4, as, h, du, ys);
-      ys = fmaf(dt, A51 * k1y + A52 * k2y + A53 * k3y + A54 * k4y, y0); as = fmaf(dt, A51 * k1a + A52 * k2a + A53 * k3a + A54 * k4a, a0);
+      theta_acc(S, DP5_B4, as, h, du, ys); theta_acc(E, DP5_E4, as, h, du, ys); theta_acc(M, DP5_C4, as, h, du, ys);
+      ys = fmaf(dt, DP5_A51 * k1y + DP5_A52 * k2y + DP5_A53 * k3y + DP5_A54 * k4y, y0); as = fmaf(dt, DP5_A51 * k1a + DP5_A52 * k2a + DP5_A53 * k3a + DP5_A54 * k4a, a0);
       float k5y, k5a; eval(ys, as, k5y, k5a, h, du);
-      theta_acc(S, B5, as, h, du, ys); theta_acc(E, E5, as, h, du, ys); theta_acc(M, C5, as, h, du, ys);
-      ys = fmaf(dt, A61 * k1y + A62 * k2y + A63 * k3y + A64 * k4y + A65 * k5y, y0);
-      as = fmaf(dt, A61 * k1a + A62 * k2a + A63 * k3a + A64 * k4a + A65 * k5a, a0);
+      theta_acc(S, DP5_B5, as, h, du, ys); theta_acc(E, DP5_E5, as, h, du, ys); theta_acc(M, DP5_C5, as, h, du, ys);
+      ys = fmaf(dt, DP5_A61 * k1y + DP5_A62 * k2y + DP5_A63 * k3y + DP5_A64 * k4y + DP5_A65 * k5y, y0);
+      as = fmaf(dt, DP5_A61 * k1a + DP5_A62 * k2a + DP5_A63 * k3a + DP5_A64 * k4a + DP5_A65 * k5a, a0);
       float k6y, k6a; eval(ys, as, k6y, k6a, h, du);
-      theta_acc(S, B6, as, h, du, ys); theta_acc(E, E6, as, h, du, ys); theta_acc(M, C6, as, h, du, ys);
-      const float y1 = fmaf(dt, B1 * k1y + B3 * k3y + B4 * k4y + B5 * k5y + B6 * k6y, y0);
-      const float a1 = fmaf(dt, B1 * k1a + B3 * k3a + B4 * k4a + B5 * k5a + B6 * k6a, a0);
+      theta_acc(S, DP5_B6, as, h, du, ys); theta_acc(E, DP5_E6, as, h, du, ys); theta_acc(M, DP5_C6, as, h, du, ys);
+      const float y1 = fmaf(dt, DP5_B1 * k1y + DP5_B3 * k3y + DP5_B4 * k4y + DP5_B5 * k5y + DP5_B6 * k6y, y0);
+      const float a1 = fmaf(dt, DP5_B1 * k1a + DP5_B3 * k3a + DP5_B4 * k4a + DP5_B5 * k5a + DP5_B6 * k6a, a0);
       float k7y, k7a, h7, du7; eval(y1, a1, k7y, k7a, h7, du7);
-      theta_acc(E, E7, a1, h7, du7, y1); theta_acc(M, C7, a1, h7, du7, y1);
-      const float erry = dt * (E1 * k1y + E3 * k3y + E4 * k4y + E5 * k5y + E6 * k6y + E7 * k7y);
-      const float erra = dt * (E1 * k1a + E3 * k3a + E4 * k4a + E5 * k5a + E6 * k6a + E7 * k7a);
+      theta_acc(E, DP5_E7, a1, h7, du7, y1); theta_acc(M, DP5_C7, a1, h7, du7, y1);
+      const float erry = dt * (DP5_E1 * k1y + DP5_E3 * k3y + DP5_E4 * k4y + DP5_E5 * k5y + DP5_E6 * k6y + DP5_E7 * k7y);
+      const float erra = dt * (DP5_E1 * k1a + DP5_E3 * k3a + DP5_E4 * k4a + DP5_E5 * k5a + DP5_E6 * k6a + DP5_E7 * k7a);
       put_image(0, E, dt);
       put_image(1, S, dt);
       const float toly = atol + rtol * fmaxf(fabsf(y0), fabsf(y1)), tola = atol + rtol * fmaxf(fabsf(a0), fabsf(a1));
@@ -722,7 +567,7 @@ struct AdjV {
           const float x = ((float)tau1 - (float)tcur) / ((float)(tcur + dtd) - (float)tcur);
           float wS, wM, w1c, w7c;
           interp_weights(x, wS, wM, w1c, w7c);
-          const float dmid = C1 * k1a + C3 * k3a + C4 * k4a + C5 * k5a + C6 * k6a + C7 * k7a;
+          const float dmid = DP5_C1 * k1a + DP5_C3 * k3a + DP5_C4 * k4a + DP5_C5 * k5a + DP5_C6 * k6a + DP5_C7 * k7a;
           const float aend = a0 + wS * (a1 - a0) + dt * (wM * dmid + w1c * k1a + w7c * k7a);
           Acc4 dG;
           dG.W1 = wS * S.W1 + wM * M.W1; dG.W2 = wS * S.W2 + wM * M.W2;
@@ -749,7 +594,7 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_bwd_valu_kernel(const RnnBw
   __shared__ float P[TH_N + 96];       // W1, b1, W2, b2 (gradient-vector order), bih, bhh
   __shared__ float GP[GP_N];           // Wih, Whh with padded rows
   __shared__ AdjLdsV lds;
-  __shared__ RedLds R;
+  __shared__ RnnRed R;
   int job = 0, wg = blockIdx.x;
   while (job + 1 < J.count && wg >= J.nblk[job]) { wg -= J.nblk[job]; ++job; }
   const gode_odernn_bwd_op a = J.op[job];
@@ -866,7 +711,7 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_bwd_valu_kernel(const RnnBw
   }
   // ---- output: a launch of ONE workgroup writes (or adds to) grads directly; otherwise every workgroup writes one row of
   // its op's `work` (the ODEFunc block holds the BATCH total in every workgroup of an op: row 0 carries it, the other rows
-  // carry zeros) and odernn_bwd_rows_kernel adds the rows in fixed order
+  // carry zeros) and latent_rows_kernel adds the rows in fixed order
   float* out = J.direct ? a.grads : a.work + (int64_t)wg * RO_N;
   const bool direct_acc = J.direct && a.accumulate;
   __syncthreads();
@@ -885,17 +730,6 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_bwd_valu_kernel(const RnnBw
       out[dst] = direct_acc ? out[dst] + v : v;
     }
   }
-}
-
-// rows of `work` (one per workgroup; the ops that share a grads pointer, in array order) -> grads, fixed order
-struct RowsArgs { const float* work[RV_MAX_JOBS]; int32_t rows[RV_MAX_JOBS]; int32_t count, accumulate; float* grads; };
-__global__ void __launch_bounds__(256) odernn_bwd_rows_kernel(const RowsArgs A) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= RO_N) return;
-  float s = 0.f;
-  for (int j = 0; j < A.count; ++j)
-    for (int b = 0; b < A.rows[j]; ++b) s += A.work[j][(int64_t)b * RO_N + k];
-  A.grads[k] = A.accumulate ? A.grads[k] + s : s;
 }
 
 int gode_launch_odernn_bwd_mfma(const gode_odernn_bwd_op* op, hipStream_t st);   // odernn.hip: fixed substeps / fallback
@@ -928,18 +762,10 @@ static int rnn_bwd_launch(const gode_odernn_bwd_op* ops, int count, hipStream_t 
   hipLaunchKernelGGL(odernn_bwd_valu_kernel, dim3(grid), dim3(RV_THREADS), 0, st, J);
   GODE_LAUNCH_CHECK();
   if (J.direct) return 0;
-  bool done[RV_MAX_JOBS] = {false};
-  for (int k = 0; k < count; ++k) {
-    if (done[k]) continue;
-    RowsArgs A;
-    A.count = 0; A.grads = ops[k].grads; A.accumulate = ops[k].accumulate;     // later ops of the group add by construction
-    for (int j = k; j < count; ++j) {
-      if (!done[j] && ops[j].grads == ops[k].grads) { A.work[A.count] = ops[j].work; A.rows[A.count] = J.nblk[j]; A.count += 1; done[j] = true; }
-    }
-    hipLaunchKernelGGL(odernn_bwd_rows_kernel, dim3((RO_N + 255) / 256), dim3(256), 0, st, A);
-    GODE_LAUNCH_CHECK();
-  }
-  return 0;
+  return gode_for_each_grads_group(ops, J.nblk, count, [&](RowsArgs& A) {
+    A.nparam = RO_N; A.first = 0;
+    return gode_launch_rows(A, st);
+  });
 }
 
 extern "C" int gode_odernn_bwd_multi(const gode_odernn_bwd_op* ops, int32_t count, void* stream) {
@@ -977,35 +803,16 @@ extern "C" int gode_odernn_bwd(const gode_odernn_bwd_op* op, void* stream) { ret
 // whole-batch norm and multi-solve launches as the ODE-RNN kernels above; the round-2 MFMA kernels (odernn.hip,
 // adj_adaptive.hip) remain above GODE_ODERNN_SYNC_MAX_N trajectories per launch.
 // =================================================================================================================
-#define DP_WA 0
-#define DP_BA 1024
-#define DP_WB 1088
-#define DP_BB 2112
-#define DP_W1 2128
-#define DP_B1 2384
-#define DP_W2 2400
-#define DP_B2 2656
+// LDS image: the gode_ode_params block (OFF_*), then M = W1 W2 and c = W1 b2
 #define DP_M GODE_ODE_NPARAM
 #define DP_C (GODE_ODE_NPARAM + 256)
 #define DP_N (GODE_ODE_NPARAM + 272)
-
-__device__ __forceinline__ void stage_ode_params(const gode_ode_params& p, int prenet, float* P) {
-  const int t = threadIdx.x;
-  if (prenet) {
-    for (int k = t; k < 1024; k += RV_THREADS) { P[DP_WA + k] = p.Wa[k]; P[DP_WB + k] = p.Wb[k]; }
-    if (t < 64) P[DP_BA + t] = p.ba[t];
-    if (t < 16) P[DP_BB + t] = p.bb[t];
-  }
-  for (int k = t; k < 256; k += RV_THREADS) { P[DP_W1 + k] = p.W1[k]; P[DP_W2 + k] = p.W2[k]; }
-  if (t < 16) { P[DP_B1 + t] = p.b1[t]; P[DP_B2 + t] = p.b2[t]; }
-  __syncthreads();
-}
 
 struct OdeFwdJobs { gode_ode_fwd_op op[RV_MAX_JOBS]; int32_t nblk[RV_MAX_JOBS]; int32_t count; };
 
 __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_fwd_valu_kernel(const OdeFwdJobs J) {
   __shared__ float P[DP_N];
-  __shared__ RedLds R;
+  __shared__ RnnRed R;
   int job = 0, wg = blockIdx.x;
   while (job + 1 < J.count && wg >= J.nblk[job]) { wg -= J.nblk[job]; ++job; }
   const gode_ode_fwd_op a = J.op[job];
@@ -1023,43 +830,43 @@ __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_fwd_valu_kernel(const O
   if (threadIdx.x == 0) R.dead = 0;
 
   float y0 = valid ? a.x[(int64_t)n * 16 + i] : 0.f;
-  stage_ode_params(a.p, a.prenet, P);
+  stage_ode_params<RV_THREADS>(a.p, a.prenet, P);
   if (threadIdx.x < 256) {           // M = W1 W2, c = W1 b2 (fp64 accumulation)
     const int r = threadIdx.x >> 4, j = threadIdx.x & 15;
     double s = 0.0;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) s += (double)P[DP_W1 + r * 16 + k] * (double)P[DP_W2 + k * 16 + j];
+    for (int k = 0; k < 16; ++k) s += (double)P[OFF_W1 + r * 16 + k] * (double)P[OFF_W2 + k * 16 + j];
     P[DP_M + threadIdx.x] = (float)s;
   } else if (threadIdx.x < 272) {
     const int r = threadIdx.x - 256;
     double s = 0.0;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) s += (double)P[DP_W1 + r * 16 + k] * (double)P[DP_B2 + k];
+    for (int k = 0; k < 16; ++k) s += (double)P[OFF_W1 + r * 16 + k] * (double)P[OFF_B2 + k];
     P[DP_C + r] = (float)s;
   }
   __syncthreads();
-  if (a.content) rnn_broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, n0);      // stores only
+  if (a.content) broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, n0, RV_TRAJ, threadIdx.x, RV_THREADS);      // stores only
 
   int src[16];
   probe_sources(i, src);
   if (a.prenet) {
     // Linear(16,64) -> LReLU -> Linear(64,16) -> LReLU: the 64 hidden units as four row-resident chunks
-    float acc = P[DP_BB + i];
+    float acc = P[OFF_BB + i];
 #pragma unroll 1
     for (int m = 0; m < 4; ++m) {
       W16 wa, wb;
-      load_rows(wa, P + DP_WA, 16, 16 * m, 0, i, src);
-      load_rows(wb, P + DP_WB, 64, 0, 16 * m, i, src);
-      const float hh = lrelu1(mv16c(wa, y0, P[DP_BA + 16 * m + i]));
+      load_rows(wa, P + OFF_WA, 16, 16 * m, 0, i, src);
+      load_rows(wb, P + OFF_WB, 64, 0, 16 * m, i, src);
+      const float hh = lrelu1(mv16c(wa, y0, P[OFF_BA + 16 * m + i]));
       acc = mv16c(wb, hh, acc);
     }
     y0 = lrelu1(acc);
   }
   W16 Mw, w1, w2;
   load_rows(Mw, P + DP_M, 16, 0, 0, i, src);
-  load_rows(w1, P + DP_W1, 16, 0, 0, i, src);
-  load_rows(w2, P + DP_W2, 16, 0, 0, i, src);
-  const float b1 = P[DP_B1 + i], b2 = P[DP_B2 + i], cq = P[DP_C + i];
+  load_rows(w1, P + OFF_W1, 16, 0, 0, i, src);
+  load_rows(w2, P + OFF_W2, 16, 0, 0, i, src);
+  const float b1 = P[OFF_B1 + i], b2 = P[OFF_B2 + i], cq = P[DP_C + i];
   const int tsel = (a.sel_t && valid) ? a.sel_t[n] : -1;
   auto emit = [&](int t, float v) {
     if (!valid) return;
@@ -1077,12 +884,12 @@ __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_fwd_valu_kernel(const O
     const float f0 = mv16c(w2, h1, b2);
     const float sc = atol + fabsf(y0) * rtol;
     float v[2] = {valid ? (y0 / sc) * (y0 / sc) : 0.f, valid ? (f0 / sc) * (f0 / sc) : 0.f};
-    batch_sum<2>(v, &R, par, X);
+    batch_sum<2>(v, R, par, X);
     const float d0 = sqrtf(v[0] * inv_count), d1 = sqrtf(v[1] * inv_count);
     const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
     const float df = mv16c(w2, fast_tanh(fmaf(h0, q1, u0)) - h1, 0.f);
     float w[1] = {valid ? (df / sc) * (df / sc) : 0.f};
-    batch_sum<1>(w, &R, par, X);
+    batch_sum<1>(w, R, par, X);
     const float d2 = sqrtf(w[0] * inv_count) / h0;
     const float hh = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : fast_pow(0.01f / fmaxf(d1, d2), 0.2f);
     dtd = (double)fminf(100.f * h0, hh);
@@ -1097,32 +904,32 @@ __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_fwd_valu_kernel(const O
     while (target > seg1) {
       if (R.dead || steps >= RV_MAX_TRIALS || !(tcur + dtd > tcur)) { stalled = true; break; }
       const float dt = (float)dtd;
-      const float h2 = fast_tanh(fmaf(dt * A21, q1, u0));
+      const float h2 = fast_tanh(fmaf(dt * DP5_A21, q1, u0));
       const float q2 = mv16c(Mw, h2, cq);
-      const float h3 = fast_tanh(fmaf(dt, A31 * q1 + A32 * q2, u0));
+      const float h3 = fast_tanh(fmaf(dt, DP5_A31 * q1 + DP5_A32 * q2, u0));
       const float q3 = mv16c(Mw, h3, cq);
-      const float h4 = fast_tanh(fmaf(dt, A41 * q1 + A42 * q2 + A43 * q3, u0));
+      const float h4 = fast_tanh(fmaf(dt, DP5_A41 * q1 + DP5_A42 * q2 + DP5_A43 * q3, u0));
       const float q4 = mv16c(Mw, h4, cq);
-      const float h5 = fast_tanh(fmaf(dt, A51 * q1 + A52 * q2 + A53 * q3 + A54 * q4, u0));
+      const float h5 = fast_tanh(fmaf(dt, DP5_A51 * q1 + DP5_A52 * q2 + DP5_A53 * q3 + DP5_A54 * q4, u0));
       const float q5 = mv16c(Mw, h5, cq);
-      const float h6 = fast_tanh(fmaf(dt, A61 * q1 + A62 * q2 + A63 * q3 + A64 * q4 + A65 * q5, u0));
+      const float h6 = fast_tanh(fmaf(dt, DP5_A61 * q1 + DP5_A62 * q2 + DP5_A63 * q3 + DP5_A64 * q4 + DP5_A65 * q5, u0));
       const float q6 = mv16c(Mw, h6, cq);
-      const float u7 = fmaf(dt, B1 * q1 + B3 * q3 + B4 * q4 + B5 * q5 + B6 * q6, u0);
+      const float u7 = fmaf(dt, DP5_B1 * q1 + DP5_B3 * q3 + DP5_B4 * q4 + DP5_B5 * q5 + DP5_B6 * q6, u0);
       const float h7 = fast_tanh(u7);
-      const float Hb = B1 * h1 + B3 * h3 + B4 * h4 + B5 * h5 + B6 * h6;
-      const float He = E1 * h1 + E3 * h3 + E4 * h4 + E5 * h5 + E6 * h6 + E7 * h7;
+      const float Hb = DP5_B1 * h1 + DP5_B3 * h3 + DP5_B4 * h4 + DP5_B5 * h5 + DP5_B6 * h6;
+      const float He = DP5_E1 * h1 + DP5_E3 * h3 + DP5_E4 * h4 + DP5_E5 * h5 + DP5_E6 * h6 + DP5_E7 * h7;
       const float y1 = fmaf(dt, mv16c(w2, Hb, b2), y0);
       const float err = dt * mv16c(w2, He, 0.f);
       const float tol = atol + rtol * fmaxf(fabsf(y0), fabsf(y1));
       const float rr = err / tol;
       float v[1] = {valid ? rr * rr : 0.f};
       const float q7 = mv16c(Mw, h7, cq);
-      batch_sum<1>(v, &R, par, X);
+      batch_sum<1>(v, R, par, X);
       const float ratio = sqrtf(v[0] * inv_count);
       ++steps;
       if (ratio <= 1.f) {
         sy = y0; sdt = dt; sHb = Hb; sh1 = h1; sh7 = h7;
-        sHm = C1 * h1 + C3 * h3 + C4 * h4 + C5 * h5 + C6 * h6 + C7 * h7;
+        sHm = DP5_C1 * h1 + DP5_C3 * h3 + DP5_C4 * h4 + DP5_C5 * h5 + DP5_C6 * h6 + DP5_C7 * h7;
         seg0 = tcur; seg1 = tcur + dtd;
         tcur = seg1; y0 = y1; u0 = u7; h1 = h7; q1 = q7;
       }
@@ -1144,7 +951,7 @@ struct OdeBwdJobs { gode_ode_bwd_op op[RV_MAX_JOBS]; int32_t nblk[RV_MAX_JOBS]; 
 __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_bwd_valu_kernel(const OdeBwdJobs J) {
   __shared__ float P[GODE_ODE_NPARAM];
   __shared__ AdjLdsV lds;
-  __shared__ RedLds R;
+  __shared__ RnnRed R;
   int job = 0, wg = blockIdx.x;
   while (job + 1 < J.count && wg >= J.nblk[job]) { wg -= J.nblk[job]; ++job; }
   const gode_ode_bwd_op a = J.op[job];
@@ -1163,14 +970,14 @@ __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_bwd_valu_kernel(const O
   S.st[0] = S.st[1] = 0.f; S.gt[0] = S.gt[1] = 0.f;
   if (threadIdx.x == 0) R.dead = 0;
   const float x = (valid && a.prenet) ? a.x[(int64_t)n * 16 + i] : 0.f;      // needed by the pre-net backward at the very end
-  stage_ode_params(a.p, a.prenet, P);
+  stage_ode_params<RV_THREADS>(a.p, a.prenet, P);
   int src[16];
   probe_sources(i, src);
-  load_rows(S.w1, P + DP_W1, 16, 0, 0, i, src);
-  load_rows(S.w2, P + DP_W2, 16, 0, 0, i, src);
-  load_cols(S.w1t, P + DP_W1, 16, 0, 0, i, src);
-  load_cols(S.w2t, P + DP_W2, 16, 0, 0, i, src);
-  S.b1 = P[DP_B1 + i]; S.b2 = P[DP_B2 + i];
+  load_rows(S.w1, P + OFF_W1, 16, 0, 0, i, src);
+  load_rows(S.w2, P + OFF_W2, 16, 0, 0, i, src);
+  load_cols(S.w1t, P + OFF_W1, 16, 0, 0, i, src);
+  load_cols(S.w2t, P + OFF_W2, 16, 0, 0, i, src);
+  S.b1 = P[OFF_B1 + i]; S.b2 = P[OFF_B2 + i];
 
   const int tsel = (a.sel_t && valid) ? a.sel_t[n] : -1;
   auto upstream = [&](int t) -> float {
@@ -1189,38 +996,38 @@ __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_bwd_valu_kernel(const O
   if (a.nsteps && wg == 0 && threadIdx.x == 0) a.nsteps[0] = steps;
   // ---- output row: [Wa 1024 | ba 64 | Wb 1024 | bb 16 | W1 256 | b1 16 | W2 256 | b2 16].  One launch of ONE workgroup writes (or
   // adds to) grads directly; otherwise one row of `work` per workgroup (the ODEFunc block holds the BATCH total in every
-  // workgroup: row 0 carries it, the others zeros), added by ode_rows_kernel
+  // workgroup: row 0 carries it, the others zeros), added by latent_rows_kernel
   float* out = J.direct ? a.grads : a.work + (int64_t)wg * GODE_ODE_NPARAM;
   const bool acc_out = J.direct && a.accumulate;
   auto put = [&](int dst, float v) { out[dst] = acc_out ? out[dst] + v : v; };
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int e = (int)threadIdx.x + RV_THREADS * k;
-    if (e < TH_N) put(DP_W1 + e, (wg == 0 && steps >= 0) ? S.gt[k] : 0.f);     // TH_* order == W1, b1, W2, b2
+    if (e < TH_N) put(OFF_W1 + e, (wg == 0 && steps >= 0) ? S.gt[k] : 0.f);     // TH_* order == W1, b1, W2, b2
   }
   if (!a.prenet) {
-    // no pre-net: [0, DP_W1) of grads is not the caller's memory (gode.h) -- only a work row gets its zeros
+    // no pre-net: [0, OFF_W1) of grads is not the caller's memory (gode.h) -- only a work row gets its zeros
     if (!J.direct)
-      for (int k = threadIdx.x; k < DP_W1; k += RV_THREADS) put(k, 0.f);
+      for (int k = threadIdx.x; k < OFF_W1; k += RV_THREADS) put(k, 0.f);
     return;
   }
   // ---- pre-net backward; adj = dL/d(pre-net output).  With one (trajectory, feature) value per lane the batch sums of
   // outer products are one MFMA per 16x16 chunk (k = the wave's 4 trajectories); the waves' images meet in LDS per chunk.
   float hpre[4];
-  float acc = P[DP_BB + i];
+  float acc = P[OFF_BB + i];
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     W16 wa, wb;
-    load_rows(wa, P + DP_WA, 16, 16 * m, 0, i, src);
-    load_rows(wb, P + DP_WB, 64, 0, 16 * m, i, src);
-    hpre[m] = mv16c(wa, x, P[DP_BA + 16 * m + i]);
+    load_rows(wa, P + OFF_WA, 16, 16 * m, 0, i, src);
+    load_rows(wb, P + OFF_WB, 64, 0, 16 * m, i, src);
+    hpre[m] = mv16c(wa, x, P[OFF_BA + 16 * m + i]);
     acc = mv16c(wb, lrelu1(hpre[m]), acc);
   }
   const float g0 = valid ? (acc > 0.f ? adj : 0.2f * adj) : 0.f;
 #pragma unroll 1
   for (int m = 0; m < 4; ++m) {
     W16 wbt;
-    load_cols(wbt, P + DP_WB, 64, 0, 16 * m, i, src);      // (Wb chunk)^T
+    load_cols(wbt, P + OFF_WB, 64, 0, 16 * m, i, src);      // (Wb chunk)^T
     const float tt = mv16c(wbt, g0, 0.f);
     const float gh = valid ? (hpre[m] > 0.f ? tt : 0.2f * tt) : 0.f;
     const f32x4 dWb = MFMA16(g0, lrelu1(hpre[m]), zero4());   // [i][j] = sum_n g0_i lrelu(hpre_m)_j -> Wb[i][16m + j]
@@ -1237,24 +1044,12 @@ __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_bwd_valu_kernel(const O
     __syncthreads();
     for (int k = threadIdx.x; k < TH_N; k += RV_THREADS) {
       const float v = S.img_total(0, k);
-      if (k < 256) put(DP_WB + (k >> 4) * 64 + 16 * m + (k & 15), v);
-      else if (k < 512) put(DP_WA + (16 * m + ((k - 256) >> 4)) * 16 + (k & 15), v);
-      else if (k < 528) put(DP_BA + 16 * m + (k - 512), v);
-      else if (m == 0) put(DP_BB + (k - 528), v);
+      if (k < 256) put(OFF_WB + (k >> 4) * 64 + 16 * m + (k & 15), v);
+      else if (k < 512) put(OFF_WA + (16 * m + ((k - 256) >> 4)) * 16 + (k & 15), v);
+      else if (k < 528) put(OFF_BA + 16 * m + (k - 512), v);
+      else if (m == 0) put(OFF_BB + (k - 528), v);
     }
   }
-}
-
-// rows of `work` (ops sharing a grads pointer, in array order) -> grads, fixed order; row length 2,672.  Entries below
-// `first` are not touched (DP_W1 when none of the ops has a pre-net: that block of grads is then not the caller's)
-struct OdeRowsArgs { const float* work[RV_MAX_JOBS]; int32_t rows[RV_MAX_JOBS]; int32_t count, accumulate, first; float* grads; };
-__global__ void __launch_bounds__(256) ode_rows_kernel(const OdeRowsArgs A) {
-  const int k = A.first + blockIdx.x * 256 + threadIdx.x;
-  if (k >= GODE_ODE_NPARAM) return;
-  float s = 0.f;
-  for (int j = 0; j < A.count; ++j)
-    for (int b = 0; b < A.rows[j]; ++b) s += A.work[j][(int64_t)b * GODE_ODE_NPARAM + k];
-  A.grads[k] = A.accumulate ? A.grads[k] + s : s;
 }
 
 int gode_launch_ode_dopri5(const gode_ode_fwd_op* op, hipStream_t st);          // odernn.hip (MFMA fallback)
@@ -1318,21 +1113,14 @@ static int ode5_bwd_launch(const gode_ode_bwd_op* ops, int count, hipStream_t st
   hipLaunchKernelGGL(ode_dopri5_bwd_valu_kernel, dim3(grid), dim3(RV_THREADS), 0, st, J);
   GODE_LAUNCH_CHECK();
   if (J.direct) return 0;
-  bool done[RV_MAX_JOBS] = {false};
-  for (int k = 0; k < count; ++k) {
-    if (done[k]) continue;
-    OdeRowsArgs A;
-    A.count = 0; A.grads = ops[k].grads; A.accumulate = ops[k].accumulate; A.first = DP_W1;
-    for (int j = k; j < count; ++j) {
-      if (!done[j] && ops[j].grads == ops[k].grads) {
-        A.work[A.count] = ops[j].work; A.rows[A.count] = J.nblk[j]; A.count += 1; done[j] = true;
-        if (ops[j].prenet) A.first = 0;
-      }
-    }
-    hipLaunchKernelGGL(ode_rows_kernel, dim3((GODE_ODE_NPARAM - A.first + 255) / 256), dim3(256), 0, st, A);
-    GODE_LAUNCH_CHECK();
-  }
-  return 0;
+  // entries below `first` are not touched: OFF_W1 when none of the group's ops has a pre-net (that block of grads is then
+  // not the caller's)
+  return gode_for_each_grads_group(ops, J.nblk, count, [&](RowsArgs& A) {
+    A.nparam = GODE_ODE_NPARAM; A.first = OFF_W1;
+    for (int j = 0; j < count; ++j)
+      if (ops[j].grads == A.grads && ops[j].prenet) A.first = 0;
+    return gode_launch_rows(A, st);
+  });
 }
 
 // the adaptive adjoints (method == 1, substeps == 0) of `count` (<= 8) dopri5 solves in one launch

@@ -18,11 +18,12 @@
 #include "ode_common.h"
 #include "valu_common.h"
 
-// parameter block (gode_sde_params order; also the layout of `grads` with the pre-net)
-#define SP_WA 0
-#define SP_BA 1024
-#define SP_WB 1088
-#define SP_BB 2112
+// parameter block (gode_sde_params order; also the layout of `grads` with the pre-net): the pre-net's four tensors sit
+// where gode_ode_params has them (prenet_fwd reads them there)
+#define SP_WA OFF_WA
+#define SP_BA OFF_BA
+#define SP_WB OFF_WB
+#define SP_BB OFF_BB
 #define SP_WF1 2128
 #define SP_BF1 2384
 #define SP_WF2 2400
@@ -48,38 +49,6 @@ __device__ __forceinline__ void sde_stage_params(const gode_sde_params& p, int p
   __syncthreads();
 }
 
-// content columns 16..65 (the same 50 values on every row of a trajectory) + zero pad: as ode_valu.hip
-__device__ __forceinline__ void sde_broadcast_content(const gode_sde_fwd_op& a, int n0) {
-  const int rows_per = a.sel_t ? 1 : a.T;
-  const int q4 = (a.zcols - 16) >> 2;
-  const int total4 = 16 * rows_per * q4;
-  for (int k = threadIdx.x; k < total4; k += 256) {
-    const int rr = k / q4, q = k - rr * q4;
-    const int ns = rr / rows_per, tt = rr - ns * rows_per;
-    if (n0 + ns < a.N) {
-      const float* c = a.content + (int64_t)(n0 + ns) * 50 + 4 * q;
-      f32x4 v = zero4();
-      if (q < 12) v = f32x4{c[0], c[1], c[2], c[3]};
-      else if (q == 12) v = f32x4{c[0], c[1], 0.f, 0.f};
-      *reinterpret_cast<f32x4*>(a.z + ((int64_t)(n0 + ns) * rows_per + tt) * a.zcols + 16 + 4 * q) = v;
-    }
-  }
-}
-
-// pre-net Linear(16,64) -> LReLU -> Linear(64,16) -> LReLU, the 64 hidden units as four row-resident chunks
-__device__ __forceinline__ float sde_prenet(const float* P, float y, int i, const int* src) {
-  float acc = P[SP_BB + i];
-#pragma unroll 1
-  for (int m = 0; m < 4; ++m) {
-    W16 wa, wb;
-    load_rows(wa, P + SP_WA, 16, 16 * m, 0, i, src);
-    load_rows(wb, P + SP_WB, 64, 0, 16 * m, i, src);
-    const float h = lrelu1(mv16(wa, y, P[SP_BA + 16 * m + i]));
-    acc = mv16(wb, h, acc);
-  }
-  return lrelu1(acc);
-}
-
 __global__ void __launch_bounds__(256) sde_fwd_kernel(const gode_sde_fwd_op a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, tl = lane >> 4;
@@ -90,11 +59,11 @@ __global__ void __launch_bounds__(256) sde_fwd_kernel(const gode_sde_fwd_op a) {
   __shared__ float P[GODE_SDE_NPARAM];
   float y = valid ? a.x[(int64_t)n * 16 + i] : 0.f;
   sde_stage_params(a.p, a.prenet, P);
-  if (a.content) sde_broadcast_content(a, n0);          // stores only; nothing below waits for them
+  if (a.content) broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, n0, 16, threadIdx.x, 256);
 
   int src[16];
   probe_sources(i, src);
-  if (a.prenet) y = sde_prenet(P, y, i, src);
+  if (a.prenet) y = prenet_fwd(P, y, i, src);
   W16 wf1, wf2, wg1, wg2;
   load_rows(wf1, P + SP_WF1, 16, 0, 0, i, src);
   load_rows(wf2, P + SP_WF2, 16, 0, 0, i, src);
@@ -263,26 +232,6 @@ __global__ void __launch_bounds__(256) sde_bwd_kernel(const gode_sde_bwd_op a) {
     part[k] = (R[0][k] + R[1][k]) + (R[2][k] + R[3][k]);
 }
 
-// second level: grads[k - first] (+)= sum over the workgroup rows b = 0, stride, 2*stride, ... of work[b][k]
-__global__ void __launch_bounds__(256) sde_bwd_reduce_kernel(const float* work, float* grads, int nblk, int stride,
-                                                             int accumulate, int first) {
-  const int k = first + blockIdx.x * 256 + threadIdx.x;
-  if (k >= GODE_SDE_NPARAM) return;
-  float s = 0.f;
-  for (int b = 0; b < nblk; b += stride) s += work[(int64_t)b * GODE_SDE_NPARAM + k];
-  grads[k - first] = accumulate ? grads[k - first] + s : s;
-}
-// many workgroups: chunks of `chunk` consecutive rows summed in place into their first row (fixed order), first
-__global__ void __launch_bounds__(256) sde_bwd_reduce_chunks_kernel(float* work, int nblk, int chunk, int first) {
-  const int k = first + blockIdx.x * 256 + threadIdx.x;
-  if (k >= GODE_SDE_NPARAM) return;
-  const int b0 = blockIdx.y * chunk, b1 = b0 + chunk < nblk ? b0 + chunk : nblk;
-  float s = 0.f;
-#pragma unroll 8
-  for (int b = b0; b < b1; ++b) s += work[(int64_t)b * GODE_SDE_NPARAM + k];
-  work[(int64_t)b0 * GODE_SDE_NPARAM + k] = s;
-}
-
 static bool sde_params_ok(const gode_sde_params& p, int prenet) {
   if (!p.Wf1 || !p.bf1 || !p.Wf2 || !p.bf2 || !p.Wg1 || !p.bg1 || !p.Wg2 || !p.bg2) return false;
   return !prenet || (p.Wa && p.ba && p.Wb && p.bb);
@@ -314,17 +263,7 @@ extern "C" int gode_sde_bwd(const gode_sde_bwd_op* op, void* stream) {
   const int nblk = (op->N + 15) / 16;
   hipLaunchKernelGGL(sde_bwd_kernel, dim3(nblk), dim3(256), 0, st, *op);
   GODE_LAUNCH_CHECK();
+  // without the pre-net `grads` holds the drift / diffusion block only; two levels above 128 rows
   const int first = op->prenet ? 0 : SP_WF1;
-  const int gx = (GODE_SDE_NPARAM - first + 255) / 256;
-  int stride = 1;
-  if (nblk > 128) {
-    stride = 64;
-    hipLaunchKernelGGL(sde_bwd_reduce_chunks_kernel, dim3(gx, (nblk + stride - 1) / stride), dim3(256), 0, st, op->work,
-                       nblk, stride, first);
-    GODE_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(sde_bwd_reduce_kernel, dim3(gx), dim3(256), 0, st, op->work, op->grads, nblk, stride, op->accumulate,
-                     first);
-  GODE_LAUNCH_CHECK();
-  return 0;
+  return gode_reduce_rows(op->work, op->grads, nblk, GODE_SDE_NPARAM, first, first, op->accumulate, nullptr, 128, 64, st);
 }

@@ -1,8 +1,10 @@
-// valu_common.h -- the VECTOR-ALU / DPP mapping of the 16-wide mat-vecs shared by ode_valu.hip and odernn_valu.hip:
-// one lane = one (trajectory, feature) pair, the 16 features of a trajectory in one DPP row (16 lanes), 4 trajectories
-// per wave.  See the header comment of ode_valu.hip.
+// valu_common.h -- the VECTOR-ALU / DPP mapping of the 16-wide mat-vecs shared by the *_valu.hip kernels: one lane = one
+// (trajectory, feature) pair, the 16 features of a trajectory in one DPP row (16 lanes), 4 trajectories per wave (see the
+// header comment of ode_valu.hip); the staging of the gode_ode_params block, the pre-net on it, and the whole-batch sum
+// with its cross-workgroup exchange.
 #pragma once
 #include "common.h"
+#include "ode_common.h"
 
 template <int R> __device__ __forceinline__ float row_ror(float v) {
   if (R == 0) return v;
@@ -134,4 +136,125 @@ __device__ __forceinline__ float traj_sum(float v) {
   const float d = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((i + 32) << 2, b));
   const float e = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((i + 48) << 2, b));
   return (a + c) + (d + e);
+}
+// the same sum, (a + c) + (d + e) in every lane, as two butterfly levels: ode_bwd_valu_kernel's form, kept beside traj_sum because swapping it changes that kernel's instructions
+__device__ __forceinline__ float sum_traj(float v) {
+  v += __shfl_xor(v, 16);
+  v += __shfl_xor(v, 32);
+  return v;
+}
+
+
+// ---- the gode_ode_params block in LDS ------------------------------------------------------------------------------
+// All 2,672 parameters (10.7 KB) go to LDS with ONE round of coalesced loads before anything else: the per-lane weight
+// arrangement is then gathered from LDS.  (Gathering it from global memory cost the config-size adjoint launch more
+// than its whole time loop: twelve dependent batches of L2-missing loads in the pre-net backward, 60k of 126k cycles.)
+template <int THREADS>
+__device__ __forceinline__ void stage_ode_params(const gode_ode_params& p, int prenet, float* P) {
+  const int t = threadIdx.x;
+  if (prenet) {
+    for (int k = t; k < 1024; k += THREADS) { P[OFF_WA + k] = p.Wa[k]; P[OFF_WB + k] = p.Wb[k]; }
+    if (t < 64) P[OFF_BA + t] = p.ba[t];
+    if (t < 16) P[OFF_BB + t] = p.bb[t];
+  }
+  static_assert(THREADS >= 256, "one 16x16 matrix per round");
+  if (THREADS == 256 || t < 256) { P[OFF_W1 + t] = p.W1[t]; P[OFF_W2 + t] = p.W2[t]; }     // (256 threads: no guard)
+  if (t < 16) { P[OFF_B1 + t] = p.b1[t]; P[OFF_B2 + t] = p.b2[t]; }
+  __syncthreads();
+}
+// pre-net Linear(16,64) -> LReLU -> Linear(64,16) -> LReLU on a staged block whose first four tensors are Wa, ba, Wb, bb:
+// the 64 hidden units as four row-resident chunks (not unrolled: two weight arrangements live at a time)
+__device__ __forceinline__ float prenet_fwd(const float* P, float y, int i, const int* src) {
+  float acc = P[OFF_BB + i];
+#pragma unroll 1
+  for (int m = 0; m < 4; ++m) {
+    W16 wa, wb;
+    load_rows(wa, P + OFF_WA, 16, 16 * m, 0, i, src);
+    load_rows(wb, P + OFF_WB, 64, 0, 16 * m, i, src);
+    const float h = lrelu1(mv16(wa, y, P[OFF_BA + 16 * m + i]));
+    acc = mv16(wb, h, acc);
+  }
+  return lrelu1(acc);
+}
+
+
+// ---- whole-batch sums ----------------------------------------------------------------------------------------------
+// The workgroups of a call exchange partial sums through the caller's `sync` buffer: XS_HDR ints (sync[0] counts the
+// arrivals over all exchanges of the launch; the host zeroes the header before every launch), then the slots.
+#define XS_HDR 16
+struct XSync {
+  int* counter;     // sync[0]
+  float* slots;     // sync + XS_HDR: [2][nwg][VALS] partial sums, double-buffered by exchange parity
+  int nwg, wg, seq;
+};
+// WAVES waves per workgroup, VALS floats per slot; PAIRWISE: the 4 per-wave partials are added as (r0 + r1) + (r2 + r3)
+// instead of one after the other (the order is part of each kernel's results: do not change it)
+template <int WAVES, int VALS, bool PAIRWISE = false>
+struct RedLds {
+  float red[2][WAVES][VALS];         // per-wave partials, double-buffered: one barrier per sum
+  float bc[2][VALS];                 // cross-workgroup totals broadcast to the workgroup
+  int dead;                          // a spin timed out somewhere: every thread of the workgroup bails out
+};
+// ONE thread of the workgroup: publish what the workgroup stored (release), then wait until every workgroup of the call
+// has arrived at exchange X.seq.  The spin is bounded; a workgroup that never arrives sets *dead instead of hanging us.
+__device__ __forceinline__ void xs_arrive_and_wait(const XSync& X, int* dead) {
+  __hip_atomic_fetch_add(X.counter, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  const int target = (X.seq + 1) * X.nwg;
+  int spins = 0;
+  while (__hip_atomic_load(X.counter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) {
+    __builtin_amdgcn_s_sleep(2);
+    if (++spins > (1 << 20)) { *dead = 1; break; }     // ~seconds: a workgroup of the call never arrived
+  }
+}
+// v[0..K): per-thread values -> the sums over ALL threads of ALL workgroups of the call, in every thread, fixed order.
+template <int K, int WAVES, int VALS, bool PAIRWISE>
+__device__ __forceinline__ void batch_sum(float* v, RedLds<WAVES, VALS, PAIRWISE>& R, int& par, XSync& X) {
+  static_assert(K <= VALS && (!PAIRWISE || WAVES == 4), "batch_sum");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) R.red[par][wave][k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if constexpr (PAIRWISE) {
+      v[k] = (R.red[par][0][k] + R.red[par][1][k]) + (R.red[par][2][k] + R.red[par][3][k]);
+    } else {
+      float s = 0.f;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) s += R.red[par][w][k];
+      v[k] = s;
+    }
+  }
+  if (X.nwg > 1) {
+    float* slot = X.slots + (size_t)(X.seq & 1) * X.nwg * VALS;
+    if (wave == 0) {
+      if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) __hip_atomic_store(&slot[X.wg * VALS + k], v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        xs_arrive_and_wait(X, &R.dead);
+      }
+      float t[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) t[k] = 0.f;
+      for (int w = lane; w < X.nwg; w += 64) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) t[k] += __hip_atomic_load(&slot[w * VALS + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+#pragma unroll
+      for (int k = 0; k < K; ++k) t[k] = wave_sum(t[k]);
+      if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) R.bc[par][k] = t[k];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = R.bc[par][k];
+    X.seq += 1;
+  }
+  par ^= 1;
 }

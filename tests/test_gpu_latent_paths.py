@@ -5,12 +5,12 @@ The library picks the kernels from N, the method, whether a `sync` buffer is giv
 the test ids name the path:
   rk4-valu       N <= 8192: ode_valu.hip
   rk4-mfma       N > 8192: ode_fwd_kernel / ode_bwd_kernel (ode.hip; 256 threads with a content code, 64 without)
-  reduce2        an rk4 / dopri5-fallback adjoint with more than 128 partial rows (N > 2048): ode_bwd_reduce_chunks_kernel
+  reduce2        an rk4 / dopri5-fallback adjoint with more than 128 partial rows (N > 2048): latent_reduce_chunks_kernel
   dopri5-valu    N <= 32 (one workgroup, grads written directly) or N <= 4096 with `sync` (the cap: 128 workgroups
                  exchanging the whole-batch error norm)
   dopri5-mfma    N > 4096, N > 32 without `sync`, or the jobs of one _multi call spinning > 128 workgroups together:
                  ode_dopri5_fwd_kernel / ode_dopri5_bwd_kernel, one error norm per 64-trajectory workgroup
-  dopri5-multi   several solves in one gode_ode_fwd_multi / gode_ode_bwd_multi launch (+ ode_rows_kernel)
+  dopri5-multi   several solves in one gode_ode_fwd_multi / gode_ode_bwd_multi launch (+ latent_rows_kernel)
 A dopri5 reference uses the device's norm grouping: one oracle solve over the batch for the whole-batch norm, one per
 consecutive 64-trajectory chunk for the fallback (reference gradient = the sum of the chunks').  Without a pre-net the
 first 2128 floats of `grads` belong to the caller's neighbours (GradArena hands the adjoint a pointer that far in front
