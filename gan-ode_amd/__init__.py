@@ -5,17 +5,19 @@ Python host side that mirrors the reference's class surface.  Importing the pack
 anything does, and there is no fallback path.
 """
 from . import _lib
-from .modules import (CDEFunc, Noise, ODEFunc, PatchImageDiscriminator, SDEFunc, VideoDiscriminator, VideoGenerator,
+from .modules import (CategoricalVideoDiscriminator, CDEFunc, Noise, ODEFunc, PatchImageDiscriminator, SDEFunc, VideoDiscriminator, VideoGenerator,
                       VideoGeneratorCDE, VideoGeneratorGRU, VideoGeneratorMNIST, VideoGeneratorMNISTODE, VideoGeneratorMNISTODERNN,
                       VideoGeneratorSDE)
 from .train import (FusedAdam, GanTrainer, WassersteinDiscriminatorLoss, WassersteinGeneratorLoss, bce_with_logits_const,
-                    bce_with_logits_halves, bce_with_logits_pair, build_mnist, build_ucf, freeze_host_gc, host_cpu_quota,
+                    bce_with_logits_halves, bce_with_logits_pair, bce_ce_head, bce_ce_head_halves, bce_ce_head_pair,
+                    bce_ce_heads, categorical_cross_entropy, build_mnist, build_ucf, freeze_host_gc, host_cpu_quota,
                     limit_host_threads, train_step, unit_grad, wasserstein_discriminator_loss,
                     wasserstein_discriminator_loss_halves, wasserstein_generator_loss, wasserstein_generator_loss_pair)
 
-__all__ = ["Noise", "ODEFunc", "PatchImageDiscriminator", "VideoDiscriminator", "VideoGenerator",
+__all__ = ["Noise", "ODEFunc", "PatchImageDiscriminator", "VideoDiscriminator", "CategoricalVideoDiscriminator", "VideoGenerator",
            "VideoGeneratorMNIST", "VideoGeneratorMNISTODE", "VideoGeneratorMNISTODERNN", "SDEFunc", "VideoGeneratorSDE", "CDEFunc", "VideoGeneratorCDE", "VideoGeneratorGRU", "FusedAdam", "GanTrainer", "bce_with_logits_const",
-           "bce_with_logits_pair", "bce_with_logits_halves", "WassersteinGeneratorLoss", "WassersteinDiscriminatorLoss",
+           "bce_with_logits_pair", "bce_with_logits_halves", "categorical_cross_entropy", "bce_ce_head", "bce_ce_head_pair",
+           "bce_ce_head_halves", "bce_ce_heads", "WassersteinGeneratorLoss", "WassersteinDiscriminatorLoss",
            "wasserstein_generator_loss", "wasserstein_generator_loss_pair", "wasserstein_discriminator_loss",
            "wasserstein_discriminator_loss_halves", "unit_grad", "build_mnist", "build_ucf", "train_step", "host_cpu_quota", "limit_host_threads", "freeze_host_gc", "_lib"]
 

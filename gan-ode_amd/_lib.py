@@ -20,6 +20,7 @@ OP_CDE_FWD, OP_CDE_BWD = 16, 17
 OP_WGAN = 18
 OP_GRU_FWD, OP_GRU_BWD = 19, 20
 OP_DNOISE = 21
+OP_CATEG, OP_CE = 22, 23
 REC_ADAM_NOISE = -1          # gode_sizeof index of the gode_adam_noise_tensor table record
 ODE_NPARAM = 2672
 ODERNN_NPARAM = 2176
@@ -178,8 +179,20 @@ class Col2imOp(C.Structure):
 
 class BceOp(C.Structure):
     _fields_ = [("logits", ptr), ("grad", ptr), ("loss", ptr), ("n", i64), ("target", f32), ("gscale", f32),
-                ("accumulate", i32), ("pad_", i32)]
+                ("accumulate", i32), ("stride", i32)]
     KIND = OP_BCE
+
+
+class CategOp(C.Structure):
+    _fields_ = [("cls", ptr), ("z", ptr), ("labels_out", ptr), ("n_traj", i32), ("rows_per", i32), ("C", i32),
+                ("zcols", i32), ("col0", i32), ("pad_", i32)]
+    KIND = OP_CATEG
+
+
+class CeOp(C.Structure):
+    _fields_ = [("logits", ptr), ("labels", ptr), ("grad", ptr), ("loss", ptr), ("B", i32), ("n_lab", i32), ("C", i32),
+                ("ld", i32), ("gld", i32), ("gscale", f32), ("accumulate", i32), ("rows_per_label", i32)]
+    KIND = OP_CE
 
 
 class WganOp(C.Structure):
@@ -207,7 +220,7 @@ _STRUCTS = {0: ConvGeom, OP_IGEMM: IgemmOp, OP_WGRAD: WgradOp, OP_BN_FINALIZE: B
             OP_ODE_FWD: OdeFwdOp, OP_ODE_BWD: OdeBwdOp, OP_BCE: BceOp, OP_ADAM: AdamOp, OP_PACK: PackOp,
             OP_ODERNN_FWD: OdeRnnFwdOp, OP_ODERNN_BWD: OdeRnnBwdOp, OP_BN_APPLY: BnApplyOp, OP_COL2IM: Col2imOp,
             OP_SDE_FWD: SdeFwdOp, OP_SDE_BWD: SdeBwdOp, OP_CDE_FWD: CdeFwdOp, OP_CDE_BWD: CdeBwdOp, OP_WGAN: WganOp,
-            OP_GRU_FWD: GruFwdOp, OP_GRU_BWD: GruBwdOp, OP_DNOISE: DnoiseOp, REC_ADAM_NOISE: AdamNoiseTensor}
+            OP_GRU_FWD: GruFwdOp, OP_GRU_BWD: GruBwdOp, OP_DNOISE: DnoiseOp, OP_CATEG: CategOp, OP_CE: CeOp, REC_ADAM_NOISE: AdamNoiseTensor}
 
 EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "gode_igemm_stats_segments", "gode_igemm_model_cycles", "gode_igemm_work_size", "gode_pack_size", "gode_pack_weights", "gode_wgrad",
            "gode_wgrad_work_size", "gode_wgrad_auto_splits", "gode_bn_finalize", "gode_bn_bwd",
@@ -216,7 +229,7 @@ EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "god
            "gode_odernn_bwd_multi", "gode_sde_fwd", "gode_sde_bwd", "gode_sde_bwd_work_size", "gode_cde_fwd", "gode_cde_bwd", "gode_cde_sync_size", "gode_cde_state_size", "gode_cde_bwd_work_size", "gode_gru_fwd", "gode_gru_bwd", "gode_gru_fwd_multi",
            "gode_gru_bwd_multi", "gode_gru_bwd_work_size", "gode_bce_logits",
            "gode_wgan_logits", "gode_adam_l2", "gode_adam_multi", "gode_adam_multi_dev", "gode_adam_noise_multi",
-           "gode_adam_noise_multi_dev", "gode_param_noise", "gode_dnoise", "gode_dnoise_normals", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
+           "gode_adam_noise_multi_dev", "gode_param_noise", "gode_dnoise", "gode_dnoise_normals", "gode_categ_onehot", "gode_ce_logits", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
 
 _lib = None
 
@@ -240,7 +253,7 @@ def lib():
     for name in ("gode_igemm", "gode_wgrad", "gode_bn_finalize", "gode_bn_bwd", "gode_ode_fwd", "gode_ode_bwd",
                  "gode_bce_logits", "gode_adam_l2", "gode_odernn_fwd", "gode_odernn_bwd", "gode_bn_apply", "gode_col2im",
                  "gode_sde_fwd", "gode_sde_bwd", "gode_cde_fwd", "gode_cde_bwd", "gode_wgan_logits", "gode_gru_fwd",
-                 "gode_gru_bwd", "gode_dnoise"):
+                 "gode_gru_bwd", "gode_dnoise", "gode_categ_onehot", "gode_ce_logits"):
         getattr(L, name).argtypes = [ptr, ptr]
         getattr(L, name).restype = C.c_int
     L.gode_igemm_stats_rows.argtypes = [ptr]
@@ -354,5 +367,5 @@ def _run_one(op, stream):
           OP_BN_APPLY: "gode_bn_apply", OP_COL2IM: "gode_col2im", OP_SDE_FWD: "gode_sde_fwd",
           OP_SDE_BWD: "gode_sde_bwd", OP_CDE_FWD: "gode_cde_fwd", OP_CDE_BWD: "gode_cde_bwd",
           OP_WGAN: "gode_wgan_logits", OP_GRU_FWD: "gode_gru_fwd", OP_GRU_BWD: "gode_gru_bwd",
-          OP_DNOISE: "gode_dnoise"}[op.KIND]
+          OP_DNOISE: "gode_dnoise", OP_CATEG: "gode_categ_onehot", OP_CE: "gode_ce_logits"}[op.KIND]
     check(getattr(lib(), fn)(C.byref(op), stream), fn)

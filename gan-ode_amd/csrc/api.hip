@@ -28,6 +28,8 @@ extern "C" int gode_sizeof(int kind) {
     case GODE_OP_GRU_FWD: return (int)sizeof(gode_gru_fwd_op);
     case GODE_OP_GRU_BWD: return (int)sizeof(gode_gru_bwd_op);
     case GODE_OP_DNOISE: return (int)sizeof(gode_dnoise_op);
+    case GODE_OP_CATEG: return (int)sizeof(gode_categ_op);
+    case GODE_OP_CE: return (int)sizeof(gode_ce_op);
   }
   return GODE_E_KIND;
 }
@@ -61,6 +63,8 @@ extern "C" int gode_run(const int32_t* kinds, const void* const* ops, int32_t n,
       case GODE_OP_GRU_FWD: rc = gode_gru_fwd((const gode_gru_fwd_op*)ops[i], stream); break;
       case GODE_OP_GRU_BWD: rc = gode_gru_bwd((const gode_gru_bwd_op*)ops[i], stream); break;
       case GODE_OP_DNOISE: rc = gode_dnoise((const gode_dnoise_op*)ops[i], stream); break;
+      case GODE_OP_CATEG: rc = gode_categ_onehot((const gode_categ_op*)ops[i], stream); break;
+      case GODE_OP_CE: rc = gode_ce_logits((const gode_ce_op*)ops[i], stream); break;
       case GODE_OP_PACK: {
         // every run of consecutive pack ops goes out as one launch per 8 panels
         int j = i;

@@ -484,13 +484,14 @@ __global__ void __launch_bounds__(256) bce_kernel(const gode_bce_op a) {
   const int tid = threadIdx.x;
   double s = 0.0;
   const float inv = 1.f / (float)a.n;
+  const int64_t ld = a.stride > 1 ? a.stride : 1;      // (column 0 of a categorical head: one logit per row)
   for (int64_t i = tid; i < a.n; i += 256) {
-    const float x = a.logits[i];
+    const float x = a.logits[i * ld];
     const float l = fmaxf(x, 0.f) - x * a.target + log1pf(expf(-fabsf(x)));
     s += (double)l;
     if (a.grad) {
       const float sig = 1.f / (1.f + expf(-x));
-      a.grad[i] = a.gscale * (sig - a.target) * inv;
+      a.grad[i * ld] = a.gscale * (sig - a.target) * inv;
     }
   }
   red[tid] = s;

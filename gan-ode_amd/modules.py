@@ -23,6 +23,8 @@ from . import _lib as L
 from .engine import ConvStack, LayerParams, LayerSpec, conv_out, dptr, make_geom, stream_ptr
 
 Z_COLS = 96  # latent row: [motion 16 | content 50 | zero pad 30]: K % 32 == 0 puts the first decoder GEMM on the FAST path
+Z_CATEG0 = 66        # dim_z_category = C > 0: the one-hot lives in the first C pad columns (gode_categ_onehot)
+MAX_CATEG = Z_COLS - Z_CATEG0
 
 
 def _require_gpu(t: torch.Tensor, what: str):
@@ -146,9 +148,22 @@ def solver_grid_arrays(T, step_size):
                 bstep_off=torch.tensor(off, dtype=torch.int32), bstep_dt=torch.cat(steps))
 
 
+def latent_co_perm(n_categ=0):
+    """Latent column -> row of the first decoder weight (the reference's z = cat([content, category, motion]),
+    models/mocogan.py:264-267): columns [motion 16 | content 50 | one-hot C | pad] -> rows [50+C .. 65+C | 0 .. 49 |
+    50 .. 49+C | -1 (no row: the column multiplies zeros)]."""
+    C_ = int(n_categ)
+    return ([50 + C_ + i for i in range(16)] + list(range(50)) + [50 + i for i in range(C_)]
+            + [-1] * (Z_COLS - Z_CATEG0 - C_))
+
+
 class _GenPlan:
     """ODE solve + decoder for `n_traj` trajectories.  full: rows = n_traj*T; select: rows = n_traj (one chosen
     time per trajectory, sample_images)."""
+
+    # categorical state (dim_z_category > 0): class-level defaults, so that the latent-only plans built without
+    # __init__ (sample_z_m: _LatentFn and its SDE / CDE twins) are unconditional
+    ncat, cls, labels = 0, None, None
 
     def __init__(self, gen: "VideoGenerator", n_traj: int, T: int, select: bool, zbuf=None):
         """zbuf: latent rows of a joint pass (_GenJointPlan) -- the plan then is the latent half only (no decoder stack)."""
@@ -158,12 +173,17 @@ class _GenPlan:
         f32 = dict(dtype=torch.float32, device=dev)
         # host-drawn inputs live in ONE device buffer [x 16 | content 50 | sel (int32 bits) 1] per trajectory block, so a
         # call stages them with a single H2D copy
+        # (dim_z_category > 0: + the trajectory's class as int32 bits, one more word per trajectory)
         xs = self._x_shape(n_traj, T)
         nx = int(np.prod(xs))
-        self._in = torch.zeros(nx + n_traj * 51, **f32)
+        self.ncat = int(getattr(gen, "dim_z_category", 0))
+        per = 52 if self.ncat else 51
+        self._in = torch.zeros(nx + n_traj * per, **f32)
         self.x = self._in[:nx].view(xs)
         self.content = self._in[nx:nx + n_traj * 50].view(n_traj, 50)
-        self.sel = self._in[nx + n_traj * 50:].view(torch.int32) if select else None
+        self.sel = self._in[nx + n_traj * 50:nx + n_traj * 51].view(torch.int32) if select else None
+        self.cls = self._in[nx + n_traj * 51:].view(torch.int32) if self.ncat else None
+        self.labels = None           # int64 classes of the staged call (written by the one-hot op; full mode only)
         self.traj = torch.empty(n_traj, T, 16, **f32)
         tt = torch.linspace(0, 1, T).float()            # models/mocogan_ode.py:143 -- fp32 grid built on the host
         self.dt = (tt[1:] - tt[:-1]).to(dev) if T > 1 else torch.zeros(1, **f32)
@@ -179,9 +199,9 @@ class _GenPlan:
         # drains (no host/GPU overlap between consecutive calls); slots are recycled behind an event
         self._ring = []
         for _ in range(4):
-            buf = torch.zeros(nx + n_traj * 51).pin_memory()
+            buf = torch.zeros(nx + n_traj * per).pin_memory()
             self._ring.append(dict(buf=buf, x=buf[:nx].view(xs), c=buf[nx:nx + n_traj * 50].view(n_traj, 50),
-                                   s=buf[nx + n_traj * 50:].view(torch.int32), ev=None))
+                                   s=buf[nx + n_traj * 50:nx + n_traj * 51].view(torch.int32), ev=None))
         self._ring_i = 0
 
     @staticmethod
@@ -246,14 +266,29 @@ class _GenPlan:
                 self.fwd_op.G = gd["G"]
                 self.fwd_op.grid_dt, self.fwd_op.emit_at, self.fwd_op.emit_w = dptr(gd["grid_dt"]), dptr(gd["emit_at"]), dptr(gd["emit_w"])
                 self.bwd_op.bstep_off, self.bwd_op.bstep_dt = dptr(gd["bstep_off"]), dptr(gd["bstep_dt"])
-            self.fwd_prog = L.Program([self.fwd_op])
+            self.categ_op = None
+            if self.ncat:
+                # the one-hot columns follow the solve in the same program (the solve's content broadcast zeroes the pad)
+                self.categ_op = L.CategOp(cls=dptr(self.cls), z=dptr(zbuf), labels_out=None, n_traj=self.n,
+                                          rows_per=1 if self.select else self.T, C=self.ncat, zcols=zcols, col0=Z_CATEG0)
+            self.fwd_prog = L.Program([self.fwd_op] + ([self.categ_op] if self.ncat else []))
         self.fwd_op.substeps = self.bwd_op.substeps = self.gen.ode_substeps
         if self.gen.ode_method == "dopri5":
             self.bwd_op.substeps = self.gen.adjoint_substeps
 
-    def stage_inputs(self, x_host, content_host, sel_host):
-        """Host-drawn inputs -> the plan's device block, on the current stream (one H2D copy)."""
+    def stage_inputs(self, x_host, content_host, sel_host, cls_host=None):
+        """Host-drawn inputs -> the plan's device block, on the current stream (one H2D copy).  cls_host: the trajectories'
+        classes (dim_z_category > 0)."""
         self._programs()
+        if self.ncat:
+            if cls_host is None:
+                raise RuntimeError("a categorical generator plan needs the classes of its trajectories")
+            if getattr(self.gen, "_feed", None) is not None and self.gen._feed.recording:
+                raise NotImplementedError("categorical latents are not captured in a graph (GanTrainer(graph=True))")
+            if not self.select:      # a fresh tensor per call: it leaves the plan as sample_videos' second result
+                self.labels = torch.empty(self.n, dtype=torch.int64, device=self.device)
+            self.categ_op.labels_out = dptr(self.labels) if not self.select else None
+            self._cls_host = cls_host
         feed = getattr(self.gen, "_feed", None)
         if feed is not None and feed.recording:
             # graph capture (GanTrainer(graph=True)): the inputs travel in the trainer's HostFeed block; the recorded
@@ -273,14 +308,17 @@ class _GenPlan:
                 slot["ev"] = torch.cuda.Event()
             slot["ev"].record()
 
-    def forward(self, x_host, content_host, sel_host, training, keep):
+    def forward(self, x_host, content_host, sel_host, training, keep, cls_host=None):
         """x_host None: the latent rows of this call were produced ahead of time by VideoGenerator.prefetch_latents (on
         its own stream); only the decoder runs here, after the latent's event."""
         if x_host is None:
             torch.cuda.current_stream().wait_event(self._latent_ev)
             out = self.stack.forward(training)
         else:
-            self.stage_inputs(x_host, content_host, sel_host)
+            if cls_host is None:
+                self.stage_inputs(x_host, content_host, sel_host)
+            else:
+                self.stage_inputs(x_host, content_host, sel_host, cls_host)
             out = self.stack.forward(training, pre_ops_program=self.fwd_prog)
         self.busy = keep
         return out
@@ -292,6 +330,8 @@ class _GenPlan:
         buf[nx:nx + n * 50].copy_(content_host.reshape(-1))
         if self.select:
             buf[nx + n * 50:nx + n * 51].view(torch.int32).copy_(sel_host)
+        if self.ncat:
+            buf[nx + n * 51:nx + n * 52].view(torch.int32).copy_(torch.from_numpy(self._cls_host.astype(np.int32)))
 
     def _decoder_into(self, arena):
         """Per decoder layer (weight, gamma, beta gradient targets, accumulate?) inside the trainer's arena: the first
@@ -457,8 +497,11 @@ class _GenFn(torch.autograd.Function):
     """Whole generator pass (pre-net + RK4 + decoder) as one autograd node; backward = decoder backward + adjoint."""
 
     @staticmethod
-    def forward(ctx, plan, x_host, content_host, sel_host, training, keep, n_dec, *params):
-        out = plan.forward(x_host, content_host, sel_host, training, keep)
+    def forward(ctx, plan, x_host, content_host, sel_host, cls_host, training, keep, n_dec, *params):
+        if cls_host is None:
+            out = plan.forward(x_host, content_host, sel_host, training, keep)
+        else:
+            out = plan.forward(x_host, content_host, sel_host, training, keep, cls_host=cls_host)
         ctx.plan, ctx.n_dec, ctx.n_params = plan, n_dec, len(params)
         ctx.lease = _Lease(plan)
         return out
@@ -470,7 +513,7 @@ class _GenFn(torch.autograd.Function):
         arena = getattr(plan.gen, "_gode_arena", None)
         if arena is not None and arena.active:
             plan.backward(gout, arena)
-            return (None,) * (7 + ctx.n_params)
+            return (None,) * (8 + ctx.n_params)
         views, motion = plan.backward(gout)
         grads = []
         for wv, gv, bv in views:
@@ -478,7 +521,7 @@ class _GenFn(torch.autograd.Function):
             if gv is not None:
                 grads += [gv, bv]
         assert len(grads) == ctx.n_dec and len(motion) == ctx.n_params - ctx.n_dec
-        return (None, None, None, None, None, None, None, *grads, *motion)
+        return (None, None, None, None, None, None, None, None, *grads, *motion)
 
 
 class _LatentFn(torch.autograd.Function):
@@ -527,6 +570,7 @@ class VideoGenerator(nn.Module):
 
     mnist = False
     _plan_cls = None   # set below (_GenPlan)
+    _categorical_ok = True     # dim_z_category > 0 is served (the other motion latents switch it off)
     # the reference passes method='rk4' (models/mocogan_ode.py:50,144); 'dopri5' is what BASELINE configs[3] words
     ode_method = "rk4"
     # adjoint_substeps (dopri5 only): 0 = the adjoint is integrated adaptively with the same controller and
@@ -536,8 +580,12 @@ class VideoGenerator(nn.Module):
     def __init__(self, n_channels, dim_z_content, dim_z_category, dim_z_motion, video_length, ode_fn=ODEFunc,
                  dim_hidden=None, linear=True, ngf=64):
         super().__init__()
-        if dim_z_category != 0:
-            raise NotImplementedError("categorical latents are never used by the stage-3 scripts (dim_z_category=0)")
+        if not self._categorical_ok and dim_z_category != 0:
+            raise NotImplementedError(f"categorical latents (dim_z_category={dim_z_category}) are implemented for the "
+                                      f"Neural-ODE generators only, not for {type(self).__name__}")
+        if not (0 <= int(dim_z_category) <= MAX_CATEG) or int(dim_z_category) != dim_z_category:
+            raise NotImplementedError(f"dim_z_category={dim_z_category}: the categorical one-hot lives in the {MAX_CATEG} pad "
+                                      f"columns of the {Z_COLS}-column latent row (0 <= dim_z_category <= {MAX_CATEG})")
         if dim_z_motion != 16 or dim_z_content != 50:
             raise NotImplementedError("libgode's fused ODE kernels are specialised for dim_z_motion=16, "
                                       "dim_z_content=50 (mnist_moco_ode.py:78, ucf_moco_ode.py:80)")
@@ -604,8 +652,7 @@ class VideoGenerator(nn.Module):
     def _decoder_specs(self, rows):
         ngf, nc = self.ngf, self.n_channels
         dev = self.main[0].weight.device
-        perm = torch.tensor([50 + i for i in range(16)] + list(range(50)) + [-1] * (Z_COLS - 66), dtype=torch.int32,
-                            device=dev)
+        perm = torch.tensor(latent_co_perm(self.dim_z_category), dtype=torch.int32, device=dev)
         one = (1, 1, 1)
         specs = [LayerSpec(make_geom(rows, ngf * 8, Z_COLS, (1, 4, 4), one, (1, 4, 4), one, (0, 0, 0)), L.DGRAD,
                            L.ACT_RELU, True, co_perm=perm)]
@@ -685,14 +732,14 @@ class VideoGenerator(nn.Module):
         x = torch.randn(num_samples, self.dim_z_motion)
         return torch.from_numpy(content), x
 
-    def _run(self, n_traj, T, select, x, content, sel, plan=None):
+    def _run(self, n_traj, T, select, x, content, sel, plan=None, cls=None):
         _require_gpu(self.main[0].weight, type(self).__name__)
         if plan is None:
             plan = self._pool.get((n_traj, T, select), lambda: self._plan_cls(self, n_traj, T, select))
         dec, ode = self._param_list()
         # (grad mode is off inside Function.forward, so decide here whether the plan must be kept for a backward)
         keep = torch.is_grad_enabled() and any(p.requires_grad for p in dec + ode)
-        return _GenFn.apply(plan, x, content, sel, self.training, keep, len(dec), *dec, *ode)
+        return _GenFn.apply(plan, x, content, sel, cls, self.training, keep, len(dec), *dec, *ode)
 
     # -- latents ahead of time ----------------------------------------------------------------------------------------
     def prefetch_latents(self, calls):
@@ -759,6 +806,8 @@ class VideoGenerator(nn.Module):
                 chunk = plans[k:k + 8]
                 arr = (L.OdeFwdOp * len(chunk))(*[p.fwd_op for p in chunk])
                 L.call("ode_fwd_multi", lambda: L.check(L.lib().gode_ode_fwd_multi(arr, len(chunk), st), "gode_ode_fwd_multi"))
+            if self.dim_z_category:          # the one-hot columns of every solve, behind the solves
+                L.Program([p.categ_op for p in plans]).run(st)
             return
         for p in plans:
             p.fwd_prog.run(st)
@@ -800,6 +849,17 @@ class VideoGenerator(nn.Module):
         sel int32 [n_traj] or None).  sample_images: the reference integrates B*T*2 trajectories and decodes B randomly
         chosen rows of the B*T*2*T latent rows (models/mocogan.py:287-295); all draws are made, only the chosen
         trajectories are kept."""
+        if self.dim_z_category:
+            # + the classes, drawn between the content and the motion noise (models/mocogan.py:259-262): a 4-tuple
+            if not select:
+                content, cls, x = self._draw_categorical(num_samples)
+                return x, content, None, cls
+            n_all = num_samples * T * 2
+            content, cls, x = self._draw_categorical(n_all)
+            j = np.sort(np.random.choice(n_all * T, num_samples, replace=False)).astype(np.int64)
+            traj = torch.from_numpy(j // T)
+            sel = torch.from_numpy((j % T).astype(np.int32))
+            return self._take_trajectories(x, traj), content[traj].contiguous(), sel, cls[j // T]
         if not select:
             content, x = self._draw(num_samples, T)
             return x, content, None
@@ -810,13 +870,21 @@ class VideoGenerator(nn.Module):
         sel = torch.from_numpy((j % T).astype(np.int32))
         return self._take_trajectories(x, traj), content[traj].contiguous(), sel
 
+    def _draw_categorical(self, num_samples):
+        """_draw with the class draw at the reference's place: content (NumPy normal), classes (ONE np.random.randint(C,
+        size=n), models/mocogan.py:237), motion noise (torch.randn)."""
+        content = np.random.normal(0, 1, (num_samples, self.dim_z_content)).astype(np.float32)
+        cls = np.random.randint(self.dim_z_category, size=num_samples)
+        x = torch.randn(num_samples, self.dim_z_motion)
+        return torch.from_numpy(content), cls, x
+
     @staticmethod
     def _take_trajectories(x, traj):
         return x[traj].contiguous()
 
     def _fill_host_inputs(self, buf, select, num_samples, T):
         """Graph replay (HostFeed): the same draws, written straight into the feed block's region for this call site."""
-        x, content, sel = self._host_inputs(select, num_samples, T)
+        x, content, sel = self._host_inputs(select, num_samples, T)[:3]
         nx, n = x.numel(), content.shape[0]
         buf[:nx].copy_(x.reshape(-1))
         buf[nx:nx + n * 50].copy_(content.reshape(-1))
@@ -824,16 +892,24 @@ class VideoGenerator(nn.Module):
             buf[nx + n * 50:nx + n * 51].view(torch.int32).copy_(sel)
 
     def sample_videos(self, num_samples, video_len=None):
-        """-> (videos [B, C, T, H, W] fp32, float64 zero labels [B]); models/mocogan.py:271-285."""
+        """-> (videos [B, C, T, H, W] fp32, float64 zero labels [B]); models/mocogan.py:271-285.  dim_z_category > 0: the
+        second result is the int64 classes the videos were generated for (on the device, as the reference's)."""
         T = video_len if video_len is not None else self.video_length
         plan = self._take_prefetched(False, num_samples, T)
         if plan is not None:
             h = self._run(num_samples, T, False, None, None, None, plan=plan)
+        elif self.dim_z_category:
+            _require_gpu(self.main[0].weight, type(self).__name__)
+            plan = self._pool.get((num_samples, T, False), lambda: self._plan_cls(self, num_samples, T, False))
+            x, content, _, cls = self._host_inputs(False, num_samples, T)
+            h = self._run(num_samples, T, False, x, content, None, plan=plan, cls=cls)    # (plan.labels: the int64 classes)
         else:
             x, content, _ = self._host_inputs(False, num_samples, T)
             h = self._run(num_samples, T, False, x, content, None)        # [B*T, 1, H, W, C]
         H, W = h.size(2), h.size(3)
         h = h.view(num_samples, T, H, W, self.n_channels).permute(0, 4, 1, 2, 3)
+        if self.dim_z_category:
+            return h, plan.labels
         return h, self._zero_labels(num_samples, h.device)
 
     def sample_images(self, num_samples):
@@ -848,6 +924,9 @@ class VideoGenerator(nn.Module):
         plan = self._take_prefetched(True, num_samples, T)
         if plan is not None:
             h = self._run(num_samples, T, True, None, None, None, plan=plan)
+        elif self.dim_z_category:
+            x, content, sel, cls = self._host_inputs(True, num_samples, T)
+            h = self._run(num_samples, T, True, x, content, sel, cls=cls)
         else:
             x, content, sel = self._host_inputs(True, num_samples, T)
             h = self._run(num_samples, T, True, x, content, sel)
@@ -877,7 +956,7 @@ class VideoGenerator(nn.Module):
         H, W = hv.size(2), hv.size(3)
         vid = hv.view(n_videos, T, H, W, self.n_channels).permute(0, 4, 1, 2, 3)
         img = hi.view(n_images, H, W, self.n_channels).permute(0, 3, 1, 2)
-        return (vid, self._zero_labels(n_videos, vid.device)), (img, None)
+        return (vid, plan.vid.labels if self.dim_z_category else self._zero_labels(n_videos, vid.device)), (img, None)
 
     def can_pair(self, n_videos, n_images, images_first=False):
         """Can sample_pair decode these two batches in one pass?  (Builds the plan on first use.)"""
@@ -905,8 +984,15 @@ class VideoGenerator(nn.Module):
         return torch.from_numpy(c).to(self.main[0].weight.device)
 
     def sample_z_categ(self, num_samples, video_len=None):
-        """models/mocogan.py:231-247 with dim_z_category == 0 (the only case stage 3 uses): (None, np.zeros(N))."""
-        return None, np.zeros(num_samples)
+        """models/mocogan.py:231-247: dim_z_category == 0 -> (None, np.zeros(N)); else ONE np.random.randint(C, size=N)
+        -> (one-hot [N*T, C] on the device, the same row on all T rows of a video; the classes as a NumPy array)."""
+        if self.dim_z_category <= 0:
+            return None, np.zeros(num_samples)
+        T = video_len if video_len is not None else self.video_length
+        classes = np.random.randint(self.dim_z_category, size=num_samples)
+        one_hot = np.zeros((num_samples, self.dim_z_category), dtype=np.float32)
+        one_hot[np.arange(num_samples), classes] = 1
+        return torch.from_numpy(np.repeat(one_hot, T, axis=0)).to(self.main[0].weight.device), classes
 
     def sample_z_m(self, num_samples, video_len=None):
         """models/mocogan_ode.py:133-148 (UCF class :39-54): torch.randn(N, 16) on the CPU generator -> pre-net ->
@@ -929,6 +1015,8 @@ class VideoGenerator(nn.Module):
         z_content = self.sample_z_content(num_samples, video_len)
         z_category, z_category_labels = self.sample_z_categ(num_samples, video_len)
         z_motion = self.sample_z_m(num_samples, video_len)
+        if z_category is not None:
+            return torch.cat([z_content, z_category, z_motion], dim=1), z_category_labels
         return torch.cat([z_content, z_motion], dim=1), z_category_labels
 
     def forward(self, *a, **k):
@@ -1078,6 +1166,8 @@ class VideoGeneratorMNISTODERNN(VideoGeneratorMNIST):
     Noise: the reference calls T.FloatTensor(n, d).normal_() (models/mocogan.py:297-301), i.e. the DEVICE generator on
     a GPU; here it is always drawn from the global torch CPU generator in the same order and copied to the device, so
     that runs are comparable with the CPU oracle at identical seeds ("ROCm .cuda() semantics")."""
+
+    _categorical_ok = False     # dim_z_category > 0 is refused: categorical latents exist for the Neural-ODE generators only
 
     _plan_cls = _RnnGenPlan
     ode_rtol, ode_atol = 1e-7, 1e-9
@@ -1493,6 +1583,8 @@ class VideoGeneratorSDE(VideoGeneratorMNIST):
     RNG order: sample_videos(n): content (NumPy), x0 = randn(n, 16), xi = randn(S, n, 16); sample_images(n): content and
     x0 of all n*T*2 trajectories, np.random.choice, then xi for the kept trajectories only ([S, n, 16])."""
 
+    _categorical_ok = False     # dim_z_category > 0 is refused: categorical latents exist for the Neural-ODE generators only
+
     _plan_cls = _SdeGenPlan
     _sde_dt = 2.5e-2
     _gode_graph_capture = False     # GanTrainer(graph=True) refuses this generator (not captured / verified)
@@ -1760,6 +1852,8 @@ class VideoGeneratorCDE(VideoGeneratorMNIST):
     RNG order: sample_videos(n): content (NumPy), x = randn(n, 16); sample_images(n): content and x of all n*T*2
     trajectories, then np.random.choice.  Dead parameters (never used by sample_z_m, no gradient): recurrent.*,
     linear.*."""
+
+    _categorical_ok = False     # dim_z_category > 0 is refused: categorical latents exist for the Neural-ODE generators only
 
     _plan_cls = _CdeGenPlan
     _gode_graph_capture = False     # GanTrainer(graph=True) refuses this generator (not captured / verified)
@@ -2044,6 +2138,14 @@ class _DiscBase(nn.Module):
             del self._pool.pack_cache[k]
 
     def forward(self, input):
+        out = self._forward_raw(input)
+        h = out.permute(0, 4, 1, 2, 3)
+        if input.dim() == 4:
+            h = h.squeeze(2)       # (a squeeze, not h[:, :, 0]: select's backward allocates a zero tensor and copies)
+        return h.squeeze(), None
+
+    def _forward_raw(self, input):
+        """The stack's output as written: channels-last [B, Do, Ho, Wo, C]."""
         _require_gpu(self.main[1].weight, type(self).__name__)
         _require_gpu(input, type(self).__name__ + " input")
         if input.dtype != torch.float32:
@@ -2064,11 +2166,7 @@ class _DiscBase(nn.Module):
                 params += [p.gamma, p.beta]
         keep = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
         noise = self._noise_args(1)
-        out = _DiscFn.apply(plan, strides, self.training, keep, getattr(self, "_gode_arena", None), noise, x, *params)      # [B, Do, Ho, Wo, 1]
-        h = out.permute(0, 4, 1, 2, 3)
-        if input.dim() == 4:
-            h = h.squeeze(2)       # (a squeeze, not h[:, :, 0]: select's backward allocates a zero tensor and copies)
-        return h.squeeze(), None
+        return _DiscFn.apply(plan, strides, self.training, keep, getattr(self, "_gode_arena", None), noise, x, *params)      # [B, Do, Ho, Wo, C]
 
 
     @staticmethod
@@ -2162,8 +2260,9 @@ class VideoDiscriminator(_DiscBase):
     def __init__(self, n_channels, n_output_neurons=1, bn_use_gamma=True, use_noise=False, noise_sigma=None, ndf=64,
                  ksize=4):
         super().__init__()
-        if n_output_neurons != 1:
-            raise NotImplementedError("n_output_neurons != 1 is only used by the categorical discriminator")
+        if int(n_output_neurons) != n_output_neurons or not (1 <= n_output_neurons <= 1 + MAX_CATEG):
+            raise NotImplementedError(f"n_output_neurons={n_output_neurons}: 1 (the reference's scripts) up to "
+                                      f"{1 + MAX_CATEG} (CategoricalVideoDiscriminator with {MAX_CATEG} classes)")
         self._init_noise(use_noise, noise_sigma, stream=1)
         self.n_channels, self.n_output_neurons = n_channels, n_output_neurons
         self.bn_use_gamma, self.ndf, self.ksize = bn_use_gamma, ndf, ksize
@@ -2192,6 +2291,36 @@ class VideoDiscriminator(_DiscBase):
                                    noise=self._noise_active() and i in self.NOISED_LAYERS))
             D, H, W = Do, Ho, Wo
         Do, Ho, Wo = conv_out(D, k, 1, 0), conv_out(H, k, 1, 0), conv_out(W, k, 1, 0)
-        specs.append(LayerSpec(make_geom(B, chans[4], 1, (D, H, W), (Do, Ho, Wo), (k, k, k), (1, 1, 1), (0, 0, 0)),
-                               L.FPROP, L.ACT_NONE, False))
+        specs.append(LayerSpec(make_geom(B, chans[4], self.n_output_neurons, (D, H, W), (Do, Ho, Wo), (k, k, k), (1, 1, 1),
+                                         (0, 0, 0)), L.FPROP, L.ACT_NONE, False))
         return specs
+
+
+class CategoricalVideoDiscriminator(VideoDiscriminator):
+    """models/mocogan.py:167-182: a VideoDiscriminator whose final convolution has n_output_neurons + dim_categorical
+    outputs; forward -> (labels [B, n_output_neurons], categ [B, dim_categorical]), two views of the ONE [B, 1 + C] head
+    buffer the stack wrote (autograd sums their gradients into one upstream tensor and the stack's backward runs once).
+    Where the stack's output is not 1x1x1 (the 28x28 MNIST videos with ksize=2: 11x2x2 positions) the reference's
+    squeeze() + split give labels [B, n_out, Do, Ho, Wo] and categ [B, C, Do, Ho, Wo], and so does this class.
+    The head (<= 31 columns, K = 8 ndf k^3) runs on the stack's generic implicit-GEMM and weight-gradient kernels (DESIGN
+    section 13).  `ndf`, `ksize` are keyword extensions, as on VideoDiscriminator."""
+
+    def __init__(self, n_channels, dim_categorical, n_output_neurons=1, use_noise=False, noise_sigma=None, ndf=64, ksize=4):
+        if int(dim_categorical) != dim_categorical or not (1 <= dim_categorical <= MAX_CATEG):
+            raise NotImplementedError(f"dim_categorical={dim_categorical}: 1 .. {MAX_CATEG} classes")
+        super().__init__(n_channels=n_channels, n_output_neurons=n_output_neurons + dim_categorical, use_noise=use_noise,
+                         noise_sigma=noise_sigma, ndf=ndf, ksize=ksize)
+        self.dim_categorical = dim_categorical
+
+    def split(self, input):
+        return input[:, :input.size(1) - self.dim_categorical], input[:, input.size(1) - self.dim_categorical:]
+
+    def forward_head(self, input):
+        """The raw head as ONE channels-last tensor [B, Do, Ho, Wo, n_output_neurons] (labels | categ columns per output
+        position) -- what the fused losses (train.bce_ce_head*) read; [B, n_output_neurons] when the output is 1x1x1."""
+        out = self._forward_raw(input)
+        return out.view(out.shape[0], out.shape[4]) if out.numel() == out.shape[0] * out.shape[4] else out
+
+    def forward(self, input):
+        h = self.forward_head(input)
+        return self.split(h if h.dim() == 2 else h.permute(0, 4, 1, 2, 3))

@@ -153,6 +153,132 @@ def bce_with_logits_pair(logits_a, target_a: float, logits_b, target_b: float) -
     return _BceConstFn.apply(logits_a, target_a, logits_b, target_b)
 
 
+# Categorical MoCoGAN (models/mocogan.py:167-182): nn.CrossEntropyLoss() on the class logits, alone or fused with the
+# BCE terms of the same optimiser step.  A categorical head is ONE [B, 1 + C] tensor (column 0: the real/fake logit,
+# columns 1..C: the class logits); every term of a step adds into one device scalar and writes its part of the head's
+# upstream gradient in place, so the step keeps one loss node and its backward launches nothing.
+class _TermsFn(torch.autograd.Function):
+    """sum of loss terms over 1..n input tensors as one autograd node.  terms (applied in order, the first stores the loss
+    scalar, the others add): ("bce", input, first element, n, element stride, target) -- gode_bce_logits;
+    ("ce", input, first class column, C, rows, labelled rows, labels, rows per label) -- gode_ce_logits over a [rows, width]
+    input.  The terms of an input together write every element of its gradient."""
+
+    @staticmethod
+    def forward(ctx, terms, *xs):
+        xs = [x.contiguous() for x in xs]
+        loss = torch.empty((), dtype=torch.float32, device=xs[0].device)
+        grads = [torch.empty_like(x) for x in xs]
+        st = stream_ptr()
+        for k, t in enumerate(terms):
+            x, g = xs[t[1]], grads[t[1]]
+            if t[0] == "bce":
+                _, _, off, n, stride, target = t
+                op = L.BceOp(logits=x.data_ptr() + 4 * off, grad=g.data_ptr() + 4 * off, loss=loss.data_ptr(), n=n,
+                             target=float(target), gscale=1.0, accumulate=1 if k else 0, stride=stride)
+            else:
+                _, _, col0, ncls, rows, n_lab, labels, rpl = t
+                ld = x.numel() // rows
+                op = L.CeOp(logits=x.data_ptr() + 4 * col0, labels=None if labels is None else labels.data_ptr(),
+                            grad=g.data_ptr() + 4 * col0, loss=loss.data_ptr(), B=rows, n_lab=n_lab, C=ncls, ld=ld, gld=ld,
+                            gscale=1.0, accumulate=1 if k else 0, rows_per_label=rpl)
+            L.run_one(op, st)
+        ctx.save_for_backward(*grads)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        return (None, *[_scaled(g, gout) for g in ctx.saved_tensors])
+
+
+def _check_labels(labels, rows, what):
+    if not (torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.int64 and labels.dim() == 1
+            and labels.shape[0] == rows):
+        raise RuntimeError(f"{what}: labels must be an int64 device tensor [{rows}]")
+    return labels.contiguous()
+
+
+def _check_head(head, what):
+    """-> (videos, rows, width): a categorical head is [B, 1 + C], or channels-last [B, Do, Ho, Wo, 1 + C] as the stack
+    writes it -- rows = B * Do * Ho * Wo positions of 1 + C columns each (a patch head when Do * Ho * Wo > 1: every
+    position carries a real/fake logit and classifies its video)."""
+    if not (torch.is_tensor(head) and head.is_cuda):
+        raise RuntimeError(f"{what} runs only on the GPU through libgode.so")
+    if head.dtype != torch.float32 or head.dim() not in (2, 5) or head.shape[-1] < 2:
+        raise RuntimeError(f"{what}: a float32 categorical head [B, 1 + C] or [B, Do, Ho, Wo, 1 + C] is expected")
+    W = head.shape[-1]
+    return head.shape[0], head.numel() // W, W
+
+
+class _CeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, categ, labels):
+        x = categ if (categ.stride(1) == 1 and categ.stride(0) >= categ.shape[1]) else categ.contiguous()
+        B, ncls = x.shape
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        grad = torch.empty((B, ncls), dtype=torch.float32, device=x.device)
+        L.run_one(L.CeOp(logits=x.data_ptr(), labels=labels.data_ptr(), grad=grad.data_ptr(), loss=loss.data_ptr(), B=B,
+                         n_lab=B, C=ncls, ld=x.stride(0), gld=ncls, gscale=1.0, accumulate=0), stream_ptr())
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        (grad,) = ctx.saved_tensors
+        return _scaled(grad, gout), None
+
+
+def categorical_cross_entropy(categ: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """nn.CrossEntropyLoss()(categ, labels): categ [B, C] fp32 (a view of a categorical head is read in place), labels
+    int64 [B] on the device; one launch, fixed summation order."""
+    if not (torch.is_tensor(categ) and categ.is_cuda):
+        raise RuntimeError("categorical_cross_entropy runs only on the GPU through libgode.so")
+    if categ.dtype != torch.float32 or categ.dim() != 2:
+        raise RuntimeError("categorical_cross_entropy: float32 class logits [B, C] are expected")
+    return _CeFn.apply(categ, _check_labels(labels, categ.shape[0], "categorical_cross_entropy"))
+
+
+def bce_ce_head(head, target: float, labels) -> torch.Tensor:
+    """BCEWithLogits(head[..., :1], target) + CrossEntropy(head[..., 1:], labels) on a categorical head (_check_head); a
+    patch head's positions all take their video's label, each term is the mean over all positions."""
+    B, R, W = _check_head(head, "bce_ce_head")
+    labels = _check_labels(labels, B, "bce_ce_head")
+    return _TermsFn.apply([("bce", 0, 0, R, W, target), ("ce", 0, 1, W - 1, R, R, labels, R // B)], head)
+
+
+def bce_ce_head_pair(head, target: float, labels, logits_b, target_b: float) -> torch.Tensor:
+    """bce_ce_head's two terms with BCEWithLogits(logits_b, target_b) between them (the generator step: video head, image
+    logits, class term): BCE(head[:, :1]) + BCE(logits_b) + CE(head[:, 1:], labels), added in that order."""
+    B, R, W = _check_head(head, "bce_ce_head_pair")
+    if not logits_b.is_cuda:
+        raise RuntimeError("bce_ce_head_pair runs only on the GPU through libgode.so")
+    labels = _check_labels(labels, B, "bce_ce_head_pair")
+    return _TermsFn.apply([("bce", 0, 0, R, W, target), ("bce", 1, 0, logits_b.numel(), 1, target_b),
+                           ("ce", 0, 1, W - 1, R, R, labels, R // B)], head, logits_b)
+
+
+def bce_ce_head_halves(joint, target_first: float, target_second: float, labels_first) -> torch.Tensor:
+    """On the joint categorical head [2B, 1 + C] of forward_pair_joint(real, fake): BCE(first half, t1) + BCE(second
+    half, t2) + CE(class logits of the first half, labels_first); the second half's class columns get zero gradient."""
+    n2, R2, W = _check_head(joint, "bce_ce_head_halves")
+    if n2 % 2:
+        raise RuntimeError("bce_ce_head_halves: an even leading dimension is expected")
+    B, R = n2 // 2, R2 // 2
+    labels = _check_labels(labels_first, B, "bce_ce_head_halves")
+    return _TermsFn.apply([("bce", 0, 0, R, W, target_first), ("bce", 0, R * W, R, W, target_second),
+                           ("ce", 0, 1, W - 1, R2, R, labels, R // B)], joint)
+
+
+def bce_ce_heads(head_a, target_a: float, labels_a, head_b, target_b: float) -> torch.Tensor:
+    """bce_ce_head_halves for two separate passes: BCE(a, ta) + BCE(b, tb) + CE(class logits of a, labels_a)."""
+    B, R, W = _check_head(head_a, "bce_ce_heads")
+    _, Rb, Wb = _check_head(head_b, "bce_ce_heads")
+    if Wb != W:
+        raise RuntimeError("bce_ce_heads: both heads must have the same width")
+    labels = _check_labels(labels_a, B, "bce_ce_heads")
+    return _TermsFn.apply([("bce", 0, 0, R, W, target_a), ("bce", 1, 0, Rb, W, target_b),
+                           ("ce", 0, 1, W - 1, R, R, labels, R // B), ("ce", 1, 1, W - 1, Rb, 0, None, 1)], head_a, head_b)
+
+
 # Wasserstein loss (torchgan.losses, mnist_moco_ode_wgan.py:13,97-98): generator -reduce(fgz), discriminator
 # reduce(fgz - fx), no clipping, no gradient penalty.  The terms of one loss accumulate into one device scalar.
 _REDUCTIONS = {"mean": 0, "sum": 1}
@@ -734,6 +860,23 @@ class GanTrainer:
         self.loss = loss
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0
+        # categorical MoCoGAN: a generator with dim_z_category = C > 0 trains against a CategoricalVideoDiscriminator with
+        # dim_categorical = C and one real/fake logit; the video-D and the G step gain a class term (see step())
+        self.ncat = int(getattr(gen, "dim_z_category", 0) or 0)
+        dcat = int(getattr(dis_vid, "dim_categorical", 0) or 0)
+        if self.ncat != dcat:
+            raise ValueError(f"GanTrainer: the generator has dim_z_category={self.ncat} but the video discriminator has "
+                             f"dim_categorical={dcat}; they must match (0: unconditional)")
+        if self.ncat:
+            if getattr(dis_vid, "n_output_neurons", 1 + dcat) != 1 + dcat:
+                raise ValueError("GanTrainer: the categorical video discriminator must have one real/fake logit "
+                                 "(n_output_neurons=1)")
+            if loss != "bce":
+                raise NotImplementedError("GanTrainer: categorical training is implemented for loss='bce'")
+            if graph:
+                raise NotImplementedError("GanTrainer(graph=True) does not capture categorical training")
+            if self.world > 1:
+                raise NotImplementedError("GanTrainer: categorical training is single-process (no data parallelism)")
         # discriminator instance noise (VideoDiscriminator / PatchImageDiscriminator(use_noise=True)): noise_seed, when given,
         # keys both discriminators' streams (default: each module's torch.initial_seed() at construction).  Replicas take
         # rank 0's seeds; each replica and virtual-replica shard draws the noise of its own samples (_noise_shard).
@@ -1013,9 +1156,27 @@ class GanTrainer:
             torch.cuda.current_stream().wait_stream(self._side)
             self._side_pending = False
 
-    def d_video_step(self, real_vid, _defer=False):
-        """mnist_moco_ode.py:133-150.  real_vid: [B,T,C,H,W], or a list of such shards."""
+    def _labels_for(self, real_labels, B, what):
+        """Categorical training: the int64 [B] device labels of a real video batch (None when categories are off)."""
+        if not self.ncat:
+            if real_labels is not None:
+                raise ValueError(f"{what}: real_labels given, but the networks are unconditional (dim_z_category=0)")
+            return None
+        if real_labels is None:
+            raise ValueError(f"{what}: categorical training (dim_z_category={self.ncat}) needs real_labels, the int64 "
+                             "class of every real video")
+        if not (torch.is_tensor(real_labels) and real_labels.dtype == torch.int64 and real_labels.dim() == 1
+                and real_labels.shape[0] == B and real_labels.is_cuda):
+            raise ValueError(f"{what}: real_labels must be an int64 device tensor [{B}]")
+        return real_labels
+
+    def d_video_step(self, real_vid, _defer=False, real_labels=None):
+        """mnist_moco_ode.py:133-150.  real_vid: [B,T,C,H,W], or a list of such shards.  Categorical training:
+        real_labels int64 [B]; the loss gains CE(categ(real), real_labels)."""
         shards = _shards(real_vid)
+        if self.ncat and len(shards) > 1:
+            raise NotImplementedError("categorical training does not take virtual-replica shards")
+        labels = self._labels_for(real_labels, shards[0].shape[0], "d_video_step")
         losses = []
         begun = False
         call0 = getattr(self.dis_vid, "_noise_call", 0)
@@ -1027,7 +1188,7 @@ class GanTrainer:
                 self._begin(self.dis_vid, self.vid_opt)
                 begun = True
             if not self.pair_d:
-                pr, _ = self.dis_vid(real)
+                pr = self.dis_vid.forward_head(real) if self.ncat else self.dis_vid(real)[0]
             with torch.no_grad():
                 fake, self._paired_fake_vid = self._paired_fake_vid, None
                 if fake is not None:                     # generated by the d_image_step before (see _pair_videos)
@@ -1040,7 +1201,12 @@ class GanTrainer:
                 # all-reduce -- deferred, see overlap_allreduce -- has been running under it; now wait, update, begin
                 self._begin(self.dis_vid, self.vid_opt)
                 begun = True
-            if self.pair_d:
+            if self.ncat:          # BCE(real, 1) + BCE(fake, 0) + CE(categ(real), real_labels): one node
+                if self.pair_d:
+                    loss = bce_ce_head_halves(self.dis_vid.forward_pair_joint(real, fake), 1.0, 0.0, labels)
+                else:
+                    loss = bce_ce_heads(pr, 1.0, labels, self.dis_vid.forward_head(fake), 0.0)
+            elif self.pair_d:
                 loss = self._d_loss_joint(self.dis_vid.forward_pair_joint(real, fake))
             else:
                 pf, _ = self.dis_vid(fake)
@@ -1057,7 +1223,11 @@ class GanTrainer:
             self.gen.can_pair(n_videos, n_images, images_first)
 
     def g_step(self, B, shards=1):
-        """mnist_moco_ode.py:153-163; `shards` virtual replicas of batch B each."""
+        """mnist_moco_ode.py:153-163; `shards` virtual replicas of batch B each.  Categorical training: the loss gains
+        CE(categ(D_vid(fake)), the classes the fake videos were generated for)."""
+        if self.ncat and shards > 1:
+            raise NotImplementedError("categorical training does not take virtual-replica shards")
+        vid_head = (lambda v: self.dis_vid.forward_head(v)) if self.ncat else (lambda v: self.dis_vid(v)[0])
         self._begin(self.gen, self.gen_opt)
         frozen = []
         if self.freeze_d:
@@ -1078,9 +1248,9 @@ class GanTrainer:
                 for m, c0 in zip((self.dis_vid, self.dis_img), calls0):
                     self._noise_shard(m, k, B, shards, c0)
                 if joint:          # both calls' rows in one decoder pass (two BatchNorm batches)
-                    (fake_vid, _), (fake_img, _) = self.gen.sample_pair(B, B)
+                    (fake_vid, classes), (fake_img, _) = self.gen.sample_pair(B, B)
                 else:
-                    fake_vid, _ = self.gen.sample_videos(B)
+                    fake_vid, classes = self.gen.sample_videos(B)
                     fake_img, _ = self.gen.sample_images(B)
                 side = self._side if shards == 1 else None
                 if side is not None:
@@ -1092,13 +1262,15 @@ class GanTrainer:
                     fake_img.record_stream(side)
                     with torch.cuda.stream(side):
                         pi, _ = self.dis_img(fake_img)
-                    pv, _ = self.dis_vid(fake_vid)
+                    pv = vid_head(fake_vid)
                     main.wait_stream(side)
                     pi.record_stream(main)
                 else:
-                    pv, _ = self.dis_vid(fake_vid)
+                    pv = vid_head(fake_vid)
                     pi, _ = self.dis_img(fake_img)
-                if self.loss == "wasserstein":
+                if self.ncat:      # BCE(D_vid(fake), 1) + BCE(D_img(fake_img), 1) + CE(categ(fake), generated classes)
+                    loss = bce_ce_head_pair(pv, 1.0, classes, pi, 1.0)
+                elif self.loss == "wasserstein":
                     loss = wasserstein_generator_loss_pair(pi, pv)      # image term first (mnist_moco_ode_wgan.py:174)
                 else:
                     loss = bce_with_logits_pair(pv, 1.0, pi, 1.0)
@@ -1124,16 +1296,29 @@ class GanTrainer:
         self._flush(self.gen)              # weights are current when the step returns (checkpoints, the next prefetch)
         return self._mean(losses)
 
-    def step(self, real_imgs: Sequence, real_vids: Sequence):
+    def step(self, real_imgs: Sequence, real_vids: Sequence, real_labels: Optional[Sequence] = None):
         """real_imgs[i]: [B,C,H,W], real_vids[i]: [B,T,C,H,W] for i < d_iters (each may instead be a LIST of shard
         tensors: virtual replicas, see the class docstring).  Returns the three losses of the last inner pass as
         device scalars (the reference prints them every 100 iterations); with shards, their mean over the shards.
-        In graph mode the returned scalars are static tensors that the next step() overwrites."""
+        In graph mode the returned scalars are static tensors that the next step() overwrites.
+        real_labels (categorical training, dim_z_category > 0: required; else it must stay None): real_labels[i] is the
+        int64 [B] device tensor of real_vids[i]'s classes.  MoCoGAN's objective: the video-D step minimises BCE(real, 1) +
+        BCE(fake, 0) + CE(categ(real), real_labels), the G step BCE(D_vid(fake), 1) + BCE(D_img(fake_img), 1) +
+        CE(categ(D_vid(fake)), generated classes); the image-D step is unchanged."""
+        if self.ncat or real_labels is not None:
+            if self.ncat and (real_labels is None or len(real_labels) < self.d_iters):
+                raise ValueError(f"GanTrainer.step: categorical training (dim_z_category={self.ncat}) needs real_labels, one "
+                                 "int64 [B] tensor per inner discriminator pass")
+            for i in range(self.d_iters):
+                v = real_vids[i]
+                if isinstance(v, (list, tuple)):
+                    raise NotImplementedError("categorical training does not take virtual-replica shards")
+                self._labels_for(real_labels[i], v.shape[0], "GanTrainer.step")
         if self._graph_mode and self._iters >= 2 and not isinstance(real_imgs[0], (list, tuple)):
             return self._graph_step(real_imgs, real_vids)
-        return self._eager_step(real_imgs, real_vids)
+        return self._eager_step(real_imgs, real_vids, real_labels)
 
-    def _eager_step(self, real_imgs, real_vids):
+    def _eager_step(self, real_imgs, real_vids, real_labels=None):
         first = _shards(real_imgs[0])
         B, nsh = first[0].shape[0], len(first)
         li = lv = None
@@ -1160,7 +1345,7 @@ class GanTrainer:
             for i in range(self.d_iters):
                 # (inside step() the discriminators' optimiser steps are deferred: see overlap_allreduce)
                 li = self.d_image_step(real_imgs[i], _join=False, _defer=True, _pair_videos=pair[i])    # side stream
-                lv = self.d_video_step(real_vids[i], _defer=True)
+                lv = self.d_video_step(real_vids[i], _defer=True, real_labels=real_labels[i] if self.ncat else None)
             if self._pending:
                 # the G step reads both discriminators: their deferred updates land now (the image discriminator's on its
                 # side stream, where its step ran)
@@ -1240,6 +1425,6 @@ class GanTrainer:
         graph.replay()
 
 
-def train_step(trainer: GanTrainer, real_imgs, real_vids):
+def train_step(trainer: GanTrainer, real_imgs, real_vids, real_labels=None):
     """Functional spelling of GanTrainer.step for parity tests that read like oracle.mocogan_ref.train_step."""
-    return trainer.step(real_imgs, real_vids)
+    return trainer.step(real_imgs, real_vids, real_labels)

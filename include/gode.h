@@ -433,11 +433,30 @@ int gode_gru_bwd_multi(const gode_gru_bwd_op* ops, int32_t count, void* stream);
 
 /* ---- loss and optimiser (mnist_moco_ode.py:86-89) ------------------------------------------------------------
  * BCE-with-logits, mean reduced, constant target: loss (+)= mean(max(x,0) - x*t + log1p(exp(-|x|))) and
- * g[i] = gscale*(sigmoid(x[i]) - t)/n.  loss is one device float; accumulate!=0 adds to it. */
+ * g[i] = gscale*(sigmoid(x[i]) - t)/n.  loss is one device float; accumulate!=0 adds to it.  stride > 1: logit i and its
+ * gradient sit at element i*stride of their arrays (column 0 of a [B][1+C] categorical head); 0 or 1: contiguous. */
 typedef struct gode_bce_op {
-  const float* logits; float* grad; float* loss; int64_t n; float target, gscale; int32_t accumulate, pad_;
+  const float* logits; float* grad; float* loss; int64_t n; float target, gscale; int32_t accumulate, stride;
 } gode_bce_op;
 int gode_bce_logits(const gode_bce_op* op, void* stream);
+/* ---- categorical MoCoGAN (models/mocogan.py:167-182,231-247) ----------------------------------------------------
+ * One-hot columns of the latent rows: row r (trajectory r / rows_per; rows_per = T, or 1 when one row per trajectory
+ * was selected) receives z[r*zcols + col0 + c] = (cls[trajectory] == c), c < C; col0 + C <= zcols.  Runs after the
+ * latent solve of the same rows on the same stream.  labels_out (nullable): cls widened to int64[n_traj]. */
+typedef struct gode_categ_op {
+  const int32_t* cls; float* z; int64_t* labels_out; int32_t n_traj, rows_per, C, zcols, col0, pad_;
+} gode_categ_op;
+int gode_categ_onehot(const gode_categ_op* op, void* stream);
+/* nn.CrossEntropyLoss(): loss (+)= mean over rows r < n_lab of -log_softmax(logits[r*ld .. r*ld+C))[labels[r]], summed
+ * in a fixed order (no atomics).  grad (nullable) rows r < n_lab: gscale*(softmax - onehot)/n_lab at grad[r*gld + c];
+ * rows n_lab <= r < B: zeros (n_lab == 0: only that, the loss is not touched).  labels are int64 on the device.
+ * rows_per_label = P > 1: row r takes labels[r / P] (the P output positions of a video's patch head share its class);
+ * 0 or 1: one label per row.  loss is one device float; accumulate != 0 adds to it. */
+typedef struct gode_ce_op {
+  const float* logits; const int64_t* labels; float* grad; float* loss;
+  int32_t B, n_lab, C, ld, gld; float gscale; int32_t accumulate, rows_per_label;
+} gode_ce_op;
+int gode_ce_logits(const gode_ce_op* op, void* stream);
 /* torch.optim.Adam with L2-coupled weight_decay on one tensor: g+=wd*p; m,v update; bias-corrected step. */
 typedef struct gode_adam_op {
   float* p; const float* g; float* m; float* v; int64_t n;
@@ -530,7 +549,7 @@ enum { GODE_OP_IGEMM = 1, GODE_OP_WGRAD = 2, GODE_OP_BN_FINALIZE = 3, GODE_OP_BN
        GODE_OP_ODE_BWD = 6, GODE_OP_BCE = 7, GODE_OP_ADAM = 8, GODE_OP_PACK = 9, GODE_OP_ODERNN_FWD = 10,
        GODE_OP_ODERNN_BWD = 11, GODE_OP_BN_APPLY = 12, GODE_OP_COL2IM = 13, GODE_OP_SDE_FWD = 14,
        GODE_OP_SDE_BWD = 15, GODE_OP_CDE_FWD = 16, GODE_OP_CDE_BWD = 17, GODE_OP_WGAN = 18,
-       GODE_OP_GRU_FWD = 19, GODE_OP_GRU_BWD = 20, GODE_OP_DNOISE = 21 };
+       GODE_OP_GRU_FWD = 19, GODE_OP_GRU_BWD = 20, GODE_OP_DNOISE = 21, GODE_OP_CATEG = 22, GODE_OP_CE = 23 };
 typedef struct gode_pack_op {
   gode_conv_geom g; int32_t dir, co_canon; const float* w; float* wpack; const int32_t* co_perm;
 } gode_pack_op;

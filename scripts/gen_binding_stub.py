@@ -65,7 +65,8 @@ KIND_STRUCT = {"GODE_OP_IGEMM": "gode_igemm_op", "GODE_OP_WGRAD": "gode_wgrad_op
                "GODE_OP_SDE_BWD": "gode_sde_bwd_op", "GODE_OP_CDE_FWD": "gode_cde_fwd_op",
                "GODE_OP_CDE_BWD": "gode_cde_bwd_op", "GODE_OP_WGAN": "gode_wgan_op",
                "GODE_OP_GRU_FWD": "gode_gru_fwd_op", "GODE_OP_GRU_BWD": "gode_gru_bwd_op",
-               "GODE_OP_DNOISE": "gode_dnoise_op"}
+               "GODE_OP_DNOISE": "gode_dnoise_op", "GODE_OP_CATEG": "gode_categ_op",
+               "GODE_OP_CE": "gode_ce_op"}
 
 
 def generate():
