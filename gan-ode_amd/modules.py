@@ -157,60 +157,106 @@ def latent_co_perm(n_categ=0):
             + [-1] * (Z_COLS - Z_CATEG0 - C_))
 
 
+def _input_slices(nx, n):
+    """The host-drawn inputs of a call travel as ONE block of floats, so that a call stages them with a single H2D
+    copy: [x (nx) | content 50 per trajectory | sel 1 per trajectory | class 1 per trajectory], sel and class as int32
+    bits (sel: sample_images only; class: dim_z_category > 0 only, the block then ends one word per trajectory later)."""
+    a, b = nx + n * 50, nx + n * 51
+    return slice(0, nx), slice(nx, a), slice(a, b), slice(b, b + n)
+
+
+def _pack_inputs(buf, x_host, content_host, sel_host=None, cls_host=None):
+    sx, sc, ss, sk = _input_slices(x_host.numel(), content_host.shape[0])
+    buf[sx].copy_(x_host.reshape(-1))
+    buf[sc].copy_(content_host.reshape(-1))
+    if sel_host is not None:
+        buf[ss].view(torch.int32).copy_(sel_host)
+    if cls_host is not None:
+        buf[sk].view(torch.int32).copy_(torch.from_numpy(cls_host.astype(np.int32)))
+
+
+def _run_multi(ops, op_type, name, stream):
+    """gode_<name>(ops, count, stream): several latent solves (or adjoints) side by side, at most 8 per launch."""
+    fn = getattr(L.lib(), "gode_" + name)
+    for k in range(0, len(ops), 8):
+        chunk = ops[k:k + 8]
+        arr = (op_type * len(chunk))(*chunk)
+        L.call(name, lambda: L.check(fn(arr, len(chunk), stream), "gode_" + name))
+
+
+_ODE_GRAD_OFFS = [(0, 1024, (64, 16)), (1024, 64, (64,)), (1088, 1024, (16, 64)), (2112, 16, (16,)),
+                  (2128, 256, (16, 16)), (2384, 16, (16,)), (2400, 256, (16, 16)), (2656, 16, (16,))]
+_PRENET_NPARAM = 2128      # the pre-net's four tensors: the head of the ODE and SDE gradient blocks when it is present
+
+
 class _GenPlan:
     """ODE solve + decoder for `n_traj` trajectories.  full: rows = n_traj*T; select: rows = n_traj (one chosen
-    time per trajectory, sample_images)."""
+    time per trajectory, sample_images).  The subclasses swap the motion latent: each states its buffers (_alloc), its
+    parameters (_params), its ops (_programs) and the class attributes below; the algorithm around them lives here."""
 
-    # categorical state (dim_z_category > 0): class-level defaults, so that the latent-only plans built without
-    # __init__ (sample_z_m: _LatentFn and its SDE / CDE twins) are unconditional
-    ncat, cls, labels = 0, None, None
+    zcols = 68                   # row width of a latent-only plan (sample_z_m); plans with a decoder write Z_COLS
+    rows_in_traj = True          # sample_z_m's rows: the kernel's trajectory buffer (else the first 16 latent columns)
+    nparam, grad_offs = L.ODE_NPARAM, _ODE_GRAD_OFFS       # the adjoint kernel's gradient block
+    # no pre-net: this kernel keeps its offsets (the block's first _PRENET_NPARAM floats stay unwritten); the SDE
+    # kernel's block starts at the first tensor present
+    grads_from_first_present = False
+    # gode_<stem>_fwd_multi / _bwd_multi launch several solves at once (None: no such entry); multi_always False: only
+    # the adaptive solver's, and its adjoints only when they are adaptive too
+    multi, multi_always = ("ode", L.OdeFwdOp, L.OdeBwdOp), False
 
-    def __init__(self, gen: "VideoGenerator", n_traj: int, T: int, select: bool, zbuf=None):
-        """zbuf: latent rows of a joint pass (_GenJointPlan) -- the plan then is the latent half only (no decoder stack)."""
+    def __init__(self, gen: "VideoGenerator", n_traj: int, T: int, select: bool, zbuf=None, x=None):
+        """zbuf: latent rows of a joint pass (_GenJointPlan) -- the plan then is the latent half only (no decoder stack).
+        x: the motion noise on the device -- sample_z_m's plan: the latent half alone on its own [n_traj*T, zcols] rows, no
+        content, no classes, nothing staged."""
         dev = gen.main[0].weight.device
         self.gen, self.n, self.T, self.select, self.device = gen, n_traj, T, select, dev
         self.rows = n_traj if select else n_traj * T
         f32 = dict(dtype=torch.float32, device=dev)
-        # host-drawn inputs live in ONE device buffer [x 16 | content 50 | sel (int32 bits) 1] per trajectory block, so a
-        # call stages them with a single H2D copy
-        # (dim_z_category > 0: + the trajectory's class as int32 bits, one more word per trajectory)
-        xs = self._x_shape(n_traj, T)
-        nx = int(np.prod(xs))
-        self.ncat = int(getattr(gen, "dim_z_category", 0))
-        per = 52 if self.ncat else 51
-        self._in = torch.zeros(nx + n_traj * per, **f32)
-        self.x = self._in[:nx].view(xs)
-        self.content = self._in[nx:nx + n_traj * 50].view(n_traj, 50)
-        self.sel = self._in[nx + n_traj * 50:nx + n_traj * 51].view(torch.int32) if select else None
-        self.cls = self._in[nx + n_traj * 51:].view(torch.int32) if self.ncat else None
+        self.ncat = int(getattr(gen, "dim_z_category", 0)) if x is None else 0
         self.labels = None           # int64 classes of the staged call (written by the one-hot op; full mode only)
-        self.traj = torch.empty(n_traj, T, 16, **f32)
-        tt = torch.linspace(0, 1, T).float()            # models/mocogan_ode.py:143 -- fp32 grid built on the host
-        self.dt = (tt[1:] - tt[:-1]).to(dev) if T > 1 else torch.zeros(1, **f32)
-        if zbuf is None:
+        self.x, self.content, self.sel, self.cls = x, None, None, None
+        self._ring = []
+        if x is None:
+            xs = self._x_shape(n_traj, T)
+            sx, sc, ss, sk = _input_slices(int(np.prod(xs)), n_traj)
+            nin = sk.stop if self.ncat else sk.start
+            self._in = torch.zeros(nin, **f32)
+            self.x, self.content = self._in[sx].view(xs), self._in[sc].view(n_traj, 50)
+            self.sel = self._in[ss].view(torch.int32) if select else None
+            self.cls = self._in[sk].view(torch.int32) if self.ncat else None
+            # pinned staging ring for the host-drawn noise: a pageable H2D copy would block the host until the stream
+            # drains (no host/GPU overlap between consecutive calls); slots are recycled behind an event
+            self._ring = [dict(buf=torch.zeros(nin).pin_memory(), ev=None) for _ in range(4)]
+        self._ring_i = 0
+        # the latent rows the kernels write: the decoder's input, the caller's, or the plan's own
+        self.stack = None
+        if x is not None:
+            self._zbuf, self._zcols = torch.empty(n_traj * T, self.zcols, **f32), self.zcols
+        elif zbuf is not None:
+            self._zbuf, self._zcols = zbuf, Z_COLS
+        else:
             self.stack = ConvStack(gen._decoder_specs(self.rows), gen._decoder_params(), dev, owns_input=True,
                                    pack_cache=gen._pool.pack_cache, two_lane_backward=True)
-        else:
-            self.stack, self._zbuf = None, zbuf
-        self.ode_work = torch.empty(L.lib().gode_ode_bwd_work_size(n_traj), **f32)
+            self._zbuf, self._zcols = self.stack.x_in, Z_COLS
+        self._alloc()
         self._ode_ptrs = None
         self.busy = False
-        # pinned staging ring for the host-drawn noise: a pageable H2D copy would block the host until the stream
-        # drains (no host/GPU overlap between consecutive calls); slots are recycled behind an event
-        self._ring = []
-        for _ in range(4):
-            buf = torch.zeros(nx + n_traj * per).pin_memory()
-            self._ring.append(dict(buf=buf, x=buf[:nx].view(xs), c=buf[nx:nx + n_traj * 50].view(n_traj, 50),
-                                   s=buf[nx + n_traj * 50:nx + n_traj * 51].view(torch.int32), ev=None))
-        self._ring_i = 0
 
     @staticmethod
     def _x_shape(n_traj, T):
         """Shape of the host-drawn noise block: the ODE's initial states."""
         return (n_traj, 16)
 
+    def _alloc(self):
+        """The solver's own device buffers."""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.traj = torch.empty(self.n, self.T, 16, **f32)
+        tt = torch.linspace(0, 1, self.T).float()       # models/mocogan_ode.py:143 -- fp32 grid built on the host
+        self.dt = (tt[1:] - tt[:-1]).to(self.device) if self.T > 1 else torch.zeros(1, **f32)
+        self.ode_work = torch.empty(L.lib().gode_ode_bwd_work_size(self.n), **f32)
 
-    def _ode_params(self):
+    def _params(self):
+        """The latent's tensors in the adjoint kernel's output order (None: an absent pre-net tensor)."""
         g = self.gen
         lin = g.linear
         if isinstance(lin, nn.Identity):
@@ -220,21 +266,36 @@ class _GenPlan:
         f = g.ode_fn.fn
         return pre + (f[0].weight, f[0].bias, f[2].weight, f[2].bias)
 
+    @classmethod
+    def multi_ok(cls, gen, adjoint):
+        """Do this generator's solves (adjoint: their backward passes) go out through the gode_*_multi entries?"""
+        if cls.multi is None:
+            return False
+        return cls.multi_always or (gen.ode_method == "dopri5" and not (adjoint and gen.adjoint_substeps != 0))
+
+    def check_solve(self):
+        """Host-side look at a finished solve (the CDE plan's: it raises when the kernel stopped early)."""
+
+    def latent_rows(self):
+        """sample_z_m's result [n*T, 16] of a latent-only plan: the ODE kernel writes its trajectory in that very order; the
+        other kernels' latent rows hold it in their first 16 columns."""
+        if self.rows_in_traj:
+            return self.traj.view(self.n * self.T, 16)
+        return self._zbuf if self._zcols == 16 else self._zbuf[:, :16].contiguous()
+
     def _solver_grid(self, step_size):
         gd = solver_grid_arrays(self.T, step_size)
         return {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in gd.items()}
 
     def _programs(self):
-        ps = self._ode_params()
+        ps = self._params()
         ptrs = tuple(dptr(p) for p in ps) + (self.gen.ode_step_size, self.gen.ode_method, self.gen.ode_rtol,
                                              self.gen.ode_atol)
         if ptrs != self._ode_ptrs:
             self._ode_ptrs = ptrs
             op = L.OdeParams(*ptrs[:8])
             prenet = 0 if ps[0] is None else 1
-            zbuf = getattr(self, "_zbuf", None)
-            zbuf = self.stack.x_in if zbuf is None else zbuf
-            zcols = getattr(self, "_zcols", Z_COLS)
+            zbuf, zcols = self._zbuf, self._zcols
             self.fwd_op = L.OdeFwdOp(p=op, x=dptr(self.x), content=dptr(self.content), dt=dptr(self.dt),
                                      sel_t=dptr(self.sel), z=dptr(zbuf), traj=dptr(self.traj), N=self.n,
                                      T=self.T, substeps=self.gen.ode_substeps, prenet=prenet, zcols=zcols)
@@ -288,21 +349,20 @@ class _GenPlan:
             if not self.select:      # a fresh tensor per call: it leaves the plan as sample_videos' second result
                 self.labels = torch.empty(self.n, dtype=torch.int64, device=self.device)
             self.categ_op.labels_out = dptr(self.labels) if not self.select else None
-            self._cls_host = cls_host
         feed = getattr(self.gen, "_feed", None)
         if feed is not None and feed.recording:
             # graph capture (GanTrainer(graph=True)): the inputs travel in the trainer's HostFeed block; the recorded
             # copy is device -> device from the block's static region for this call site
             nfl = self._in.numel()
             pin, dev = feed.noise_region(self.gen, self.select, self.n, self.T, nfl)
-            self._pack_inputs(pin, x_host, content_host, sel_host)
+            _pack_inputs(pin, x_host, content_host, sel_host, cls_host)
             self._in.copy_(dev)
         else:
             slot = self._ring[self._ring_i]
             self._ring_i = (self._ring_i + 1) % len(self._ring)
             if slot["ev"] is not None:
                 slot["ev"].synchronize()
-            self._pack_inputs(slot["buf"], x_host, content_host, sel_host)
+            _pack_inputs(slot["buf"], x_host, content_host, sel_host, cls_host)
             self._in.copy_(slot["buf"], non_blocking=True)
             if slot["ev"] is None:
                 slot["ev"] = torch.cuda.Event()
@@ -315,23 +375,10 @@ class _GenPlan:
             torch.cuda.current_stream().wait_event(self._latent_ev)
             out = self.stack.forward(training)
         else:
-            if cls_host is None:
-                self.stage_inputs(x_host, content_host, sel_host)
-            else:
-                self.stage_inputs(x_host, content_host, sel_host, cls_host)
+            self.stage_inputs(x_host, content_host, sel_host, cls_host)
             out = self.stack.forward(training, pre_ops_program=self.fwd_prog)
         self.busy = keep
         return out
-
-    def _pack_inputs(self, buf, x_host, content_host, sel_host):
-        """[x | content 50 per trajectory | sel (int32 bits) 1 per trajectory] -- the layout of self._in."""
-        nx, n = x_host.numel(), self.n
-        buf[:nx].copy_(x_host.reshape(-1))
-        buf[nx:nx + n * 50].copy_(content_host.reshape(-1))
-        if self.select:
-            buf[nx + n * 50:nx + n * 51].view(torch.int32).copy_(sel_host)
-        if self.ncat:
-            buf[nx + n * 51:nx + n * 52].view(torch.int32).copy_(torch.from_numpy(self._cls_host.astype(np.int32)))
 
     def _decoder_into(self, arena):
         """Per decoder layer (weight, gamma, beta gradient targets, accumulate?) inside the trainer's arena: the first
@@ -368,36 +415,36 @@ class _GenPlan:
         return views, motion
 
     def latent_backward(self, gz_ptr, arena, keep):
-        """Adjoint of the latent half given the gradient wrt its latent rows (gz_ptr: first row, Z_COLS floats per row).
-        arena: gradients go straight into the trainer's arena (first writer of a step stores, later ones add) and the
-        launch may be deferred into the trainer's batch; else -> list of gradient tensors (pre-net + ODEFunc order)."""
-        self.bwd_op.gz = gz_ptr
+        """Adjoint of the latent half given the gradient wrt its latent rows (gz_ptr: first row, the op's zcols floats per
+        row).  arena: gradients go straight into the trainer's arena, whose tail holds the latent's tensors contiguously in
+        the kernel's output order (first writer of a step stores, later ones add), and the launch may be deferred into the
+        trainer's batch; else -> list of gradient tensors in _params order (those present)."""
+        op = self.bwd_op
+        op.gz = gz_ptr
+        ps = self._params()
+        absent = _PRENET_NPARAM if ps[0] is None else 0          # floats of the block that belong to no tensor
+        cut = absent if self.grads_from_first_present else 0     # ... and how many of them the kernel leaves out
         if arena is not None:
-            ode = [q for q in self._ode_params() if q is not None]
-            tgt = [arena.target(q) for q in ode]
+            tgt = [arena.target(q) for q in ps if q is not None]      # (every tensor: marks its .grad as written)
             base, acc = tgt[0]
-            off = base.data_ptr() - (0 if self._ode_ptrs[0] is not None else 2128 * 4)   # kernel offsets start at Wa
-            self.bwd_op.grads = off
-            self.bwd_op.accumulate = 1 if acc else 0
+            op.grads = base.data_ptr() - 4 * (absent - cut)
+            op.accumulate = 1 if acc else 0
             batch = getattr(self.gen, "_adjoint_batch", None)
-            if batch is not None and self.gen.ode_method == "dopri5" and self.gen.adjoint_substeps == 0:
-                # adaptive adjoints of the video and the image path: one launch (see _RnnGenPlan.latent_backward)
-                batch["ops"].append(self.bwd_op)
+            if batch is not None and self.multi_ok(self.gen, True):
+                # the trainer announced how many generator passes this backward holds (video + image path of the G step):
+                # their adjoints -- one workgroup each -- go out as ONE launch once the last decoder backward is through
+                batch["ops"].append(op)
                 batch["keep"].append(keep)
                 if len(batch["ops"]) >= batch["expect"]:
                     self.gen.flush_adjoints()
             else:
-                L.run_one(self.bwd_op, stream_ptr())
+                L.run_one(op, stream_ptr())
             return None
-        grads = torch.empty(L.ODE_NPARAM, dtype=torch.float32, device=self.device)
-        self.bwd_op.grads = grads.data_ptr()
-        self.bwd_op.accumulate = 0
-        L.run_one(self.bwd_op, stream_ptr())
-        offs = [(0, 1024, (64, 16)), (1024, 64, (64,)), (1088, 1024, (16, 64)), (2112, 16, (16,)),
-                (2128, 256, (16, 16)), (2384, 16, (16,)), (2400, 256, (16, 16)), (2656, 16, (16,))]
-        if self._ode_ptrs[0] is None:
-            offs = offs[4:]
-        return [grads[o:o + n].view(shp) for o, n, shp in offs]
+        grads = torch.empty(self.nparam - cut, dtype=torch.float32, device=self.device)
+        op.grads = grads.data_ptr()
+        op.accumulate = 0
+        L.run_one(op, stream_ptr())
+        return [grads[o - cut:o - cut + n].view(shp) for o, n, shp in self.grad_offs[4 if absent else 0:]]
 
 
 class _GenJointPlan:
@@ -498,10 +545,7 @@ class _GenFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, x_host, content_host, sel_host, cls_host, training, keep, n_dec, *params):
-        if cls_host is None:
-            out = plan.forward(x_host, content_host, sel_host, training, keep)
-        else:
-            out = plan.forward(x_host, content_host, sel_host, training, keep, cls_host=cls_host)
+        out = plan.forward(x_host, content_host, sel_host, training, keep, cls_host)
         ctx.plan, ctx.n_dec, ctx.n_params = plan, n_dec, len(params)
         ctx.lease = _Lease(plan)
         return out
@@ -525,42 +569,24 @@ class _GenFn(torch.autograd.Function):
 
 
 class _LatentFn(torch.autograd.Function):
-    """sample_z_m as its own autograd node: the fused ODE kernel alone, trajectory written as [N][T][16] = the
-    reference's transpose(0,1).reshape(-1,16) row order."""
+    """sample_z_m as its own autograd node: the generator's latent kernel alone on a latent-only plan, rows [N*T, 16] in
+    the reference's transpose(0, 1).reshape(-1, 16) order (row n*T + t); backward = the plan's adjoint."""
 
     @staticmethod
     def forward(ctx, gen, x_host, n, T, *params):
-        dev = gen.main[0].weight.device
-        lp = _GenPlan.__new__(_GenPlan)           # only the ODE half of a plan: no decoder buffers
-        lp.gen, lp.n, lp.T, lp.select, lp.device = gen, n, T, False, dev
-        f32 = dict(dtype=torch.float32, device=dev)
-        lp.x = x_host.to(dev)
-        lp.content, lp.sel = None, None
-        lp.traj = torch.empty(n, T, 16, **f32)
-        tt = torch.linspace(0, 1, T).float()
-        lp.dt = (tt[1:] - tt[:-1]).to(dev) if T > 1 else torch.zeros(1, **f32)
-        lp._z = torch.empty(n * T, 68, **f32)     # the kernel's latent-row output (unused columns stay unwritten)
-        lp.ode_work = torch.empty(L.lib().gode_ode_bwd_work_size(n), **f32)
-        lp._ode_ptrs = None
-        lp._zbuf, lp._zcols = lp._z, 68
+        lp = gen._plan_cls(gen, n, T, False, x=x_host.to(gen.main[0].weight.device))
         lp._programs()
         lp.fwd_prog.run(stream_ptr())
+        lp.check_solve()
         ctx.lp = lp
-        return lp.traj.view(n * T, 16)
+        return lp.latent_rows()
 
     @staticmethod
     def backward(ctx, gout):
         lp = ctx.lp
         g = gout.contiguous()
-        grads = torch.empty(L.ODE_NPARAM, dtype=torch.float32, device=lp.device)
-        op = lp.bwd_op
-        op.gz, op.zcols, op.grads, op.accumulate = g.data_ptr(), 16, grads.data_ptr(), 0
-        L.run_one(op, stream_ptr())
-        offs = [(0, 1024, (64, 16)), (1024, 64, (64,)), (1088, 1024, (16, 64)), (2112, 16, (16,)),
-                (2128, 256, (16, 16)), (2384, 16, (16,)), (2400, 256, (16, 16)), (2656, 16, (16,))]
-        if lp._ode_ptrs[0] is None:
-            offs = offs[4:]
-        return (None, None, None, None, *[grads[o:o + k].view(shp) for o, k, shp in offs])
+        lp.bwd_op.zcols = 16
+        return (None, None, None, None, *lp.latent_backward(g.data_ptr(), None, g))
 
 
 class VideoGenerator(nn.Module):
@@ -679,18 +705,21 @@ class VideoGenerator(nn.Module):
         out.append(LayerParams(m[12].weight))
         return out
 
-    def _param_list(self):
+    def _decoder_list(self):
         dec = []
         for p in self._decoder_params():
             dec.append(p.weight)
             if p.gamma is not None:
                 dec += [p.gamma, p.beta]
+        return dec
+
+    def _param_list(self):
         ode = []
         if not isinstance(self.linear, nn.Identity):
             ode += [self.linear[0].weight, self.linear[0].bias, self.linear[2].weight, self.linear[2].bias]
         f = self.ode_fn.fn
         ode += [f[0].weight, f[0].bias, f[2].weight, f[2].bias]
-        return dec, ode
+        return self._decoder_list(), ode
 
     def _apply(self, fn, *a, **k):
         r = super()._apply(fn, *a, **k)
@@ -732,7 +761,8 @@ class VideoGenerator(nn.Module):
         x = torch.randn(num_samples, self.dim_z_motion)
         return torch.from_numpy(content), x
 
-    def _run(self, n_traj, T, select, x, content, sel, plan=None, cls=None):
+    def _run(self, n_traj, T, select, x, content, sel, cls=None, plan=None):
+        # (cls before plan: callers splat _host_inputs' three or four values into x, content, sel[, cls])
         _require_gpu(self.main[0].weight, type(self).__name__)
         if plan is None:
             plan = self._pool.get((n_traj, T, select), lambda: self._plan_cls(self, n_traj, T, select))
@@ -800,29 +830,27 @@ class VideoGenerator(nn.Module):
         self._prefetched = queue
 
     def _launch_latents(self, plans):
+        """The latent solves of `plans`: through the plan class's gode_*_fwd_multi entry where it has one -- solves of one
+        workgroup each at the config sizes run side by side instead of back to back -- else program by program."""
         st = stream_ptr()
-        if self.ode_method == "dopri5":     # adaptive solves, one workgroup each at the config sizes: one launch per 8
-            for k in range(0, len(plans), 8):
-                chunk = plans[k:k + 8]
-                arr = (L.OdeFwdOp * len(chunk))(*[p.fwd_op for p in chunk])
-                L.call("ode_fwd_multi", lambda: L.check(L.lib().gode_ode_fwd_multi(arr, len(chunk), st), "gode_ode_fwd_multi"))
+        pc = self._plan_cls
+        if pc.multi_ok(self, False):
+            _run_multi([p.fwd_op for p in plans], pc.multi[1], pc.multi[0] + "_fwd_multi", st)
             if self.dim_z_category:          # the one-hot columns of every solve, behind the solves
                 L.Program([p.categ_op for p in plans]).run(st)
-            return
+        else:
+            for p in plans:
+                p.fwd_prog.run(st)
         for p in plans:
-            p.fwd_prog.run(st)
+            p.check_solve()
 
     def flush_adjoints(self):
-        """Launch the adaptive adjoints collected during a backward pass (GanTrainer.g_step: video + image path)."""
+        """Launch the adjoints collected during a backward pass (GanTrainer.g_step: video + image path)."""
         batch = getattr(self, "_adjoint_batch", None)
         if not batch or not batch["ops"]:
             return
-        ops = batch["ops"]
-        st = stream_ptr()
-        for k in range(0, len(ops), 8):
-            chunk = ops[k:k + 8]
-            arr = (L.OdeBwdOp * len(chunk))(*chunk)
-            L.call("ode_bwd_multi", lambda: L.check(L.lib().gode_ode_bwd_multi(arr, len(chunk), st), "gode_ode_bwd_multi"))
+        pc = self._plan_cls
+        _run_multi(batch["ops"], pc.multi[2], pc.multi[0] + "_bwd_multi", stream_ptr())
         batch["ops"], batch["keep"] = [], []
 
     def discard_prefetched(self):
@@ -846,29 +874,24 @@ class VideoGenerator(nn.Module):
     def _host_inputs(self, select, num_samples, T):
         """The host-drawn inputs of one sample_videos (select False) / sample_images (select True) call, consuming the
         NumPy and torch CPU generators exactly as the reference does: -> (x [n_traj, 16], content [n_traj, 50],
-        sel int32 [n_traj] or None).  sample_images: the reference integrates B*T*2 trajectories and decodes B randomly
-        chosen rows of the B*T*2*T latent rows (models/mocogan.py:287-295); all draws are made, only the chosen
-        trajectories are kept."""
+        sel int32 [n_traj] or None), and dim_z_category > 0: + the trajectories' classes, drawn between the content and the
+        motion noise (models/mocogan.py:259-262).  sample_images: the reference integrates B*T*2 trajectories and decodes
+        B randomly chosen rows of the B*T*2*T latent rows (models/mocogan.py:287-295); all draws are made, only the
+        chosen trajectories are kept."""
+        self._check_len(T)
+        n_all = num_samples * T * 2 if select else num_samples
         if self.dim_z_category:
-            # + the classes, drawn between the content and the motion noise (models/mocogan.py:259-262): a 4-tuple
-            if not select:
-                content, cls, x = self._draw_categorical(num_samples)
-                return x, content, None, cls
-            n_all = num_samples * T * 2
             content, cls, x = self._draw_categorical(n_all)
+        else:
+            (content, x), cls = self._draw(n_all, T), None
+        sel = None
+        if select:
             j = np.sort(np.random.choice(n_all * T, num_samples, replace=False)).astype(np.int64)
             traj = torch.from_numpy(j // T)
             sel = torch.from_numpy((j % T).astype(np.int32))
-            return self._take_trajectories(x, traj), content[traj].contiguous(), sel, cls[j // T]
-        if not select:
-            content, x = self._draw(num_samples, T)
-            return x, content, None
-        n_all = num_samples * T * 2
-        content, x = self._draw(n_all, T)
-        j = np.sort(np.random.choice(n_all * T, num_samples, replace=False)).astype(np.int64)
-        traj = torch.from_numpy(j // T)
-        sel = torch.from_numpy((j % T).astype(np.int32))
-        return self._take_trajectories(x, traj), content[traj].contiguous(), sel
+            x, content = self._take_trajectories(x, traj), content[traj].contiguous()
+            cls = cls[j // T] if cls is not None else None
+        return (x, content, sel) if cls is None else (x, content, sel, cls)
 
     def _draw_categorical(self, num_samples):
         """_draw with the class draw at the reference's place: content (NumPy normal), classes (ONE np.random.randint(C,
@@ -882,14 +905,12 @@ class VideoGenerator(nn.Module):
     def _take_trajectories(x, traj):
         return x[traj].contiguous()
 
+    def _check_len(self, T):
+        """Refuses a video length the motion latent cannot serve, before anything is drawn (VideoGeneratorCDE)."""
+
     def _fill_host_inputs(self, buf, select, num_samples, T):
         """Graph replay (HostFeed): the same draws, written straight into the feed block's region for this call site."""
-        x, content, sel = self._host_inputs(select, num_samples, T)[:3]
-        nx, n = x.numel(), content.shape[0]
-        buf[:nx].copy_(x.reshape(-1))
-        buf[nx:nx + n * 50].copy_(content.reshape(-1))
-        if select:
-            buf[nx + n * 50:nx + n * 51].view(torch.int32).copy_(sel)
+        _pack_inputs(buf, *self._host_inputs(select, num_samples, T))
 
     def sample_videos(self, num_samples, video_len=None):
         """-> (videos [B, C, T, H, W] fp32, float64 zero labels [B]); models/mocogan.py:271-285.  dim_z_category > 0: the
@@ -898,14 +919,11 @@ class VideoGenerator(nn.Module):
         plan = self._take_prefetched(False, num_samples, T)
         if plan is not None:
             h = self._run(num_samples, T, False, None, None, None, plan=plan)
-        elif self.dim_z_category:
-            _require_gpu(self.main[0].weight, type(self).__name__)
-            plan = self._pool.get((num_samples, T, False), lambda: self._plan_cls(self, num_samples, T, False))
-            x, content, _, cls = self._host_inputs(False, num_samples, T)
-            h = self._run(num_samples, T, False, x, content, None, plan=plan, cls=cls)    # (plan.labels: the int64 classes)
         else:
-            x, content, _ = self._host_inputs(False, num_samples, T)
-            h = self._run(num_samples, T, False, x, content, None)        # [B*T, 1, H, W, C]
+            if self.dim_z_category:          # the plan is needed here: its `labels` are the call's int64 classes
+                _require_gpu(self.main[0].weight, type(self).__name__)
+                plan = self._pool.get((num_samples, T, False), lambda: self._plan_cls(self, num_samples, T, False))
+            h = self._run(num_samples, T, False, *self._host_inputs(False, num_samples, T), plan=plan)  # [B*T, 1, H, W, C]
         H, W = h.size(2), h.size(3)
         h = h.view(num_samples, T, H, W, self.n_channels).permute(0, 4, 1, 2, 3)
         if self.dim_z_category:
@@ -924,12 +942,8 @@ class VideoGenerator(nn.Module):
         plan = self._take_prefetched(True, num_samples, T)
         if plan is not None:
             h = self._run(num_samples, T, True, None, None, None, plan=plan)
-        elif self.dim_z_category:
-            x, content, sel, cls = self._host_inputs(True, num_samples, T)
-            h = self._run(num_samples, T, True, x, content, sel, cls=cls)
         else:
-            x, content, sel = self._host_inputs(True, num_samples, T)
-            h = self._run(num_samples, T, True, x, content, sel)
+            h = self._run(num_samples, T, True, *self._host_inputs(True, num_samples, T))
         return h.view(num_samples, h.size(2), h.size(3), self.n_channels).permute(0, 3, 1, 2), None
 
     def sample_pair(self, n_videos, n_images, images_first=False):
@@ -996,15 +1010,17 @@ class VideoGenerator(nn.Module):
 
     def sample_z_m(self, num_samples, video_len=None):
         """models/mocogan_ode.py:133-148 (UCF class :39-54): torch.randn(N, 16) on the CPU generator -> pre-net ->
-        odeint(rk4 on linspace(0, 1, T)) -> transpose(0, 1).reshape(-1, 16): [N*T, 16], row n*T + t.  One launch of the
-        fused kernel (gode_ode_fwd); differentiable (gode_ode_bwd).  sample_videos()/sample_images() do NOT go
-        through here -- they fuse the solve with the content broadcast and the decoder -- this method exists for
-        the reference's public surface."""
+        odeint(rk4 on linspace(0, 1, T)) -> transpose(0, 1).reshape(-1, 16): [N*T, 16], row n*T + t -- and the same for the
+        other motion latents (mocogan_ode_rnn.py:39-51 and mocogan.py:217-229: row n*T + t = h_{t+1}; mocogan_sde.py:49-64;
+        mocogan_cde.py:60-84), each with its own noise (_draw_motion).  One launch of the generator's fused latent
+        kernel, differentiable through its adjoint kernel.  sample_videos()/sample_images() do NOT go through here -- they
+        fuse the solve with the content broadcast and the decoder -- this method exists for the reference's public
+        surface (and is what sample_z_video calls)."""
         T = video_len if video_len is not None else self.video_length
+        self._check_len(T)
         _require_gpu(self.main[0].weight, type(self).__name__)
         x = self._draw_motion(num_samples, T)
-        _, ode = self._param_list()
-        return _LatentFn.apply(self, x, num_samples, T, *ode)
+        return _LatentFn.apply(self, x, num_samples, T, *self._param_list()[1])
 
     def _draw_motion(self, num_samples, T):
         return torch.randn(num_samples, self.dim_z_motion)
@@ -1046,11 +1062,19 @@ class VideoGeneratorMNISTODE(VideoGeneratorMNIST):
         self.linear = self._make_prenet(linear)
 
 
+_RNN_GRAD_OFFS = [(0, 256, (16, 16)), (256, 16, (16,)), (272, 256, (16, 16)), (528, 16, (16,)),
+                  (544, 768, (48, 16)), (1312, 768, (48, 16)), (2080, 48, (48,)), (2128, 48, (48,))]
+
+
 class _RnnGenPlan(_GenPlan):
     """ODE-RNN latent (gode_odernn_fwd/bwd) + decoder.  x_host carries the noise stack [T+1, n, 16]."""
 
-    def __init__(self, gen, n_traj, T, select, zbuf=None):
-        super().__init__(gen, n_traj, T, select, zbuf=zbuf)
+    rows_in_traj = False
+    nparam, grad_offs = L.ODERNN_NPARAM, _RNN_GRAD_OFFS
+    multi, multi_always = ("odernn", L.OdeRnnFwdOp, L.OdeRnnBwdOp), True
+
+    def _alloc(self):
+        n_traj, T = self.n, self.T
         f32 = dict(dtype=torch.float32, device=self.device)
         self.noise = self.x        # [T+1, n, 16]: h_0 and the per-frame GRU inputs (staged by the base class)
         self.hp = torch.empty(n_traj, T, 16, **f32)
@@ -1066,97 +1090,29 @@ class _RnnGenPlan(_GenPlan):
     def _x_shape(n_traj, T):
         return (T + 1, n_traj, 16)
 
-    def _rnn_params(self):
+    def _params(self):
         g = self.gen
         f, r = g.ode_fn.fn, g.recurrent
         return (f[0].weight, f[0].bias, f[2].weight, f[2].bias, r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh)
 
     def _programs(self):
-        ptrs = tuple(dptr(p) for p in self._rnn_params())
+        ptrs = tuple(dptr(p) for p in self._params())
         if ptrs != self._ode_ptrs:
             self._ode_ptrs = ptrs
             op = L.OdeRnnParams(*ptrs)
             self.fwd_op = L.OdeRnnFwdOp(p=op, noise=dptr(self.noise), content=dptr(self.content), sel_t=dptr(self.sel),
-                                        z=dptr(self.stack.x_in if self.stack is not None else self._zbuf), hs=None,
-                                        hp=dptr(self.hp), nsteps=dptr(self.nsteps),
-                                        N=self.n, T=self.T, rtol=self.gen.ode_rtol, atol=self.gen.ode_atol, zcols=Z_COLS,
+                                        z=dptr(self._zbuf), hs=None, hp=dptr(self.hp), nsteps=dptr(self.nsteps),
+                                        N=self.n, T=self.T, rtol=self.gen.ode_rtol, atol=self.gen.ode_atol, zcols=self._zcols,
                                         sync=dptr(self.sync_f))
             self.bwd_op = L.OdeRnnBwdOp(p=op, noise=dptr(self.noise), hp=dptr(self.hp), sel_t=dptr(self.sel), gz=None,
                                         work=dptr(self.rnn_work), grads=None, N=self.n, T=self.T,
-                                        substeps=self.gen.adjoint_substeps, accumulate=0, zcols=Z_COLS,
+                                        substeps=self.gen.adjoint_substeps, accumulate=0, zcols=self._zcols,
                                         rtol=self.gen.ode_rtol, atol=self.gen.ode_atol, sync=dptr(self.sync_b),
                                         nsteps=dptr(self.nsteps_bwd))
             self.fwd_prog = L.Program([self.fwd_op])
         self.fwd_op.rtol, self.fwd_op.atol = self.gen.ode_rtol, self.gen.ode_atol
         self.bwd_op.rtol, self.bwd_op.atol = self.gen.ode_rtol, self.gen.ode_atol
         self.bwd_op.substeps = self.gen.adjoint_substeps
-
-    def latent_backward(self, gz_ptr, arena, keep):
-        self.bwd_op.gz = gz_ptr
-        if arena is not None:
-            # the 2176 ODEFunc + GRU gradients go straight into the trainer's arena: the eight tensors are its tail,
-            # contiguous in the kernel's output order (VideoGeneratorMNISTODERNN._arena_tail)
-            tgt = [arena.target(q) for q in self._rnn_params()]
-            base, acc = tgt[0]
-            self.bwd_op.grads = base.data_ptr()
-            self.bwd_op.accumulate = 1 if acc else 0
-            batch = getattr(self.gen, "_adjoint_batch", None)
-            if batch is not None:
-                # the trainer announced how many generator passes this backward holds (video + image path of the G step):
-                # their adjoints -- one workgroup each -- go out as ONE launch once the last decoder backward is through
-                batch["ops"].append(self.bwd_op)
-                batch["keep"].append(keep)
-                if len(batch["ops"]) >= batch["expect"]:
-                    self.gen.flush_adjoints()
-            else:
-                L.run_one(self.bwd_op, stream_ptr())
-            return None
-        grads = torch.empty(L.ODERNN_NPARAM, dtype=torch.float32, device=self.device)
-        self.bwd_op.grads = grads.data_ptr()
-        self.bwd_op.accumulate = 0
-        L.run_one(self.bwd_op, stream_ptr())
-        return [grads[o:o + n].view(shp) for o, n, shp in _RNN_GRAD_OFFS]
-
-
-_RNN_GRAD_OFFS = [(0, 256, (16, 16)), (256, 16, (16,)), (272, 256, (16, 16)), (528, 16, (16,)),
-                  (544, 768, (48, 16)), (1312, 768, (48, 16)), (2080, 48, (48,)), (2128, 48, (48,))]
-
-
-class _RnnLatentFn(torch.autograd.Function):
-    """VideoGeneratorMNISTODERNN.sample_z_m as its own autograd node: gode_odernn_fwd alone (latent rows [N*T, 16],
-    row n*T + t = h_{t+1}), backward = gode_odernn_bwd (GRU backward + adaptive adjoint per frame)."""
-
-    @staticmethod
-    def forward(ctx, gen, noise_host, n, T, *params):
-        dev = gen.main[0].weight.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        noise = noise_host.to(dev)                                    # [T+1, n, 16]: h_0, e_1 .. e_T
-        hp = torch.empty(n, T, 16, **f32)
-        z = torch.empty(n * T, 68, **f32)                             # the kernel's latent-row layout; columns 0..15 used
-        nsteps = torch.zeros(T, dtype=torch.int32, device=dev)
-        ns = L.lib().gode_odernn_sync_size(n)
-        sync = torch.zeros(ns, dtype=torch.int32, device=dev) if ns else None
-        prm = L.OdeRnnParams(*[dptr(p) for p in params])
-        fop = L.OdeRnnFwdOp(p=prm, noise=dptr(noise), content=None, sel_t=None, z=dptr(z), hs=None, hp=dptr(hp),
-                            nsteps=dptr(nsteps), N=n, T=T, rtol=gen.ode_rtol, atol=gen.ode_atol, zcols=68, sync=dptr(sync))
-        L.run_one(fop, stream_ptr())
-        ctx.keep = (gen, noise, hp, n, T, [p.detach() for p in params], sync)
-        ctx.nsteps = nsteps
-        return z[:, :16].contiguous()
-
-    @staticmethod
-    def backward(ctx, gout):
-        gen, noise, hp, n, T, params, sync = ctx.keep
-        dev = noise.device
-        g = gout.contiguous()
-        grads = torch.empty(L.ODERNN_NPARAM, dtype=torch.float32, device=dev)
-        work = torch.empty(L.lib().gode_odernn_bwd_work_size(n), dtype=torch.float32, device=dev)
-        prm = L.OdeRnnParams(*[dptr(p) for p in params])
-        bop = L.OdeRnnBwdOp(p=prm, noise=dptr(noise), hp=dptr(hp), sel_t=None, gz=dptr(g), work=dptr(work),
-                            grads=dptr(grads), N=n, T=T, substeps=gen.adjoint_substeps, accumulate=0, zcols=16,
-                            rtol=gen.ode_rtol, atol=gen.ode_atol, sync=dptr(sync))
-        L.run_one(bop, stream_ptr())
-        return (None, None, None, None, *[grads[o:o + k].view(shp) for o, k, shp in _RNN_GRAD_OFFS])
 
 
 class VideoGeneratorMNISTODERNN(VideoGeneratorMNIST):
@@ -1179,9 +1135,9 @@ class VideoGeneratorMNISTODERNN(VideoGeneratorMNIST):
         self.linear = self._make_prenet(linear)
 
     def _param_list(self):
-        dec, _ = super()._param_list()
         f, r = self.ode_fn.fn, self.recurrent
-        return dec, [f[0].weight, f[0].bias, f[2].weight, f[2].bias, r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh]
+        return self._decoder_list(), [f[0].weight, f[0].bias, f[2].weight, f[2].bias,
+                                      r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh]
 
     def _draw(self, num_samples, video_len):
         """content (NumPy) first, then h_0 and one e_t per frame from FloatTensor(...).normal_()
@@ -1202,27 +1158,6 @@ class VideoGeneratorMNISTODERNN(VideoGeneratorMNIST):
     def _take_trajectories(noise, traj):
         return noise[:, traj].contiguous()        # noise stack [T+1, n, 16]: trajectories are the middle axis
 
-    def _launch_latents(self, plans):
-        """All prefetched ODE-RNN solves in one launch (<= 8 per launch), each with its own whole-batch error norm."""
-        st = stream_ptr()
-        for k in range(0, len(plans), 8):
-            chunk = plans[k:k + 8]
-            arr = (L.OdeRnnFwdOp * len(chunk))(*[p.fwd_op for p in chunk])
-            L.call("odernn_fwd_multi", lambda: L.check(L.lib().gode_odernn_fwd_multi(arr, len(chunk), st), "gode_odernn_fwd_multi"))
-
-    def flush_adjoints(self):
-        """Launch the adjoints collected during a backward pass (see _RnnGenPlan.backward)."""
-        batch = getattr(self, "_adjoint_batch", None)
-        if not batch or not batch["ops"]:
-            return
-        ops = batch["ops"]
-        st = stream_ptr()
-        for k in range(0, len(ops), 8):
-            chunk = ops[k:k + 8]
-            arr = (L.OdeRnnBwdOp * len(chunk))(*chunk)
-            L.call("odernn_bwd_multi", lambda: L.check(L.lib().gode_odernn_bwd_multi(arr, len(chunk), st), "gode_odernn_bwd_multi"))
-        batch["ops"], batch["keep"] = [], []
-
     def _draw_motion(self, num_samples, T):
         """h_0 and one e_t per frame, each a fresh FloatTensor(n, d).normal_() on the global torch CPU generator
         (models/mocogan.py:297-301; call order of models/mocogan_ode_rnn.py:42-46) -> [T+1, n, 16]."""
@@ -1231,108 +1166,46 @@ class VideoGeneratorMNISTODERNN(VideoGeneratorMNIST):
             buf[i].normal_()
         return buf
 
-    def sample_z_m(self, num_samples, video_len=None):
-        """models/mocogan_ode_rnn.py:39-51 -> [N*T, 16], row n*T + t = h_{t+1}: one gode_odernn_fwd launch, differentiable
-        (gode_odernn_bwd).  sample_videos()/sample_images() fuse the same launch with the content broadcast and the
-        decoder; this method is the reference's public surface (and what the inherited sample_z_video calls)."""
-        T = video_len if video_len is not None else self.video_length
-        _require_gpu(self.main[0].weight, type(self).__name__)
-        noise = self._draw_motion(num_samples, T)
-        _, rnn = self._param_list()
-        return _RnnLatentFn.apply(self, noise, num_samples, T, *rnn)
-
 
 # ------------------------------------------------------------------------------------------------------------------
 # GRU motion latent: the original MoCoGAN generator (models/mocogan.py:185-301)
 # ------------------------------------------------------------------------------------------------------------------
+_GRU_GRAD_OFFS = [(0, 768, (48, 16)), (768, 768, (48, 16)), (1536, 48, (48,)), (1584, 48, (48,))]
+
+
 class _GruGenPlan(_GenPlan):
     """GRU latent (gode_gru_fwd/bwd) + decoder.  x_host carries the noise stack [T+1, n, 16] (h_0, e_0 .. e_{T-1})."""
 
-    def __init__(self, gen, n_traj, T, select, zbuf=None):
-        super().__init__(gen, n_traj, T, select, zbuf=zbuf)
+    rows_in_traj = False
+    zcols = 16
+    nparam, grad_offs = L.GRU_NPARAM, _GRU_GRAD_OFFS
+    multi, multi_always = ("gru", L.GruFwdOp, L.GruBwdOp), True
+
+    def _alloc(self):
         f32 = dict(dtype=torch.float32, device=self.device)
         self.noise = self.x        # [T+1, n, 16], staged by the base class
-        self.hs = torch.empty(n_traj, T + 1, 16, **f32)                  # every h_t, kept for the backward
-        self.gru_work = torch.empty(L.lib().gode_gru_bwd_work_size(n_traj), **f32)
+        self.hs = torch.empty(self.n, self.T + 1, 16, **f32)             # every h_t, kept for the backward
+        self.gru_work = torch.empty(L.lib().gode_gru_bwd_work_size(self.n), **f32)
 
     @staticmethod
     def _x_shape(n_traj, T):
         return (T + 1, n_traj, 16)
 
-    def _gru_params(self):
+    def _params(self):
         r = self.gen.recurrent
         return (r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh)
 
     def _programs(self):
-        ptrs = tuple(dptr(p) for p in self._gru_params())
+        ptrs = tuple(dptr(p) for p in self._params())
         if ptrs != self._ode_ptrs:
             self._ode_ptrs = ptrs
             op = L.GruParams(*ptrs)
-            zbuf = self.stack.x_in if self.stack is not None else self._zbuf
             self.fwd_op = L.GruFwdOp(p=op, noise=dptr(self.noise), content=dptr(self.content), sel_t=dptr(self.sel),
-                                     z=dptr(zbuf), hs=dptr(self.hs), N=self.n, T=self.T, zcols=Z_COLS)
+                                     z=dptr(self._zbuf), hs=dptr(self.hs), N=self.n, T=self.T, zcols=self._zcols)
             self.bwd_op = L.GruBwdOp(p=op, noise=dptr(self.noise), hs=dptr(self.hs), sel_t=dptr(self.sel), gz=None,
-                                     work=dptr(self.gru_work), grads=None, N=self.n, T=self.T, accumulate=0, zcols=Z_COLS)
+                                     work=dptr(self.gru_work), grads=None, N=self.n, T=self.T, accumulate=0,
+                                     zcols=self._zcols)
             self.fwd_prog = L.Program([self.fwd_op])
-
-    def latent_backward(self, gz_ptr, arena, keep):
-        self.bwd_op.gz = gz_ptr
-        if arena is not None:
-            # the 1632 GRU gradients go straight into the trainer's arena: the four tensors are its tail, contiguous in
-            # the kernel's output order (VideoGeneratorGRU._arena_tail)
-            tgt = [arena.target(q) for q in self._gru_params()]       # (every tensor: marks its .grad as written)
-            base, acc = tgt[0]
-            self.bwd_op.grads = base.data_ptr()
-            self.bwd_op.accumulate = 1 if acc else 0
-            batch = getattr(self.gen, "_adjoint_batch", None)
-            if batch is not None:
-                # video + image path of the G step: their BPTT passes go out as ONE launch (VideoGeneratorGRU.flush_adjoints)
-                batch["ops"].append(self.bwd_op)
-                batch["keep"].append(keep)
-                if len(batch["ops"]) >= batch["expect"]:
-                    self.gen.flush_adjoints()
-            else:
-                L.run_one(self.bwd_op, stream_ptr())
-            return None
-        grads = torch.empty(L.GRU_NPARAM, dtype=torch.float32, device=self.device)
-        self.bwd_op.grads = grads.data_ptr()
-        self.bwd_op.accumulate = 0
-        L.run_one(self.bwd_op, stream_ptr())
-        return [grads[o:o + n].view(shp) for o, n, shp in _GRU_GRAD_OFFS]
-
-
-_GRU_GRAD_OFFS = [(0, 768, (48, 16)), (768, 768, (48, 16)), (1536, 48, (48,)), (1584, 48, (48,))]
-
-
-class _GruLatentFn(torch.autograd.Function):
-    """VideoGeneratorGRU.sample_z_m as its own autograd node: gode_gru_fwd alone (latent rows [N*T, 16], row n*T + t =
-    h_{t+1}), backward = gode_gru_bwd (BPTT)."""
-
-    @staticmethod
-    def forward(ctx, gen, noise_host, n, T, *params):
-        dev = gen.main[0].weight.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        noise = noise_host.to(dev)                                    # [T+1, n, 16]: h_0, e_0 .. e_{T-1}
-        hs = torch.empty(n, T + 1, 16, **f32)
-        z = torch.empty(n * T, 16, **f32)
-        prm = L.GruParams(*[dptr(p) for p in params])
-        fop = L.GruFwdOp(p=prm, noise=dptr(noise), content=None, sel_t=None, z=dptr(z), hs=dptr(hs), N=n, T=T, zcols=16)
-        L.run_one(fop, stream_ptr())
-        ctx.keep = (noise, hs, n, T, [p.detach() for p in params])
-        return z
-
-    @staticmethod
-    def backward(ctx, gout):
-        noise, hs, n, T, params = ctx.keep
-        dev = noise.device
-        g = gout.contiguous()
-        grads = torch.empty(L.GRU_NPARAM, dtype=torch.float32, device=dev)
-        work = torch.empty(L.lib().gode_gru_bwd_work_size(n), dtype=torch.float32, device=dev)
-        prm = L.GruParams(*[dptr(p) for p in params])
-        bop = L.GruBwdOp(p=prm, noise=dptr(noise), hs=dptr(hs), sel_t=None, gz=dptr(g), work=dptr(work),
-                         grads=dptr(grads), N=n, T=T, accumulate=0, zcols=16)
-        L.run_one(bop, stream_ptr())
-        return (None, None, None, None, *[grads[o:o + k].view(shp) for o, k, shp in _GRU_GRAD_OFFS])
 
 
 class VideoGeneratorGRU(VideoGenerator):
@@ -1360,13 +1233,8 @@ class VideoGeneratorGRU(VideoGenerator):
         pass                        # recurrent + main only, as the reference's class
 
     def _param_list(self):
-        dec = []
-        for p in self._decoder_params():
-            dec.append(p.weight)
-            if p.gamma is not None:
-                dec += [p.gamma, p.beta]
         r = self.recurrent
-        return dec, [r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh]
+        return self._decoder_list(), [r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh]
 
     def _draw(self, num_samples, video_len):
         """content (NumPy) first, then h_0 and one e_t per frame (models/mocogan.py:252,297-301) as ONE normal_() over
@@ -1386,37 +1254,6 @@ class VideoGeneratorGRU(VideoGenerator):
     def _draw_motion(self, num_samples, T):
         """h_0 and one e_t per frame -> [T+1, n, 16] (see _draw)"""
         return torch.empty(T + 1, num_samples, self.dim_z_motion).normal_()
-
-    def _launch_latents(self, plans):
-        """All prefetched GRU chains in one launch (<= 8 per launch)."""
-        st = stream_ptr()
-        for k in range(0, len(plans), 8):
-            chunk = plans[k:k + 8]
-            arr = (L.GruFwdOp * len(chunk))(*[p.fwd_op for p in chunk])
-            L.call("gru_fwd_multi", lambda: L.check(L.lib().gode_gru_fwd_multi(arr, len(chunk), st), "gode_gru_fwd_multi"))
-
-    def flush_adjoints(self):
-        """Launch the BPTT passes collected during a backward pass (the video and the image path of the G step)."""
-        batch = getattr(self, "_adjoint_batch", None)
-        if not batch or not batch["ops"]:
-            return
-        ops = batch["ops"]
-        st = stream_ptr()
-        for k in range(0, len(ops), 8):
-            chunk = ops[k:k + 8]
-            arr = (L.GruBwdOp * len(chunk))(*chunk)
-            L.call("gru_bwd_multi", lambda: L.check(L.lib().gode_gru_bwd_multi(arr, len(chunk), st), "gode_gru_bwd_multi"))
-        batch["ops"], batch["keep"] = [], []
-
-    def sample_z_m(self, num_samples, video_len=None):
-        """models/mocogan.py:217-229 -> [N*T, 16], row n*T + t = h_{t+1}: one gode_gru_fwd launch, differentiable
-        (gode_gru_bwd).  sample_videos()/sample_images() fuse the same launch with the content broadcast and the decoder;
-        this method is the reference's public surface (and what the inherited sample_z_video calls)."""
-        T = video_len if video_len is not None else self.video_length
-        _require_gpu(self.main[0].weight, type(self).__name__)
-        noise = self._draw_motion(num_samples, T)
-        _, rnn = self._param_list()
-        return _GruLatentFn.apply(self, noise, num_samples, T, *rnn)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1476,28 +1313,26 @@ _SDE_GRAD_OFFS = [(0, 1024, (64, 16)), (1024, 64, (64,)), (1088, 1024, (16, 64))
                   (2672, 256, (16, 16)), (2928, 16, (16,)), (2944, 256, (16, 16)), (3200, 16, (16,))]
 
 
-def _sde_grad_views(grads, prenet):
-    """The gradient block of gode_sde_bwd as tensors in gode_sde_params order (it starts at the first present one)."""
-    if prenet:
-        return [grads[o:o + n].view(shp) for o, n, shp in _SDE_GRAD_OFFS]
-    return [grads[o - 2128:o - 2128 + n].view(shp) for o, n, shp in _SDE_GRAD_OFFS[4:]]
-
-
 class _SdeGenPlan(_GenPlan):
     """Neural-SDE latent (gode_sde_fwd/bwd) + decoder.  x_host carries [x0 | xi_0 .. xi_{S-1}] = [1+S, n, 16]."""
 
-    def __init__(self, gen, n_traj, T, select, zbuf=None):
-        self._sched = gen._sde_schedule(T, gen.main[0].weight.device)
+    rows_in_traj = False
+    zcols = 16
+    nparam, grad_offs = L.SDE_NPARAM, _SDE_GRAD_OFFS
+    grads_from_first_present = True      # no pre-net: the block starts at drift_fn's first weight, nothing in front of it
+    multi = None
+
+    def _alloc(self):
+        self._sched = self.gen._sde_schedule(self.T, self.device)
         self.S = self._sched["S"]
-        super().__init__(gen, n_traj, T, select, zbuf=zbuf)
         f32 = dict(dtype=torch.float32, device=self.device)
-        self.states = torch.empty(n_traj, self.S + 1, 16, **f32)      # every Euler state, kept for the backward
-        self.sde_work = torch.empty(L.lib().gode_sde_bwd_work_size(n_traj), **f32)
+        self.states = torch.empty(self.n, self.S + 1, 16, **f32)      # every Euler state, kept for the backward
+        self.sde_work = torch.empty(L.lib().gode_sde_bwd_work_size(self.n), **f32)
 
     def _x_shape(self, n_traj, T):
-        return (1 + self.S, n_traj, 16)
+        return (1 + self.gen._sde_schedule(T, self.device)["S"], n_traj, 16)
 
-    def _sde_params(self):
+    def _params(self):
         g = self.gen
         lin = g.linear
         pre = (None,) * 4 if isinstance(lin, nn.Identity) else (lin[0].weight, lin[0].bias, lin[2].weight, lin[2].bias)
@@ -1505,72 +1340,20 @@ class _SdeGenPlan(_GenPlan):
         return pre + (d[0].weight, d[0].bias, d[2].weight, d[2].bias, s[0].weight, s[0].bias, s[2].weight, s[2].bias)
 
     def _programs(self):
-        ps = self._sde_params()
+        ps = self._params()
         ptrs = tuple(dptr(p) for p in ps)
         if ptrs != self._ode_ptrs:
             self._ode_ptrs = ptrs
             prenet = 0 if ps[0] is None else 1
-            zbuf = getattr(self, "_zbuf", None)
-            zbuf = self.stack.x_in if zbuf is None else zbuf
             sc = self._sched
             common = dict(p=L.SdeParams(*ptrs), x=dptr(self.x), sel_t=dptr(self.sel), dt=dptr(sc["dt"]),
                           sqrt_dt=dptr(sc["sqrt_dt"]), emit_at=dptr(sc["emit_at"]), emit_w0=dptr(sc["w0"]),
                           emit_w1=dptr(sc["w1"]), N=self.n, T=self.T, S=self.S, prenet=prenet,
-                          zcols=getattr(self, "_zcols", Z_COLS))
-            self.fwd_op = L.SdeFwdOp(content=dptr(self.content), z=dptr(zbuf), states=dptr(self.states), **common)
+                          zcols=self._zcols)
+            self.fwd_op = L.SdeFwdOp(content=dptr(self.content), z=dptr(self._zbuf), states=dptr(self.states), **common)
             self.bwd_op = L.SdeBwdOp(states=dptr(self.states), gz=None, work=dptr(self.sde_work), grads=None,
                                      accumulate=0, **common)
             self.fwd_prog = L.Program([self.fwd_op])
-
-    def latent_backward(self, gz_ptr, arena, keep):
-        """As _GenPlan.latent_backward; the gradient block starts at the first present tensor (no pre-net: drift_fn's
-        first weight), so nothing in front of it is written."""
-        self.bwd_op.gz = gz_ptr
-        prenet = self.bwd_op.prenet
-        if arena is not None:
-            # the pre-net / drift / diffusion tensors are the arena's tail, contiguous in the kernel's output order
-            tgt = [arena.target(q) for q in self._sde_params() if q is not None]
-            base, acc = tgt[0]
-            self.bwd_op.grads = base.data_ptr()
-            self.bwd_op.accumulate = 1 if acc else 0
-            L.run_one(self.bwd_op, stream_ptr())
-            return None
-        grads = torch.empty(L.SDE_NPARAM if prenet else L.SDE_NPARAM - 2128, dtype=torch.float32, device=self.device)
-        self.bwd_op.grads = grads.data_ptr()
-        self.bwd_op.accumulate = 0
-        L.run_one(self.bwd_op, stream_ptr())
-        return _sde_grad_views(grads, prenet)
-
-
-class _SdeLatentFn(torch.autograd.Function):
-    """VideoGeneratorSDE.sample_z_m as its own autograd node: gode_sde_fwd alone, latent rows [N*T, 16] (row n*T + t,
-    the reference's transpose(0, 1).reshape(-1, 16) order); backward = gode_sde_bwd."""
-
-    @staticmethod
-    def forward(ctx, gen, x_host, n, T, *params):
-        dev = gen.main[0].weight.device
-        lp = _SdeGenPlan.__new__(_SdeGenPlan)          # only the latent half of a plan: no decoder buffers
-        lp.gen, lp.n, lp.T, lp.select, lp.device = gen, n, T, False, dev
-        lp._sched = gen._sde_schedule(T, dev)
-        lp.S = lp._sched["S"]
-        f32 = dict(dtype=torch.float32, device=dev)
-        lp.x = x_host.to(dev)                            # [1+S, n, 16]
-        lp.content, lp.sel = None, None
-        lp.states = torch.empty(n, lp.S + 1, 16, **f32)
-        lp.sde_work = torch.empty(L.lib().gode_sde_bwd_work_size(n), **f32)
-        lp._zbuf, lp._zcols = torch.empty(n * T, 16, **f32), 16
-        lp._ode_ptrs = None
-        lp._programs()
-        lp.fwd_prog.run(stream_ptr())
-        ctx.lp = lp
-        return lp._zbuf
-
-    @staticmethod
-    def backward(ctx, gout):
-        lp = ctx.lp
-        g = gout.contiguous()
-        grads = lp.latent_backward(g.data_ptr(), None, g)
-        return (None, None, None, None, *grads)
 
 
 class VideoGeneratorSDE(VideoGeneratorMNIST):
@@ -1646,17 +1429,12 @@ class VideoGeneratorSDE(VideoGeneratorMNIST):
         return r
 
     def _param_list(self):
-        dec = []
-        for p in self._decoder_params():
-            dec.append(p.weight)
-            if p.gamma is not None:
-                dec += [p.gamma, p.beta]
         sde = []
         if not isinstance(self.linear, nn.Identity):
             sde += [self.linear[0].weight, self.linear[0].bias, self.linear[2].weight, self.linear[2].bias]
         for net in (self.ode_fn.drift_fn, self.ode_fn.diffusion_fn):
             sde += [net[0].weight, net[0].bias, net[2].weight, net[2].bias]
-        return dec, sde
+        return self._decoder_list(), sde
 
     def _steps(self, T):
         return self._sde_schedule(T, torch.device("cpu"))["S"]
@@ -1679,23 +1457,8 @@ class VideoGeneratorSDE(VideoGeneratorMNIST):
     def _take_trajectories(self, x, traj):
         return self._with_noise(x[traj], self.video_length)
 
-    def _launch_latents(self, plans):
-        st = stream_ptr()
-        for p in plans:
-            p.fwd_prog.run(st)
-
     def _draw_motion(self, num_samples, T):
         return self._with_noise(torch.randn(num_samples, self.dim_z_motion), T)
-
-    def sample_z_m(self, num_samples, video_len=None):
-        """models/mocogan_sde.py:49-64 -> [N*T, 16], row n*T + t: one gode_sde_fwd launch, differentiable
-        (gode_sde_bwd).  sample_videos()/sample_images() fuse the same launch with the content broadcast and the
-        decoder; this method is the reference's public surface (and what the inherited sample_z_video calls)."""
-        T = video_len if video_len is not None else self.video_length
-        _require_gpu(self.main[0].weight, type(self).__name__)
-        x = self._draw_motion(num_samples, T)
-        _, sde = self._param_list()
-        return _SdeLatentFn.apply(self, x, num_samples, T, *sde)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1731,14 +1494,18 @@ _CDE_GRAD_OFFS = [(0, 128, (64, 2)), (128, 64, (64,)), (192, 1024, (16, 64)), (1
 class _CdeGenPlan(_GenPlan):
     """Neural-CDE latent (gode_cde_fwd/bwd) + decoder.  x_host carries the noise channel's knots [n, T]."""
 
-    def __init__(self, gen, n_traj, T, select, zbuf=None):
-        if n_traj > L.CDE_MAX_N:
+    rows_in_traj = False
+    zcols = 16
+    nparam, grad_offs = L.CDE_NPARAM, _CDE_GRAD_OFFS
+    multi = None
+
+    def __init__(self, gen, n_traj, T, select, zbuf=None, x=None):
+        if x is None and n_traj > L.CDE_MAX_N:       # (sample_z_m's plan: gode_cde_fwd itself refuses)
             raise ValueError(f"{type(gen).__name__}: {n_traj} trajectories in one solve; the whole-batch error norm of "
                              f"gode_cde_fwd needs all workgroups co-resident, at most {L.CDE_MAX_N} trajectories")
-        super().__init__(gen, n_traj, T, select, zbuf=zbuf)
-        self._cde_alloc()
+        super().__init__(gen, n_traj, T, select, zbuf=zbuf, x=x)
 
-    def _cde_alloc(self):
+    def _alloc(self):
         f32 = dict(dtype=torch.float32, device=self.device)
         self.S_cap = int(self.gen.cde_max_steps)
         self.tslope = cde_time_slopes(self.T).to(self.device)
@@ -1753,23 +1520,21 @@ class _CdeGenPlan(_GenPlan):
     def _x_shape(self, n_traj, T):
         return (n_traj, T)
 
-    def _cde_params(self):
+    def _params(self):
         g = self.gen
         f, fn = g.f, g.ode_fn
         return (f[0].weight, f[0].bias, f[2].weight, f[2].bias, fn.linear1.weight, fn.linear1.bias,
                 fn.linear2.weight, fn.linear2.bias)
 
     def _programs(self):
-        ps = self._cde_params()
+        ps = self._params()
         key = tuple(dptr(p) for p in ps) + (self.gen.cde_rtol, self.gen.cde_atol)
         if key != self._ode_ptrs:
             self._ode_ptrs = key
-            zbuf = getattr(self, "_zbuf", None)
-            zbuf = self.stack.x_in if zbuf is None else zbuf
             common = dict(p=L.CdeParams(*key[:8]), x=dptr(self.x), tslope=dptr(self.tslope), sel_t=dptr(self.sel),
                           states=dptr(self.states), sched=dptr(self.sched), counts=dptr(self.counts), N=self.n,
-                          T=self.T, S_cap=self.S_cap, zcols=getattr(self, "_zcols", Z_COLS))
-            self.fwd_op = L.CdeFwdOp(content=dptr(self.content), z=dptr(zbuf), sync=dptr(self.sync),
+                          T=self.T, S_cap=self.S_cap, zcols=self._zcols)
+            self.fwd_op = L.CdeFwdOp(content=dptr(self.content), z=dptr(self._zbuf), sync=dptr(self.sync),
                                      rtol=float(self.gen.cde_rtol), atol=float(self.gen.cde_atol), **common)
             self.bwd_op = L.CdeBwdOp(gz=None, work=dptr(self.cde_work), grads=None, accumulate=0, **common)
             self.fwd_prog = L.Program([self.fwd_op])
@@ -1785,59 +1550,15 @@ class _CdeGenPlan(_GenPlan):
                                "size underflowed; raise cde_max_steps or loosen cde_rtol / cde_atol")
         return c
 
-    def forward(self, x_host, content_host, sel_host, training, keep):
+    def forward(self, x_host, content_host, sel_host, training, keep, cls_host=None):
         if x_host is None:                     # prefetched (checked by _launch_latents)
             return super().forward(None, content_host, sel_host, training, keep)
-        self.stage_inputs(x_host, content_host, sel_host)
+        self.stage_inputs(x_host, content_host, sel_host, cls_host)
         self.fwd_prog.run(stream_ptr())
         self.check_solve()
         out = self.stack.forward(training)
         self.busy = keep
         return out
-
-    def latent_backward(self, gz_ptr, arena, keep):
-        """As _GenPlan.latent_backward: f's and CDEFunc's 8 tensors, contiguous in the kernel's order."""
-        self.bwd_op.gz = gz_ptr
-        if arena is not None:
-            tgt = [arena.target(q) for q in self._cde_params()]
-            base, acc = tgt[0]
-            self.bwd_op.grads = base.data_ptr()
-            self.bwd_op.accumulate = 1 if acc else 0
-            L.run_one(self.bwd_op, stream_ptr())
-            return None
-        grads = torch.empty(L.CDE_NPARAM, dtype=torch.float32, device=self.device)
-        self.bwd_op.grads = grads.data_ptr()
-        self.bwd_op.accumulate = 0
-        L.run_one(self.bwd_op, stream_ptr())
-        return [grads[o:o + k].view(shp) for o, k, shp in _CDE_GRAD_OFFS]
-
-
-class _CdeLatentFn(torch.autograd.Function):
-    """VideoGeneratorCDE.sample_z_m as its own autograd node: gode_cde_fwd alone, latent rows [N*T, 16] (row n*T + t,
-    the reference's z_T.reshape(-1, T) order); backward = gode_cde_bwd."""
-
-    @staticmethod
-    def forward(ctx, gen, x_host, n, T, *params):
-        dev = gen.main[0].weight.device
-        lp = _CdeGenPlan.__new__(_CdeGenPlan)          # only the latent half of a plan: no decoder buffers
-        lp.gen, lp.n, lp.T, lp.select, lp.device = gen, n, T, False, dev
-        lp.x = x_host.to(dev).contiguous()               # [n, T]
-        lp.content, lp.sel = None, None
-        lp._cde_alloc()
-        lp._zbuf, lp._zcols = torch.empty(n * T, 16, dtype=torch.float32, device=dev), 16
-        lp._ode_ptrs = None
-        lp._programs()
-        lp.fwd_prog.run(stream_ptr())
-        lp.check_solve()
-        ctx.lp = lp
-        return lp._zbuf
-
-    @staticmethod
-    def backward(ctx, gout):
-        lp = ctx.lp
-        g = gout.contiguous()
-        grads = lp.latent_backward(g.data_ptr(), None, g)
-        return (None, None, None, None, *grads)
 
 
 class VideoGeneratorCDE(VideoGeneratorMNIST):
@@ -1892,42 +1613,15 @@ class VideoGeneratorCDE(VideoGeneratorMNIST):
         self.f = nn.Sequential(nn.Linear(cde_input_dim, 64), nn.LeakyReLU(0.2), nn.Linear(64, d), nn.LeakyReLU(0.2))
 
     def _param_list(self):
-        dec = []
-        for p in self._decoder_params():
-            dec.append(p.weight)
-            if p.gamma is not None:
-                dec += [p.gamma, p.beta]
         fn = self.ode_fn
         cde = [self.f[0].weight, self.f[0].bias, self.f[2].weight, self.f[2].bias, fn.linear1.weight, fn.linear1.bias,
                fn.linear2.weight, fn.linear2.bias]
-        return dec, cde
+        return self._decoder_list(), cde
 
     def _check_len(self, T):
         if T != self.dim_z_motion:
             raise ValueError(f"video_len={T}: models/mocogan_cde.py views the [n, {self.dim_z_motion}] motion noise as "
                              f"[n, video_len, 1], which needs video_len == dim_z_motion ({self.dim_z_motion})")
-
-    def _host_inputs(self, select, num_samples, T):
-        self._check_len(T)
-        return super()._host_inputs(select, num_samples, T)
-
-    def _launch_latents(self, plans):
-        st = stream_ptr()
-        for p in plans:
-            p.fwd_prog.run(st)
-        for p in plans:
-            p.check_solve()
-
-    def sample_z_m(self, num_samples, video_len=None):
-        """models/mocogan_cde.py:60-84 -> [N*T, 16], row n*T + t: one gode_cde_fwd launch, differentiable
-        (gode_cde_bwd).  sample_videos()/sample_images() fuse the same launch with the content broadcast and the
-        decoder; this method is the reference's public surface (and what the inherited sample_z_video calls)."""
-        T = video_len if video_len is not None else self.video_length
-        self._check_len(T)
-        _require_gpu(self.main[0].weight, type(self).__name__)
-        x = self._draw_motion(num_samples, T)
-        _, cde = self._param_list()
-        return _CdeLatentFn.apply(self, x, num_samples, T, *cde)
 
 
 # ==================================================================================================================
