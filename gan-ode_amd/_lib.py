@@ -229,7 +229,7 @@ EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "god
            "gode_odernn_bwd_multi", "gode_sde_fwd", "gode_sde_bwd", "gode_sde_bwd_work_size", "gode_cde_fwd", "gode_cde_bwd", "gode_cde_sync_size", "gode_cde_state_size", "gode_cde_bwd_work_size", "gode_gru_fwd", "gode_gru_bwd", "gode_gru_fwd_multi",
            "gode_gru_bwd_multi", "gode_gru_bwd_work_size", "gode_bce_logits",
            "gode_wgan_logits", "gode_adam_l2", "gode_adam_multi", "gode_adam_multi_dev", "gode_adam_noise_multi",
-           "gode_adam_noise_multi_dev", "gode_param_noise", "gode_dnoise", "gode_dnoise_normals", "gode_categ_onehot", "gode_ce_logits", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
+           "gode_adam_noise_multi_dev", "gode_param_noise", "gode_ode_step", "gode_ode_step_chunks", "gode_axpy_multi", "gode_dnoise", "gode_dnoise_normals", "gode_categ_onehot", "gode_ce_logits", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
 
 _lib = None
 
@@ -300,6 +300,10 @@ def lib():
     L.gode_adam_noise_multi_dev.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, ptr, u64, u32, f32, ptr]
     L.gode_param_noise.argtypes = [ptr, i64, u64, u32, u32, i64, f32, i32, ptr]
     L.gode_dnoise_normals.argtypes = [ptr, i64, u64, u32, u32, u32, i64, i32, ptr]
+    L.gode_ode_step_chunks.argtypes = [ptr, i64]
+    L.gode_ode_step_chunks.restype = i64
+    L.gode_ode_step.argtypes = [ptr, i32, i64, i32, f32, f32, f32, f32, f32, ptr, ptr]
+    L.gode_axpy_multi.argtypes = [ptr, i32, i64, f32, ptr, ptr, f32, ptr, ptr, ptr]
     L.gode_run.argtypes = [ptr, ptr, i32, ptr]
     _lib = L
     return L

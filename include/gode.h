@@ -541,6 +541,36 @@ int gode_dnoise(const gode_dnoise_op* op, void* stream);
 int gode_dnoise_normals(float* out, int64_t n, uint64_t seed, uint32_t noise_stream, uint32_t layer, uint32_t call,
                         int64_t e_off, int32_t raw, void* stream);
 
+/* ---- ODE-GAN training (GANODETrainer of stage2/ode_training.py: Euler / Heun / RK4 steps in parameter space) ---------
+ * One stage update of a whole network in ONE launch, on `count` fp32 tensors described by a DEVICE table:
+ *   p += c1*g[0] + c2*g[1] + c3*g[2] + c4*g[3] + cq*(qp - qm)
+ * terms: bit k (k < 4) says that g[k] takes part, bit 4 that the q pair does; an absent term is neither read nor added.  The
+ * sum is formed left to right with fused multiply-adds (the first present term is a plain product), then added to p: at
+ * most 4 + 2 + 1 roundings.  A record in which a participating pointer is NULL is skipped: that tensor is not touched
+ * (autograd returned None for it).  cq_dev != NULL: cq is multiplied by the device float cq_dev[0] (the reciprocal
+ * difference step written by gode_axpy_multi), so no value has to travel to the host.
+ * Tensors need 4-byte alignment only; those whose participating pointers share p's offset within 16 bytes move as 16-byte
+ * vectors between a scalar head and tail, the others element by element.  chunk0 of record k is the sum of
+ * gode_ode_step_chunks(p, n) over the records before it, and `chunks` the sum over all of them: the workgroups stride over
+ * that concatenated space. */
+#define GODE_STEP_QUADS 256
+#define GODE_AXPY_MAX_BLOCKS 512
+typedef struct gode_ode_step_tensor {
+  float* p; const float* g[4]; const float* qp; const float* qm; int64_t n; int64_t chunk0;
+} gode_ode_step_tensor;
+int64_t gode_ode_step_chunks(const void* p, int64_t n);
+int gode_ode_step(const gode_ode_step_tensor* table, int32_t count, int64_t chunks, int32_t terms, float c1, float c2,
+                  float c3, float c4, float cq, const float* cq_dev, void* stream);
+/* p = base + a*v on `count` tensors (one fused multiply-add; a == 0 or v == NULL copies base bit for bit; p may alias base),
+ * a multiplied by the device float a_dev[0] when a_dev != NULL.  sums != NULL: sums[0] = sum v^2, sums[1] = sum base^2 over
+ * all tensors, accumulated in double in a fixed order (two passes, no atomics: two runs give the same bits).  step != NULL
+ * (needs sums): step[0] = fp32(h * (1 + sqrt(sums[1])) / sqrt(sums[0])), the central-difference step of DESIGN section 14,
+ * and step[1] = fp32(1 / step[0]); both 0 when sums[0] == 0.  work: 2 * GODE_AXPY_MAX_BLOCKS doubles of device scratch.
+ * chunk0 / chunks as above. */
+typedef struct gode_axpy_tensor { float* p; const float* base; const float* v; int64_t n; int64_t chunk0; } gode_axpy_tensor;
+int gode_axpy_multi(const gode_axpy_tensor* table, int32_t count, int64_t chunks, float a, const float* a_dev, double* sums,
+                    float h, float* step, double* work, void* stream);
+
 /* out[i] = a[i]*alpha (+ out[i] if accumulate); small utility for gradient bucket handling */
 int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulate, void* stream);
 
