@@ -9,6 +9,7 @@ from .modules import (CategoricalVideoDiscriminator, CDEFunc, Noise, ODEFunc, Pa
                       VideoGeneratorCDE, VideoGeneratorGRU, VideoGeneratorMNIST, VideoGeneratorMNISTODE, VideoGeneratorMNISTODERNN,
                       VideoGeneratorSDE)
 from .ode_training import GANODETrainer
+from .gres import ConditionalNorm, GResBlock, SpectralNorm
 from .train import (FusedAdam, GanTrainer, WassersteinDiscriminatorLoss, WassersteinGeneratorLoss, bce_with_logits_const,
                     bce_with_logits_halves, bce_with_logits_pair, bce_ce_head, bce_ce_head_halves, bce_ce_head_pair,
                     bce_ce_heads, categorical_cross_entropy, build_mnist, build_ucf, freeze_host_gc, host_cpu_quota,
@@ -16,7 +17,7 @@ from .train import (FusedAdam, GanTrainer, WassersteinDiscriminatorLoss, Wassers
                     wasserstein_discriminator_loss_halves, wasserstein_generator_loss, wasserstein_generator_loss_pair)
 
 __all__ = ["Noise", "ODEFunc", "PatchImageDiscriminator", "VideoDiscriminator", "CategoricalVideoDiscriminator", "VideoGenerator",
-           "VideoGeneratorMNIST", "VideoGeneratorMNISTODE", "VideoGeneratorMNISTODERNN", "SDEFunc", "VideoGeneratorSDE", "CDEFunc", "VideoGeneratorCDE", "VideoGeneratorGRU", "FusedAdam", "GanTrainer", "GANODETrainer", "bce_with_logits_const",
+           "VideoGeneratorMNIST", "VideoGeneratorMNISTODE", "VideoGeneratorMNISTODERNN", "SDEFunc", "VideoGeneratorSDE", "CDEFunc", "VideoGeneratorCDE", "VideoGeneratorGRU", "FusedAdam", "GanTrainer", "GANODETrainer", "SpectralNorm", "ConditionalNorm", "GResBlock", "bce_with_logits_const",
            "bce_with_logits_pair", "bce_with_logits_halves", "categorical_cross_entropy", "bce_ce_head", "bce_ce_head_pair",
            "bce_ce_head_halves", "bce_ce_heads", "WassersteinGeneratorLoss", "WassersteinDiscriminatorLoss",
            "wasserstein_generator_loss", "wasserstein_generator_loss_pair", "wasserstein_discriminator_loss",

@@ -21,6 +21,7 @@ OP_WGAN = 18
 OP_GRU_FWD, OP_GRU_BWD = 19, 20
 OP_DNOISE = 21
 OP_CATEG, OP_CE = 22, 23
+OP_CHSTATS, OP_CBN_EMBED, OP_CBN_EMBED_BWD, OP_CBN_APPLY, OP_CBN_BWD, OP_GRES_OUT, OP_GRES_OUT_BWD, OP_SN_FWD, OP_SN_BWD = range(24, 33)
 REC_ADAM_NOISE = -1          # gode_sizeof index of the gode_adam_noise_tensor table record
 ODE_NPARAM = 2672
 ODERNN_NPARAM = 2176
@@ -28,6 +29,7 @@ SDE_NPARAM = 3216
 CDE_NPARAM = 7536
 CDE_MAX_N = 4096
 GRU_NPARAM = 1632
+SN_BWD_BLOCKS = 64
 
 
 class ConvGeom(C.Structure):
@@ -201,6 +203,59 @@ class WganOp(C.Structure):
     KIND = OP_WGAN
 
 
+class ChstatsOp(C.Structure):
+    _fields_ = [("x", ptr), ("stats", ptr), ("xs", i64 * 4), ("N", i32), ("H", i32), ("W", i32), ("C", i32), ("rows", i32),
+                ("pad_", i32)]
+    KIND = OP_CHSTATS
+
+
+class CbnEmbedOp(C.Structure):
+    _fields_ = [("cond", ptr), ("W", ptr), ("b", ptr), ("gb", ptr), ("N", i32), ("K", i32), ("C2", i32), ("pad_", i32)]
+    KIND = OP_CBN_EMBED
+
+
+class CbnEmbedBwdOp(C.Structure):
+    _fields_ = [("cond", ptr), ("W", ptr), ("dgb", ptr), ("dW", ptr), ("db", ptr), ("dcond", ptr), ("N", i32), ("K", i32),
+                ("C2", i32), ("pad_", i32)]
+    KIND = OP_CBN_EMBED_BWD
+
+
+class CbnApplyOp(C.Structure):
+    _fields_ = [("src", ptr), ("bias", ptr), ("mean", ptr), ("invstd", ptr), ("gb", ptr), ("out", ptr), ("ss", i64 * 4),
+                ("N", i32), ("H", i32), ("W", i32), ("C", i32), ("f", i32), ("act", i32)]
+    KIND = OP_CBN_APPLY
+
+
+class CbnBwdOp(C.Structure):
+    _fields_ = [("g_a", ptr), ("a", ptr), ("src", ptr), ("bias", ptr), ("mean", ptr), ("invstd", ptr), ("gb", ptr),
+                ("gadd", ptr), ("work", ptr), ("dgb", ptr), ("dbias", ptr), ("g_out", ptr), ("ss", i64 * 4), ("gos", i64 * 4),
+                ("N", i32), ("H", i32), ("W", i32), ("C", i32), ("f", i32), ("act", i32), ("eval_mode", i32), ("pad_", i32)]
+    KIND = OP_CBN_BWD
+
+
+class GresOutOp(C.Structure):
+    _fields_ = [("main", ptr), ("sc", ptr), ("b_main", ptr), ("b_sc", ptr), ("y", ptr), ("N", i32), ("H", i32), ("W", i32),
+                ("C", i32), ("f", i32), ("down", i32)]
+    KIND = OP_GRES_OUT
+
+
+class GresOutBwdOp(C.Structure):
+    _fields_ = [("g_y", ptr), ("g_sc", ptr), ("g_main", ptr), ("db", ptr), ("work", ptr), ("gys", i64 * 4), ("N", i32),
+                ("H", i32), ("W", i32), ("C", i32), ("f", i32), ("down", i32)]
+    KIND = OP_GRES_OUT_BWD
+
+
+class SnOp(C.Structure):
+    _fields_ = [("wbar", ptr), ("u", ptr), ("v", ptr), ("wout", ptr), ("sigma", ptr), ("work", ptr), ("h", i32), ("w", i32)]
+    KIND = OP_SN_FWD
+
+
+class SnBwdOp(C.Structure):
+    _fields_ = [("G", ptr), ("wbar", ptr), ("u", ptr), ("v", ptr), ("sigma", ptr), ("dwbar", ptr), ("work", ptr), ("h", i32),
+                ("w", i32)]
+    KIND = OP_SN_BWD
+
+
 class AdamNoiseTensor(C.Structure):
     _fields_ = [("p", ptr), ("g", ptr), ("m", ptr), ("v", ptr), ("n", i64), ("noise_off", i64)]
 
@@ -220,7 +275,9 @@ _STRUCTS = {0: ConvGeom, OP_IGEMM: IgemmOp, OP_WGRAD: WgradOp, OP_BN_FINALIZE: B
             OP_ODE_FWD: OdeFwdOp, OP_ODE_BWD: OdeBwdOp, OP_BCE: BceOp, OP_ADAM: AdamOp, OP_PACK: PackOp,
             OP_ODERNN_FWD: OdeRnnFwdOp, OP_ODERNN_BWD: OdeRnnBwdOp, OP_BN_APPLY: BnApplyOp, OP_COL2IM: Col2imOp,
             OP_SDE_FWD: SdeFwdOp, OP_SDE_BWD: SdeBwdOp, OP_CDE_FWD: CdeFwdOp, OP_CDE_BWD: CdeBwdOp, OP_WGAN: WganOp,
-            OP_GRU_FWD: GruFwdOp, OP_GRU_BWD: GruBwdOp, OP_DNOISE: DnoiseOp, OP_CATEG: CategOp, OP_CE: CeOp, REC_ADAM_NOISE: AdamNoiseTensor}
+            OP_GRU_FWD: GruFwdOp, OP_GRU_BWD: GruBwdOp, OP_DNOISE: DnoiseOp, OP_CATEG: CategOp, OP_CE: CeOp, REC_ADAM_NOISE: AdamNoiseTensor,
+            OP_CHSTATS: ChstatsOp, OP_CBN_EMBED: CbnEmbedOp, OP_CBN_EMBED_BWD: CbnEmbedBwdOp, OP_CBN_APPLY: CbnApplyOp,
+            OP_CBN_BWD: CbnBwdOp, OP_GRES_OUT: GresOutOp, OP_GRES_OUT_BWD: GresOutBwdOp, OP_SN_FWD: SnOp, OP_SN_BWD: SnBwdOp}
 
 EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "gode_igemm_stats_segments", "gode_igemm_model_cycles", "gode_igemm_work_size", "gode_pack_size", "gode_pack_weights", "gode_wgrad",
            "gode_wgrad_work_size", "gode_wgrad_auto_splits", "gode_bn_finalize", "gode_bn_bwd",
@@ -229,7 +286,7 @@ EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "god
            "gode_odernn_bwd_multi", "gode_sde_fwd", "gode_sde_bwd", "gode_sde_bwd_work_size", "gode_cde_fwd", "gode_cde_bwd", "gode_cde_sync_size", "gode_cde_state_size", "gode_cde_bwd_work_size", "gode_gru_fwd", "gode_gru_bwd", "gode_gru_fwd_multi",
            "gode_gru_bwd_multi", "gode_gru_bwd_work_size", "gode_bce_logits",
            "gode_wgan_logits", "gode_adam_l2", "gode_adam_multi", "gode_adam_multi_dev", "gode_adam_noise_multi",
-           "gode_adam_noise_multi_dev", "gode_param_noise", "gode_ode_step", "gode_ode_step_chunks", "gode_axpy_multi", "gode_dnoise", "gode_dnoise_normals", "gode_categ_onehot", "gode_ce_logits", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
+           "gode_adam_noise_multi_dev", "gode_param_noise", "gode_ode_step", "gode_ode_step_chunks", "gode_axpy_multi", "gode_dnoise", "gode_dnoise_normals", "gode_categ_onehot", "gode_ce_logits", "gode_chstats", "gode_chstats_rows", "gode_cbn_embed", "gode_cbn_embed_bwd", "gode_cbn_apply", "gode_cbn_bwd", "gode_cbn_bwd_work_size", "gode_gres_out", "gode_gres_out_bwd", "gode_gres_out_bwd_work_size", "gode_sn_fwd", "gode_sn_bwd", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
 
 _lib = None
 
@@ -253,7 +310,9 @@ def lib():
     for name in ("gode_igemm", "gode_wgrad", "gode_bn_finalize", "gode_bn_bwd", "gode_ode_fwd", "gode_ode_bwd",
                  "gode_bce_logits", "gode_adam_l2", "gode_odernn_fwd", "gode_odernn_bwd", "gode_bn_apply", "gode_col2im",
                  "gode_sde_fwd", "gode_sde_bwd", "gode_cde_fwd", "gode_cde_bwd", "gode_wgan_logits", "gode_gru_fwd",
-                 "gode_gru_bwd", "gode_dnoise", "gode_categ_onehot", "gode_ce_logits"):
+                 "gode_gru_bwd", "gode_dnoise", "gode_categ_onehot", "gode_ce_logits", "gode_chstats", "gode_cbn_embed",
+                 "gode_cbn_embed_bwd", "gode_cbn_apply", "gode_cbn_bwd", "gode_gres_out", "gode_gres_out_bwd", "gode_sn_fwd",
+                 "gode_sn_bwd"):
         getattr(L, name).argtypes = [ptr, ptr]
         getattr(L, name).restype = C.c_int
     L.gode_igemm_stats_rows.argtypes = [ptr]
@@ -292,6 +351,11 @@ def lib():
     L.gode_gru_bwd_multi.argtypes = [ptr, i32, ptr]
     L.gode_gru_bwd_work_size.argtypes = [i32]
     L.gode_gru_bwd_work_size.restype = i64
+    L.gode_chstats_rows.argtypes = [i64]
+    L.gode_cbn_bwd_work_size.argtypes = [i32, i32, i32, i32]
+    L.gode_cbn_bwd_work_size.restype = i64
+    L.gode_gres_out_bwd_work_size.argtypes = [i32, i32, i32, i32, i32, i32]
+    L.gode_gres_out_bwd_work_size.restype = i64
     L.gode_scale.argtypes = [ptr, ptr, i64, f32, C.c_int, ptr]
     L.gode_adam_multi.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, f32, i32, ptr]
     L.gode_adam_multi_dev.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, ptr, ptr]
@@ -371,5 +435,8 @@ def _run_one(op, stream):
           OP_BN_APPLY: "gode_bn_apply", OP_COL2IM: "gode_col2im", OP_SDE_FWD: "gode_sde_fwd",
           OP_SDE_BWD: "gode_sde_bwd", OP_CDE_FWD: "gode_cde_fwd", OP_CDE_BWD: "gode_cde_bwd",
           OP_WGAN: "gode_wgan_logits", OP_GRU_FWD: "gode_gru_fwd", OP_GRU_BWD: "gode_gru_bwd",
-          OP_DNOISE: "gode_dnoise", OP_CATEG: "gode_categ_onehot", OP_CE: "gode_ce_logits"}[op.KIND]
+          OP_DNOISE: "gode_dnoise", OP_CATEG: "gode_categ_onehot", OP_CE: "gode_ce_logits", OP_CHSTATS: "gode_chstats",
+          OP_CBN_EMBED: "gode_cbn_embed", OP_CBN_EMBED_BWD: "gode_cbn_embed_bwd", OP_CBN_APPLY: "gode_cbn_apply",
+          OP_CBN_BWD: "gode_cbn_bwd", OP_GRES_OUT: "gode_gres_out", OP_GRES_OUT_BWD: "gode_gres_out_bwd",
+          OP_SN_FWD: "gode_sn_fwd", OP_SN_BWD: "gode_sn_bwd"}[op.KIND]
     check(getattr(lib(), fn)(C.byref(op), stream), fn)

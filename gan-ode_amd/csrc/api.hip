@@ -30,6 +30,15 @@ extern "C" int gode_sizeof(int kind) {
     case GODE_OP_DNOISE: return (int)sizeof(gode_dnoise_op);
     case GODE_OP_CATEG: return (int)sizeof(gode_categ_op);
     case GODE_OP_CE: return (int)sizeof(gode_ce_op);
+    case GODE_OP_CHSTATS: return (int)sizeof(gode_chstats_op);
+    case GODE_OP_CBN_EMBED: return (int)sizeof(gode_cbn_embed_op);
+    case GODE_OP_CBN_EMBED_BWD: return (int)sizeof(gode_cbn_embed_bwd_op);
+    case GODE_OP_CBN_APPLY: return (int)sizeof(gode_cbn_apply_op);
+    case GODE_OP_CBN_BWD: return (int)sizeof(gode_cbn_bwd_op);
+    case GODE_OP_GRES_OUT: return (int)sizeof(gode_gres_out_op);
+    case GODE_OP_GRES_OUT_BWD: return (int)sizeof(gode_gres_out_bwd_op);
+    case GODE_OP_SN_FWD: return (int)sizeof(gode_sn_op);
+    case GODE_OP_SN_BWD: return (int)sizeof(gode_sn_bwd_op);
   }
   return GODE_E_KIND;
 }
@@ -65,6 +74,15 @@ extern "C" int gode_run(const int32_t* kinds, const void* const* ops, int32_t n,
       case GODE_OP_DNOISE: rc = gode_dnoise((const gode_dnoise_op*)ops[i], stream); break;
       case GODE_OP_CATEG: rc = gode_categ_onehot((const gode_categ_op*)ops[i], stream); break;
       case GODE_OP_CE: rc = gode_ce_logits((const gode_ce_op*)ops[i], stream); break;
+      case GODE_OP_CHSTATS: rc = gode_chstats((const gode_chstats_op*)ops[i], stream); break;
+      case GODE_OP_CBN_EMBED: rc = gode_cbn_embed((const gode_cbn_embed_op*)ops[i], stream); break;
+      case GODE_OP_CBN_EMBED_BWD: rc = gode_cbn_embed_bwd((const gode_cbn_embed_bwd_op*)ops[i], stream); break;
+      case GODE_OP_CBN_APPLY: rc = gode_cbn_apply((const gode_cbn_apply_op*)ops[i], stream); break;
+      case GODE_OP_CBN_BWD: rc = gode_cbn_bwd((const gode_cbn_bwd_op*)ops[i], stream); break;
+      case GODE_OP_GRES_OUT: rc = gode_gres_out((const gode_gres_out_op*)ops[i], stream); break;
+      case GODE_OP_GRES_OUT_BWD: rc = gode_gres_out_bwd((const gode_gres_out_bwd_op*)ops[i], stream); break;
+      case GODE_OP_SN_FWD: rc = gode_sn_fwd((const gode_sn_op*)ops[i], stream); break;
+      case GODE_OP_SN_BWD: rc = gode_sn_bwd((const gode_sn_bwd_op*)ops[i], stream); break;
       case GODE_OP_PACK: {
         // every run of consecutive pack ops goes out as one launch per 8 panels
         int j = i;

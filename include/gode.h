@@ -571,6 +571,92 @@ typedef struct gode_axpy_tensor { float* p; const float* base; const float* v; i
 int gode_axpy_multi(const gode_axpy_tensor* table, int32_t count, int64_t chunks, float a, const float* a_dev, double* sums,
                     float h, float* step, double* work, void* stream);
 
+/* ---- stage 1: DVD-GAN generator residual block (stage1/GResBlock.py: SpectralNorm :10-64, ConditionalNorm :66-88,
+ * GResBlock :90-167) -- the pieces around gode_igemm / gode_wgrad, which run the 3x3 and 1x1 convolutions on materialised
+ * channels-last tensors.  2-D maps; strides are ELEMENT strides {N, H, W, C}, all zero = channels-last contiguous (so a tensor
+ * whose genuine strides are all zero -- one element expanded -- must be materialised by the caller first).  Every C is accepted.  Reductions run in a fixed order without float atomics: two runs give the same bits. */
+
+/* Per-channel partial sums of a strided tensor: stats[2][C][rows] (sum, then sum of squares; row r covers positions
+ * [r*chunk, (r+1)*chunk) of the N*H*W positions, chunk = ceil(N*H*W / rows)) -- the layout gode_bn_finalize reads
+ * (ncols = C).  rows >= 1 is the caller's choice (gode_chstats_rows: the default). */
+typedef struct gode_chstats_op {
+  const float* x; float* stats; int64_t xs[4]; int32_t N, H, W, C, rows, pad_;
+} gode_chstats_op;
+int gode_chstats(const gode_chstats_op* op, void* stream);
+int gode_chstats_rows(int64_t positions);
+
+/* ConditionalNorm's embedding: gb[n][2C] = condition[n][K] . W[2C][K]^T + b[2C]  ([gamma | beta] per sample). */
+typedef struct gode_cbn_embed_op {
+  const float* cond; const float* W; const float* b; float* gb; int32_t N, K, C2, pad_;
+} gode_cbn_embed_op;
+int gode_cbn_embed(const gode_cbn_embed_op* op, void* stream);
+/* its backward from dgb[n][2C] (gode_cbn_bwd writes it): dW[2C][K] = dgb^T cond, db[2C] = column sums, dcond[n][K] =
+ * dgb W (each nullable), every sum in index order. */
+typedef struct gode_cbn_embed_bwd_op {
+  const float* cond; const float* W; const float* dgb; float* dW; float* db; float* dcond; int32_t N, K, C2, pad_;
+} gode_cbn_embed_bwd_op;
+int gode_cbn_embed_bwd(const gode_cbn_embed_bwd_op* op, void* stream);
+
+/* Conditional BatchNorm + activation + nearest upsample on the store:
+ *   a[n][h*f+i][w*f+j][c] = act(gamma[n,c] * (v + bias[c] - mean[c]) * invstd[c] + beta[n,c]),  i, j < f,  f in {1, 2}
+ * v = src[n,h,w,c] read through ss.  gb = [gamma | beta][N][2C] (gode_cbn_embed).  mean == NULL: no normalisation,
+ * a = act(v + bias).  bias nullable.  (Train mode over a convolution output: its bias cancels against the batch mean, so the
+ * caller passes the raw output, the raw mean and bias = NULL.)  out is channels-last [N][H*f][W*f][C]. */
+typedef struct gode_cbn_apply_op {
+  const float* src; const float* bias; const float* mean; const float* invstd; const float* gb; float* out;
+  int64_t ss[4]; int32_t N, H, W, C, f, act;
+} gode_cbn_apply_op;
+int gode_cbn_apply(const gode_cbn_apply_op* op, void* stream);
+
+/* Backward of the above from g_a[N][H*f][W*f][C] (channels-last): g_z = act'(a) * (sum of the f x f replicas of g_a), with a the
+ * forward's output (ReLU: a > 0);  dgb[n][2C] = [sum_hw g_z * xhat | sum_hw g_z];  with g_xhat = gamma[n,c] * g_z
+ *   g_v = invstd * (g_xhat - mean(g_xhat) - xhat * mean(g_xhat * xhat))        (eval_mode != 0: invstd * g_xhat)
+ * the means over all N*H*W positions of a channel; mean == NULL (no normalisation): g_v = g_z.  g_out = g_v (+ gadd, a
+ * channels-last [N][H][W][C] tensor: the skip path's input gradient), written through gos (the caller's x layout or
+ * channels-last).  dbias (nullable, [C]): the gradient of `bias`, sum of g_v -- exactly 0 behind a train-mode normalisation.
+ * work: >= gode_cbn_bwd_work_size floats, 8-byte aligned. */
+typedef struct gode_cbn_bwd_op {
+  const float* g_a; const float* a; const float* src; const float* bias; const float* mean; const float* invstd;
+  const float* gb; const float* gadd; float* work; float* dgb; float* dbias; float* g_out;
+  int64_t ss[4]; int64_t gos[4]; int32_t N, H, W, C, f, act, eval_mode, pad_;
+} gode_cbn_bwd_op;
+int gode_cbn_bwd(const gode_cbn_bwd_op* op, void* stream);
+int64_t gode_cbn_bwd_work_size(int32_t N, int32_t H, int32_t W, int32_t C);
+
+/* Block output: main[N][H*f][W*f][C] = conv1's raw output, sc[N][H][W][C] = the 1x1 skip convolution's raw output at the INPUT
+ * resolution (a 1x1 convolution commutes with nearest upsampling), both channels-last:
+ *   down == 1: y[n][p][q][c] = main[n][p][q][c] + b_main[c] + sc[n][p/f][q/f][c] + b_sc[c]
+ *   down == 2 (f == 1): y = avg_pool2(main + b_main) + avg_pool2(sc + b_sc), [N][H/2][W/2][C]. */
+typedef struct gode_gres_out_op {
+  const float* main; const float* sc; const float* b_main; const float* b_sc; float* y; int32_t N, H, W, C, f, down;
+} gode_gres_out_op;
+int gode_gres_out(const gode_gres_out_op* op, void* stream);
+/* its inverse from g_y[N][Ho][Wo][C] read through gys: db[C] = column sums of g_y (the gradient of BOTH biases);
+ * g_sc[N][H][W][C] = the f x f sums of g_y (down == 2: 0.25 * g_y[p/2][q/2], zero on an odd last row / column; f == down == 1:
+ * a copy); g_main (nullable, down == 1 only): the channels-last copy of g_y ([N][H*f][W*f][C]; down == 2: conv1's output
+ * gradient IS g_sc).  work: >= gode_gres_out_bwd_work_size floats (needed only with db). */
+typedef struct gode_gres_out_bwd_op {
+  const float* g_y; float* g_sc; float* g_main; float* db; float* work; int64_t gys[4]; int32_t N, H, W, C, f, down;
+} gode_gres_out_bwd_op;
+int gode_gres_out_bwd(const gode_gres_out_bwd_op* op, void* stream);
+int64_t gode_gres_out_bwd_work_size(int32_t N, int32_t H, int32_t W, int32_t C, int32_t f, int32_t down);
+
+/* Spectral normalisation, one power iteration on wbar[h][w] (l2n(x) = x / (|x| + 1e-12)), launches in stream order:
+ *   v <- l2n(wbar^T u);  u <- l2n(wbar v);  sigma = u . (wbar v);  wout = wbar / sigma  (a true division).
+ * u[h], v[w] are updated in place, sigma is one device float.  work: >= h + w floats. */
+typedef struct gode_sn_op {
+  const float* wbar; float* u; float* v; float* wout; float* sigma; float* work; int32_t h, w;
+} gode_sn_op;
+int gode_sn_fwd(const gode_sn_op* op, void* stream);
+/* dwbar = G / sigma - (<G, wbar> / sigma^2) u v^T  (u, v constants), <G, wbar> reduced in double in a fixed order.
+ * work: >= 2 * GODE_SN_BWD_BLOCKS floats, 8-byte aligned. */
+#define GODE_SN_BWD_BLOCKS 64
+typedef struct gode_sn_bwd_op {
+  const float* G; const float* wbar; const float* u; const float* v; const float* sigma; float* dwbar; float* work;
+  int32_t h, w;
+} gode_sn_bwd_op;
+int gode_sn_bwd(const gode_sn_bwd_op* op, void* stream);
+
 /* out[i] = a[i]*alpha (+ out[i] if accumulate); small utility for gradient bucket handling */
 int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulate, void* stream);
 
@@ -579,7 +665,9 @@ enum { GODE_OP_IGEMM = 1, GODE_OP_WGRAD = 2, GODE_OP_BN_FINALIZE = 3, GODE_OP_BN
        GODE_OP_ODE_BWD = 6, GODE_OP_BCE = 7, GODE_OP_ADAM = 8, GODE_OP_PACK = 9, GODE_OP_ODERNN_FWD = 10,
        GODE_OP_ODERNN_BWD = 11, GODE_OP_BN_APPLY = 12, GODE_OP_COL2IM = 13, GODE_OP_SDE_FWD = 14,
        GODE_OP_SDE_BWD = 15, GODE_OP_CDE_FWD = 16, GODE_OP_CDE_BWD = 17, GODE_OP_WGAN = 18,
-       GODE_OP_GRU_FWD = 19, GODE_OP_GRU_BWD = 20, GODE_OP_DNOISE = 21, GODE_OP_CATEG = 22, GODE_OP_CE = 23 };
+       GODE_OP_GRU_FWD = 19, GODE_OP_GRU_BWD = 20, GODE_OP_DNOISE = 21, GODE_OP_CATEG = 22, GODE_OP_CE = 23,
+       GODE_OP_CHSTATS = 24, GODE_OP_CBN_EMBED = 25, GODE_OP_CBN_EMBED_BWD = 26, GODE_OP_CBN_APPLY = 27,
+       GODE_OP_CBN_BWD = 28, GODE_OP_GRES_OUT = 29, GODE_OP_GRES_OUT_BWD = 30, GODE_OP_SN_FWD = 31, GODE_OP_SN_BWD = 32 };
 typedef struct gode_pack_op {
   gode_conv_geom g; int32_t dir, co_canon; const float* w; float* wpack; const int32_t* co_perm;
 } gode_pack_op;

@@ -66,7 +66,10 @@ KIND_STRUCT = {"GODE_OP_IGEMM": "gode_igemm_op", "GODE_OP_WGRAD": "gode_wgrad_op
                "GODE_OP_CDE_BWD": "gode_cde_bwd_op", "GODE_OP_WGAN": "gode_wgan_op",
                "GODE_OP_GRU_FWD": "gode_gru_fwd_op", "GODE_OP_GRU_BWD": "gode_gru_bwd_op",
                "GODE_OP_DNOISE": "gode_dnoise_op", "GODE_OP_CATEG": "gode_categ_op",
-               "GODE_OP_CE": "gode_ce_op"}
+               "GODE_OP_CE": "gode_ce_op", "GODE_OP_CHSTATS": "gode_chstats_op", "GODE_OP_CBN_EMBED": "gode_cbn_embed_op",
+               "GODE_OP_CBN_EMBED_BWD": "gode_cbn_embed_bwd_op", "GODE_OP_CBN_APPLY": "gode_cbn_apply_op",
+               "GODE_OP_CBN_BWD": "gode_cbn_bwd_op", "GODE_OP_GRES_OUT": "gode_gres_out_op",
+               "GODE_OP_GRES_OUT_BWD": "gode_gres_out_bwd_op", "GODE_OP_SN_FWD": "gode_sn_op", "GODE_OP_SN_BWD": "gode_sn_bwd_op"}
 
 
 def generate():
