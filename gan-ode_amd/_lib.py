@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgode.so")
 
 i32, i64, f32, ptr = C.c_int32, C.c_int64, C.c_float, C.c_void_p
+cint, u32, u64 = C.c_int, C.c_uint32, C.c_uint64
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH_OUT = 0, 1, 2, 3
 EPI_RAW, EPI_TANH = 0, 1
@@ -39,254 +40,292 @@ class ConvGeom(C.Structure):
         return tuple(getattr(self, n) for n, _ in self._fields_)
 
 
-class IgemmOp(C.Structure):
+class _Op(C.Structure):
+    """An op of gode_run (a GODE_OPS row of gode.h): a subclass names its kind and its `int FN(const op*, stream)` entry
+    point once; _STRUCTS, the prototypes, EXPORTS and run_one's dispatch all follow from the subclasses."""
+
+
+class IgemmOp(_Op):
     _fields_ = [("g", ConvGeom), ("dir", i32), ("act", i32), ("epilogue", i32), ("tile", i32), ("src", ptr),
                 ("wpack", ptr), ("out", ptr), ("scale", ptr), ("shift", ptr), ("stats", ptr), ("gs", i64 * 5),
                 ("work", ptr), ("groups", i32), ("pad3_", i32)]
-    KIND = OP_IGEMM
+    KIND, FN = OP_IGEMM, "gode_igemm"
 
 
-class WgradOp(C.Structure):
+class WgradOp(_Op):
     _fields_ = [("g", ConvGeom), ("act", i32), ("xform_on_y", i32), ("splits", i32), ("accumulate", i32),
                 ("x", ptr), ("y", ptr), ("scale", ptr), ("shift", ptr), ("work", ptr), ("dw", ptr),
                 ("co_perm", ptr), ("co_canon", i64), ("xs", i64 * 5)]
-    KIND = OP_WGRAD
+    KIND, FN = OP_WGRAD, "gode_wgrad"
 
 
-class BnFinalizeOp(C.Structure):
+class BnFinalizeOp(_Op):
     _fields_ = [("stats", ptr), ("rows", i32), ("ncols", i32), ("C", i32), ("count", i64), ("gamma", ptr),
                 ("beta", ptr), ("running_mean", ptr), ("running_var", ptr), ("num_batches_tracked", ptr),
                 ("mean", ptr), ("invstd", ptr), ("scale", ptr), ("shift", ptr), ("momentum", f32), ("eps", f32),
                 ("training", i32), ("pad_", i32), ("groups", i32), ("rows0", i32), ("nseg", i32), ("order", i32),
                 ("count1", i64), ("seg", i32 * 24), ("stats1", ptr), ("rows1", i32), ("pad3_", i32)]
-    KIND = OP_BN_FINALIZE
+    KIND, FN = OP_BN_FINALIZE, "gode_bn_finalize"
 
 
-class BnBwdOp(C.Structure):
+class BnBwdOp(_Op):
     _fields_ = [("g", ptr), ("y", ptr), ("M", i64), ("C", i32), ("act", i32), ("gamma", ptr), ("mean", ptr),
                 ("invstd", ptr), ("scale", ptr), ("shift", ptr), ("dgamma", ptr), ("dbeta", ptr), ("work", ptr),
                 ("accumulate", i32), ("eval_mode", i32), ("gin", ptr), ("groups", i32), ("pad2_", i32), ("M0", i64),
                 ("r1_s", ptr), ("r1_w", ptr), ("r1_H", i32), ("r1_W", i32), ("r1_h", i32), ("r1_wd", i32), ("r1_off", i32),
                 ("pad3_", i32)]
-    KIND = OP_BN_BWD
+    KIND, FN = OP_BN_BWD, "gode_bn_bwd"
 
 
 class OdeParams(C.Structure):
     _fields_ = [(n, ptr) for n in "Wa ba Wb bb W1 b1 W2 b2".split()]
 
 
-class OdeFwdOp(C.Structure):
+class OdeFwdOp(_Op):
     _fields_ = [("p", OdeParams), ("x", ptr), ("content", ptr), ("dt", ptr), ("sel_t", ptr), ("z", ptr),
                 ("traj", ptr), ("N", i32), ("T", i32), ("substeps", i32), ("prenet", i32), ("zcols", i32), ("G", i32),
                 ("grid_dt", ptr), ("emit_at", ptr), ("emit_w", ptr), ("method", i32), ("pad2_", i32), ("rtol", f32),
                 ("atol", f32), ("tout", ptr), ("nsteps", ptr), ("sync", ptr)]
-    KIND = OP_ODE_FWD
+    KIND, FN = OP_ODE_FWD, "gode_ode_fwd"
 
 
-class OdeBwdOp(C.Structure):
+class OdeBwdOp(_Op):
     _fields_ = [("p", OdeParams), ("x", ptr), ("traj", ptr), ("dt", ptr), ("sel_t", ptr), ("gz", ptr),
                 ("work", ptr), ("grads", ptr), ("N", i32), ("T", i32), ("substeps", i32), ("prenet", i32),
                 ("accumulate", i32), ("zcols", i32), ("bstep_off", ptr), ("bstep_dt", ptr), ("method", i32),
                 ("pad_", i32), ("rtol", f32), ("atol", f32), ("tout", ptr), ("nsteps", ptr), ("sync", ptr)]
-    KIND = OP_ODE_BWD
+    KIND, FN = OP_ODE_BWD, "gode_ode_bwd"
 
 
 class OdeRnnParams(C.Structure):
     _fields_ = [(n, ptr) for n in "W1 b1 W2 b2 Wih Whh bih bhh".split()]
 
 
-class OdeRnnFwdOp(C.Structure):
+class OdeRnnFwdOp(_Op):
     _fields_ = [("p", OdeRnnParams), ("noise", ptr), ("content", ptr), ("sel_t", ptr), ("z", ptr), ("hs", ptr),
                 ("hp", ptr), ("nsteps", ptr), ("N", i32), ("T", i32), ("rtol", f32), ("atol", f32), ("zcols", i32),
                 ("pad_", i32), ("sync", ptr)]
-    KIND = OP_ODERNN_FWD
+    KIND, FN = OP_ODERNN_FWD, "gode_odernn_fwd"
 
 
-class OdeRnnBwdOp(C.Structure):
+class OdeRnnBwdOp(_Op):
     _fields_ = [("p", OdeRnnParams), ("noise", ptr), ("hp", ptr), ("sel_t", ptr), ("gz", ptr), ("work", ptr),
                 ("grads", ptr), ("N", i32), ("T", i32), ("substeps", i32), ("accumulate", i32), ("zcols", i32),
                 ("pad_", i32), ("rtol", f32), ("atol", f32), ("sync", ptr), ("nsteps", ptr)]
-    KIND = OP_ODERNN_BWD
+    KIND, FN = OP_ODERNN_BWD, "gode_odernn_bwd"
 
 
 class SdeParams(C.Structure):
     _fields_ = [(n, ptr) for n in "Wa ba Wb bb Wf1 bf1 Wf2 bf2 Wg1 bg1 Wg2 bg2".split()]
 
 
-class SdeFwdOp(C.Structure):
+class SdeFwdOp(_Op):
     _fields_ = [("p", SdeParams), ("x", ptr), ("content", ptr), ("sel_t", ptr), ("dt", ptr), ("sqrt_dt", ptr),
                 ("emit_at", ptr), ("emit_w0", ptr), ("emit_w1", ptr), ("z", ptr), ("states", ptr), ("N", i32),
                 ("T", i32), ("S", i32), ("prenet", i32), ("zcols", i32), ("pad_", i32)]
-    KIND = OP_SDE_FWD
+    KIND, FN = OP_SDE_FWD, "gode_sde_fwd"
 
 
-class SdeBwdOp(C.Structure):
+class SdeBwdOp(_Op):
     _fields_ = [("p", SdeParams), ("x", ptr), ("states", ptr), ("sel_t", ptr), ("dt", ptr), ("sqrt_dt", ptr),
                 ("emit_at", ptr), ("emit_w0", ptr), ("emit_w1", ptr), ("gz", ptr), ("work", ptr), ("grads", ptr),
                 ("N", i32), ("T", i32), ("S", i32), ("prenet", i32), ("accumulate", i32), ("zcols", i32)]
-    KIND = OP_SDE_BWD
+    KIND, FN = OP_SDE_BWD, "gode_sde_bwd"
 
 
 class CdeParams(C.Structure):
     _fields_ = [(n, ptr) for n in "Wa ba Wb bb W1 b1 W2 b2".split()]
 
 
-class CdeFwdOp(C.Structure):
+class CdeFwdOp(_Op):
     _fields_ = [("p", CdeParams), ("x", ptr), ("tslope", ptr), ("content", ptr), ("sel_t", ptr), ("z", ptr),
                 ("states", ptr), ("sched", ptr), ("counts", ptr), ("sync", ptr), ("N", i32), ("T", i32),
                 ("S_cap", i32), ("zcols", i32), ("rtol", f32), ("atol", f32)]
-    KIND = OP_CDE_FWD
+    KIND, FN = OP_CDE_FWD, "gode_cde_fwd"
 
 
-class CdeBwdOp(C.Structure):
+class CdeBwdOp(_Op):
     _fields_ = [("p", CdeParams), ("x", ptr), ("tslope", ptr), ("sel_t", ptr), ("states", ptr), ("sched", ptr),
                 ("counts", ptr), ("gz", ptr), ("work", ptr), ("grads", ptr), ("N", i32), ("T", i32), ("S_cap", i32),
                 ("accumulate", i32), ("zcols", i32), ("pad_", i32)]
-    KIND = OP_CDE_BWD
+    KIND, FN = OP_CDE_BWD, "gode_cde_bwd"
 
 
 class GruParams(C.Structure):
     _fields_ = [(n, ptr) for n in "Wih Whh bih bhh".split()]
 
 
-class GruFwdOp(C.Structure):
+class GruFwdOp(_Op):
     _fields_ = [("p", GruParams), ("noise", ptr), ("content", ptr), ("sel_t", ptr), ("z", ptr), ("hs", ptr), ("N", i32),
                 ("T", i32), ("zcols", i32), ("pad_", i32)]
-    KIND = OP_GRU_FWD
+    KIND, FN = OP_GRU_FWD, "gode_gru_fwd"
 
 
-class GruBwdOp(C.Structure):
+class GruBwdOp(_Op):
     _fields_ = [("p", GruParams), ("noise", ptr), ("hs", ptr), ("sel_t", ptr), ("gz", ptr), ("work", ptr), ("grads", ptr),
                 ("N", i32), ("T", i32), ("accumulate", i32), ("zcols", i32)]
-    KIND = OP_GRU_BWD
+    KIND, FN = OP_GRU_BWD, "gode_gru_bwd"
 
 
-class BnApplyOp(C.Structure):
+class BnApplyOp(_Op):
     _fields_ = [("y", ptr), ("out", ptr), ("scale", ptr), ("shift", ptr), ("M", i64), ("C", i32), ("act", i32),
                 ("M0", i64)]
-    KIND = OP_BN_APPLY
+    KIND, FN = OP_BN_APPLY, "gode_bn_apply"
 
 
-class DnoiseOp(C.Structure):
+class DnoiseOp(_Op):
     _fields_ = [("x", ptr), ("out", ptr), ("scale", ptr), ("shift", ptr), ("call_dev", ptr), ("M", i64), ("C", i32),
                 ("act", i32), ("M0", i64), ("e_off", i64), ("xs", i64 * 5), ("N", i32), ("D", i32), ("H", i32), ("W", i32),
                 ("seed", i64), ("stream", i32), ("layer", i32), ("call", i32), ("sigma", f32)]
-    KIND = OP_DNOISE
+    KIND, FN = OP_DNOISE, "gode_dnoise"
 
 
-class Col2imOp(C.Structure):
+class Col2imOp(_Op):
     _fields_ = [("cols", ptr), ("out", ptr)] + [(n, i32) for n in "N Hi Wi Ho Wo C kh kw sh sw ph pw epilogue pad_ Di Do kd sd pd pad2_".split()]
-    KIND = OP_COL2IM
+    KIND, FN = OP_COL2IM, "gode_col2im"
 
 
-class BceOp(C.Structure):
+class BceOp(_Op):
     _fields_ = [("logits", ptr), ("grad", ptr), ("loss", ptr), ("n", i64), ("target", f32), ("gscale", f32),
                 ("accumulate", i32), ("stride", i32)]
-    KIND = OP_BCE
+    KIND, FN = OP_BCE, "gode_bce_logits"
 
 
-class CategOp(C.Structure):
+class CategOp(_Op):
     _fields_ = [("cls", ptr), ("z", ptr), ("labels_out", ptr), ("n_traj", i32), ("rows_per", i32), ("C", i32),
                 ("zcols", i32), ("col0", i32), ("pad_", i32)]
-    KIND = OP_CATEG
+    KIND, FN = OP_CATEG, "gode_categ_onehot"
 
 
-class CeOp(C.Structure):
+class CeOp(_Op):
     _fields_ = [("logits", ptr), ("labels", ptr), ("grad", ptr), ("loss", ptr), ("B", i32), ("n_lab", i32), ("C", i32),
                 ("ld", i32), ("gld", i32), ("gscale", f32), ("accumulate", i32), ("rows_per_label", i32)]
-    KIND = OP_CE
+    KIND, FN = OP_CE, "gode_ce_logits"
 
 
-class WganOp(C.Structure):
+class WganOp(_Op):
     _fields_ = [("fake", ptr), ("real", ptr), ("grad_fake", ptr), ("grad_real", ptr), ("loss", ptr), ("n", i64),
                 ("sign", f32), ("gscale", f32), ("reduction", i32), ("accumulate", i32)]
-    KIND = OP_WGAN
+    KIND, FN = OP_WGAN, "gode_wgan_logits"
 
 
-class ChstatsOp(C.Structure):
+class ChstatsOp(_Op):
     _fields_ = [("x", ptr), ("stats", ptr), ("xs", i64 * 4), ("N", i32), ("H", i32), ("W", i32), ("C", i32), ("rows", i32),
                 ("pad_", i32)]
-    KIND = OP_CHSTATS
+    KIND, FN = OP_CHSTATS, "gode_chstats"
 
 
-class CbnEmbedOp(C.Structure):
+class CbnEmbedOp(_Op):
     _fields_ = [("cond", ptr), ("W", ptr), ("b", ptr), ("gb", ptr), ("N", i32), ("K", i32), ("C2", i32), ("pad_", i32)]
-    KIND = OP_CBN_EMBED
+    KIND, FN = OP_CBN_EMBED, "gode_cbn_embed"
 
 
-class CbnEmbedBwdOp(C.Structure):
+class CbnEmbedBwdOp(_Op):
     _fields_ = [("cond", ptr), ("W", ptr), ("dgb", ptr), ("dW", ptr), ("db", ptr), ("dcond", ptr), ("N", i32), ("K", i32),
                 ("C2", i32), ("pad_", i32)]
-    KIND = OP_CBN_EMBED_BWD
+    KIND, FN = OP_CBN_EMBED_BWD, "gode_cbn_embed_bwd"
 
 
-class CbnApplyOp(C.Structure):
+class CbnApplyOp(_Op):
     _fields_ = [("src", ptr), ("bias", ptr), ("mean", ptr), ("invstd", ptr), ("gb", ptr), ("out", ptr), ("ss", i64 * 4),
                 ("N", i32), ("H", i32), ("W", i32), ("C", i32), ("f", i32), ("act", i32)]
-    KIND = OP_CBN_APPLY
+    KIND, FN = OP_CBN_APPLY, "gode_cbn_apply"
 
 
-class CbnBwdOp(C.Structure):
+class CbnBwdOp(_Op):
     _fields_ = [("g_a", ptr), ("a", ptr), ("src", ptr), ("bias", ptr), ("mean", ptr), ("invstd", ptr), ("gb", ptr),
                 ("gadd", ptr), ("work", ptr), ("dgb", ptr), ("dbias", ptr), ("g_out", ptr), ("ss", i64 * 4), ("gos", i64 * 4),
                 ("N", i32), ("H", i32), ("W", i32), ("C", i32), ("f", i32), ("act", i32), ("eval_mode", i32), ("pad_", i32)]
-    KIND = OP_CBN_BWD
+    KIND, FN = OP_CBN_BWD, "gode_cbn_bwd"
 
 
-class GresOutOp(C.Structure):
+class GresOutOp(_Op):
     _fields_ = [("main", ptr), ("sc", ptr), ("b_main", ptr), ("b_sc", ptr), ("y", ptr), ("N", i32), ("H", i32), ("W", i32),
                 ("C", i32), ("f", i32), ("down", i32)]
-    KIND = OP_GRES_OUT
+    KIND, FN = OP_GRES_OUT, "gode_gres_out"
 
 
-class GresOutBwdOp(C.Structure):
+class GresOutBwdOp(_Op):
     _fields_ = [("g_y", ptr), ("g_sc", ptr), ("g_main", ptr), ("db", ptr), ("work", ptr), ("gys", i64 * 4), ("N", i32),
                 ("H", i32), ("W", i32), ("C", i32), ("f", i32), ("down", i32)]
-    KIND = OP_GRES_OUT_BWD
+    KIND, FN = OP_GRES_OUT_BWD, "gode_gres_out_bwd"
 
 
-class SnOp(C.Structure):
+class SnOp(_Op):
     _fields_ = [("wbar", ptr), ("u", ptr), ("v", ptr), ("wout", ptr), ("sigma", ptr), ("work", ptr), ("h", i32), ("w", i32)]
-    KIND = OP_SN_FWD
+    KIND, FN = OP_SN_FWD, "gode_sn_fwd"
 
 
-class SnBwdOp(C.Structure):
+class SnBwdOp(_Op):
     _fields_ = [("G", ptr), ("wbar", ptr), ("u", ptr), ("v", ptr), ("sigma", ptr), ("dwbar", ptr), ("work", ptr), ("h", i32),
                 ("w", i32)]
-    KIND = OP_SN_BWD
+    KIND, FN = OP_SN_BWD, "gode_sn_bwd"
 
 
 class AdamNoiseTensor(C.Structure):
     _fields_ = [("p", ptr), ("g", ptr), ("m", ptr), ("v", ptr), ("n", i64), ("noise_off", i64)]
 
 
-class AdamOp(C.Structure):
+class AdamOp(_Op):
     _fields_ = [("p", ptr), ("g", ptr), ("m", ptr), ("v", ptr), ("n", i64), ("lr", f32), ("beta1", f32),
                 ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("gscale", f32), ("step", i32), ("pad_", i32)]
-    KIND = OP_ADAM
+    KIND, FN = OP_ADAM, "gode_adam_l2"
 
 
 class PackOp(C.Structure):
+    """Not an _Op: it has no (op*, stream) entry point; gode_run batches runs of it, run_one calls gode_pack_weights."""
     _fields_ = [("g", ConvGeom), ("dir", i32), ("co_canon", i32), ("w", ptr), ("wpack", ptr), ("co_perm", ptr)]
     KIND = OP_PACK
 
 
-_STRUCTS = {0: ConvGeom, OP_IGEMM: IgemmOp, OP_WGRAD: WgradOp, OP_BN_FINALIZE: BnFinalizeOp, OP_BN_BWD: BnBwdOp,
-            OP_ODE_FWD: OdeFwdOp, OP_ODE_BWD: OdeBwdOp, OP_BCE: BceOp, OP_ADAM: AdamOp, OP_PACK: PackOp,
-            OP_ODERNN_FWD: OdeRnnFwdOp, OP_ODERNN_BWD: OdeRnnBwdOp, OP_BN_APPLY: BnApplyOp, OP_COL2IM: Col2imOp,
-            OP_SDE_FWD: SdeFwdOp, OP_SDE_BWD: SdeBwdOp, OP_CDE_FWD: CdeFwdOp, OP_CDE_BWD: CdeBwdOp, OP_WGAN: WganOp,
-            OP_GRU_FWD: GruFwdOp, OP_GRU_BWD: GruBwdOp, OP_DNOISE: DnoiseOp, OP_CATEG: CategOp, OP_CE: CeOp, REC_ADAM_NOISE: AdamNoiseTensor,
-            OP_CHSTATS: ChstatsOp, OP_CBN_EMBED: CbnEmbedOp, OP_CBN_EMBED_BWD: CbnEmbedBwdOp, OP_CBN_APPLY: CbnApplyOp,
-            OP_CBN_BWD: CbnBwdOp, OP_GRES_OUT: GresOutOp, OP_GRES_OUT_BWD: GresOutBwdOp, OP_SN_FWD: SnOp, OP_SN_BWD: SnBwdOp}
+_OPS = _Op.__subclasses__()
+_STRUCTS = {0: ConvGeom, REC_ADAM_NOISE: AdamNoiseTensor, OP_PACK: PackOp, **{st.KIND: st for st in _OPS}}
 
-EXPORTS = ["gode_igemm", "gode_igemm_stats_rows", "gode_igemm_stats_rows0", "gode_igemm_stats_segments", "gode_igemm_model_cycles", "gode_igemm_work_size", "gode_pack_size", "gode_pack_weights", "gode_wgrad",
-           "gode_wgrad_work_size", "gode_wgrad_auto_splits", "gode_bn_finalize", "gode_bn_bwd",
-           "gode_bn_bwd_work_size", "gode_bn_apply", "gode_col2im", "gode_ode_fwd", "gode_ode_bwd", "gode_ode_fwd_multi", "gode_ode_bwd_multi", "gode_ode_bwd_work_size", "gode_odernn_fwd",
-           "gode_odernn_bwd", "gode_odernn_bwd_work_size", "gode_odernn_sync_size", "gode_odernn_fwd_multi",
-           "gode_odernn_bwd_multi", "gode_sde_fwd", "gode_sde_bwd", "gode_sde_bwd_work_size", "gode_cde_fwd", "gode_cde_bwd", "gode_cde_sync_size", "gode_cde_state_size", "gode_cde_bwd_work_size", "gode_gru_fwd", "gode_gru_bwd", "gode_gru_fwd_multi",
-           "gode_gru_bwd_multi", "gode_gru_bwd_work_size", "gode_bce_logits",
-           "gode_wgan_logits", "gode_adam_l2", "gode_adam_multi", "gode_adam_multi_dev", "gode_adam_noise_multi",
-           "gode_adam_noise_multi_dev", "gode_param_noise", "gode_ode_step", "gode_ode_step_chunks", "gode_axpy_multi", "gode_dnoise", "gode_dnoise_normals", "gode_categ_onehot", "gode_ce_logits", "gode_chstats", "gode_chstats_rows", "gode_cbn_embed", "gode_cbn_embed_bwd", "gode_cbn_apply", "gode_cbn_bwd", "gode_cbn_bwd_work_size", "gode_gres_out", "gode_gres_out_bwd", "gode_gres_out_bwd_work_size", "gode_sn_fwd", "gode_sn_bwd", "gode_scale", "gode_run", "gode_version", "gode_sizeof"]
+# every entry point that is not an op's FN: name -> (argtypes, restype)
+_PROTOS = {
+    "gode_igemm_stats_rows": ([ptr], cint),
+    "gode_igemm_stats_rows0": ([ptr], cint),
+    "gode_igemm_stats_segments": ([ptr, i32, ptr], cint),
+    "gode_igemm_model_cycles": ([ptr], C.c_double),
+    "gode_igemm_work_size": ([ptr], i64),
+    "gode_pack_size": ([ptr, cint], i64),
+    "gode_pack_weights": ([ptr, cint, ptr, ptr, ptr, i32, ptr], cint),
+    "gode_wgrad_work_size": ([ptr], i64),
+    "gode_wgrad_auto_splits": ([ptr], cint),
+    "gode_bn_bwd_work_size": ([i64, i32], i64),
+    "gode_ode_bwd_work_size": ([i32], i64),
+    "gode_odernn_bwd_work_size": ([i32], i64),
+    "gode_odernn_sync_size": ([i32], i64),
+    "gode_sde_bwd_work_size": ([i32], i64),
+    "gode_cde_sync_size": ([i32], i64),
+    "gode_cde_state_size": ([i32, i32], i64),
+    "gode_cde_bwd_work_size": ([i32], i64),
+    "gode_gru_bwd_work_size": ([i32], i64),
+    "gode_ode_fwd_multi": ([ptr, i32, ptr], cint),
+    "gode_ode_bwd_multi": ([ptr, i32, ptr], cint),
+    "gode_odernn_fwd_multi": ([ptr, i32, ptr], cint),
+    "gode_odernn_bwd_multi": ([ptr, i32, ptr], cint),
+    "gode_gru_fwd_multi": ([ptr, i32, ptr], cint),
+    "gode_gru_bwd_multi": ([ptr, i32, ptr], cint),
+    "gode_chstats_rows": ([i64], cint),
+    "gode_cbn_bwd_work_size": ([i32, i32, i32, i32], i64),
+    "gode_gres_out_bwd_work_size": ([i32, i32, i32, i32, i32, i32], i64),
+    "gode_scale": ([ptr, ptr, i64, f32, cint, ptr], cint),
+    "gode_adam_multi": ([ptr, i32, i64, f32, f32, f32, f32, f32, f32, i32, ptr], cint),
+    "gode_adam_multi_dev": ([ptr, i32, i64, f32, f32, f32, f32, f32, ptr, ptr], cint),
+    "gode_adam_noise_multi": ([ptr, i32, i64, f32, f32, f32, f32, f32, f32, i32, u64, u32, u32, f32, ptr], cint),
+    "gode_adam_noise_multi_dev": ([ptr, i32, i64, f32, f32, f32, f32, f32, ptr, u64, u32, f32, ptr], cint),
+    "gode_param_noise": ([ptr, i64, u64, u32, u32, i64, f32, i32, ptr], cint),
+    "gode_dnoise_normals": ([ptr, i64, u64, u32, u32, u32, i64, i32, ptr], cint),
+    "gode_ode_step_chunks": ([ptr, i64], i64),
+    "gode_ode_step": ([ptr, i32, i64, i32, f32, f32, f32, f32, f32, ptr, ptr], cint),
+    "gode_axpy_multi": ([ptr, i32, i64, f32, ptr, ptr, f32, ptr, ptr, ptr], cint),
+    "gode_run": ([ptr, ptr, i32, ptr], cint),
+    "gode_version": (None, cint),
+    "gode_sizeof": ([cint], cint),
+}
+
+EXPORTS = [st.FN for st in _OPS] + list(_PROTOS)
 
 _lib = None
 
@@ -303,72 +342,11 @@ def lib():
     for name in EXPORTS:
         if not hasattr(L, name):
             raise RuntimeError(f"libgode.so does not export {name}")
-    L.gode_sizeof.argtypes = [C.c_int]
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = _PROTOS.get(name, ([ptr, ptr], cint))     # an op's FN: (const op*, hipStream_t)
     for kind, st in _STRUCTS.items():
         if L.gode_sizeof(kind) != C.sizeof(st):
             raise RuntimeError(f"ABI mismatch for op kind {kind}: C {L.gode_sizeof(kind)} != ctypes {C.sizeof(st)}")
-    for name in ("gode_igemm", "gode_wgrad", "gode_bn_finalize", "gode_bn_bwd", "gode_ode_fwd", "gode_ode_bwd",
-                 "gode_bce_logits", "gode_adam_l2", "gode_odernn_fwd", "gode_odernn_bwd", "gode_bn_apply", "gode_col2im",
-                 "gode_sde_fwd", "gode_sde_bwd", "gode_cde_fwd", "gode_cde_bwd", "gode_wgan_logits", "gode_gru_fwd",
-                 "gode_gru_bwd", "gode_dnoise", "gode_categ_onehot", "gode_ce_logits", "gode_chstats", "gode_cbn_embed",
-                 "gode_cbn_embed_bwd", "gode_cbn_apply", "gode_cbn_bwd", "gode_gres_out", "gode_gres_out_bwd", "gode_sn_fwd",
-                 "gode_sn_bwd"):
-        getattr(L, name).argtypes = [ptr, ptr]
-        getattr(L, name).restype = C.c_int
-    L.gode_igemm_stats_rows.argtypes = [ptr]
-    L.gode_igemm_stats_rows0.argtypes = [ptr]
-    L.gode_igemm_stats_segments.argtypes = [ptr, i32, ptr]
-    L.gode_igemm_model_cycles.argtypes = [ptr]
-    L.gode_igemm_model_cycles.restype = C.c_double
-    L.gode_igemm_work_size.argtypes = [ptr]
-    L.gode_igemm_work_size.restype = i64
-    L.gode_pack_size.argtypes = [ptr, C.c_int]
-    L.gode_pack_size.restype = i64
-    L.gode_pack_weights.argtypes = [ptr, C.c_int, ptr, ptr, ptr, i32, ptr]
-    L.gode_wgrad_work_size.argtypes = [ptr]
-    L.gode_wgrad_work_size.restype = i64
-    L.gode_wgrad_auto_splits.argtypes = [ptr]
-    L.gode_bn_bwd_work_size.argtypes = [i64, i32]
-    L.gode_bn_bwd_work_size.restype = i64
-    L.gode_ode_bwd_work_size.argtypes = [i32]
-    L.gode_ode_bwd_work_size.restype = i64
-    L.gode_odernn_bwd_work_size.argtypes = [i32]
-    L.gode_odernn_bwd_work_size.restype = i64
-    L.gode_sde_bwd_work_size.argtypes = [i32]
-    L.gode_sde_bwd_work_size.restype = i64
-    for name in ("gode_cde_sync_size", "gode_cde_bwd_work_size"):
-        getattr(L, name).argtypes = [i32]
-        getattr(L, name).restype = i64
-    L.gode_cde_state_size.argtypes = [i32, i32]
-    L.gode_cde_state_size.restype = i64
-    L.gode_odernn_sync_size.argtypes = [i32]
-    L.gode_odernn_sync_size.restype = i64
-    L.gode_ode_fwd_multi.argtypes = [ptr, i32, ptr]
-    L.gode_ode_bwd_multi.argtypes = [ptr, i32, ptr]
-    L.gode_odernn_fwd_multi.argtypes = [ptr, i32, ptr]
-    L.gode_odernn_bwd_multi.argtypes = [ptr, i32, ptr]
-    L.gode_gru_fwd_multi.argtypes = [ptr, i32, ptr]
-    L.gode_gru_bwd_multi.argtypes = [ptr, i32, ptr]
-    L.gode_gru_bwd_work_size.argtypes = [i32]
-    L.gode_gru_bwd_work_size.restype = i64
-    L.gode_chstats_rows.argtypes = [i64]
-    L.gode_cbn_bwd_work_size.argtypes = [i32, i32, i32, i32]
-    L.gode_cbn_bwd_work_size.restype = i64
-    L.gode_gres_out_bwd_work_size.argtypes = [i32, i32, i32, i32, i32, i32]
-    L.gode_gres_out_bwd_work_size.restype = i64
-    L.gode_scale.argtypes = [ptr, ptr, i64, f32, C.c_int, ptr]
-    L.gode_adam_multi.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, f32, i32, ptr]
-    L.gode_adam_multi_dev.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, ptr, ptr]
-    u32, u64 = C.c_uint32, C.c_uint64
-    L.gode_adam_noise_multi.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, f32, i32, u64, u32, u32, f32, ptr]
-    L.gode_adam_noise_multi_dev.argtypes = [ptr, i32, i64, f32, f32, f32, f32, f32, ptr, u64, u32, f32, ptr]
-    L.gode_param_noise.argtypes = [ptr, i64, u64, u32, u32, i64, f32, i32, ptr]
-    L.gode_dnoise_normals.argtypes = [ptr, i64, u64, u32, u32, u32, i64, i32, ptr]
-    L.gode_ode_step_chunks.argtypes = [ptr, i64]
-    L.gode_ode_step_chunks.restype = i64
-    L.gode_ode_step.argtypes = [ptr, i32, i64, i32, f32, f32, f32, f32, f32, ptr, ptr]
-    L.gode_axpy_multi.argtypes = [ptr, i32, i64, f32, ptr, ptr, f32, ptr, ptr, ptr]
-    L.gode_run.argtypes = [ptr, ptr, i32, ptr]
     _lib = L
     return L
 
@@ -429,14 +407,4 @@ def run_one(op, stream):
 
 
 def _run_one(op, stream):
-    fn = {OP_IGEMM: "gode_igemm", OP_WGRAD: "gode_wgrad", OP_BN_FINALIZE: "gode_bn_finalize", OP_BN_BWD: "gode_bn_bwd",
-          OP_ODE_FWD: "gode_ode_fwd", OP_ODE_BWD: "gode_ode_bwd", OP_BCE: "gode_bce_logits",
-          OP_ADAM: "gode_adam_l2", OP_ODERNN_FWD: "gode_odernn_fwd", OP_ODERNN_BWD: "gode_odernn_bwd",
-          OP_BN_APPLY: "gode_bn_apply", OP_COL2IM: "gode_col2im", OP_SDE_FWD: "gode_sde_fwd",
-          OP_SDE_BWD: "gode_sde_bwd", OP_CDE_FWD: "gode_cde_fwd", OP_CDE_BWD: "gode_cde_bwd",
-          OP_WGAN: "gode_wgan_logits", OP_GRU_FWD: "gode_gru_fwd", OP_GRU_BWD: "gode_gru_bwd",
-          OP_DNOISE: "gode_dnoise", OP_CATEG: "gode_categ_onehot", OP_CE: "gode_ce_logits", OP_CHSTATS: "gode_chstats",
-          OP_CBN_EMBED: "gode_cbn_embed", OP_CBN_EMBED_BWD: "gode_cbn_embed_bwd", OP_CBN_APPLY: "gode_cbn_apply",
-          OP_CBN_BWD: "gode_cbn_bwd", OP_GRES_OUT: "gode_gres_out", OP_GRES_OUT_BWD: "gode_gres_out_bwd",
-          OP_SN_FWD: "gode_sn_fwd", OP_SN_BWD: "gode_sn_bwd"}[op.KIND]
-    check(getattr(lib(), fn)(C.byref(op), stream), fn)
+    check(getattr(lib(), op.FN)(C.byref(op), stream), op.FN)

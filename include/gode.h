@@ -660,14 +660,46 @@ int gode_sn_bwd(const gode_sn_bwd_op* op, void* stream);
 /* out[i] = a[i]*alpha (+ out[i] if accumulate); small utility for gradient bucket handling */
 int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulate, void* stream);
 
-/* ---- program runner: executes n ops back to back on the stream (one host call per network pass) -------------*/
-enum { GODE_OP_IGEMM = 1, GODE_OP_WGRAD = 2, GODE_OP_BN_FINALIZE = 3, GODE_OP_BN_BWD = 4, GODE_OP_ODE_FWD = 5,
-       GODE_OP_ODE_BWD = 6, GODE_OP_BCE = 7, GODE_OP_ADAM = 8, GODE_OP_PACK = 9, GODE_OP_ODERNN_FWD = 10,
-       GODE_OP_ODERNN_BWD = 11, GODE_OP_BN_APPLY = 12, GODE_OP_COL2IM = 13, GODE_OP_SDE_FWD = 14,
-       GODE_OP_SDE_BWD = 15, GODE_OP_CDE_FWD = 16, GODE_OP_CDE_BWD = 17, GODE_OP_WGAN = 18,
-       GODE_OP_GRU_FWD = 19, GODE_OP_GRU_BWD = 20, GODE_OP_DNOISE = 21, GODE_OP_CATEG = 22, GODE_OP_CE = 23,
-       GODE_OP_CHSTATS = 24, GODE_OP_CBN_EMBED = 25, GODE_OP_CBN_EMBED_BWD = 26, GODE_OP_CBN_APPLY = 27,
-       GODE_OP_CBN_BWD = 28, GODE_OP_GRES_OUT = 29, GODE_OP_GRES_OUT_BWD = 30, GODE_OP_SN_FWD = 31, GODE_OP_SN_BWD = 32 };
+/* ---- program runner: executes n ops back to back on the stream (one host call per network pass) -------------
+ * The op kinds, one row each: X(NAME, GODE_OP_NAME's value, op struct, its `int fn(const op*, void* stream)`).  The enum
+ * below, gode_sizeof and gode_run's dispatch expand from this table, and scripts/gen_binding_stub.py reads it. */
+#define GODE_OPS(X) \
+  X(IGEMM,          1, gode_igemm_op,         gode_igemm)         \
+  X(WGRAD,          2, gode_wgrad_op,         gode_wgrad)         \
+  X(BN_FINALIZE,    3, gode_bn_finalize_op,   gode_bn_finalize)   \
+  X(BN_BWD,         4, gode_bn_bwd_op,        gode_bn_bwd)        \
+  X(ODE_FWD,        5, gode_ode_fwd_op,       gode_ode_fwd)       \
+  X(ODE_BWD,        6, gode_ode_bwd_op,       gode_ode_bwd)       \
+  X(BCE,            7, gode_bce_op,           gode_bce_logits)    \
+  X(ADAM,           8, gode_adam_op,          gode_adam_l2)       \
+  X(ODERNN_FWD,    10, gode_odernn_fwd_op,    gode_odernn_fwd)    \
+  X(ODERNN_BWD,    11, gode_odernn_bwd_op,    gode_odernn_bwd)    \
+  X(BN_APPLY,      12, gode_bn_apply_op,      gode_bn_apply)      \
+  X(COL2IM,        13, gode_col2im_op,        gode_col2im)        \
+  X(SDE_FWD,       14, gode_sde_fwd_op,       gode_sde_fwd)       \
+  X(SDE_BWD,       15, gode_sde_bwd_op,       gode_sde_bwd)       \
+  X(CDE_FWD,       16, gode_cde_fwd_op,       gode_cde_fwd)       \
+  X(CDE_BWD,       17, gode_cde_bwd_op,       gode_cde_bwd)       \
+  X(WGAN,          18, gode_wgan_op,          gode_wgan_logits)   \
+  X(GRU_FWD,       19, gode_gru_fwd_op,       gode_gru_fwd)       \
+  X(GRU_BWD,       20, gode_gru_bwd_op,       gode_gru_bwd)       \
+  X(DNOISE,        21, gode_dnoise_op,        gode_dnoise)        \
+  X(CATEG,         22, gode_categ_op,         gode_categ_onehot)  \
+  X(CE,            23, gode_ce_op,            gode_ce_logits)     \
+  X(CHSTATS,       24, gode_chstats_op,       gode_chstats)       \
+  X(CBN_EMBED,     25, gode_cbn_embed_op,     gode_cbn_embed)     \
+  X(CBN_EMBED_BWD, 26, gode_cbn_embed_bwd_op, gode_cbn_embed_bwd) \
+  X(CBN_APPLY,     27, gode_cbn_apply_op,     gode_cbn_apply)     \
+  X(CBN_BWD,       28, gode_cbn_bwd_op,       gode_cbn_bwd)       \
+  X(GRES_OUT,      29, gode_gres_out_op,      gode_gres_out)      \
+  X(GRES_OUT_BWD,  30, gode_gres_out_bwd_op,  gode_gres_out_bwd)  \
+  X(SN_FWD,        31, gode_sn_op,            gode_sn_fwd)        \
+  X(SN_BWD,        32, gode_sn_bwd_op,        gode_sn_bwd)
+/* GODE_OP_PACK stays outside the table: it has no (op*, stream) entry point, gode_run sends every run of consecutive pack
+ * ops out as batched launches instead. */
+#define GODE_ENUM_ROW_(name, value, op_t, fn) GODE_OP_##name = value,
+enum { GODE_OPS(GODE_ENUM_ROW_) GODE_OP_PACK = 9 };
+#undef GODE_ENUM_ROW_
 typedef struct gode_pack_op {
   gode_conv_geom g; int32_t dir, co_canon; const float* w; float* wpack; const int32_t* co_perm;
 } gode_pack_op;

@@ -1,6 +1,7 @@
 """Generates the ctypes binding stub of INTEGRATION.md section 2 from include/gode.h, so the document cannot drift
 from the header: every `typedef struct` becomes a ctypes.Structure with the same fields in the same order, every
-`GODE_OP_*` kind is listed with its struct, and the stub checks itself against gode_sizeof() when executed.
+`GODE_OP_*` kind of the header's GODE_OPS table is listed with its struct and its entry point gets its prototype, and the
+stub checks itself against gode_sizeof() when executed.
 
   python scripts/gen_binding_stub.py            # prints the stub
   python scripts/gen_binding_stub.py --write    # rewrites the block between the markers in INTEGRATION.md
@@ -51,25 +52,28 @@ def parse_structs(text):
     return out
 
 
+def parse_ops(text):
+    """The rows of the header's GODE_OPS table: (NAME, value, op struct, entry point)."""
+    table = re.search(r"#define\s+GODE_OPS\(X\)(.*?[^\\])\n", text, flags=re.S).group(1)
+    return [(n, int(v), st, fn) for n, v, st, fn in re.findall(r"X\(\s*(\w+)\s*,\s*(\d+)\s*,\s*(\w+)\s*,\s*(\w+)\s*\)", table)]
+
+
 def parse_kinds(text):
-    m = re.search(r"enum\s*\{\s*(GODE_OP_IGEMM.*?)\}", text, flags=re.S)
-    return [(k, int(v)) for k, v in re.findall(r"(GODE_OP_\w+)\s*=\s*(\d+)", m.group(1))]
+    """Every GODE_OP_* kind with its struct, in numeric order: the table rows plus PACK, which the header keeps out of the
+    table (it has no entry point of the common form)."""
+    pack = int(re.search(r"GODE_OP_PACK\s*=\s*(\d+)", text).group(1))
+    return sorted([(v, st) for _, v, st, _ in parse_ops(text)] + [(pack, "gode_pack_op")])
 
 
-KIND_STRUCT = {"GODE_OP_IGEMM": "gode_igemm_op", "GODE_OP_WGRAD": "gode_wgrad_op",
-               "GODE_OP_BN_FINALIZE": "gode_bn_finalize_op", "GODE_OP_BN_BWD": "gode_bn_bwd_op",
-               "GODE_OP_ODE_FWD": "gode_ode_fwd_op", "GODE_OP_ODE_BWD": "gode_ode_bwd_op", "GODE_OP_BCE": "gode_bce_op",
-               "GODE_OP_ADAM": "gode_adam_op", "GODE_OP_PACK": "gode_pack_op", "GODE_OP_ODERNN_FWD": "gode_odernn_fwd_op",
-               "GODE_OP_ODERNN_BWD": "gode_odernn_bwd_op", "GODE_OP_BN_APPLY": "gode_bn_apply_op",
-               "GODE_OP_COL2IM": "gode_col2im_op", "GODE_OP_SDE_FWD": "gode_sde_fwd_op",
-               "GODE_OP_SDE_BWD": "gode_sde_bwd_op", "GODE_OP_CDE_FWD": "gode_cde_fwd_op",
-               "GODE_OP_CDE_BWD": "gode_cde_bwd_op", "GODE_OP_WGAN": "gode_wgan_op",
-               "GODE_OP_GRU_FWD": "gode_gru_fwd_op", "GODE_OP_GRU_BWD": "gode_gru_bwd_op",
-               "GODE_OP_DNOISE": "gode_dnoise_op", "GODE_OP_CATEG": "gode_categ_op",
-               "GODE_OP_CE": "gode_ce_op", "GODE_OP_CHSTATS": "gode_chstats_op", "GODE_OP_CBN_EMBED": "gode_cbn_embed_op",
-               "GODE_OP_CBN_EMBED_BWD": "gode_cbn_embed_bwd_op", "GODE_OP_CBN_APPLY": "gode_cbn_apply_op",
-               "GODE_OP_CBN_BWD": "gode_cbn_bwd_op", "GODE_OP_GRES_OUT": "gode_gres_out_op",
-               "GODE_OP_GRES_OUT_BWD": "gode_gres_out_bwd_op", "GODE_OP_SN_FWD": "gode_sn_op", "GODE_OP_SN_BWD": "gode_sn_bwd_op"}
+def _wrap(head, items, indent, tail):
+    """head + the comma-separated items + tail, wrapped at ~110 columns."""
+    row, rows = head, []
+    for item in items:
+        if len(row) + len(item) + 2 > 112:
+            rows.append(row.rstrip())
+            row = indent
+        row += item + ", "
+    return rows + [row.rstrip(", ") + tail]
 
 
 def generate():
@@ -80,32 +84,19 @@ def generate():
     lines = ["import ctypes as C", "", "i32, i64, f32, ptr = C.c_int32, C.c_int64, C.c_float, C.c_void_p", ""]
     for name, fields in structs:
         lines.append(f"class {name}(C.Structure):")
-        body = ", ".join(f'("{f}", {t})' for f, t in fields)
-        # wrap at ~110 columns
-        row, rows = "    _fields_ = [", []
-        for item in body.split("), ("):
-            item = item if item.startswith("(") else "(" + item
-            item = item if item.endswith(")") else item + ")"
-            if len(row) + len(item) + 2 > 112:
-                rows.append(row.rstrip())
-                row = "                "
-            row += item + ", "
-        rows.append(row.rstrip(", ") + "]")
-        lines += rows + [""]
-    lines.append("KINDS = {0: gode_conv_geom, -1: gode_adam_noise_tensor, " + ", ".join(f"{v}: {KIND_STRUCT[k]}" for k, v in kinds) + "}")
+        lines += _wrap("    _fields_ = [", [f'("{f}", {t})' for f, t in fields], " " * 16, "]") + [""]
+    lines.append("KINDS = {0: gode_conv_geom, -1: gode_adam_noise_tensor, " + ", ".join(f"{v}: {st}" for v, st in kinds) + "}")
     lines += ["", "",
               "def load(path=\"gan-ode_amd/lib/libgode.so\"):",
               "    lib = C.CDLL(path)",
               "    lib.gode_sizeof.argtypes = [C.c_int]",
               "    for kind, st in KINDS.items():            # the mirror must match the compiled ABI, field for field",
-              "        assert lib.gode_sizeof(kind) == C.sizeof(st), (kind, st.__name__)",
-              "    for fn in (\"gode_igemm\", \"gode_wgrad\", \"gode_bn_finalize\", \"gode_bn_bwd\", \"gode_bn_apply\", \"gode_col2im\", \"gode_ode_fwd\",",
-              "               \"gode_ode_bwd\", \"gode_odernn_fwd\", \"gode_odernn_bwd\", \"gode_bce_logits\", \"gode_wgan_logits\",",
-              "               \"gode_adam_l2\"):",
-              "        getattr(lib, fn).argtypes = [ptr, ptr]          # (const op struct*, hipStream_t)",
+              "        assert lib.gode_sizeof(kind) == C.sizeof(st), (kind, st.__name__)"]
+    lines += _wrap("    for fn in (", [f'"{fn}"' for _, _, _, fn in parse_ops(text)], " " * 15, "):")
+    lines += ["        getattr(lib, fn).argtypes = [ptr, ptr]          # (const op struct*, hipStream_t)",
               "        getattr(lib, fn).restype = C.c_int              # 0 ok, <0 GODE_E_*, >0 hipError_t",
               "    return lib"]
-    missing = [s for s in KIND_STRUCT.values() if s not in names]
+    missing = [st for _, st in kinds if st not in names]
     assert not missing, missing
     return "\n".join(lines) + "\n"
 

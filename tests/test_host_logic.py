@@ -2,6 +2,7 @@
 initial weights, same state_dict keys), refusal of CPU tensors (no fallback path), the host RNG / row-selection
 contract of sample_images, and the data-parallel gradient bucket over gloo with two ranks."""
 import ctypes as C
+import importlib.util
 import os
 import re
 
@@ -27,6 +28,41 @@ def test_library_loads_and_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert declared == set(L.EXPORTS)
+
+
+def _op_table():
+    """The rows (NAME, value, struct, fn) of gode.h's GODE_OPS table, read with the binding-stub generator's parser."""
+    spec = importlib.util.spec_from_file_location("_stubgen", os.path.join(REPO, "scripts", "gen_binding_stub.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    rows = gen.parse_ops(open(gen.HEADER).read())
+    assert len(rows) >= 31 and len({v for _, v, _, _ in rows}) == len(rows), rows
+    return rows
+
+
+def test_op_table_of_the_header_matches_the_ctypes_classes_and_gode_sizeof():
+    lib = L.lib()
+    rows = _op_table()
+    for name, value, _, fn in rows:
+        assert getattr(L, "OP_" + name) == value, name
+        assert L._STRUCTS[value].KIND == value, name
+        assert L._STRUCTS[value].FN == fn, name
+        assert lib.gode_sizeof(value) == C.sizeof(L._STRUCTS[value]), name
+    assert {v for _, v, _, _ in rows} | {0, -1, L.OP_PACK} == set(L._STRUCTS)
+
+
+def test_runner_dispatches_every_table_row_to_its_entry_point():
+    """A zeroed op is an argument error (GODE_E_ARG, raised before any HIP call) from its own entry point, and gode_run
+    reports the same code with the op index folded in: -(1 * 1000 + 0)."""
+    lib = L.lib()
+    for name, value, _, fn in _op_table():
+        op = L._STRUCTS[value]()
+        assert getattr(lib, fn)(C.byref(op), None) == -1, name
+        assert lib.gode_run((L.i32 * 1)(value), (L.ptr * 1)(C.addressof(op)), 1, None) == -1000, name
+    op = L.IgemmOp()
+    assert lib.gode_run((L.i32 * 1)(99), (L.ptr * 1)(C.addressof(op)), 1, None) == -3      # GODE_E_KIND
+    assert lib.gode_sizeof(99) == -3
+    assert lib.gode_sizeof(9) == 104
 
 
 def test_argument_errors_are_reported_not_crashed():
