@@ -14,6 +14,7 @@ cint, u32, u64 = C.c_int, C.c_uint32, C.c_uint64
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH_OUT = 0, 1, 2, 3
 EPI_RAW, EPI_TANH = 0, 1
 FPROP, DGRAD = 0, 1
+PACK_BORDER = 0x100          # or'ed into a pack's dir: the pack an IgemmOp with border=1 reads
 OP_IGEMM, OP_WGRAD, OP_BN_FINALIZE, OP_BN_BWD, OP_ODE_FWD, OP_ODE_BWD, OP_BCE, OP_ADAM, OP_PACK = range(1, 10)
 OP_ODERNN_FWD, OP_ODERNN_BWD, OP_BN_APPLY, OP_COL2IM = 10, 11, 12, 13
 OP_SDE_FWD, OP_SDE_BWD = 14, 15
@@ -48,7 +49,7 @@ class _Op(C.Structure):
 class IgemmOp(_Op):
     _fields_ = [("g", ConvGeom), ("dir", i32), ("act", i32), ("epilogue", i32), ("tile", i32), ("src", ptr),
                 ("wpack", ptr), ("out", ptr), ("scale", ptr), ("shift", ptr), ("stats", ptr), ("gs", i64 * 5),
-                ("work", ptr), ("groups", i32), ("pad3_", i32)]
+                ("work", ptr), ("groups", i32), ("border", i32)]
     KIND, FN = OP_IGEMM, "gode_igemm"
 
 

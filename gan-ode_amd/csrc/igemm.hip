@@ -38,6 +38,10 @@ struct IgemmArgs {
   int32_t out_numel;
   int32_t stats_rows;   // number of partial-statistics rows of the launch (the stats buffer is [2][ncols][stats_rows])
   uint32_t src_bytes, w_bytes;   // LDS-DMA kernels address both operands as raw buffers (32-bit byte offsets): their extents
+  // FAST kernel on a border-split table (G.border): its sub-phases differ in rows AND in K, so the 1-D grid holds exactly the
+  // live tiles, sub-phase after sub-phase (longest K first): tile0[i] = first workgroup of sub-phase i, tile0[nphase] = grid
+  int32_t ntab;
+  int32_t tile0[GODE_MAX_PHASES + 1];
 };
 
 // Workgroups are dealt round-robin to the 8 XCDs in linear id order (id and id+8 share an XCD and its 4 MiB L2);
@@ -47,6 +51,20 @@ struct IgemmArgs {
 // shared by neighbouring output rows hit the same L2; the default), 0 is the plain order.  Every mode is a bijection
 // of [0, MB*NB*nphase).
 __device__ __forceinline__ void igemm_block_id(const IgemmArgs& a, int& mblk, int& nblk, int& phase, int& split) {
+  if (a.ntab > 0) {
+    // border-split table: find the sub-phase (uniform scan of <= 16 entries); inside it runs of 8 m-blocks go one to each
+    // XCD with all their n-blocks back to back (the gathered rows are fetched once per XCD, as xcd_mode 2), the last
+    // (< 8) m-blocks in the plain order.  A bijection of the sub-phase's tiles whatever its m-block count.
+    const int id = blockIdx.x;
+    int p = 0;
+    while (p + 1 < a.ntab && id >= a.tile0[p + 1]) ++p;
+    const int t = id - a.tile0[p], NB = a.NB, mb = (a.tile0[p + 1] - a.tile0[p]) / NB;
+    const int grp = t / (8 * NB), r = t - grp * 8 * NB, rest = mb - grp * 8;
+    if (rest >= 8) { mblk = grp * 8 + (r & 7); nblk = r >> 3; }
+    else { mblk = grp * 8 + r % rest; nblk = r / rest; }
+    phase = p; split = 0;
+    return;
+  }
   const int MB = a.MB, NC = a.NB * a.G.nphase;
   split = blockIdx.x / (MB * NC);
   const int id = blockIdx.x - split * (MB * NC);
@@ -1123,9 +1141,59 @@ static void choose_fast(const gode_igemm_op* op, const IgemmGeom& G, int* tile_o
   }
 }
 
-static int prepare(const gode_igemm_op* op, IgemmArgs* A, int* tile, int* max_mblk, int* rows, SplitPlan* sp, int* rows0 = nullptr) {
+// The border-split table of an op that asks for it (gode_igemm_op.border), or false: FPROP, fullk, image groups, live-tap
+// (MODE 3) launches and shapes that do not split keep the plain table.
+static bool border_table(const gode_igemm_op* op, const IgemmGeom& G, IgemmGeom* B) {
+  if (!op->border || op->dir != GODE_DGRAD || op->groups == 2 || G.fullk || igemm_wants_tapskip(op, G)) return false;
+  return gode_build_igemm_geom_border(op->g, op->dir, B) == 0 && B->border != 0;
+}
+
+// Cost of a FAST launch over a border-split table.  Its tiles differ in length (interior / edge / corner sub-phases: K, K/2,
+// K/4 on a k4 s2 layer), the grid holds only live tiles and the longest come first, so the in-order dispatcher evens the
+// CUs out and the launch lasts the summed work over the 256 CUs -- once there are clearly more tiles than workgroup slots
+// and three or more workgroups per CU.  Measured on the three decoder layers at 512 rows (profiles/border_split_layers.md):
+//   128x64 tiles (1024 / 2048 / 4096 of them on 768 slots): 0.826 / 0.929 / 1.004 of the plain launch with the same tile
+//   where the summed work is 0.771 / 0.884 / 0.944 of it -- a loss of 1.071 / 1.050 / 1.064 against the sum: BORDER_LOSS;
+//   a tail term (a share of one longest tile) fitted to the same launches came out at 0.01: the shortest tiles go last;
+//   128x128 (512 tiles on 512 slots, 1024 on 512) and 256x128 (256 / 512 tiles on 256 slots): within 1 % of plain -- all
+//   tiles are resident in one or two rounds and some CU draws only long ones.  Those tiles are not offered.
+// Same per-tile constants as choose_fast.  Never a K split.
+#define BORDER_LOSS 1.06
+static void choose_border(const gode_igemm_op* op, const IgemmGeom& B, int* tile_out, double* cycles_out) {
+  (void)op;
+  static const int tiles[4] = {TILE_128x128, TILE_128x64, TILE_64x64, TILE_256x128};
+  double best = 1e300; int best_tile = TILE_128x64;
+  for (int ti = 0; ti < 4; ++ti) {
+    const int t = tiles[ti], bm = tile_bm(t), bn = tile_bn(t);
+    if (bn >= 2 * B.Ncols && bn > 32) continue;
+    if (t != TILE_128x64 && t != TILE_64x64) continue;      // (three or more workgroups per CU: see above)
+    const double cps = t == TILE_256x128 ? 8192.0 : (t == TILE_128x128 ? 4096.0 : (t == TILE_128x64 ? 2048.0 : 1024.0));
+    const int resident = t == TILE_256x128 ? 1 : (t == TILE_128x128 ? 2 : (t == TILE_128x64 ? 3 : 4));
+    const double eff2 = t == TILE_64x64 ? 0.70 : (t == TILE_256x128 ? 0.785 : 0.76);
+    int64_t ntiles = 0; int max_slabs = 0;
+    for (int i = 0; i < B.nphase; ++i) {
+      ntiles += (int64_t)gode_ceil_div(B.ph[i].M, bm) * gode_ceil_div(B.Ncols, bn);
+      if ((B.ph[i].K >> 5) > max_slabs) max_slabs = B.ph[i].K >> 5;
+    }
+    if (3 * ntiles < 4 * 256 * (int64_t)resident) continue;     // (measured down to 4/3 tiles per slot)
+    const double eff = (resident >= 2 || t == TILE_256x128) ? eff2 : 0.8 * eff2;
+    double work = 0;
+    for (int i = 0; i < B.nphase; ++i)
+      work += (double)gode_ceil_div(B.ph[i].M, bm) * gode_ceil_div(B.Ncols, bn) * (4000.0 + (B.ph[i].K >> 5) * cps / eff);
+    const double cyc = BORDER_LOSS * work / 256.0;
+    if (cyc < best) { best = cyc; best_tile = t; }
+  }
+  *tile_out = best_tile; *cycles_out = best;
+}
+
+static int prepare(const gode_igemm_op* op, IgemmArgs* A, int* tile, int* max_mblk, int* rows, SplitPlan* sp, int* rows0 = nullptr,
+                   double* cycles = nullptr) {
   int rc = gode_build_igemm_geom(op->g, op->dir, &A->G);
   if (rc) return rc;
+  A->ntab = 0;
+  if (cycles) *cycles = -1.0;
+  IgemmGeom B;
+  const bool can_border = border_table(op, A->G, &B);
   const bool grouped = op->groups == 2;
   if (grouped) {
     // two image groups with SEPARATE BatchNorm partial statistics (one discriminator pass over [real; fake]): the
@@ -1147,11 +1215,29 @@ static int prepare(const gode_igemm_op* op, IgemmArgs* A, int* tile, int* max_mb
     *tile = ftile;
     sp->positions = op->g.N * A->G.Xd * A->G.Xh * A->G.Xw; sp->ksplit = 1; sp->slabs_per_split = 0;
     if (fk > 1) { sp->slabs_per_split = gode_ceil_div(max_slabs, fk); sp->ksplit = gode_ceil_div(max_slabs, sp->slabs_per_split); }
+    if (can_border && fk <= 1) A->G = B;     // (calibration runs time the border form with the forced tile)
   } else if (op->tile == 0 && fast_geometry(A->G) && A->G.Ncols > 4 && strides_allow_vec(op, A->G) && (!menv || atoi(menv) != 0)) {
-    choose_fast(op, A->G, tile, sp);
+    double cyc = -1.0;
+    choose_fast(op, A->G, tile, sp, &cyc);
+    if (can_border && fast_geometry(B) && sp->ksplit == 1) {
+      // per layer: the border form only where the model prices it below the plain launch (3 % hysteresis toward plain).
+      // A launch that splits K keeps doing so: a K split adds its partial sums in another order, and an op with the flag
+      // must give the raw outputs of the op without it bit for bit
+      int tb; double cb;
+      choose_border(op, B, &tb, &cb);
+      if (cb < 0.97 * cyc) { A->G = B; *tile = tb; sp->ksplit = 1; sp->slabs_per_split = 0; cyc = cb; }
+    }
+    if (cycles) *cycles = cyc;
   } else {
-  *tile = pick_tile_split_aware(op->g, A->G, op->tile);
-  *sp = plan_split(op, A->G, *tile);
+    *tile = pick_tile_split_aware(op->g, A->G, op->tile);
+    *sp = plan_split(op, A->G, *tile);
+    // a REQUESTED tile takes the border form unless a plan splits K; tile = 0 off the modelled path (generic kernel, odd
+    // channel counts) stays plain: nothing measured says it would pay there
+    if (can_border && sp->ksplit == 1 && op->tile != 0) {
+      const int tb = pick_tile_split_aware(op->g, B, op->tile);
+      const SplitPlan sb = plan_split(op, B, tb);
+      if (sb.ksplit == 1) { A->G = B; *tile = tb; *sp = sb; }
+    }
   }
   if (grouped && sp->ksplit > 1 && (sp->positions / 2) % SPLITK_ROWS != 0) {
     // the split-K finish emits one statistics row per SPLITK_ROWS output positions: the groups must not share a row
@@ -1187,12 +1273,18 @@ extern "C" double gode_igemm_model_cycles(const gode_igemm_op* op) {
   static const char* menv = getenv("GODE_IGEMM_MODEL");
   if (!fast_geometry(A.G) || A.G.Ncols <= 4 || !strides_allow_vec(op, A.G) || (menv && atoi(menv) == 0)) return -1.0;
   int tile; SplitPlan sp; double cyc = -1.0;
+  IgemmGeom B;
   choose_fast(op, A.G, &tile, &sp, &cyc);
+  if (sp.ksplit == 1 && border_table(op, A.G, &B) && fast_geometry(B)) {      // (the same choice as prepare's)
+    double cb;
+    choose_border(op, B, &tile, &cb);
+    if (cb < 0.97 * cyc) cyc = cb;
+  }
   return cyc;
 }
 
 extern "C" int gode_igemm_stats_segments(const gode_igemm_op* op, int32_t split_images, int32_t* seg) {
-  if (!op || !seg || op->groups == 2 || split_images <= 0 || split_images >= op->g.N) return GODE_E_ARG;
+  if (!op || !seg || op->groups == 2 || op->border || split_images <= 0 || split_images >= op->g.N) return GODE_E_ARG;
   IgemmArgs A; int tile, mx, rows; SplitPlan sp;
   int rc = prepare(op, &A, &tile, &mx, &rows, &sp);
   if (rc) return rc;
@@ -1270,6 +1362,14 @@ static int launch(IgemmArgs& A, bool vec, int max_mblk, bool double_buf, const S
     if (force == 3 && ok2) mode = 3;
     A.xcd_mode = mode;
     dim3 g1(MB * NC * sp.ksplit);
+    if (A.G.border) {
+      if (sp.ksplit > 1 || A.tapskip) return GODE_E_ARG;     // (prepare never plans either on a border-split table)
+      constexpr int BM = WM * TM * 32;
+      A.ntab = A.G.nphase; A.tile0[0] = 0;
+      for (int i = 0; i < A.G.nphase; ++i) A.tile0[i + 1] = A.tile0[i] + gode_ceil_div(A.G.ph[i].M, BM) * NB;
+      for (int i = A.G.nphase + 1; i <= GODE_MAX_PHASES; ++i) A.tile0[i] = A.tile0[A.G.nphase];
+      g1 = dim3(A.tile0[A.G.nphase]);
+    }
     const bool has_xf = A.scale != nullptr || A.act != GODE_ACT_NONE;
     static const char* genv = getenv("GODE_IGEMM_GLDS");
     // default; GODE_IGEMM_GLDS=0 selects register staging (as do operands beyond the 2 GiB a raw buffer's offsets span)
@@ -1332,7 +1432,7 @@ extern "C" int gode_igemm(const gode_igemm_op* op, void* stream) {
   // input gradient of a convolution with temporal taps: depth-major tiles, so that the taps falling off the tensor's ends
   // are dead for whole tiles (skipped in the FAST kernel's K loop)
   A.dmajor = 0;
-  A.tapskip = igemm_wants_tapskip(op, G);
+  A.tapskip = !G.border && igemm_wants_tapskip(op, G);
   // Depth-major rows: every tile sees one or two planes (a small plane) or a slice of one (a plane of >= 128 rows, which
   // would fill tiles by itself in image-major order too -- but depth-major with the interleaved XCD order below is 4-6 %
   // faster there as well: UCF video-D layer 1 input gradient 833 -> 800 us at N = 32, 405 -> 381 at N = 16).
@@ -1431,7 +1531,7 @@ __global__ void pack_kernel(const PackArgs a) {
 
 extern "C" int64_t gode_pack_size(const gode_conv_geom* g, int dir) {
   IgemmGeom G;
-  int rc = gode_build_igemm_geom(*g, dir, &G);
+  int rc = (dir & GODE_PACK_BORDER) ? gode_build_igemm_geom_border(*g, dir & ~GODE_PACK_BORDER, &G) : gode_build_igemm_geom(*g, dir, &G);
   return rc ? rc : gode_pack_floats(G);
 }
 
@@ -1443,7 +1543,7 @@ struct PackPhase { int32_t Th, Tw, K, Kp, kd0, kh0, kw0, pad_; int64_t w_off, to
 struct PackEntry {
   const float* w; float* wp; const int32_t* co_perm;
   int32_t nphase, Cg, fullk, dir, ks_d, ks_h, ks_w, Ci, kd, kh, kw, Co;
-  PackPhase ph[GODE_MAX_PHASES];
+  PackPhase ph[GODE_MAX_STRIDE_PHASES];     // (plain tables only: a border-form pack goes through pack_kernel)
 };
 struct PackBatch { PackEntry e[PACK_BATCH]; };
 static_assert(sizeof(PackBatch) <= 4096, "kernel-argument budget");
@@ -1522,6 +1622,8 @@ __global__ void __launch_bounds__(256) pack_tile_kernel(const PackBatch b) {
   }
 }
 
+static int gode_pack_batch_plain(const gode_pack_op* const* ops, int n, void* stream);
+
 static bool pack_tileable(const PackEntry& E) {
   const int taps = E.kd * E.kh * E.kw;
   if (E.co_perm || E.fullk || taps < 4 || taps > 64 || (taps & (taps - 1)) != 0 || E.Ci % PACK_T != 0 || E.Co % PACK_T != 0) return false;
@@ -1529,7 +1631,33 @@ static bool pack_tileable(const PackEntry& E) {
   return true;
 }
 
-extern "C" int gode_pack_batch_(const gode_pack_op* const* ops, int n, void* stream) {
+static int pack_one(const gode_conv_geom* g, int dir, int border, const float* w, float* wpack, const int32_t* co_perm, void* stream);
+
+extern "C" int gode_pack_batch_(const gode_pack_op* const* all_ops, int n_all, void* stream) {
+  // border-form packs (up to 16 panels, written once per weight version of a sampling-only program) go out one by one
+  // through the element-wise kernel; the plain ones are batched as before
+  const gode_pack_op* plain[64];
+  int n = 0;
+  for (int i = 0; i <= n_all; ++i) {
+    const gode_pack_op* op = i < n_all ? all_ops[i] : nullptr;
+    if (i < n_all && !op) return GODE_E_ARG;
+    if (op && (op->dir & GODE_PACK_BORDER)) {
+      if (!op->w || !op->wpack) return GODE_E_ARG;
+      const int rc = pack_one(&op->g, op->dir & ~GODE_PACK_BORDER, 1, op->w, op->wpack, op->co_perm, stream);
+      if (rc) return rc;
+      continue;
+    }
+    if (op) plain[n++] = op;
+    if (n == 64 || (!op && n > 0)) {
+      const int rc = gode_pack_batch_plain(plain, n, stream);
+      if (rc) return rc;
+      n = 0;
+    }
+  }
+  return 0;
+}
+
+static int gode_pack_batch_plain(const gode_pack_op* const* ops, int n, void* stream) {
   for (int at = 0; at < n; at += PACK_BATCH) {
     PackBatch B;
     const int cnt = n - at < PACK_BATCH ? n - at : PACK_BATCH;
@@ -1575,7 +1703,7 @@ extern "C" int gode_pack_batch_(const gode_pack_op* const* ops, int n, void* str
     }
     if (nr > 0 && mr > 0) {
       int blocks = (int)((mr + 1023) / 1024); if (blocks > 512) blocks = 512; if (blocks < 1) blocks = 1;
-      hipLaunchKernelGGL(pack_batch_kernel, dim3(blocks, GODE_MAX_PHASES, nr), dim3(256), 0, (hipStream_t)stream, R);
+      hipLaunchKernelGGL(pack_batch_kernel, dim3(blocks, GODE_MAX_STRIDE_PHASES, nr), dim3(256), 0, (hipStream_t)stream, R);
       GODE_LAUNCH_CHECK();
     }
   }
@@ -1586,8 +1714,25 @@ extern "C" int gode_pack_weights(const gode_conv_geom* g, int dir, const float* 
                                  int32_t co_canon, void* stream) {
   (void)co_canon;
   if (!g || !w || !wpack) return GODE_E_ARG;
+  return pack_one(g, dir & ~GODE_PACK_BORDER, (dir & GODE_PACK_BORDER) != 0, w, wpack, co_perm, stream);
+}
+
+static int pack_one(const gode_conv_geom* g, int dir, int border, const float* w, float* wpack, const int32_t* co_perm, void* stream) {
   PackArgs A;
-  int rc = gode_build_igemm_geom(*g, dir, &A.G);
+  if (border) {
+    // a border-form pack is the plain pack followed by the panels of the sub-phases that keep only part of their taps
+    int rc = pack_one(g, dir, 0, w, wpack, co_perm, stream);
+    if (rc) return rc;
+    rc = gode_build_igemm_geom_border(*g, dir, &A.G);
+    if (rc) return rc;
+    if (!A.G.border) return 0;
+    int np = 0;
+    for (int i = 0; i < A.G.nphase; ++i)
+      if (A.G.ph[i].w_off >= gode_pack_size(g, dir)) A.G.ph[np++] = A.G.ph[i];
+    A.G.nphase = np;
+    if (np == 0) return 0;
+  }
+  int rc = border ? 0 : gode_build_igemm_geom(*g, dir, &A.G);
   if (rc) return rc;
   A.g = *g; A.dir = dir; A.w = w; A.wp = wpack; A.co_perm = co_perm;
   int64_t mx = 0;

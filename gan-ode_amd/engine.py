@@ -11,6 +11,7 @@ share all kernels and this class.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -144,15 +145,20 @@ class ConvStack:
         # spills 6 % of a round into a round of its own.  Everything else of the layer (statistics finalize, BatchNorm
         # apply / backward, weight gradient) still runs once over all rows.
         self._two_f, self._two_b, self._rows_ab = {}, {}, {}
+        # layers whose forward GEMM carries gode_igemm_op.border (see _border_layers).  Every forward program of the stack
+        # does, with or without a backward behind it: a no-grad pass must give the frames of the pass a backward follows bit
+        # for bit, and the two forms group the BatchNorm partial sums differently.  GODE_BORDER_SPLIT=0: none.
+        self._border = self._border_layers() if os.environ.get("GODE_BORDER_SPLIT", "1") != "0" else {}
         for l, s in enumerate(specs):
-            n = lib.gode_pack_size(C.byref(s.geom), s.fwd_dir)
+            bord = l in self._border       # its pack: the plain pack + the edge / corner panels, under a key of its own
+            n = lib.gode_pack_size(C.byref(s.geom), s.fwd_dir | (L.PACK_BORDER if bord else 0))
             if n <= 0:
                 raise RuntimeError(f"bad geometry for pack ({n})")
-            self.wpack_f.append(self._shared_pack(l, s.fwd_dir, n))
+            self.wpack_f.append(self._shared_pack(l, "border" if bord else s.fwd_dir, n))
             C_out = s.out_dims()[4]
             two = self._two_f[l] = bool(self.split) and 0 < l < self.nl - 1 and self._two_launches(s.geom, s.fwd_dir)
             if s.has_bn:
-                probe = L.IgemmOp(g=s.geom, dir=s.fwd_dir, tile=0, groups=groups)
+                probe = L.IgemmOp(g=s.geom, dir=s.fwd_dir, tile=0, groups=groups, border=1 if bord else 0)
                 if two:     # the parts' partial sums: two arrays [2][ncols][rows of the part], one after the other
                     ra, rb = (lib.gode_igemm_stats_rows(C.byref(L.IgemmOp(g=self._part_geom(s.geom, n), dir=s.fwd_dir, tile=0)))
                               for n in (self.split, s.geom.N - self.split))
@@ -350,6 +356,21 @@ class ConvStack:
         h.N = g.N // 2
         return h
 
+    def _border_layers(self):
+        """The transposed-convolution layers whose GEMM has a border-split form (no MFMA on the padding taps at the image
+        borders: gode_igemm_op.border) -- unsplit, ungrouped stacks only."""
+        if self.groups != 1 or self.split or self.noisy:
+            return {}
+        lib, out = L.lib(), {}
+        for l, s in enumerate(self.specs):
+            if s.fwd_dir != L.DGRAD or self._head_as_gemm(l) is not None:
+                continue
+            n = lib.gode_pack_size(C.byref(s.geom), L.DGRAD | L.PACK_BORDER)
+            if n <= lib.gode_pack_size(C.byref(s.geom), L.DGRAD):
+                continue                                      # (the table does not split: nothing to gain)
+            out[l] = n
+        return out
+
     def _build_fwd(self, training: bool):
         ops = []
         packs = []
@@ -446,6 +467,11 @@ class ConvStack:
                                scale=dptr(sc), shift=dptr(sh),
                                stats=dptr(self.stats[l]) if want_stats else None,
                                groups=2 if (G2 and s.has_bn) else 0)
+                if l in self._border:
+                    # (wpack_f[l] is the border-form pack and stat_rows[l] the flagged op's row count: see __init__)
+                    packs[-1] = (l, "border", L.PackOp(g=s.geom, dir=L.DGRAD | L.PACK_BORDER, co_canon=0, w=dptr(p.weight),
+                                                       wpack=dptr(self.wpack_f[l]), co_perm=dptr(s.co_perm)))
+                    op.border = 1
                 ops.append(op)
             if l == 0:
                 patch["first"] = op

@@ -28,6 +28,8 @@ enum { GODE_ACT_NONE = 0, GODE_ACT_RELU = 1, GODE_ACT_LRELU = 2,              /*
        GODE_ACT_TANH_OUT = 3 /* bn_bwd only: y holds tanh OUTPUT, g *= 1-y^2 */ };
 enum { GODE_EPI_RAW = 0, GODE_EPI_TANH = 1 };
 enum { GODE_FPROP = 0, GODE_DGRAD = 1 };
+/* or'ed into the `dir` of gode_pack_size / gode_pack_weights / gode_pack_op: the pack an igemm op with border != 0 reads */
+enum { GODE_PACK_BORDER = 0x100 };
 
 /* A regular convolution x[N,Di,Hi,Wi,Ci] -> y[N,Do,Ho,Wo,Co].  2-D layers use D=1,kd=1,sd=1,pd=0.  A
  * ConvTranspose layer is described by the convolution whose data-gradient it is (x = its output). */
@@ -65,7 +67,14 @@ typedef struct gode_igemm_op {
    * partial statistics must stay separate -- one discriminator pass over [real; fake] keeps the per-pass batch
    * statistics of the reference's two calls (mnist_moco_ode.py:119-124,137-143).  The partial-statistics rows of group 0
    * are the first gode_igemm_stats_rows0(op) rows of every column, group 1 the rest.  0 / 1: one group. */
-  int32_t groups, pad3_;
+  int32_t groups;
+  /* border != 0 (DGRAD; ignored by FPROP, fullk, groups == 2, live-tap and split-K launches): the launch may run the
+   * border-split phase table -- every stride phase cut into interior / edge / corner sub-phases that hold only in-range
+   * taps, so no MFMA multiplies zero padding.  `wpack` must then be packed with dir = GODE_DGRAD | GODE_PACK_BORDER (that
+   * pack extends the plain one, so the launch is free to stay plain when its cost model says so).  Raw outputs are bit-identical to
+   * border == 0; the partial-statistics rows are grouped differently: gode_igemm_stats_rows / _rows0 / _work_size /
+   * _model_cycles all follow the flag.  0: as before. */
+  int32_t border;
 } gode_igemm_op;
 int gode_igemm(const gode_igemm_op* op, void* stream);
 /* floats of workspace the op can use for split-K (0: it never splits).  Deterministic from the op's geometry. */
@@ -701,7 +710,7 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
 enum { GODE_OPS(GODE_ENUM_ROW_) GODE_OP_PACK = 9 };
 #undef GODE_ENUM_ROW_
 typedef struct gode_pack_op {
-  gode_conv_geom g; int32_t dir, co_canon; const float* w; float* wpack; const int32_t* co_perm;
+  gode_conv_geom g; int32_t dir /* may carry GODE_PACK_BORDER */, co_canon; const float* w; float* wpack; const int32_t* co_perm;
 } gode_pack_op;
 int gode_run(const int32_t* kinds, const void* const* ops, int32_t n, void* stream);
 
