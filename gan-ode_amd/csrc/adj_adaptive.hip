@@ -26,10 +26,6 @@ __device__ __forceinline__ void th_axpy(Th& d, float c, const Th& x) { d.W1 += c
 __device__ __forceinline__ Th th_sub(const Th& a, const Th& b) { return Th{a.W1 - b.W1, a.W2 - b.W2, a.b1 - b.b1, a.b2 - b.b2}; }
 __device__ __forceinline__ Th th_scale(float c, const Th& a) { return Th{c * a.W1, c * a.W2, c * a.b1, c * a.b2}; }
 
-__device__ __forceinline__ f32x4 abs4f(const f32x4 v) { return f32x4{fabsf(v[0]), fabsf(v[1]), fabsf(v[2]), fabsf(v[3])}; }
-__device__ __forceinline__ f32x4 max4f(const f32x4 a, const f32x4 b) { return f32x4{fmaxf(a[0], b[0]), fmaxf(a[1], b[1]), fmaxf(a[2], b[2]), fmaxf(a[3], b[3])}; }
-__device__ __forceinline__ float sq4f(const f32x4 v) { return v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]; }
-
 struct __attribute__((aligned(16))) AdjLds {
   float tile[4][2][16 * LDT];   // per-wave transpose tiles of the outer products
   float img[4][2][TH_N];        // per-wave images of theta-shaped quantities (slot 0: V / E, slot 1: S)
@@ -124,8 +120,8 @@ struct AdjSolver {
   // torchdiffeq's mixed norm of an augmented vector given its y / a parts per lane and its theta part through theta_sq
   __device__ __forceinline__ float mixed(const f32x4 vy, const f32x4 va, int theta_mode) {
     float v[6];
-    v[0] = valid ? sq4f(vy) : 0.f;
-    v[1] = valid ? sq4f(va) : 0.f;
+    v[0] = valid ? sq4(vy) : 0.f;
+    v[1] = valid ? sq4(va) : 0.f;
     __syncthreads();                      // the images written by put_image are complete
     theta_sq(theta_mode, v + 2);
     block_sum6(v);
@@ -146,17 +142,16 @@ struct AdjSolver {
     eval(y0, a0, k1y, k1a, X1, true);
     double dtd;
     {   // _initial_step(order 4) with the mixed norm
-      const f32x4 scy = atol + abs4f(y0) * rtol, sca = atol + abs4f(a0) * rtol;
+      const f32x4 scy = atol + abs4(y0) * rtol, sca = atol + abs4(a0) * rtol;
       const float d0 = mixed(y0 / scy, a0 / sca, 2);
       put_image(0, X1);
       const float d1 = mixed(k1y / scy, k1a / sca, 0);
-      const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+      const float h0 = initial_h0(d0, d1);
       f32x4 fy, fa; Th Xb;
       eval(y0 + h0 * k1y, a0 + h0 * k1a, fy, fa, Xb, true);
       put_image(0, th_sub(Xb, X1));
       const float d2 = mixed((fy - k1y) / scy, (fa - k1a) / sca, 0) / h0;
-      const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), 0.2f);
-      dtd = (double)fminf(100.f * h0, h1);
+      dtd = (double)initial_step<LibmPow>(h0, d1, d2);
     }
     double tcur = tau0;
     const int step_limit = steps + 100000;
@@ -191,7 +186,7 @@ struct AdjSolver {
       const Th Sd = th_scale(dt, S), Ed = th_scale(dt, E);
       put_image(0, Ed);
       put_image(1, Sd);
-      const f32x4 toly = atol + rtol * max4f(abs4f(y0), abs4f(y1)), tola = atol + rtol * max4f(abs4f(a0), abs4f(a1));
+      const f32x4 toly = atol + rtol * max4(abs4(y0), abs4(y1)), tola = atol + rtol * max4(abs4(a0), abs4(a1));
       const float ratio = mixed(erry / toly, erra / tola, 1);
       ++steps;
 #ifdef GODE_ADJ_DEBUG
@@ -232,15 +227,10 @@ struct AdjSolver {
         if (last) return true;
         tcur += dtd; y0 = y1; k1y = k7y; k1a = k7a; X1 = X7;
       }
-      float fac;
-      if (ratio == 0.f) fac = 10.f;
-      else { fac = 0.9f * powf(ratio, -0.2f); fac = fminf(10.f, fmaxf(fac, ratio < 1.f ? 1.f : 0.2f)); }
-      dtd *= (double)fac;
+      dtd *= (double)step_factor<LibmPow>(ratio);
     }
   }
 };
-
-#define RNN_NPARAM 2176
 
 // ODE-RNN backward with the adaptive adjoint: per frame GRU backward, then ONE adjoint call over [1, 0] (its theta state
 // starts at zero, as each odeint_adjoint call's does).  One partial row of `work` per wave (16 trajectories).
@@ -259,7 +249,7 @@ __global__ void __launch_bounds__(ADJ_BLOCK * 4) odernn_bwd_adaptive_kernel(cons
   float rtol = a.rtol, atol = a.atol;
   asm volatile("" : "+v"(rtol), "+v"(atol));     // (see ode_dopri5_fwd_kernel: keeps hipcc off a two-SGPR packed op)
   S.rtol = rtol; S.atol = atol;
-  float* part = a.work + (int64_t)(blockIdx.x * 4 + S.wv) * RNN_NPARAM;
+  float* part = a.work + (int64_t)(blockIdx.x * 4 + S.wv) * GODE_ODERNN_NPARAM;
 
   S.w1 = ld4(a.p.W1 + s * 16 + 4 * g); S.w2 = ld4(a.p.W2 + s * 16 + 4 * g);
   S.b1 = ld4(a.p.b1 + 4 * g); S.b2 = ld4(a.p.b2 + 4 * g);

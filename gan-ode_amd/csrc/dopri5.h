@@ -1,6 +1,9 @@
 // dopri5.h -- what the adaptive solvers share: the Dormand-Prince tableau (torchdiffeq _DORMAND_PRINCE_SHAMPINE_TABLEAU),
-// the step-size controller and the weights of the 4th-order interpolant.  odernn.hip and adj_adaptive.hip take the tableau
-// only (their controller is written with powf).
+// the scalar rules of the initial step and of the step-size controller, and the weights of the 4th-order interpolant.
+// The scalar rules are stated once with the power function as their parameter: FastPow for the VALU kernels
+// (odernn_valu.hip, cde_valu.hip), LibmPow for the MFMA kernels (odernn.hip, adj_adaptive.hip) -- which one a kernel uses
+// is part of its bits.  The solvers themselves exist once per lane mapping: FwdV / AdjV (odernn_valu.hip), FwdM
+// (odernn.hip), AdjSolver (adj_adaptive.hip).
 #pragma once
 
 #define DP5_A21 (1.f / 5.f)
@@ -42,10 +45,22 @@
 // x^p through the hardware log2 / exp2 units (1 ulp each): the step-size controller needs 3-4 digits
 __device__ __forceinline__ float fast_pow(float x, float p) { return __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(x)); }
 
+struct FastPow { __device__ __forceinline__ float operator()(float x, float p) const { return fast_pow(x, p); } };
+struct LibmPow { __device__ __forceinline__ float operator()(float x, float p) const { return powf(x, p); } };
+
+// torchdiffeq _select_initial_step (order 4), its scalar part.  d0, d1: norms of y0 / scale and f0 / scale;
+// d2: norm of (f(y0 + h0 f0) - f0) / scale, divided by h0.
+__device__ __forceinline__ float initial_h0(float d0, float d1) { return (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1; }
+template <class Pow = FastPow>
+__device__ __forceinline__ float initial_step(float h0, float d1, float d2) {
+  const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : Pow()(0.01f / fmaxf(d1, d2), 0.2f);
+  return fminf(100.f * h0, h1);
+}
 // torchdiffeq _optimal_step_size (order 5): safety 0.9, ifactor 10, dfactor 0.2; a step with ratio < 1 never shrinks
+template <class Pow = FastPow>
 __device__ __forceinline__ float step_factor(float ratio) {
   if (ratio == 0.f) return 10.f;
-  const float f = 0.9f * fast_pow(ratio, -0.2f);
+  const float f = 0.9f * Pow()(ratio, -0.2f);
   return fminf(10.f, fmaxf(f, ratio < 1.f ? 1.f : 0.2f));
 }
 // weights of the 4th-order interpolant (torchdiffeq _interp_fit / _interp_eval) at abscissa x:

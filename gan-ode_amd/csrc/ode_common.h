@@ -1,6 +1,6 @@
 // ode_common.h -- device helpers shared by the motion-latent kernels: the transposed 16x16 mat-vec batch on
-// v_mfma_f32_16x16x4_f32 (see the header comment of ode.hip for the lane mapping), the activations, the layout of the
-// gode_ode_params block and the content broadcast.
+// v_mfma_f32_16x16x4_f32 (see the header comment of ode.hip for the lane mapping), the activations and the per-component
+// f32x4 helpers of the error norms (sq4 / abs4 / max4), the layout of the gode_ode_params block and the content broadcast.
 #pragma once
 #include "common.h"
 
@@ -49,6 +49,11 @@ __device__ __forceinline__ float fast_tanh(float x) {
 }
 __device__ __forceinline__ f32x4 tanh4(const f32x4 u) {
   return f32x4{fast_tanh(u[0]), fast_tanh(u[1]), fast_tanh(u[2]), fast_tanh(u[3])};
+}
+__device__ __forceinline__ float sq4(const f32x4 v) { return v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]; }
+__device__ __forceinline__ f32x4 abs4(const f32x4 v) { return f32x4{fabsf(v[0]), fabsf(v[1]), fabsf(v[2]), fabsf(v[3])}; }
+__device__ __forceinline__ f32x4 max4(const f32x4 a, const f32x4 b) {
+  return f32x4{fmaxf(a[0], b[0]), fmaxf(a[1], b[1]), fmaxf(a[2], b[2]), fmaxf(a[3], b[3])};
 }
 __device__ __forceinline__ f32x4 lrelu4(const f32x4 u) {
   f32x4 o;

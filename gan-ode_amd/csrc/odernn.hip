@@ -17,7 +17,6 @@
 // trajectories per workgroup of the forward kernel (4 waves): keeps the kernel inside the register file -- a spilling
 // build needed scratch memory, whose (re)allocation by the runtime stalled the queue for ~75 ms at a time
 #define RNN_BLOCK_SAMPLES 64
-#define RNN_NPARAM 2176
 
 // Workgroup sum, every thread gets the total (fixed order).  red[2][...] alternates per call, so ONE barrier per call
 // suffices: a wave can write slot set p again only after passing the barrier of the call in between, which every wave
@@ -32,33 +31,86 @@ __device__ __forceinline__ float block_sum(float v, float (*red)[RNN_BLOCK_SAMPL
   par ^= 1;
   return s;
 }
-__device__ __forceinline__ float sq4(const f32x4 v) { return v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]; }
-__device__ __forceinline__ f32x4 abs4(const f32x4 v) { return f32x4{fabsf(v[0]), fabsf(v[1]), fabsf(v[2]), fabsf(v[3])}; }
-__device__ __forceinline__ f32x4 max4(const f32x4 a, const f32x4 b) {
-  return f32x4{fmaxf(a[0], b[0]), fmaxf(a[1], b[1]), fmaxf(a[2], b[2]), fmaxf(a[3], b[3])};
-}
+
+// The forward dopri5 stepper of this mapping (16 trajectories per wave, a lane holds 4 features of one trajectory as an f32x4;
+// error norm: RMS over the workgroup's trajectories).  Both forward kernels drive it from their own outer loops (clock, trial
+// limit, dense output, stores).  The scalar rules are the shared ones on powf (dopri5.h).
+struct FwdM {
+  f32x4 w1, w2, b1, b2;
+  float rtol, atol, inv_count;       // (set by the kernel: ode_dopri5_fwd_kernel has to pin the tolerances to vector registers)
+  int s, g, n, nw, red_par;          // lane = (trajectory s of the wave, feature group g); n: the trajectory; nw: waves
+  bool valid;
+  float (*red)[RNN_BLOCK_SAMPLES / 16];
+  f32x4 y0, f0;                      // the accepted state and f(y0)
+  double dtd;                        // step size (fp64, as torchdiffeq keeps it)
+  float dt;                          // the last trial step: its size, stage derivatives and 5th-order solution
+  f32x4 k3, k4, k5, k6, k7, y1;
+
+  // lane mapping, the workgroup's share of the N trajectories, the ODEFunc weights as MFMA operands
+  __device__ __forceinline__ void open(int N, const float* W1, const float* B1, const float* W2, const float* B2, float (*red_)[RNN_BLOCK_SAMPLES / 16]) {
+    const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    nw = blockDim.x >> 6; s = l & 15; g = l >> 4;
+    n = blockIdx.x * RNN_BLOCK_SAMPLES + wv * 16 + s;
+    valid = n < N;
+    const int nblk = (N - blockIdx.x * RNN_BLOCK_SAMPLES) < RNN_BLOCK_SAMPLES ? (N - blockIdx.x * RNN_BLOCK_SAMPLES) : RNN_BLOCK_SAMPLES;
+    inv_count = 1.f / (float)(nblk * 16);
+    red = red_; red_par = 0;
+    w1 = ld4(W1 + s * 16 + 4 * g); w2 = ld4(W2 + s * 16 + 4 * g);
+    b1 = ld4(B1 + 4 * g); b2 = ld4(B2 + 4 * g);
+  }
+  __device__ __forceinline__ f32x4 f(const f32x4 yy) const { return matvec(w2, tanh4(matvec(w1, yy, b1)), b2); }
+  __device__ __forceinline__ float rms(const f32x4 v) { return sqrtf(block_sum(valid ? sq4(v) : 0.f, red, nw, red_par) * inv_count); }
+  // start a solve at y: the accepted state and torchdiffeq's _select_initial_step (order 4)
+  __device__ __forceinline__ void start(const f32x4 y) {
+    y0 = y; f0 = f(y);
+    const f32x4 sc = atol + abs4(y0) * rtol;
+    const float d0 = rms(y0 / sc), d1 = rms(f0 / sc);
+    const float h0 = initial_h0(d0, d1);
+    const f32x4 f1 = f(y0 + h0 * f0);
+    const float d2 = rms((f1 - f0) / sc) / h0;
+    dtd = (double)initial_step<LibmPow>(h0, d1, d2);
+  }
+  // one trial step of size dtd from the accepted state; returns the error ratio (accept when <= 1)
+  __device__ __forceinline__ float trial() {
+    dt = (float)dtd;
+    const f32x4 k1 = f0;
+    const f32x4 k2 = f(y0 + dt * (DP5_A21 * k1));
+    k3 = f(y0 + dt * (DP5_A31 * k1 + DP5_A32 * k2));
+    k4 = f(y0 + dt * (DP5_A41 * k1 + DP5_A42 * k2 + DP5_A43 * k3));
+    k5 = f(y0 + dt * (DP5_A51 * k1 + DP5_A52 * k2 + DP5_A53 * k3 + DP5_A54 * k4));
+    k6 = f(y0 + dt * (DP5_A61 * k1 + DP5_A62 * k2 + DP5_A63 * k3 + DP5_A64 * k4 + DP5_A65 * k5));
+    y1 = y0 + dt * (DP5_B1 * k1 + DP5_B3 * k3 + DP5_B4 * k4 + DP5_B5 * k5 + DP5_B6 * k6);
+    k7 = f(y1);
+    const f32x4 err = dt * (DP5_E1 * k1 + DP5_E3 * k3 + DP5_E4 * k4 + DP5_E5 * k5 + DP5_E6 * k6 + DP5_E7 * k7);
+    const f32x4 tol = atol + rtol * max4(abs4(y0), abs4(y1));
+    return rms(err / tol);
+  }
+  // the 4th-order interpolant of the last trial (fit through the mid-point): y(x) = y0 + x (cd + x (cc + x (cb + x ca)))
+  __device__ __forceinline__ void interp(f32x4& ca, f32x4& cb, f32x4& cc, f32x4& cd) const {
+    const f32x4 k1 = f0;
+    const f32x4 ymid = y0 + dt * (DP5_C1 * k1 + DP5_C3 * k3 + DP5_C4 * k4 + DP5_C5 * k5 + DP5_C6 * k6 + DP5_C7 * k7);
+    ca = 2.f * dt * (k7 - k1) - 8.f * (y1 + y0) + 16.f * ymid;
+    cb = dt * (5.f * k1 - 3.f * k7) + 18.f * y0 + 14.f * y1 - 32.f * ymid;
+    cc = dt * (k7 - 4.f * k1) - 11.f * y0 - 5.f * y1 + 16.f * ymid;
+    cd = dt * k1;
+  }
+  // the last trial becomes the accepted state
+  __device__ __forceinline__ void accept() { y0 = y1; f0 = k7; }
+};
 
 __global__ void __launch_bounds__(RNN_BLOCK_SAMPLES * 4) odernn_fwd_kernel(const gode_odernn_fwd_op a) {
   __shared__ float red[2][RNN_BLOCK_SAMPLES / 16];
-  int red_par = 0;
-  const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const int s = l & 15, g = l >> 4;
-  const int n = blockIdx.x * RNN_BLOCK_SAMPLES + wv * 16 + s;
-  const bool valid = n < a.N;
-  const int T = a.T;
-  const int nblk = (a.N - blockIdx.x * RNN_BLOCK_SAMPLES) < RNN_BLOCK_SAMPLES ? (a.N - blockIdx.x * RNN_BLOCK_SAMPLES) : RNN_BLOCK_SAMPLES;
-  const float inv_count = 1.f / (float)(nblk * 16);
-
-  const f32x4 w1 = ld4(a.p.W1 + s * 16 + 4 * g), w2 = ld4(a.p.W2 + s * 16 + 4 * g);
-  const f32x4 b1 = ld4(a.p.b1 + 4 * g), b2 = ld4(a.p.b2 + 4 * g);
-  auto f = [&](const f32x4 yy) { return matvec(w2, tanh4(matvec(w1, yy, b1)), b2); };
+  FwdM S;
+  S.open(a.N, a.p.W1, a.p.b1, a.p.W2, a.p.b2, red);
+  S.rtol = a.rtol; S.atol = a.atol;
+  const int s = S.s, g = S.g, n = S.n, T = a.T;
+  const bool valid = S.valid;
   f32x4 wih[3], whh[3], bih[3], bhh[3];
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
     wih[q] = ld4(a.p.Wih + (16 * q + s) * 16 + 4 * g); whh[q] = ld4(a.p.Whh + (16 * q + s) * 16 + 4 * g);
     bih[q] = ld4(a.p.bih + 16 * q + 4 * g); bhh[q] = ld4(a.p.bhh + 16 * q + 4 * g);
   }
-  auto rms = [&](const f32x4 v) { return sqrtf(block_sum(valid ? sq4(v) : 0.f, red, nw, red_par) * inv_count); };
 
   const int tsel = (a.sel_t && valid) ? a.sel_t[n] : -1;
   f32x4 h = valid ? ld4(a.noise + (int64_t)n * 16 + 4 * g) : zero4();
@@ -68,58 +120,24 @@ __global__ void __launch_bounds__(RNN_BLOCK_SAMPLES * 4) odernn_fwd_kernel(const
     // ---- h' = y(1), y' = f(y), y(0) = h : dopri5 with torchdiffeq's controller
     // the clock and the step size are kept in fp64 (as torchdiffeq keeps them): near the tolerance floor dt can
     // shrink below the fp32 spacing of t, and an fp32 clock would then stop advancing
-    f32x4 y0 = h, f0 = f(h), yend = h;
-    double dtd;
-    {
-      const f32x4 sc = a.atol + abs4(y0) * a.rtol;
-      const float d0 = rms(y0 / sc), d1 = rms(f0 / sc);
-      const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
-      const f32x4 f1 = f(y0 + h0 * f0);
-      const float d2 = rms((f1 - f0) / sc) / h0;
-      const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), 0.2f);
-      dtd = (double)fminf(100.f * h0, h1);
-    }
+    S.start(h);
+    f32x4 yend = h;
     double tcur = 0.0;
     int steps = 0;
     for (; steps < 100000; ++steps) {
-      const float dt = (float)dtd;
-      const f32x4 k1 = f0;
-      const f32x4 k2 = f(y0 + dt * (DP5_A21 * k1));
-      const f32x4 k3 = f(y0 + dt * (DP5_A31 * k1 + DP5_A32 * k2));
-      const f32x4 k4 = f(y0 + dt * (DP5_A41 * k1 + DP5_A42 * k2 + DP5_A43 * k3));
-      const f32x4 k5 = f(y0 + dt * (DP5_A51 * k1 + DP5_A52 * k2 + DP5_A53 * k3 +
-                                    DP5_A54 * k4));
-      const f32x4 k6 = f(y0 + dt * (DP5_A61 * k1 + DP5_A62 * k2 + DP5_A63 * k3 +
-                                    DP5_A64 * k4 + DP5_A65 * k5));
-      const f32x4 y1 = y0 + dt * (DP5_B1 * k1 + DP5_B3 * k3 + DP5_B4 * k4 +
-                                  DP5_B5 * k5 + DP5_B6 * k6);
-      const f32x4 k7 = f(y1);
-      const f32x4 err = dt * (DP5_E1 * k1 + DP5_E3 * k3 +
-                              DP5_E4 * k4 + DP5_E5 * k5 +
-                              DP5_E6 * k6 + DP5_E7 * k7);
-      const f32x4 tol = a.atol + a.rtol * max4(abs4(y0), abs4(y1));
-      const float ratio = rms(err / tol);
-      const bool accept = ratio <= 1.f;
-      if (accept) {
-        if (tcur + dtd >= 1.0) {   // dense output (4th-order fit through the mid-point) at t = 1
-          const f32x4 ymid = y0 + dt * (DP5_C1 * k1 + DP5_C3 * k3 +
-                                        DP5_C4 * k4 + DP5_C5 * k5 +
-                                        DP5_C6 * k6 + DP5_C7 * k7);
-          const f32x4 ca = 2.f * dt * (k7 - k1) - 8.f * (y1 + y0) + 16.f * ymid;
-          const f32x4 cb = dt * (5.f * k1 - 3.f * k7) + 18.f * y0 + 14.f * y1 - 32.f * ymid;
-          const f32x4 cc = dt * (k7 - 4.f * k1) - 11.f * y0 - 5.f * y1 + 16.f * ymid;
-          const f32x4 cd = dt * k1;
-          const float x = (float)((1.0 - tcur) / dtd);
-          yend = y0 + x * (cd + x * (cc + x * (cb + x * ca)));
+      const float ratio = S.trial();
+      if (ratio <= 1.f) {
+        if (tcur + S.dtd >= 1.0) {   // dense output at t = 1
+          f32x4 ca, cb, cc, cd;
+          S.interp(ca, cb, cc, cd);
+          const float x = (float)((1.0 - tcur) / S.dtd);
+          yend = S.y0 + x * (cd + x * (cc + x * (cb + x * ca)));
           ++steps;
           break;
         }
-        tcur += dtd; y0 = y1; f0 = k7;
+        tcur += S.dtd; S.accept();
       }
-      float fac;
-      if (ratio == 0.f) fac = 10.f;
-      else { fac = 0.9f * powf(ratio, -0.2f); fac = fminf(10.f, fmaxf(fac, ratio < 1.f ? 1.f : 0.2f)); }
-      dtd *= (double)fac;
+      S.dtd *= (double)step_factor<LibmPow>(ratio);
     }
     if (a.nsteps && threadIdx.x == 0 && blockIdx.x == 0) a.nsteps[t] = steps;
     if (valid && a.hp) *reinterpret_cast<f32x4*>(a.hp + ((int64_t)n * T + t) * 16 + 4 * g) = yend;
@@ -158,18 +176,15 @@ __global__ void __launch_bounds__(256) latent_content_kernel(const float* conten
 // odernn_fwd_kernel.  The interpolation abscissa is formed from the fp32-rounded times as torchdiffeq does.
 __global__ void __launch_bounds__(RNN_BLOCK_SAMPLES * 4) ode_dopri5_fwd_kernel(const gode_ode_fwd_op a) {
   __shared__ float red[2][RNN_BLOCK_SAMPLES / 16];
-  int red_par = 0;
-  const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const int s = l & 15, g = l >> 4;
-  const int n = blockIdx.x * RNN_BLOCK_SAMPLES + wv * 16 + s;
-  const bool valid = n < a.N;
-  const int T = a.T;
-  const int nblk = (a.N - blockIdx.x * RNN_BLOCK_SAMPLES) < RNN_BLOCK_SAMPLES ? (a.N - blockIdx.x * RNN_BLOCK_SAMPLES) : RNN_BLOCK_SAMPLES;
-  const float inv_count = 1.f / (float)(nblk * 16);
+  FwdM S;
+  S.open(a.N, a.p.W1, a.p.b1, a.p.W2, a.p.b2, red);
+  const int s = S.s, g = S.g, n = S.n, T = a.T;
+  const bool valid = S.valid;
   // tolerances pinned to vector registers: with both in SGPRs hipcc (ROCm 7.2) emits a packed-fp32 VOP3P with two scalar
   // sources for `atol + rtol * max(...)` and the assembler rejects it ("violates constant bus restriction")
   float rtol = a.rtol, atol = a.atol;
   asm volatile("" : "+v"(rtol), "+v"(atol));
+  S.rtol = rtol; S.atol = atol;
 
   f32x4 y0 = valid ? ld4(a.x + n * 16 + 4 * g) : zero4();
   if (a.prenet) {
@@ -181,10 +196,6 @@ __global__ void __launch_bounds__(RNN_BLOCK_SAMPLES * 4) ode_dopri5_fwd_kernel(c
     }
     y0 = lrelu4(acc);
   }
-  const f32x4 w1 = ld4(a.p.W1 + s * 16 + 4 * g), w2 = ld4(a.p.W2 + s * 16 + 4 * g);
-  const f32x4 b1 = ld4(a.p.b1 + 4 * g), b2 = ld4(a.p.b2 + 4 * g);
-  auto f = [&](const f32x4 yy) { return matvec(w2, tanh4(matvec(w1, yy, b1)), b2); };
-  auto rms = [&](const f32x4 v) { return sqrtf(block_sum(valid ? sq4(v) : 0.f, red, nw, red_par) * inv_count); };
   const int tsel = (a.sel_t && valid) ? a.sel_t[n] : -1;
   auto emit = [&](int t, const f32x4 v) {
     if (!valid) return;
@@ -194,56 +205,21 @@ __global__ void __launch_bounds__(RNN_BLOCK_SAMPLES * 4) ode_dopri5_fwd_kernel(c
   };
   emit(0, y0);
 
-  f32x4 f0 = f(y0);
-  double dtd;
-  {
-    const f32x4 sc = atol + abs4(y0) * rtol;
-    const float d0 = rms(y0 / sc), d1 = rms(f0 / sc);
-    const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
-    const f32x4 f1 = f(y0 + h0 * f0);
-    const float d2 = rms((f1 - f0) / sc) / h0;
-    const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), 0.2f);
-    dtd = (double)fminf(100.f * h0, h1);
-  }
+  S.start(y0);
   double tcur = (double)a.tout[0], seg0 = tcur, seg1 = tcur;
   f32x4 ca = y0, cb = y0, cc = y0, cd = y0, ce = y0;     // interp = (y, y, y, y, y) before the first accepted step
   int steps = 0;
   for (int j = 1; j < T; ++j) {
     const double target = (double)a.tout[j];
     while (target > seg1 && steps < 1000000) {
-      const float dt = (float)dtd;
-      const f32x4 k1 = f0;
-      const f32x4 k2 = f(y0 + dt * (DP5_A21 * k1));
-      const f32x4 k3 = f(y0 + dt * (DP5_A31 * k1 + DP5_A32 * k2));
-      const f32x4 k4 = f(y0 + dt * (DP5_A41 * k1 + DP5_A42 * k2 + DP5_A43 * k3));
-      const f32x4 k5 = f(y0 + dt * (DP5_A51 * k1 + DP5_A52 * k2 + DP5_A53 * k3 +
-                                    DP5_A54 * k4));
-      const f32x4 k6 = f(y0 + dt * (DP5_A61 * k1 + DP5_A62 * k2 + DP5_A63 * k3 +
-                                    DP5_A64 * k4 + DP5_A65 * k5));
-      const f32x4 y1 = y0 + dt * (DP5_B1 * k1 + DP5_B3 * k3 + DP5_B4 * k4 +
-                                  DP5_B5 * k5 + DP5_B6 * k6);
-      const f32x4 k7 = f(y1);
-      const f32x4 err = dt * (DP5_E1 * k1 + DP5_E3 * k3 +
-                              DP5_E4 * k4 + DP5_E5 * k5 +
-                              DP5_E6 * k6 + DP5_E7 * k7);
-      const f32x4 tol = atol + rtol * max4(abs4(y0), abs4(y1));
-      const float ratio = rms(err / tol);
+      const float ratio = S.trial();
       if (ratio <= 1.f) {
-        const f32x4 ymid = y0 + dt * (DP5_C1 * k1 + DP5_C3 * k3 +
-                                      DP5_C4 * k4 + DP5_C5 * k5 +
-                                      DP5_C6 * k6 + DP5_C7 * k7);
-        ca = 2.f * dt * (k7 - k1) - 8.f * (y1 + y0) + 16.f * ymid;
-        cb = dt * (5.f * k1 - 3.f * k7) + 18.f * y0 + 14.f * y1 - 32.f * ymid;
-        cc = dt * (k7 - 4.f * k1) - 11.f * y0 - 5.f * y1 + 16.f * ymid;
-        cd = dt * k1;
-        ce = y0;
-        seg0 = tcur; seg1 = tcur + dtd;
-        tcur = seg1; y0 = y1; f0 = k7;
+        S.interp(ca, cb, cc, cd);
+        ce = S.y0;
+        seg0 = tcur; seg1 = tcur + S.dtd;
+        tcur = seg1; S.accept();
       }
-      float fac;
-      if (ratio == 0.f) fac = 10.f;
-      else { fac = 0.9f * powf(ratio, -0.2f); fac = fminf(10.f, fmaxf(fac, ratio < 1.f ? 1.f : 0.2f)); }
-      dtd *= (double)fac;
+      S.dtd *= (double)step_factor<LibmPow>(ratio);
       ++steps;
     }
     const float x = ((float)target - (float)seg0) / ((float)seg1 - (float)seg0);
@@ -252,23 +228,9 @@ __global__ void __launch_bounds__(RNN_BLOCK_SAMPLES * 4) ode_dopri5_fwd_kernel(c
   if (a.nsteps && threadIdx.x == 0) a.nsteps[blockIdx.x] = steps;
 }
 
-int gode_launch_ode_dopri5(const gode_ode_fwd_op* op, hipStream_t st) {
-  if (op->content) {
-    const int rows_per = op->sel_t ? 1 : op->T;
-    int64_t total4 = (int64_t)op->N * rows_per * ((op->zcols - 16) >> 2);
-    int blocks = (int)((total4 + 255) / 256); if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(latent_content_kernel, dim3(blocks), dim3(256), 0, st, op->content, op->z, op->N, rows_per, op->zcols);
-    GODE_LAUNCH_CHECK();
-  }
-  const int nblocks = (op->N + RNN_BLOCK_SAMPLES - 1) / RNN_BLOCK_SAMPLES;
-  const int per = op->N < RNN_BLOCK_SAMPLES ? op->N : RNN_BLOCK_SAMPLES;
-  const int threads = ((per + 15) / 16) * 64;
-  hipLaunchKernelGGL(ode_dopri5_fwd_kernel, dim3(nblocks), dim3(threads), 0, st, *op);
-  GODE_LAUNCH_CHECK();
-  return 0;
-}
-
-int gode_launch_odernn_fwd_mfma(const gode_odernn_fwd_op* op, hipStream_t st) {
+// the content launch (if the op has content), then `kernel` with one workgroup per RNN_BLOCK_SAMPLES trajectories
+template <class Op>
+static int launch_fwd_mfma(void (*kernel)(const Op), const Op* op, hipStream_t st) {
   if (op->content) {
     const int rows_per = op->sel_t ? 1 : op->T;
     int64_t total4 = (int64_t)op->N * rows_per * ((op->zcols - 16) >> 2);
@@ -279,10 +241,12 @@ int gode_launch_odernn_fwd_mfma(const gode_odernn_fwd_op* op, hipStream_t st) {
   const int nblocks = (op->N + RNN_BLOCK_SAMPLES - 1) / RNN_BLOCK_SAMPLES;
   const int per = op->N < RNN_BLOCK_SAMPLES ? op->N : RNN_BLOCK_SAMPLES;
   const int threads = ((per + 15) / 16) * 64;     // every workgroup gets this many waves; trailing lanes are masked
-  hipLaunchKernelGGL(odernn_fwd_kernel, dim3(nblocks), dim3(threads), 0, st, *op);
+  hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(threads), 0, st, *op);
   GODE_LAUNCH_CHECK();
   return 0;
 }
+int gode_launch_ode_dopri5(const gode_ode_fwd_op* op, hipStream_t st) { return launch_fwd_mfma(ode_dopri5_fwd_kernel, op, st); }
+int gode_launch_odernn_fwd_mfma(const gode_odernn_fwd_op* op, hipStream_t st) { return launch_fwd_mfma(odernn_fwd_kernel, op, st); }
 
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) odernn_bwd_kernel(const gode_odernn_bwd_op a) {
@@ -291,7 +255,7 @@ __global__ void __launch_bounds__(64) odernn_bwd_kernel(const gode_odernn_bwd_op
   const int n = blockIdx.x * 16 + s;
   const bool valid = n < a.N;
   const int T = a.T;
-  float* part = a.work + (int64_t)blockIdx.x * RNN_NPARAM;
+  float* part = a.work + (int64_t)blockIdx.x * GODE_ODERNN_NPARAM;
 
   const f32x4 w1 = ld4(a.p.W1 + s * 16 + 4 * g), w2 = ld4(a.p.W2 + s * 16 + 4 * g);
   const f32x4 b1 = ld4(a.p.b1 + 4 * g), b2 = ld4(a.p.b2 + 4 * g);
@@ -407,5 +371,5 @@ int gode_launch_odernn_bwd_mfma(const gode_odernn_bwd_op* op, hipStream_t st) {
     hipLaunchKernelGGL(odernn_bwd_kernel, dim3(nblk), dim3(64), 0, st, *op);
     GODE_LAUNCH_CHECK();
   }
-  return gode_reduce_rows(op->work, op->grads, nblk, RNN_NPARAM, 0, 0, op->accumulate, nullptr, INT32_MAX, 1, st);   // one level
+  return gode_reduce_rows(op->work, op->grads, nblk, GODE_ODERNN_NPARAM, 0, 0, op->accumulate, nullptr, INT32_MAX, 1, st);   // one level
 }

@@ -41,75 +41,190 @@
 #define RV_MAX_TRIALS 20000          // per frame; torchdiffeq's max_num_steps is 2^31 - 1
 #define XS_VALS 8                    // floats per exchange slot of the forward kernels
 
-#define RO_N 2176
-#define RP_M 2176
-#define RP_C 2432
-#define RP_N 2448
+// LDS image of the forward kernel: the gode_odernn_params block (RO_*), then M = W1 W2 and c = W1 b2
+#define RP_M GODE_ODERNN_NPARAM
+#define RP_C (GODE_ODERNN_NPARAM + 256)
+#define RP_N (GODE_ODERNN_NPARAM + 272)
 
 // whole-batch sums (valu_common.h:batch_sum): the per-wave partials added one after the other
 typedef RedLds<RV_WAVES, XS_VALS> RnnRed;
 
-// Stage all 2,176 parameters in LDS with one round of coalesced loads, then M = W1 W2 and c = W1 b2 (fp64 accumulation).
-__device__ __forceinline__ void stage_rnn_params(const gode_odernn_params& p, float* P, bool fused) {
+// What opens the forward kernels of this file: the job (op) of this workgroup and its index inside that job, the lane mapping
+// (lane = (trajectory tl of the wave, feature i)) and the exchange of the job's workgroups.  (The adjoint kernels say why they
+// keep theirs written out.)
+template <class Op> struct JobsV { Op op[RV_MAX_JOBS]; int32_t nblk[RV_MAX_JOBS]; int32_t count; int32_t direct; };   // direct: adjoints only
+struct LanesV { int job, wg, lane, wave, i, tl, n0, n; };
+template <class Op>
+__device__ __forceinline__ LanesV open_job(const JobsV<Op>& J) {
+  int job = 0, wg = blockIdx.x;
+  while (job + 1 < J.count && wg >= J.nblk[job]) { wg -= J.nblk[job]; ++job; }
+  LanesV L;
+  L.job = job; L.wg = wg;
+  L.lane = threadIdx.x & 63; L.wave = threadIdx.x >> 6;
+  L.i = L.lane & 15; L.tl = L.lane >> 4;
+  L.n0 = L.wg * RV_TRAJ; L.n = L.n0 + L.wave * 4 + L.tl;
+  return L;
+}
+__device__ __forceinline__ XSync open_sync(int32_t* sync, int nwg, int wg, RnnRed& R) {
+  XSync X;
+  X.nwg = nwg; X.wg = wg; X.seq = 0;
+  X.counter = sync; X.slots = sync ? reinterpret_cast<float*>(sync) + XS_HDR : nullptr;
+  if (threadIdx.x == 0) R.dead = 0;
+  return X;
+}
+
+// M = W1 W2 and c = W1 b2 (fp64 accumulation) from the staged W1, W2, b2 at the given LDS offsets; ends with a barrier
+__device__ __forceinline__ void fuse_w1w2(float* P, int oW1, int oW2, int oB2, int oM, int oC) {
+  const int t = threadIdx.x;
+  if (t < 256) {
+    const int i = t >> 4, j = t & 15;
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s += (double)P[oW1 + i * 16 + k] * (double)P[oW2 + k * 16 + j];
+    P[oM + t] = (float)s;
+  } else if (t < 272) {
+    const int i = t - 256;
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s += (double)P[oW1 + i * 16 + k] * (double)P[oB2 + k];
+    P[oC + i] = (float)s;
+  }
+  __syncthreads();
+}
+
+// Stage all 2,176 parameters in LDS with one round of coalesced loads
+__device__ __forceinline__ void stage_rnn_params(const gode_odernn_params& p, float* P) {
   const int t = threadIdx.x;
   for (int k = t; k < 256; k += RV_THREADS) { P[RO_W1 + k] = p.W1[k]; P[RO_W2 + k] = p.W2[k]; }
   for (int k = t; k < 768; k += RV_THREADS) { P[RO_WIH + k] = p.Wih[k]; P[RO_WHH + k] = p.Whh[k]; }
   if (t < 16) { P[RO_B1 + t] = p.b1[t]; P[RO_B2 + t] = p.b2[t]; }
   if (t < 48) { P[RO_BIH + t] = p.bih[t]; P[RO_BHH + t] = p.bhh[t]; }
   __syncthreads();
-  if (fused) {
-    if (t < 256) {
-      const int i = t >> 4, j = t & 15;
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) s += (double)P[RO_W1 + i * 16 + k] * (double)P[RO_W2 + k * 16 + j];
-      P[RP_M + t] = (float)s;
-    } else if (t < 272) {
-      const int i = t - 256;
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) s += (double)P[RO_W1 + i * 16 + k] * (double)P[RO_B2 + k];
-      P[RP_C + i] = (float)s;
-    }
-    __syncthreads();
-  }
 }
 
-struct RnnFwdJobs { gode_odernn_fwd_op op[RV_MAX_JOBS]; int32_t nblk[RV_MAX_JOBS]; int32_t count; };
+// The forward dopri5 stepper in the fused algebra of the header (u = W1 y + b1 integrated, q_j = M h_j + c): both forward
+// kernels drive it from their own outer loops (clock, stall rule, dense output, stores).
+struct FwdV {
+  W16 Mw, w1, w2;
+  float b1, b2, cq, rtol, atol, inv_count;
+  bool valid;
+  RnnRed* R;
+  XSync X;
+  int par;
+  // the accepted state: q = M h + c, h = tanh(u), u = W1 y + b1, y.  (In THIS order: it decides how the compiler pairs the
+  // loop-carried values into packed fp32 operations, hence which multiply-adds of odernn_fwd_valu_kernel fuse -- its bits.)
+  float q1, h1, u0, y0;
+  double dtd;                        // step size (fp64, as torchdiffeq keeps it)
+  float dt, h3, h4, h5, h6, h7, Hb, y1, u7, q7;      // the last trial step
+#ifdef GODE_ODE_STAMPS
+  long long acc_stage = 0, acc_mv = 0, acc_sum = 0, acc_ctl = 0, last_end = 0, acc_trials = 0;
+#endif
+
+  // whole-batch RMS of a per-lane value
+  __device__ __forceinline__ float rms(float q) {
+    float v[1] = {valid ? q * q : 0.f};
+    batch_sum<1>(v, *R, par, X);
+    return sqrtf(v[0] * inv_count);
+  }
+  // start a solve at y: the accepted state and torchdiffeq's _select_initial_step (order 4)
+  __device__ __forceinline__ void start(float y) {
+    y0 = y;
+    u0 = mv16c(w1, y0, b1);
+    h1 = fast_tanh(u0);
+    q1 = mv16c(Mw, h1, cq);
+    const float f0 = mv16c(w2, h1, b2);
+    const float sc = atol + fabsf(y0) * rtol;
+    float v[2] = {valid ? (y0 / sc) * (y0 / sc) : 0.f, valid ? (f0 / sc) * (f0 / sc) : 0.f};
+    batch_sum<2>(v, *R, par, X);
+    const float d0 = sqrtf(v[0] * inv_count), d1 = sqrtf(v[1] * inv_count);
+    const float h0 = initial_h0(d0, d1);
+    const float df = mv16c(w2, fast_tanh(fmaf(h0, q1, u0)) - h1, 0.f);          // f(y0 + h0 f0) - f0
+    const float d2 = rms(df / sc) / h0;
+    dtd = (double)initial_step<FastPow>(h0, d1, d2);
+  }
+  // one trial step of size dtd from the accepted state; returns the error ratio (accept when <= 1)
+  __device__ __forceinline__ float trial() {
+#ifdef GODE_ODE_STAMPS
+    const long long sA = __builtin_amdgcn_s_memtime();
+#endif
+    dt = (float)dtd;
+    const float h2 = fast_tanh(fmaf(dt * DP5_A21, q1, u0));
+    const float q2 = mv16c(Mw, h2, cq);
+    h3 = fast_tanh(fmaf(dt, DP5_A31 * q1 + DP5_A32 * q2, u0));
+    const float q3 = mv16c(Mw, h3, cq);
+    h4 = fast_tanh(fmaf(dt, DP5_A41 * q1 + DP5_A42 * q2 + DP5_A43 * q3, u0));
+    const float q4 = mv16c(Mw, h4, cq);
+    h5 = fast_tanh(fmaf(dt, DP5_A51 * q1 + DP5_A52 * q2 + DP5_A53 * q3 + DP5_A54 * q4, u0));
+    const float q5 = mv16c(Mw, h5, cq);
+    h6 = fast_tanh(fmaf(dt, DP5_A61 * q1 + DP5_A62 * q2 + DP5_A63 * q3 + DP5_A64 * q4 + DP5_A65 * q5, u0));
+    const float q6 = mv16c(Mw, h6, cq);
+    u7 = fmaf(dt, DP5_B1 * q1 + DP5_B3 * q3 + DP5_B4 * q4 + DP5_B5 * q5 + DP5_B6 * q6, u0);
+    h7 = fast_tanh(u7);
+#ifdef GODE_ODE_STAMPS
+    asm volatile("" ::"v"(h7));
+    const long long sB = __builtin_amdgcn_s_memtime();
+#endif
+    Hb = DP5_B1 * h1 + DP5_B3 * h3 + DP5_B4 * h4 + DP5_B5 * h5 + DP5_B6 * h6;
+    const float He = DP5_E1 * h1 + DP5_E3 * h3 + DP5_E4 * h4 + DP5_E5 * h5 + DP5_E6 * h6 + DP5_E7 * h7;
+    y1 = fmaf(dt, mv16c(w2, Hb, b2), y0);
+    const float err = dt * mv16c(w2, He, 0.f);
+    const float tol = atol + rtol * fmaxf(fabsf(y0), fabsf(y1));
+    const float rr = err / tol;
+    float v[1] = {valid ? rr * rr : 0.f};
+    q7 = mv16c(Mw, h7, cq);            // next step's q1 if this one is accepted: issued under the sum's latency
+#ifdef GODE_ODE_STAMPS
+    asm volatile("" ::"v"(q7), "v"(v[0]));
+    const long long sC = __builtin_amdgcn_s_memtime();
+#endif
+    batch_sum<1>(v, *R, par, X);
+    const float ratio = sqrtf(v[0] * inv_count);
+#ifdef GODE_ODE_STAMPS
+    {
+      const long long sD = __builtin_amdgcn_s_memtime();
+      acc_stage += sB - sA; acc_mv += sC - sB; acc_sum += sD - sC; acc_trials += 1;
+      if (last_end) acc_ctl += sA - last_end;
+      last_end = sD;
+    }
+#endif
+    return ratio;
+  }
+  // mid-point combination of the last trial's stages (dense output)
+  __device__ __forceinline__ float Hm() const { return DP5_C1 * h1 + DP5_C3 * h3 + DP5_C4 * h4 + DP5_C5 * h5 + DP5_C6 * h6 + DP5_C7 * h7; }
+  // the last trial becomes the accepted state
+  __device__ __forceinline__ void accept() { y0 = y1; u0 = u7; h1 = h7; q1 = q7; }
+};
+
+typedef JobsV<gode_odernn_fwd_op> RnnFwdJobs;
 
 __global__ void __launch_bounds__(RV_THREADS) odernn_fwd_valu_kernel(const RnnFwdJobs J) {
   __shared__ float P[RP_N];
   __shared__ RnnRed R;
-  int job = 0, wg = blockIdx.x;
-  while (job + 1 < J.count && wg >= J.nblk[job]) { wg -= J.nblk[job]; ++job; }
-  const gode_odernn_fwd_op a = J.op[job];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = lane & 15, tl = lane >> 4;
-  const int n0 = wg * RV_TRAJ, n = n0 + wave * 4 + tl;
+  const LanesV L = open_job(J);
+  const gode_odernn_fwd_op a = J.op[L.job];
+  const int wg = L.wg, i = L.i, n = L.n;
   const bool valid = n < a.N;
   const int T = a.T;
-  const float inv_count = 1.f / ((float)a.N * 16.f);
-  float rtol = a.rtol, atol = a.atol;
-  XSync X;
-  X.nwg = J.nblk[job]; X.wg = wg; X.seq = 0;
-  X.counter = a.sync; X.slots = a.sync ? reinterpret_cast<float*>(a.sync) + XS_HDR : nullptr;
-  int par = 0;
-  if (threadIdx.x == 0) R.dead = 0;
+  FwdV S;
+  S.valid = valid; S.R = &R; S.par = 0;
+  S.inv_count = 1.f / ((float)a.N * 16.f);
+  S.rtol = a.rtol; S.atol = a.atol;
+  S.X = open_sync(a.sync, J.nblk[L.job], wg, R);
 
 #ifdef GODE_ODE_STAMPS
   const long long st0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-  long long acc_stage = 0, acc_mv = 0, acc_sum = 0, acc_ctl = 0, last_end = 0, acc_trials = 0, st_loop = 0;
+  long long st_loop = 0;
 #endif
   float h = valid ? a.noise[(int64_t)n * 16 + i] : 0.f;
-  stage_rnn_params(a.p, P, true);
-  if (a.content) broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, n0, RV_TRAJ, threadIdx.x, RV_THREADS);      // stores only
+  stage_rnn_params(a.p, P);
+  fuse_w1w2(P, RO_W1, RO_W2, RO_B2, RP_M, RP_C);
+  if (a.content) broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, L.n0, RV_TRAJ, threadIdx.x, RV_THREADS);      // stores only
 
   int src[16];
   probe_sources(i, src);
-  W16 Mw, w1, w2, wih[3], whh[3];
-  load_rows(Mw, P + RP_M, 16, 0, 0, i, src);
-  load_rows(w1, P + RO_W1, 16, 0, 0, i, src);
-  load_rows(w2, P + RO_W2, 16, 0, 0, i, src);
+  W16 wih[3], whh[3];
+  load_rows(S.Mw, P + RP_M, 16, 0, 0, i, src);
+  load_rows(S.w1, P + RO_W1, 16, 0, 0, i, src);
+  load_rows(S.w2, P + RO_W2, 16, 0, 0, i, src);
   float bih[3], bhh[3];
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
@@ -117,7 +232,7 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_fwd_valu_kernel(const RnnFw
     load_rows(whh[q], P + RO_WHH, 16, 16 * q, 0, i, src);
     bih[q] = P[RO_BIH + 16 * q + i]; bhh[q] = P[RO_BHH + 16 * q + i];
   }
-  const float b1 = P[RO_B1 + i], b2 = P[RO_B2 + i], cq = P[RP_C + i];
+  S.b1 = P[RO_B1 + i]; S.b2 = P[RO_B2 + i]; S.cq = P[RP_C + i];
   const int tsel = (a.sel_t && valid) ? a.sel_t[n] : -1;
   if (valid && a.hs) a.hs[((int64_t)n * (T + 1)) * 16 + i] = h;
 
@@ -126,93 +241,33 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_fwd_valu_kernel(const RnnFw
 #endif
   for (int t = 0; t < T; ++t) {
 #ifdef GODE_ODE_STAMPS
-    last_end = 0;
+    S.last_end = 0;
 #endif
     // (this frame's GRU input is requested now: a dependent ~2 us HBM round trip that would otherwise sit between the
     // solve and the GRU on every frame -- 25 % of the launch in the stamped build)
     const float e = valid ? a.noise[((int64_t)(t + 1) * a.N + n) * 16 + i] : 0.f;
     // ---- h' = y(1), y' = f(y), y(0) = h.  The clock and the step size are fp64, as torchdiffeq keeps them.
-    float y0 = h;
-    float u0 = mv16c(w1, y0, b1);
-    float h1 = fast_tanh(u0);
-    float q1 = mv16c(Mw, h1, cq);
-    double dtd;
-    {   // torchdiffeq _select_initial_step (order 4)
-      const float f0 = mv16c(w2, h1, b2);
-      const float sc = atol + fabsf(y0) * rtol;
-      float v[2] = {valid ? (y0 / sc) * (y0 / sc) : 0.f, valid ? (f0 / sc) * (f0 / sc) : 0.f};
-      batch_sum<2>(v, R, par, X);
-      const float d0 = sqrtf(v[0] * inv_count), d1 = sqrtf(v[1] * inv_count);
-      const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
-      const float df = mv16c(w2, fast_tanh(fmaf(h0, q1, u0)) - h1, 0.f);          // f(y0 + h0 f0) - f0
-      float w[1] = {valid ? (df / sc) * (df / sc) : 0.f};
-      batch_sum<1>(w, R, par, X);
-      const float d2 = sqrtf(w[0] * inv_count) / h0;
-      const float hh = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : fast_pow(0.01f / fmaxf(d1, d2), 0.2f);
-      dtd = (double)fminf(100.f * h0, hh);
-    }
+    S.start(h);
     double tcur = 0.0;
-    float yend = y0;
+    float yend = S.y0;
     int steps = 0;
     bool stalled = false;
     for (;;) {
-      if (R.dead || steps >= RV_MAX_TRIALS || !(tcur + dtd > tcur)) { stalled = true; break; }
-#ifdef GODE_ODE_STAMPS
-      const long long sA = __builtin_amdgcn_s_memtime();
-#endif
-      const float dt = (float)dtd;
-      const float h2 = fast_tanh(fmaf(dt * DP5_A21, q1, u0));
-      const float q2 = mv16c(Mw, h2, cq);
-      const float h3 = fast_tanh(fmaf(dt, DP5_A31 * q1 + DP5_A32 * q2, u0));
-      const float q3 = mv16c(Mw, h3, cq);
-      const float h4 = fast_tanh(fmaf(dt, DP5_A41 * q1 + DP5_A42 * q2 + DP5_A43 * q3, u0));
-      const float q4 = mv16c(Mw, h4, cq);
-      const float h5 = fast_tanh(fmaf(dt, DP5_A51 * q1 + DP5_A52 * q2 + DP5_A53 * q3 + DP5_A54 * q4, u0));
-      const float q5 = mv16c(Mw, h5, cq);
-      const float h6 = fast_tanh(fmaf(dt, DP5_A61 * q1 + DP5_A62 * q2 + DP5_A63 * q3 + DP5_A64 * q4 + DP5_A65 * q5, u0));
-      const float q6 = mv16c(Mw, h6, cq);
-      const float u7 = fmaf(dt, DP5_B1 * q1 + DP5_B3 * q3 + DP5_B4 * q4 + DP5_B5 * q5 + DP5_B6 * q6, u0);
-      const float h7 = fast_tanh(u7);
-#ifdef GODE_ODE_STAMPS
-      asm volatile("" ::"v"(h7));
-      const long long sB = __builtin_amdgcn_s_memtime();
-#endif
-      const float Hb = DP5_B1 * h1 + DP5_B3 * h3 + DP5_B4 * h4 + DP5_B5 * h5 + DP5_B6 * h6;
-      const float He = DP5_E1 * h1 + DP5_E3 * h3 + DP5_E4 * h4 + DP5_E5 * h5 + DP5_E6 * h6 + DP5_E7 * h7;
-      const float y1 = fmaf(dt, mv16c(w2, Hb, b2), y0);
-      const float err = dt * mv16c(w2, He, 0.f);
-      const float tol = atol + rtol * fmaxf(fabsf(y0), fabsf(y1));
-      const float rr = err / tol;
-      float v[1] = {valid ? rr * rr : 0.f};
-      const float q7 = mv16c(Mw, h7, cq);            // next step's q1 if this one is accepted: issued under the sum's latency
-#ifdef GODE_ODE_STAMPS
-      asm volatile("" ::"v"(q7), "v"(v[0]));
-      const long long sC = __builtin_amdgcn_s_memtime();
-#endif
-      batch_sum<1>(v, R, par, X);
-      const float ratio = sqrtf(v[0] * inv_count);
+      if (R.dead || steps >= RV_MAX_TRIALS || !(tcur + S.dtd > tcur)) { stalled = true; break; }
+      const float ratio = S.trial();
       ++steps;
-#ifdef GODE_ODE_STAMPS
-      {
-        const long long sD = __builtin_amdgcn_s_memtime();
-        acc_stage += sB - sA; acc_mv += sC - sB; acc_sum += sD - sC; acc_trials += 1;
-        if (last_end) acc_ctl += sA - last_end;
-        last_end = sD;
-      }
-#endif
       if (ratio <= 1.f) {
-        if (tcur + dtd >= 1.0) {   // dense output at t = 1 (4th-order interpolant through the mid-point)
-          const float x = (float)((1.0 - tcur) / dtd);
+        if (tcur + S.dtd >= 1.0) {   // dense output at t = 1 (4th-order interpolant through the mid-point)
+          const float x = (float)((1.0 - tcur) / S.dtd);
           float wS, wM, w1c, w7c;
           interp_weights(x, wS, wM, w1c, w7c);
-          const float Hm = DP5_C1 * h1 + DP5_C3 * h3 + DP5_C4 * h4 + DP5_C5 * h5 + DP5_C6 * h6 + DP5_C7 * h7;
-          const float Hx = wS * Hb + wM * Hm + w1c * h1 + w7c * h7;
-          yend = fmaf(dt, mv16c(w2, Hx, b2 * (wS + 0.5f * wM + w1c + w7c)), y0);
+          const float Hx = wS * S.Hb + wM * S.Hm() + w1c * S.h1 + w7c * S.h7;
+          yend = fmaf(S.dt, mv16c(S.w2, Hx, S.b2 * (wS + 0.5f * wM + w1c + w7c)), S.y0);
           break;
         }
-        tcur += dtd; y0 = y1; u0 = u7; h1 = h7; q1 = q7;
+        tcur += S.dtd; S.accept();
       }
-      dtd *= (double)step_factor(ratio);
+      S.dtd *= (double)step_factor(ratio);
     }
     if (a.nsteps && wg == 0 && threadIdx.x == 0) a.nsteps[t] = stalled ? -steps - 1 : steps;
     if (stalled) return;              // uniform over the workgroup (and, through the shared norm, over the call)
@@ -233,8 +288,8 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_fwd_valu_kernel(const RnnFw
     const long long st1 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
     printf("odernn_fwd_valu: %lld cycles in %.1f us -> %.0f MHz; set-up %lld; %lld trial steps: 6 stages %lld | y1, err, q7 mat-vecs %lld | "
            "batch sum %lld | controller %lld; rest of the frames (initial step, dense output, GRU, stores) %lld\n",
-           st1 - st0, (double)(rt1 - rt0) / 100.0, (double)(st1 - st0) / ((double)(rt1 - rt0) / 100.0), st_loop - st0, acc_trials,
-           acc_stage, acc_mv, acc_sum, acc_ctl, (st1 - st_loop) - acc_stage - acc_mv - acc_sum - acc_ctl);
+           st1 - st0, (double)(rt1 - rt0) / 100.0, (double)(st1 - st0) / ((double)(rt1 - rt0) / 100.0), st_loop - st0, S.acc_trials,
+           S.acc_stage, S.acc_mv, S.acc_sum, S.acc_ctl, (st1 - st_loop) - S.acc_stage - S.acc_mv - S.acc_sum - S.acc_ctl);
   }
 #endif
 }
@@ -255,38 +310,95 @@ static bool rnn_fwd_args_ok(const gode_odernn_fwd_op* op) {
 
 int gode_launch_odernn_fwd_mfma(const gode_odernn_fwd_op* op, hipStream_t st);   // odernn.hip (fallback above the co-residency limit)
 
-extern "C" int gode_odernn_fwd_multi(const gode_odernn_fwd_op* ops, int32_t count, void* stream) {
+// ---- the `_multi` launchers --------------------------------------------------------------------------------------------
+// Which kernel each op of a `_multi` call takes.  An op of more than one workgroup spins on its exchange; when the spinning
+// workgroups of a call are more than are guaranteed co-resident (RV_MAX_WGS), those ops take the MFMA kernels (one norm per
+// 64-trajectory workgroup, see the header), and so does an op that `never_valu` names; one-workgroup ops stay here.
+struct RouteV { int32_t nblk[RV_MAX_JOBS]; bool mfma[RV_MAX_JOBS]; bool any_mfma; };
+template <class Op, class Ok, class Never>
+static int route_ops(const Op* ops, int count, Ok args_ok, Never never_valu, RouteV& R) {
   if (!ops || count < 1 || count > RV_MAX_JOBS) return GODE_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  RnnFwdJobs J;
-  J.count = 0;
-  int spinning = 0;      // workgroups that wait for each other (solves of more than one workgroup)
+  int spinning = 0;
   for (int k = 0; k < count; ++k) {
-    if (!rnn_fwd_args_ok(&ops[k])) return GODE_E_ARG;
-    const int nblk = (ops[k].N + RV_TRAJ - 1) / RV_TRAJ;
-    if (nblk > 1) spinning += nblk;
+    if (!args_ok(&ops[k])) return GODE_E_ARG;
+    R.nblk[k] = (ops[k].N + RV_TRAJ - 1) / RV_TRAJ;
+    R.mfma[k] = never_valu(ops[k], R.nblk[k]);
+    if (!R.mfma[k] && R.nblk[k] > 1) spinning += R.nblk[k];
   }
+  R.any_mfma = false;
   for (int k = 0; k < count; ++k) {
-    const int nblk = (ops[k].N + RV_TRAJ - 1) / RV_TRAJ;
-    if (spinning > RV_MAX_WGS && nblk > 1) {
-      // too many workgroups to guarantee co-residency of a spinning launch: these solves take the MFMA kernel with one
-      // norm per 64-trajectory workgroup (see the header); one-workgroup solves stay below
-      const int rc = gode_launch_odernn_fwd_mfma(&ops[k], st);
-      if (rc) return rc;
-      continue;
-    }
-    if (nblk > 1) {
-      const hipError_t e = hipMemsetAsync(ops[k].sync, 0, XS_HDR * sizeof(int32_t), st);
-      if (e != hipSuccess) return (int)e;
-    }
-    J.op[J.count] = ops[k]; J.nblk[J.count] = nblk; J.count += 1;
+    if (R.nblk[k] > 1 && spinning > RV_MAX_WGS) R.mfma[k] = true;
+    R.any_mfma = R.any_mfma || R.mfma[k];
   }
-  if (J.count == 0) return 0;
+  return 0;
+}
+// an op joins the job table of a launch: its exchange header is zeroed on the stream first
+template <class Op>
+static int add_job(JobsV<Op>& J, const Op& op, int nblk, hipStream_t st) {
+  if (nblk > 1) {
+    const hipError_t e = hipMemsetAsync(op.sync, 0, XS_HDR * sizeof(int32_t), st);
+    if (e != hipSuccess) return (int)e;
+  }
+  J.op[J.count] = op; J.nblk[J.count] = nblk; J.count += 1;
+  return 0;
+}
+template <class Op>
+static int launch_jobs(void (*kernel)(const JobsV<Op>), JobsV<Op>& J, bool adjoint, hipStream_t st) {
   int grid = 0;
   for (int k = 0; k < J.count; ++k) grid += J.nblk[k];
-  hipLaunchKernelGGL(odernn_fwd_valu_kernel, dim3(grid), dim3(RV_THREADS), 0, st, J);
+  J.direct = (adjoint && J.count == 1 && grid == 1) ? 1 : 0;     // ONE workgroup in all: it writes grads itself
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(RV_THREADS), 0, st, J);
   GODE_LAUNCH_CHECK();
   return 0;
+}
+// forward solves: the ops that stay on the VALU kernel share ONE launch, issued after the fallback ops' own launches
+template <class Op, class Ok, class Never, class Fallback>
+static int fwd_multi(void (*kernel)(const JobsV<Op>), const Op* ops, int count, hipStream_t st, Ok args_ok, Never never_valu, Fallback fallback) {
+  RouteV R;
+  int rc = route_ops(ops, count, args_ok, never_valu, R);
+  if (rc) return rc;
+  JobsV<Op> J;
+  J.count = 0;
+  for (int k = 0; k < count; ++k) {
+    rc = R.mfma[k] ? fallback(&ops[k], st) : add_job(J, ops[k], R.nblk[k], st);
+    if (rc) return rc;
+  }
+  return J.count ? launch_jobs(kernel, J, false, st) : 0;
+}
+// adjoints: one launch, then `rows(ops, count, A)` + latent_rows_kernel add the work rows of each group of ops that share a
+// `grads`.  With a fallback op in the call the ops run one after the other in array order (each with its own accumulate flag),
+// the fallback ones on their MFMA kernels.
+template <class Op, class Rows>
+static int bwd_launch(void (*kernel)(const JobsV<Op>), const Op* ops, int count, const int32_t* nblk, hipStream_t st, Rows rows) {
+  JobsV<Op> J;
+  J.count = 0;
+  for (int k = 0; k < count; ++k) {
+    const int rc = add_job(J, ops[k], nblk[k], st);
+    if (rc) return rc;
+  }
+  const int rc = launch_jobs(kernel, J, true, st);
+  if (rc || J.direct) return rc;
+  return gode_for_each_grads_group(ops, nblk, count, [&](RowsArgs& A) {
+    rows(ops, count, A);
+    return gode_launch_rows(A, st);
+  });
+}
+template <class Op, class Ok, class Never, class Fallback, class Rows>
+static int bwd_multi(void (*kernel)(const JobsV<Op>), const Op* ops, int count, hipStream_t st, Ok args_ok, Never never_valu, Fallback fallback, Rows rows) {
+  RouteV R;
+  int rc = route_ops(ops, count, args_ok, never_valu, R);
+  if (rc) return rc;
+  if (!R.any_mfma) return bwd_launch(kernel, ops, count, R.nblk, st, rows);
+  for (int k = 0; k < count; ++k) {
+    rc = R.mfma[k] ? fallback(&ops[k], st) : bwd_launch(kernel, &ops[k], 1, &R.nblk[k], st, rows);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+extern "C" int gode_odernn_fwd_multi(const gode_odernn_fwd_op* ops, int32_t count, void* stream) {
+  return fwd_multi(odernn_fwd_valu_kernel, ops, count, (hipStream_t)stream, rnn_fwd_args_ok,
+                   [](const gode_odernn_fwd_op&, int) { return false; }, gode_launch_odernn_fwd_mfma);
 }
 
 extern "C" int gode_odernn_fwd(const gode_odernn_fwd_op* op, void* stream) { return gode_odernn_fwd_multi(op, 1, stream); }
@@ -512,7 +624,7 @@ struct AdjV {
       theta_acc(X1, 1.f, a0, h1, du1, y0);
       put_image(0, X1, 1.f);
       const float d1 = mixed(k1y / scy, k1a / sca, 0);
-      const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+      const float h0 = initial_h0(d0, d1);
       float fy, fa, hb, dub;
       const float yb = fmaf(h0, k1y, y0), ab = fmaf(h0, k1a, a0);
       eval(yb, ab, fy, fa, hb, dub);
@@ -521,8 +633,7 @@ struct AdjV {
       theta_acc(Xd, -1.f, a0, h1, du1, y0);
       put_image(0, Xd, 1.f);
       const float d2 = mixed((fy - k1y) / scy, (fa - k1a) / sca, 0) / h0;
-      const float hh = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : fast_pow(0.01f / fmaxf(d1, d2), 0.2f);
-      dtd = (double)fminf(100.f * h0, hh);
+      dtd = (double)initial_step<FastPow>(h0, d1, d2);
     }
     double tcur = tau0;
     const int step_limit = steps + RV_MAX_TRIALS;
@@ -588,13 +699,15 @@ struct AdjV {
   }
 };
 
-struct RnnBwdJobs { gode_odernn_bwd_op op[RV_MAX_JOBS]; int32_t nblk[RV_MAX_JOBS]; int32_t count; int32_t direct; };
+typedef JobsV<gode_odernn_bwd_op> RnnBwdJobs;
 
 __global__ void __launch_bounds__(RV_THREADS) odernn_bwd_valu_kernel(const RnnBwdJobs J) {
   __shared__ float P[TH_N + 96];       // W1, b1, W2, b2 (gradient-vector order), bih, bhh
   __shared__ float GP[GP_N];           // Wih, Whh with padded rows
   __shared__ AdjLdsV lds;
   __shared__ RnnRed R;
+  // (the adjoint kernels keep their prologue written out: through open_job / open_sync, or through a member of AdjV, the
+  // compiler allocates this kernel's scalar registers differently and it measured 1 % slower)
   int job = 0, wg = blockIdx.x;
   while (job + 1 < J.count && wg >= J.nblk[job]) { wg -= J.nblk[job]; ++job; }
   const gode_odernn_bwd_op a = J.op[job];
@@ -712,7 +825,7 @@ __global__ void __launch_bounds__(RV_THREADS) odernn_bwd_valu_kernel(const RnnBw
   // ---- output: a launch of ONE workgroup writes (or adds to) grads directly; otherwise every workgroup writes one row of
   // its op's `work` (the ODEFunc block holds the BATCH total in every workgroup of an op: row 0 carries it, the other rows
   // carry zeros) and latent_rows_kernel adds the rows in fixed order
-  float* out = J.direct ? a.grads : a.work + (int64_t)wg * RO_N;
+  float* out = J.direct ? a.grads : a.work + (int64_t)wg * GODE_ODERNN_NPARAM;
   const bool direct_acc = J.direct && a.accumulate;
   __syncthreads();
 #pragma unroll
@@ -743,53 +856,13 @@ static bool rnn_bwd_args_ok(const gode_odernn_bwd_op* op) {
   return true;
 }
 
-extern "C" int64_t gode_odernn_bwd_work_size(int32_t N) { return (int64_t)((N + 15) / 16) * RO_N; }
+extern "C" int64_t gode_odernn_bwd_work_size(int32_t N) { return (int64_t)((N + 15) / 16) * GODE_ODERNN_NPARAM; }
 
-static int rnn_bwd_launch(const gode_odernn_bwd_op* ops, int count, hipStream_t st) {
-  RnnBwdJobs J;
-  J.count = count;
-  int grid = 0;
-  for (int k = 0; k < count; ++k) {
-    const int nblk = (ops[k].N + RV_TRAJ - 1) / RV_TRAJ;
-    if (nblk > 1) {
-      const hipError_t e = hipMemsetAsync(ops[k].sync, 0, XS_HDR * sizeof(int32_t), st);
-      if (e != hipSuccess) return (int)e;
-    }
-    J.op[k] = ops[k]; J.nblk[k] = nblk;
-    grid += nblk;
-  }
-  J.direct = (count == 1 && grid == 1) ? 1 : 0;
-  hipLaunchKernelGGL(odernn_bwd_valu_kernel, dim3(grid), dim3(RV_THREADS), 0, st, J);
-  GODE_LAUNCH_CHECK();
-  if (J.direct) return 0;
-  return gode_for_each_grads_group(ops, J.nblk, count, [&](RowsArgs& A) {
-    A.nparam = RO_N; A.first = 0;
-    return gode_launch_rows(A, st);
-  });
-}
-
+// fixed Kutta-3/8 substeps always run on odernn.hip's kernel
 extern "C" int gode_odernn_bwd_multi(const gode_odernn_bwd_op* ops, int32_t count, void* stream) {
-  if (!ops || count < 1 || count > RV_MAX_JOBS) return GODE_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  int spinning = 0;
-  bool fallback = false;
-  for (int k = 0; k < count; ++k) {
-    if (!rnn_bwd_args_ok(&ops[k])) return GODE_E_ARG;
-    const int nblk = (ops[k].N + RV_TRAJ - 1) / RV_TRAJ;
-    if (ops[k].substeps > 0) fallback = true;
-    else if (nblk > 1) spinning += nblk;
-  }
-  if (spinning > RV_MAX_WGS) fallback = true;
-  if (!fallback) return rnn_bwd_launch(ops, count, st);
-  // fixed Kutta-3/8 substeps, or more spinning workgroups than are guaranteed co-resident: the ops run one after the other
-  // in array order (each with its own accumulate flag), the affected ones on the MFMA kernels of odernn.hip
-  for (int k = 0; k < count; ++k) {
-    const int nblk = (ops[k].N + RV_TRAJ - 1) / RV_TRAJ;
-    const bool mfma = ops[k].substeps > 0 || (nblk > 1 && spinning > RV_MAX_WGS);
-    const int rc = mfma ? gode_launch_odernn_bwd_mfma(&ops[k], st) : rnn_bwd_launch(&ops[k], 1, st);
-    if (rc) return rc;
-  }
-  return 0;
+  return bwd_multi(odernn_bwd_valu_kernel, ops, count, (hipStream_t)stream, rnn_bwd_args_ok,
+                   [](const gode_odernn_bwd_op& op, int) { return op.substeps > 0; }, gode_launch_odernn_bwd_mfma,
+                   [](const gode_odernn_bwd_op*, int, RowsArgs& A) { A.nparam = GODE_ODERNN_NPARAM; A.first = 0; });
 }
 
 extern "C" int gode_odernn_bwd(const gode_odernn_bwd_op* op, void* stream) { return gode_odernn_bwd_multi(op, 1, stream); }
@@ -808,65 +881,47 @@ extern "C" int gode_odernn_bwd(const gode_odernn_bwd_op* op, void* stream) { ret
 #define DP_C (GODE_ODE_NPARAM + 256)
 #define DP_N (GODE_ODE_NPARAM + 272)
 
-struct OdeFwdJobs { gode_ode_fwd_op op[RV_MAX_JOBS]; int32_t nblk[RV_MAX_JOBS]; int32_t count; };
+typedef JobsV<gode_ode_fwd_op> OdeFwdJobs;
 
 __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_fwd_valu_kernel(const OdeFwdJobs J) {
   __shared__ float P[DP_N];
   __shared__ RnnRed R;
-  int job = 0, wg = blockIdx.x;
-  while (job + 1 < J.count && wg >= J.nblk[job]) { wg -= J.nblk[job]; ++job; }
-  const gode_ode_fwd_op a = J.op[job];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = lane & 15, tl = lane >> 4;
-  const int n0 = wg * RV_TRAJ, n = n0 + wave * 4 + tl;
+  const LanesV L = open_job(J);
+  const gode_ode_fwd_op a = J.op[L.job];
+  const int wg = L.wg, i = L.i, n = L.n;
   const bool valid = n < a.N;
   const int T = a.T;
-  const float inv_count = 1.f / ((float)a.N * 16.f);
-  const float rtol = a.rtol, atol = a.atol;
-  XSync X;
-  X.nwg = J.nblk[job]; X.wg = wg; X.seq = 0;
-  X.counter = a.sync; X.slots = a.sync ? reinterpret_cast<float*>(a.sync) + XS_HDR : nullptr;
-  int par = 0;
-  if (threadIdx.x == 0) R.dead = 0;
+  FwdV S;
+  S.valid = valid; S.R = &R; S.par = 0;
+  S.inv_count = 1.f / ((float)a.N * 16.f);
+  S.rtol = a.rtol; S.atol = a.atol;
+  S.X = open_sync(a.sync, J.nblk[L.job], wg, R);
 
-  float y0 = valid ? a.x[(int64_t)n * 16 + i] : 0.f;
+  float x0 = valid ? a.x[(int64_t)n * 16 + i] : 0.f;
   stage_ode_params<RV_THREADS>(a.p, a.prenet, P);
-  if (threadIdx.x < 256) {           // M = W1 W2, c = W1 b2 (fp64 accumulation)
-    const int r = threadIdx.x >> 4, j = threadIdx.x & 15;
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s += (double)P[OFF_W1 + r * 16 + k] * (double)P[OFF_W2 + k * 16 + j];
-    P[DP_M + threadIdx.x] = (float)s;
-  } else if (threadIdx.x < 272) {
-    const int r = threadIdx.x - 256;
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s += (double)P[OFF_W1 + r * 16 + k] * (double)P[OFF_B2 + k];
-    P[DP_C + r] = (float)s;
-  }
-  __syncthreads();
-  if (a.content) broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, n0, RV_TRAJ, threadIdx.x, RV_THREADS);      // stores only
+  fuse_w1w2(P, OFF_W1, OFF_W2, OFF_B2, DP_M, DP_C);
+  if (a.content) broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, L.n0, RV_TRAJ, threadIdx.x, RV_THREADS);      // stores only
 
   int src[16];
   probe_sources(i, src);
   if (a.prenet) {
-    // Linear(16,64) -> LReLU -> Linear(64,16) -> LReLU: the 64 hidden units as four row-resident chunks
+    // Linear(16,64) -> LReLU -> Linear(64,16) -> LReLU: the 64 hidden units as four row-resident chunks (valu_common.h's
+    // prenet_fwd on the one-chain mat-vec: a different instruction sequence, so not interchangeable)
     float acc = P[OFF_BB + i];
 #pragma unroll 1
     for (int m = 0; m < 4; ++m) {
       W16 wa, wb;
       load_rows(wa, P + OFF_WA, 16, 16 * m, 0, i, src);
       load_rows(wb, P + OFF_WB, 64, 0, 16 * m, i, src);
-      const float hh = lrelu1(mv16c(wa, y0, P[OFF_BA + 16 * m + i]));
+      const float hh = lrelu1(mv16c(wa, x0, P[OFF_BA + 16 * m + i]));
       acc = mv16c(wb, hh, acc);
     }
-    y0 = lrelu1(acc);
+    x0 = lrelu1(acc);
   }
-  W16 Mw, w1, w2;
-  load_rows(Mw, P + DP_M, 16, 0, 0, i, src);
-  load_rows(w1, P + OFF_W1, 16, 0, 0, i, src);
-  load_rows(w2, P + OFF_W2, 16, 0, 0, i, src);
-  const float b1 = P[OFF_B1 + i], b2 = P[OFF_B2 + i], cq = P[DP_C + i];
+  load_rows(S.Mw, P + DP_M, 16, 0, 0, i, src);
+  load_rows(S.w1, P + OFF_W1, 16, 0, 0, i, src);
+  load_rows(S.w2, P + OFF_W2, 16, 0, 0, i, src);
+  S.b1 = P[OFF_B1 + i]; S.b2 = P[OFF_B2 + i]; S.cq = P[DP_C + i];
   const int tsel = (a.sel_t && valid) ? a.sel_t[n] : -1;
   auto emit = [&](int t, float v) {
     if (!valid) return;
@@ -874,66 +929,27 @@ __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_fwd_valu_kernel(const O
     if (a.sel_t == nullptr) a.z[((int64_t)n * T + t) * a.zcols + i] = v;
     else if (t == tsel) a.z[(int64_t)n * a.zcols + i] = v;
   };
-  emit(0, y0);
+  emit(0, x0);
 
-  float u0 = mv16c(w1, y0, b1);
-  float h1 = fast_tanh(u0);
-  float q1 = mv16c(Mw, h1, cq);
-  double dtd;
-  {   // torchdiffeq _select_initial_step (order 4)
-    const float f0 = mv16c(w2, h1, b2);
-    const float sc = atol + fabsf(y0) * rtol;
-    float v[2] = {valid ? (y0 / sc) * (y0 / sc) : 0.f, valid ? (f0 / sc) * (f0 / sc) : 0.f};
-    batch_sum<2>(v, R, par, X);
-    const float d0 = sqrtf(v[0] * inv_count), d1 = sqrtf(v[1] * inv_count);
-    const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
-    const float df = mv16c(w2, fast_tanh(fmaf(h0, q1, u0)) - h1, 0.f);
-    float w[1] = {valid ? (df / sc) * (df / sc) : 0.f};
-    batch_sum<1>(w, R, par, X);
-    const float d2 = sqrtf(w[0] * inv_count) / h0;
-    const float hh = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : fast_pow(0.01f / fmaxf(d1, d2), 0.2f);
-    dtd = (double)fminf(100.f * h0, hh);
-  }
+  S.start(x0);
   double tcur = (double)a.tout[0], seg0 = tcur, seg1 = tcur;
   // the interpolant of the last accepted step, in the linear-in-h form: y(x) = sy + sdt (W2 (wS sHb + wM sHm + w1 sh1 + w7 sh7) + b2 (...))
-  float sy = y0, sdt = 0.f, sHb = 0.f, sHm = 0.f, sh1 = 0.f, sh7 = 0.f;
+  float sy = S.y0, sdt = 0.f, sHb = 0.f, sHm = 0.f, sh1 = 0.f, sh7 = 0.f;
   int steps = 0;
   bool stalled = false;
   for (int j = 1; j < T && !stalled; ++j) {
     const double target = (double)a.tout[j];
     while (target > seg1) {
-      if (R.dead || steps >= RV_MAX_TRIALS || !(tcur + dtd > tcur)) { stalled = true; break; }
-      const float dt = (float)dtd;
-      const float h2 = fast_tanh(fmaf(dt * DP5_A21, q1, u0));
-      const float q2 = mv16c(Mw, h2, cq);
-      const float h3 = fast_tanh(fmaf(dt, DP5_A31 * q1 + DP5_A32 * q2, u0));
-      const float q3 = mv16c(Mw, h3, cq);
-      const float h4 = fast_tanh(fmaf(dt, DP5_A41 * q1 + DP5_A42 * q2 + DP5_A43 * q3, u0));
-      const float q4 = mv16c(Mw, h4, cq);
-      const float h5 = fast_tanh(fmaf(dt, DP5_A51 * q1 + DP5_A52 * q2 + DP5_A53 * q3 + DP5_A54 * q4, u0));
-      const float q5 = mv16c(Mw, h5, cq);
-      const float h6 = fast_tanh(fmaf(dt, DP5_A61 * q1 + DP5_A62 * q2 + DP5_A63 * q3 + DP5_A64 * q4 + DP5_A65 * q5, u0));
-      const float q6 = mv16c(Mw, h6, cq);
-      const float u7 = fmaf(dt, DP5_B1 * q1 + DP5_B3 * q3 + DP5_B4 * q4 + DP5_B5 * q5 + DP5_B6 * q6, u0);
-      const float h7 = fast_tanh(u7);
-      const float Hb = DP5_B1 * h1 + DP5_B3 * h3 + DP5_B4 * h4 + DP5_B5 * h5 + DP5_B6 * h6;
-      const float He = DP5_E1 * h1 + DP5_E3 * h3 + DP5_E4 * h4 + DP5_E5 * h5 + DP5_E6 * h6 + DP5_E7 * h7;
-      const float y1 = fmaf(dt, mv16c(w2, Hb, b2), y0);
-      const float err = dt * mv16c(w2, He, 0.f);
-      const float tol = atol + rtol * fmaxf(fabsf(y0), fabsf(y1));
-      const float rr = err / tol;
-      float v[1] = {valid ? rr * rr : 0.f};
-      const float q7 = mv16c(Mw, h7, cq);
-      batch_sum<1>(v, R, par, X);
-      const float ratio = sqrtf(v[0] * inv_count);
+      if (R.dead || steps >= RV_MAX_TRIALS || !(tcur + S.dtd > tcur)) { stalled = true; break; }
+      const float ratio = S.trial();
       ++steps;
       if (ratio <= 1.f) {
-        sy = y0; sdt = dt; sHb = Hb; sh1 = h1; sh7 = h7;
-        sHm = DP5_C1 * h1 + DP5_C3 * h3 + DP5_C4 * h4 + DP5_C5 * h5 + DP5_C6 * h6 + DP5_C7 * h7;
-        seg0 = tcur; seg1 = tcur + dtd;
-        tcur = seg1; y0 = y1; u0 = u7; h1 = h7; q1 = q7;
+        sy = S.y0; sdt = S.dt; sHb = S.Hb; sh1 = S.h1; sh7 = S.h7;
+        sHm = S.Hm();
+        seg0 = tcur; seg1 = tcur + S.dtd;
+        tcur = seg1; S.accept();
       }
-      dtd *= (double)step_factor(ratio);
+      S.dtd *= (double)step_factor(ratio);
     }
     if (stalled) break;
     // (the abscissa is formed from the fp32-rounded times, as torchdiffeq does)
@@ -941,12 +957,12 @@ __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_fwd_valu_kernel(const O
     float wS, wM, w1c, w7c;
     interp_weights(x, wS, wM, w1c, w7c);
     const float Hx = wS * sHb + wM * sHm + w1c * sh1 + w7c * sh7;
-    emit(j, fmaf(sdt, mv16c(w2, Hx, b2 * (wS + 0.5f * wM + w1c + w7c)), sy));
+    emit(j, fmaf(sdt, mv16c(S.w2, Hx, S.b2 * (wS + 0.5f * wM + w1c + w7c)), sy));
   }
   if (a.nsteps && wg == 0 && threadIdx.x == 0) a.nsteps[0] = stalled ? -steps - 1 : steps;
 }
 
-struct OdeBwdJobs { gode_ode_bwd_op op[RV_MAX_JOBS]; int32_t nblk[RV_MAX_JOBS]; int32_t count; int32_t direct; };
+typedef JobsV<gode_ode_bwd_op> OdeBwdJobs;
 
 __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_bwd_valu_kernel(const OdeBwdJobs J) {
   __shared__ float P[GODE_ODE_NPARAM];
@@ -1063,89 +1079,31 @@ static bool ode5_fwd_ok(const gode_ode_fwd_op* op) {
   return true;
 }
 
-// `count` (<= 8) dopri5 latent solves (method == 1 ops) in one launch (ops: HOST array)
-extern "C" int gode_ode_fwd_multi(const gode_ode_fwd_op* ops, int32_t count, void* stream) {
-  if (!ops || count < 1 || count > RV_MAX_JOBS) return GODE_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  OdeFwdJobs J;
-  J.count = 0;
-  int spinning = 0;
-  for (int k = 0; k < count; ++k) {
-    if (!ode5_fwd_ok(&ops[k])) return GODE_E_ARG;
-    const int nblk = (ops[k].N + RV_TRAJ - 1) / RV_TRAJ;
-    if (nblk > 1 && ops[k].sync) spinning += nblk;
-  }
-  for (int k = 0; k < count; ++k) {
-    const int nblk = (ops[k].N + RV_TRAJ - 1) / RV_TRAJ;
-    if (nblk > 1 && (!ops[k].sync || spinning > RV_MAX_WGS)) {       // no exchange buffer, or too many workgroups to be co-resident
-      const int rc = gode_launch_ode_dopri5(&ops[k], st);
-      if (rc) return rc;
-      continue;
-    }
-    if (nblk > 1) {
-      const hipError_t e = hipMemsetAsync(ops[k].sync, 0, XS_HDR * sizeof(int32_t), st);
-      if (e != hipSuccess) return (int)e;
-    }
-    J.op[J.count] = ops[k]; J.nblk[J.count] = nblk; J.count += 1;
-  }
-  if (J.count == 0) return 0;
-  int grid = 0;
-  for (int k = 0; k < J.count; ++k) grid += J.nblk[k];
-  hipLaunchKernelGGL(ode_dopri5_fwd_valu_kernel, dim3(grid), dim3(RV_THREADS), 0, st, J);
-  GODE_LAUNCH_CHECK();
-  return 0;
+static bool ode5_bwd_ok(const gode_ode_bwd_op* op) {
+  if (!op || op->method != 1 || op->substeps != 0 || !op->traj || !op->gz || !op->work || !op->grads || !op->tout || op->N <= 0 || op->T < 1 ||
+      !(op->rtol > 0.f) || !(op->atol >= 0.f) || op->zcols < 16 || op->zcols % 4 != 0)
+    return false;
+  if (!op->p.W1 || !op->p.b1 || !op->p.W2 || !op->p.b2) return false;
+  if (op->prenet && (!op->x || !op->p.Wa || !op->p.ba || !op->p.Wb || !op->p.bb)) return false;
+  return true;
 }
 
-static int ode5_bwd_launch(const gode_ode_bwd_op* ops, int count, hipStream_t st) {
-  OdeBwdJobs J;
-  J.count = count;
-  int grid = 0;
-  for (int k = 0; k < count; ++k) {
-    const int nblk = (ops[k].N + RV_TRAJ - 1) / RV_TRAJ;
-    if (nblk > 1) {
-      const hipError_t e = hipMemsetAsync(ops[k].sync, 0, XS_HDR * sizeof(int32_t), st);
-      if (e != hipSuccess) return (int)e;
-    }
-    J.op[k] = ops[k]; J.nblk[k] = nblk;
-    grid += nblk;
-  }
-  J.direct = (count == 1 && grid == 1) ? 1 : 0;
-  hipLaunchKernelGGL(ode_dopri5_bwd_valu_kernel, dim3(grid), dim3(RV_THREADS), 0, st, J);
-  GODE_LAUNCH_CHECK();
-  if (J.direct) return 0;
-  // entries below `first` are not touched: OFF_W1 when none of the group's ops has a pre-net (that block of grads is then
-  // not the caller's)
-  return gode_for_each_grads_group(ops, J.nblk, count, [&](RowsArgs& A) {
-    A.nparam = GODE_ODE_NPARAM; A.first = OFF_W1;
-    for (int j = 0; j < count; ++j)
-      if (ops[j].grads == A.grads && ops[j].prenet) A.first = 0;
-    return gode_launch_rows(A, st);
-  });
+// `count` (<= 8) dopri5 latent solves (method == 1 ops) in one launch (ops: HOST array); an op of more than one workgroup
+// without an exchange buffer takes the MFMA kernel
+extern "C" int gode_ode_fwd_multi(const gode_ode_fwd_op* ops, int32_t count, void* stream) {
+  return fwd_multi(ode_dopri5_fwd_valu_kernel, ops, count, (hipStream_t)stream, ode5_fwd_ok,
+                   [](const gode_ode_fwd_op& op, int nblk) { return nblk > 1 && !op.sync; }, gode_launch_ode_dopri5);
 }
 
 // the adaptive adjoints (method == 1, substeps == 0) of `count` (<= 8) dopri5 solves in one launch
 extern "C" int gode_ode_bwd_multi(const gode_ode_bwd_op* ops, int32_t count, void* stream) {
-  if (!ops || count < 1 || count > RV_MAX_JOBS) return GODE_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  int spinning = 0;
-  bool fallback = false;
-  for (int k = 0; k < count; ++k) {
-    const gode_ode_bwd_op* op = &ops[k];
-    if (op->method != 1 || op->substeps != 0 || !op->traj || !op->gz || !op->work || !op->grads || !op->tout || op->N <= 0 || op->T < 1 ||
-        !(op->rtol > 0.f) || !(op->atol >= 0.f) || op->zcols < 16 || op->zcols % 4 != 0)
-      return GODE_E_ARG;
-    if (!op->p.W1 || !op->p.b1 || !op->p.W2 || !op->p.b2) return GODE_E_ARG;
-    if (op->prenet && (!op->x || !op->p.Wa || !op->p.ba || !op->p.Wb || !op->p.bb)) return GODE_E_ARG;
-    const int nblk = (op->N + RV_TRAJ - 1) / RV_TRAJ;
-    if (nblk > 1) { if (!op->sync) fallback = true; else spinning += nblk; }
-  }
-  if (spinning > RV_MAX_WGS) fallback = true;
-  if (!fallback) return ode5_bwd_launch(ops, count, st);
-  for (int k = 0; k < count; ++k) {       // in array order, each with its own accumulate flag
-    const int nblk = (ops[k].N + RV_TRAJ - 1) / RV_TRAJ;
-    const bool mfma = nblk > 1 && (!ops[k].sync || spinning > RV_MAX_WGS);
-    const int rc = mfma ? gode_launch_ode_dopri5_bwd_mfma(&ops[k], st) : ode5_bwd_launch(&ops[k], 1, st);
-    if (rc) return rc;
-  }
-  return 0;
+  return bwd_multi(ode_dopri5_bwd_valu_kernel, ops, count, (hipStream_t)stream, ode5_bwd_ok,
+                   [](const gode_ode_bwd_op& op, int nblk) { return nblk > 1 && !op.sync; }, gode_launch_ode_dopri5_bwd_mfma,
+                   [](const gode_ode_bwd_op* ops, int count, RowsArgs& A) {
+                     // entries below `first` are not touched: OFF_W1 when none of the group's ops has a pre-net (that block of
+                     // grads is then not the caller's)
+                     A.nparam = GODE_ODE_NPARAM; A.first = OFF_W1;
+                     for (int j = 0; j < count; ++j)
+                       if (ops[j].grads == A.grads && ops[j].prenet) A.first = 0;
+                   });
 }
