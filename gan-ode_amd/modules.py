@@ -95,6 +95,43 @@ def _plan_generation(plan):
     return plan.stack.generation if hasattr(plan, "stack") else plan.generation
 
 
+# The parameters of a ConvStack cross autograd in one order: per layer the weight, then gamma and beta where the layer has a
+# BatchNorm.  The nodes below take the parameters (_flat_params) and return the gradients (_flat_grads) in it.
+def _flat_grads(views):
+    """ConvStack.backward's per-layer (weight, gamma, beta) gradient views -> the flat list."""
+    out = []
+    for w, g, b in views:
+        out.append(w)
+        if g is not None:
+            out += [g, b]
+    return out
+
+
+def _flat_params(layer_params):
+    return _flat_grads((lp.weight, lp.gamma, lp.beta) for lp in layer_params)
+
+
+def _grads_into(arena, layer_params):
+    """Per layer (weight, gamma, beta gradient targets, accumulate?) inside the trainer's arena, ConvStack.backward's
+    `into`: the first writer of an optimiser step stores, later ones add."""
+    into = []
+    for lp in layer_params:
+        wt, acc = arena.target(lp.weight)
+        gt = bt = None
+        if lp.gamma is not None:
+            gt, _ = arena.target(lp.gamma)
+            bt, _ = arena.target(lp.beta)
+        into.append((wt, gt, bt, acc))
+    return into
+
+
+def _strides5(x):
+    """Element strides {N, D, H, W, C} of an [N, C, H, W] or [N, C, D, H, W] tensor."""
+    if x.dim() == 5:
+        return (x.stride(0), x.stride(2), x.stride(3), x.stride(4), x.stride(1))
+    return (x.stride(0), 0, x.stride(2), x.stride(3), x.stride(1))
+
+
 # ==================================================================================================================
 # generator
 # ==================================================================================================================
@@ -380,19 +417,6 @@ class _GenPlan:
         self.busy = keep
         return out
 
-    def _decoder_into(self, arena):
-        """Per decoder layer (weight, gamma, beta gradient targets, accumulate?) inside the trainer's arena: the first
-        writer of an optimiser step stores, later ones add."""
-        into = []
-        for lp in self.gen._decoder_params():
-            wt, acc = arena.target(lp.weight)
-            gt = bt = None
-            if lp.gamma is not None:
-                gt, _ = arena.target(lp.gamma)
-                bt, _ = arena.target(lp.beta)
-            into.append((wt, gt, bt, acc))
-        return into
-
     def _decoder_pass_done(self):
         """The trainer may ask to be told when the LAST decoder backward of a generator step has been queued (the decoder
         block of the gradient arena is then complete and its all-reduce can start under the latent adjoint)."""
@@ -404,7 +428,8 @@ class _GenPlan:
 
     def backward(self, gout, arena=None):
         if arena is not None:
-            _, _, gz = self.stack.backward(gout, need_input_grad=True, into=self._decoder_into(arena))
+            into = _grads_into(arena, self.gen._decoder_params())
+            _, _, gz = self.stack.backward(gout, need_input_grad=True, into=into)
             self._decoder_pass_done()
             self.latent_backward(gz.data_ptr(), arena, gz)
             self.busy = False
@@ -490,7 +515,8 @@ class _GenJointPlan:
         subs = (self.vid, self.img)
         offs = (0, 4 * self.rows_v * Z_COLS)
         if arena is not None:
-            _, _, gz = self.stack.backward(g_joint, need_input_grad=True, into=self.vid._decoder_into(arena))
+            into = _grads_into(arena, self.gen._decoder_params())
+            _, _, gz = self.stack.backward(g_joint, need_input_grad=True, into=into)
             self.vid._decoder_pass_done()
             for sub, off in zip(subs, offs):
                 sub.latent_backward(gz.data_ptr() + off, arena, gz)
@@ -503,6 +529,19 @@ class _GenJointPlan:
             motion = m if motion is None else [a + b for a, b in zip(motion, m)]
         self.busy = False
         return views, motion
+
+
+def _gen_backward(ctx, plan, gout, n_other):
+    """The tail of both generator nodes' backward: the plan's backward, then one gradient per forward argument (n_other
+    non-parameter arguments first) -- all None when the kernels wrote into the trainer's arena."""
+    arena = getattr(plan.gen, "_gode_arena", None)
+    if arena is not None and arena.active:
+        plan.backward(gout, arena)
+        return (None,) * (n_other + ctx.n_params)
+    views, motion = plan.backward(gout, None)
+    grads = _flat_grads(views)
+    assert len(grads) == ctx.n_dec and len(motion) == ctx.n_params - ctx.n_dec
+    return (None,) * n_other + (*grads, *motion)
 
 
 class _GenJointFn(torch.autograd.Function):
@@ -526,18 +565,7 @@ class _GenJointFn(torch.autograd.Function):
                 part.zero_()
             else:
                 part.copy_(gg)
-        arena = getattr(plan.gen, "_gode_arena", None)
-        if arena is not None and arena.active:
-            plan.backward(g, arena)
-            return (None,) * (5 + ctx.n_params)
-        views, motion = plan.backward(g, None)
-        grads = []
-        for wv, gvw, bv in views:
-            grads.append(wv)
-            if gvw is not None:
-                grads += [gvw, bv]
-        assert len(grads) == ctx.n_dec and len(motion) == ctx.n_params - ctx.n_dec
-        return (None, None, None, None, None, *grads, *motion)
+        return _gen_backward(ctx, plan, g, 5)
 
 
 class _GenFn(torch.autograd.Function):
@@ -554,18 +582,7 @@ class _GenFn(torch.autograd.Function):
     def backward(ctx, gout):
         plan = ctx.plan
         ctx.lease.check(type(plan.gen).__name__)
-        arena = getattr(plan.gen, "_gode_arena", None)
-        if arena is not None and arena.active:
-            plan.backward(gout, arena)
-            return (None,) * (8 + ctx.n_params)
-        views, motion = plan.backward(gout)
-        grads = []
-        for wv, gv, bv in views:
-            grads.append(wv)
-            if gv is not None:
-                grads += [gv, bv]
-        assert len(grads) == ctx.n_dec and len(motion) == ctx.n_params - ctx.n_dec
-        return (None, None, None, None, None, None, None, None, *grads, *motion)
+        return _gen_backward(ctx, plan, gout, 8)
 
 
 class _LatentFn(torch.autograd.Function):
@@ -706,12 +723,7 @@ class VideoGenerator(nn.Module):
         return out
 
     def _decoder_list(self):
-        dec = []
-        for p in self._decoder_params():
-            dec.append(p.weight)
-            if p.gamma is not None:
-                dec += [p.gamma, p.beta]
-        return dec
+        return _flat_params(self._decoder_params())
 
     def _param_list(self):
         ode = []
@@ -1678,92 +1690,34 @@ class Noise(nn.Module):
 
 
 class _DiscFn(torch.autograd.Function):
+    """One pass of a discriminator as one autograd node: over x1 alone (x2 None; x1 may want its gradient), or over
+    [x1; x2] (real and fake batches of equal shape, detached) with per-group BatchNorm statistics on a groups=2 plan.
+    Returns the raw channels-last output [B, Do, Ho, Wo, C] ([2B, ...] for the pair, x1's group first)."""
+
     @staticmethod
-    def forward(ctx, plan, strides, training, keep, arena, noise, x, *params):
-        out = plan.forward(training, x=x, x_strides=strides, noise=noise)
+    def forward(ctx, plan, training, keep, arena, noise, x1, x2, *params):
+        out = plan.forward(training, x=x1, x_strides=_strides5(x1), x2=x2,
+                           x2_strides=None if x2 is None else _strides5(x2), noise=noise)
         plan.busy = keep
-        ctx.plan = plan
-        ctx.lease = _Lease(plan)
-        ctx.x_shape = x.shape
-        ctx.arena = arena
+        ctx.plan, ctx.lease, ctx.arena = plan, _Lease(plan), arena
+        ctx.x_dim, ctx.paired = x1.dim(), x2 is not None
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        plan = ctx.plan
-        ctx.lease.check("discriminator")
-        need_x = ctx.needs_input_grad[6]
-        need_p = any(ctx.needs_input_grad[7:])
-        arena = ctx.arena
-        into = None
-        if need_p and arena is not None and arena.active:
-            into = []
-            for lp in plan.params:
-                wt, acc = arena.target(lp.weight)
-                gt = bt = None
-                if lp.gamma is not None:
-                    gt, _ = arena.target(lp.gamma)
-                    bt, _ = arena.target(lp.beta)
-                into.append((wt, gt, bt, acc))
-        flat, views, g_in = plan.backward(gout, need_input_grad=need_x, need_param_grad=need_p, into=into)
-        grads = []
-        if into is not None:
-            grads = [None] * (len(ctx.needs_input_grad) - 7)
-        elif need_p:
-            for wv, gv, bv in views:
-                grads.append(wv)
-                if gv is not None:
-                    grads += [gv, bv]
-        else:
-            grads = [None] * (len(ctx.needs_input_grad) - 7)
-        gx = None
-        if need_x:
-            g = g_in                                       # [N, D, H, W, C] channels-last, allocated for this call
-            gx = g.permute(0, 4, 1, 2, 3) if len(ctx.x_shape) == 5 else g.squeeze(1).permute(0, 3, 1, 2)
-        return (None, None, None, None, None, None, gx, *grads)
-
-
-class _DiscPairFn(torch.autograd.Function):
-    """One pass of a discriminator over [first; second] (real and fake batches of equal shape) with per-group BatchNorm
-    statistics: returns the joint raw output [2B, Do, Ho, Wo, 1]."""
-
-    @staticmethod
-    def forward(ctx, plan, strides1, strides2, training, keep, arena, noise, x1, x2, *params):
-        out = plan.forward(training, x=x1, x_strides=strides1, x2=x2, x2_strides=strides2, noise=noise)
-        plan.busy = keep
-        ctx.plan = plan
-        ctx.lease = _Lease(plan)
-        ctx.arena = arena
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        plan = ctx.plan
-        ctx.lease.check("discriminator (paired pass)")
-        if ctx.needs_input_grad[7] or ctx.needs_input_grad[8]:
+        plan, arena = ctx.plan, ctx.arena
+        ctx.lease.check("discriminator (paired pass)" if ctx.paired else "discriminator")
+        need_x = ctx.needs_input_grad[5]
+        if ctx.paired and (need_x or ctx.needs_input_grad[6]):
             raise NotImplementedError("the paired discriminator pass is for discriminator updates (detached inputs)")
-        need_p = any(ctx.needs_input_grad[9:])
-        arena = ctx.arena
-        nparams = len(ctx.needs_input_grad) - 9
-        into = None
-        if need_p and arena is not None and arena.active:
-            into = []
-            for lp in plan.params:
-                wt, acc = arena.target(lp.weight)
-                gt = bt = None
-                if lp.gamma is not None:
-                    gt, _ = arena.target(lp.gamma)
-                    bt, _ = arena.target(lp.beta)
-                into.append((wt, gt, bt, acc))
-        flat, views, _ = plan.backward(gout, need_input_grad=False, need_param_grad=need_p, into=into)
-        grads = [None] * nparams
-        if into is None and need_p:
-            grads = []
-            for wv, gv, bv in views:
-                grads.append(wv)
-                if gv is not None:
-                    grads += [gv, bv]
-        return (None, None, None, None, None, None, None, None, None, *grads)
+        need_p = any(ctx.needs_input_grad[7:])
+        into = _grads_into(arena, plan.params) if need_p and arena is not None and arena.active else None
+        _, views, g_in = plan.backward(gout, need_input_grad=need_x, need_param_grad=need_p, into=into)
+        grads = _flat_grads(views) if need_p and into is None else [None] * (len(ctx.needs_input_grad) - 7)
+        gx = None
+        if need_x:      # g_in: [N, D, H, W, C] channels-last, allocated for this call
+            gx = g_in.permute(0, 4, 1, 2, 3) if ctx.x_dim == 5 else g_in.squeeze(1).permute(0, 3, 1, 2)
+        return (None, None, None, None, None, gx, None, *grads)
 
 
 class _DiscBase(nn.Module):
@@ -1831,43 +1785,41 @@ class _DiscBase(nn.Module):
         for k in [k for k in self._pool.pack_cache if k[0] == "ver"]:
             del self._pool.pack_cache[k]
 
-    def forward(self, input):
-        out = self._forward_raw(input)
-        h = out.permute(0, 4, 1, 2, 3)
-        if input.dim() == 4:
-            h = h.squeeze(2)       # (a squeeze, not h[:, :, 0]: select's backward allocates a zero tensor and copies)
-        return h.squeeze(), None
-
-    def _forward_raw(self, input):
-        """The stack's output as written: channels-last [B, Do, Ho, Wo, C]."""
-        _require_gpu(self.main[1].weight, type(self).__name__)
-        _require_gpu(input, type(self).__name__ + " input")
-        if input.dtype != torch.float32:
-            raise RuntimeError("fp32 input expected")
-        x = input
-        if x.dim() == 5:
-            strides = (x.stride(0), x.stride(2), x.stride(3), x.stride(4), x.stride(1))
-        else:
-            strides = (x.stride(0), 0, x.stride(2), x.stride(3), x.stride(1))
-        key = tuple(x.shape) + (("noise",) if self._noise_active() else ())
-        plan = self._pool.get(key, lambda: ConvStack(self._specs(x.shape), self._layer_params(),
-                                                     self.main[1].weight.device, owns_input=False,
-                                                     pack_cache=self._pool.pack_cache, two_lane_backward=self.two_lane_backward))
-        params = []
-        for p in self._layer_params():
-            params.append(p.weight)
-            if p.gamma is not None:
-                params += [p.gamma, p.beta]
-        keep = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-        noise = self._noise_args(1)
-        return _DiscFn.apply(plan, strides, self.training, keep, getattr(self, "_gode_arena", None), noise, x, *params)      # [B, Do, Ho, Wo, C]
-
-
     @staticmethod
-    def _strides5(x):
-        if x.dim() == 5:
-            return (x.stride(0), x.stride(2), x.stride(3), x.stride(4), x.stride(1))
-        return (x.stride(0), 0, x.stride(2), x.stride(3), x.stride(1))
+    def _logits(out, ndim):
+        """The stack's channels-last output -> the reference's squeezed logits for an ndim-dimensional input."""
+        h = out.permute(0, 4, 1, 2, 3)
+        if ndim == 4:
+            h = h.squeeze(2)       # (a squeeze, not h[:, :, 0]: select's backward allocates a zero tensor and copies)
+        return h.squeeze()
+
+    def forward(self, input):
+        return self._logits(self._forward_raw(input), input.dim()), None
+
+    def _forward_raw(self, first, second=None):
+        """The stack's output as written, channels-last [B, Do, Ho, Wo, C]: one pass over `first`, or (forward_pair_joint)
+        over [first; second] on a groups=2 plan."""
+        _require_gpu(self.main[1].weight, type(self).__name__)
+        xs = [first] if second is None else [first, second]
+        for t in xs:
+            _require_gpu(t, type(self).__name__ + " input")
+            if t.dtype != torch.float32:
+                raise RuntimeError("fp32 input expected")
+        shape, n = tuple(first.shape), len(xs)
+        if second is not None:
+            if shape != tuple(second.shape):
+                raise RuntimeError("paired pass: both inputs must have the same shape")
+            if first.requires_grad or second.requires_grad:
+                raise RuntimeError("paired pass: inputs must be detached (it is the discriminator-update pass)")
+        key = (("pair",) if n == 2 else ()) + shape + (("noise",) if self._noise_active() else ())
+        plan = self._pool.get(key, lambda: ConvStack(self._specs((n * shape[0],) + shape[1:]), self._layer_params(),
+                                                     self.main[1].weight.device, owns_input=False,
+                                                     pack_cache=self._pool.pack_cache, groups=n,
+                                                     two_lane_backward=self.two_lane_backward))
+        params = _flat_params(self._layer_params())
+        keep = torch.is_grad_enabled() and any(t.requires_grad for t in xs + params)
+        noise = self._noise_args(n)
+        return _DiscFn.apply(plan, self.training, keep, getattr(self, "_gode_arena", None), noise, first, second, *params)
 
     def forward_pair_joint(self, first, second):
         """D(first) and D(second) in ONE pass -- the same launches over [first; second] with PER-GROUP BatchNorm batch
@@ -1875,42 +1827,13 @@ class _DiscBase(nn.Module):
         137-143): running statistics receive first's update, then second's.  Returns the joint raw logits
         [2B, Do, Ho, Wo, 1] (first group first); GanTrainer feeds them to bce_with_logits_halves.  Twice the rows per
         launch fill the GPU better (video-D GEMMs +14 %) and every elementwise / reduction launch is issued once."""
-        _require_gpu(self.main[1].weight, type(self).__name__)
-        for t in (first, second):
-            _require_gpu(t, type(self).__name__ + " input")
-            if t.dtype != torch.float32:
-                raise RuntimeError("fp32 input expected")
-        if tuple(first.shape) != tuple(second.shape):
-            raise RuntimeError("paired pass: both inputs must have the same shape")
-        if first.requires_grad or second.requires_grad:
-            raise RuntimeError("paired pass: inputs must be detached (it is the discriminator-update pass)")
-        joint_shape = (2 * first.shape[0],) + tuple(first.shape[1:])
-        key = ("pair",) + tuple(first.shape) + (("noise",) if self._noise_active() else ())
-        plan = self._pool.get(key, lambda: ConvStack(self._specs(joint_shape), self._layer_params(),
-                                                     self.main[1].weight.device, owns_input=False,
-                                                     pack_cache=self._pool.pack_cache, groups=2,
-                                                     two_lane_backward=self.two_lane_backward))
-        params = []
-        for p in self._layer_params():
-            params.append(p.weight)
-            if p.gamma is not None:
-                params += [p.gamma, p.beta]
-        keep = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        noise = self._noise_args(2)
-        return _DiscPairFn.apply(plan, self._strides5(first), self._strides5(second), self.training, keep,
-                                 getattr(self, "_gode_arena", None), noise, first, second, *params)
+        return self._forward_raw(first, second)
 
     def forward_pair(self, first, second):
         """-> ((logits_first, None), (logits_second, None)) with forward()'s shapes."""
         out = self.forward_pair_joint(first, second)
         B = first.shape[0]
-        res = []
-        for h in (out[:B], out[B:]):
-            h = h.permute(0, 4, 1, 2, 3)
-            if first.dim() == 4:
-                h = h.squeeze(2)
-            res.append((h.squeeze(), None))
-        return tuple(res)
+        return tuple((self._logits(h, first.dim()), None) for h in (out[:B], out[B:]))
 
 
 class PatchImageDiscriminator(_DiscBase):

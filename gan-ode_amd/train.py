@@ -78,71 +78,78 @@ def _scaled(grad, gout):
     return grad * gout      # a caller-supplied upstream gradient (not the training loop's path)
 
 
-class _BceConstFn(torch.autograd.Function):
-    """sum_k BCEWithLogits(logits_k, target_k) (mean-reduced each) for 1 or 2 logit tensors in one autograd node: the
-    second term accumulates into the same device scalar (gode_bce_logits accumulate=1), so a discriminator loss
-    `bce(real, 1) + bce(fake, 0)` (mnist_moco_ode.py:126-128) needs no elementwise add."""
+# Every loss of the training loops is ONE autograd node: its terms add into one device scalar (the first stores, the
+# others accumulate: `bce(real, 1) + bce(fake, 0)`, mnist_moco_ode.py:126-128, needs no elementwise add) and write the
+# upstream gradient of their inputs in place, so the backward launches nothing.
+#
+# A term is (op class, {pointer field: (input, first element)}, the op's other fields): the named field receives the
+# input's data pointer and its gradient field (_GRAD_FIELD) the same place in the input's gradient -- the same element offset,
+# so a term whose gradient rows are not laid out like its input rows (_ce with gld != ld) must start at element 0.  Terms are
+# applied in order -- the order of the fp32 sum.  The terms of an input together write every element of its gradient.
+_GRAD_FIELD = {"logits": "grad", "fake": "grad_fake", "real": "grad_real"}
+_REDUCTIONS = {"mean": 0, "sum": 1}
+
+
+def _bce(i, first, n, stride, target):
+    """gode_bce_logits: mean BCEWithLogits of n elements of input i, `stride` apart from element `first`, against target."""
+    return L.BceOp, {"logits": (i, first)}, dict(n=n, stride=stride, target=float(target))
+
+
+def _ce(i, col0, ncls, rows, n_lab, labels, rows_per_label, ld, gld=None):
+    """gode_ce_logits over the class columns col0 .. col0 + ncls of the [rows, ld] input i (gradient rows gld apart): the
+    first n_lab rows are labelled, rows_per_label consecutive rows share a label; the others get zero gradient."""
+    return L.CeOp, {"logits": (i, col0)}, dict(labels=None if labels is None else labels.data_ptr(), B=rows, n_lab=n_lab,
+                                               C=ncls, ld=ld, gld=ld if gld is None else gld,
+                                               rows_per_label=rows_per_label)
+
+
+def _wgan(sign, reduction, n, fake, real=None):
+    """gode_wgan_logits: sign * reduce(fake [- real]) over n elements; fake, real: (input, first element)."""
+    return L.WganOp, ({"fake": fake} if real is None else {"real": real, "fake": fake}), dict(
+        n=n, sign=sign, reduction=_REDUCTIONS[reduction])
+
+
+class _LossFn(torch.autograd.Function):
+    """sum of loss terms (see above) over 1..n input tensors.  There is one gradient tensor per input, in the layout of
+    the contiguous input.  in_place: the inputs are read as they are (categorical_cross_entropy's strided view; its term
+    carries the leading dimensions) instead of through .contiguous()."""
 
     @staticmethod
-    def forward(ctx, *args):
-        pairs = [(args[i], args[i + 1]) for i in range(0, len(args), 2)]
-        loss = torch.empty((), dtype=torch.float32, device=pairs[0][0].device)
-        grads = []
+    def forward(ctx, terms, in_place, *xs):
+        if not in_place:
+            xs = [x.contiguous() for x in xs]
+        loss = torch.empty((), dtype=torch.float32, device=xs[0].device)
+        grads = [torch.empty_like(x, memory_format=torch.contiguous_format) for x in xs]
         st = stream_ptr()
-        for k, (logits, target) in enumerate(pairs):
-            x = logits.contiguous()
-            grad = torch.empty_like(x)
-            op = L.BceOp(logits=x.data_ptr(), grad=grad.data_ptr(), loss=loss.data_ptr(), n=x.numel(),
-                         target=float(target), gscale=1.0, accumulate=1 if k else 0)
+        for k, (op_cls, ptrs, fields) in enumerate(terms):
+            op = op_cls(loss=loss.data_ptr(), gscale=1.0, accumulate=1 if k else 0, **fields)
+            for name, (i, first) in ptrs.items():
+                setattr(op, name, xs[i].data_ptr() + 4 * first)
+                setattr(op, _GRAD_FIELD[name], grads[i].data_ptr() + 4 * first)
             L.run_one(op, st)
-            grads.append(grad)
         ctx.save_for_backward(*grads)
         return loss
 
     @staticmethod
     def backward(ctx, gout):
-        out = []
-        for g in ctx.saved_tensors:
-            out += [_scaled(g, gout), None]
-        return tuple(out)
+        return (None, None, *[_scaled(g, gout) for g in ctx.saved_tensors])
 
 
 def bce_with_logits_const(logits: torch.Tensor, target: float) -> torch.Tensor:
     """nn.BCEWithLogitsLoss()(logits, full_like(logits, target)) -- mean reduction (mnist_moco_ode.py:89,126-128)."""
     if not logits.is_cuda:
         raise RuntimeError("bce_with_logits_const runs only on the GPU through libgode.so")
-    return _BceConstFn.apply(logits, target)
-
-
-class _BceHalvesFn(torch.autograd.Function):
-    """bce(x[:B], t_first) + bce(x[B:], t_second), each mean-reduced over its half, on ONE joint logits tensor (the
-    paired discriminator pass): one autograd node, the gradient is one tensor in the joint layout."""
-
-    @staticmethod
-    def forward(ctx, joint, t_first, t_second):
-        x = joint.contiguous()
-        n = x.numel() // 2
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        grad = torch.empty_like(x)
-        st = stream_ptr()
-        for k, tgt in enumerate((t_first, t_second)):
-            L.run_one(L.BceOp(logits=x.data_ptr() + 4 * n * k, grad=grad.data_ptr() + 4 * n * k, loss=loss.data_ptr(), n=n,
-                              target=float(tgt), gscale=1.0, accumulate=k), st)
-        ctx.save_for_backward(grad)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gout):
-        (grad,) = ctx.saved_tensors
-        return _scaled(grad, gout), None, None
+    return _LossFn.apply([_bce(0, 0, logits.numel(), 1, target)], False, logits)
 
 
 def bce_with_logits_halves(joint: torch.Tensor, target_first: float, target_second: float) -> torch.Tensor:
     """nn.BCEWithLogitsLoss()(x[:B], t1) + nn.BCEWithLogitsLoss()(x[B:], t2) for the joint output of
-    forward_pair_joint (mnist_moco_ode.py:126-128,145-147)."""
+    forward_pair_joint (mnist_moco_ode.py:126-128,145-147): each term is mean-reduced over its half, the gradient is one
+    tensor in the joint layout."""
     if not joint.is_cuda or joint.shape[0] % 2:
         raise RuntimeError("bce_with_logits_halves: a CUDA tensor with an even leading dimension is expected")
-    return _BceHalvesFn.apply(joint, target_first, target_second)
+    n = joint.numel() // 2
+    return _LossFn.apply([_bce(0, 0, n, 1, target_first), _bce(0, n, n, 1, target_second)], False, joint)
 
 
 def bce_with_logits_pair(logits_a, target_a: float, logits_b, target_b: float) -> torch.Tensor:
@@ -150,46 +157,13 @@ def bce_with_logits_pair(logits_a, target_a: float, logits_b, target_b: float) -
     mean-reduced on its own, the two means are added in fp32)."""
     if not (logits_a.is_cuda and logits_b.is_cuda):
         raise RuntimeError("bce_with_logits_pair runs only on the GPU through libgode.so")
-    return _BceConstFn.apply(logits_a, target_a, logits_b, target_b)
+    return _LossFn.apply([_bce(0, 0, logits_a.numel(), 1, target_a), _bce(1, 0, logits_b.numel(), 1, target_b)], False,
+                         logits_a, logits_b)
 
 
 # Categorical MoCoGAN (models/mocogan.py:167-182): nn.CrossEntropyLoss() on the class logits, alone or fused with the
 # BCE terms of the same optimiser step.  A categorical head is ONE [B, 1 + C] tensor (column 0: the real/fake logit,
-# columns 1..C: the class logits); every term of a step adds into one device scalar and writes its part of the head's
-# upstream gradient in place, so the step keeps one loss node and its backward launches nothing.
-class _TermsFn(torch.autograd.Function):
-    """sum of loss terms over 1..n input tensors as one autograd node.  terms (applied in order, the first stores the loss
-    scalar, the others add): ("bce", input, first element, n, element stride, target) -- gode_bce_logits;
-    ("ce", input, first class column, C, rows, labelled rows, labels, rows per label) -- gode_ce_logits over a [rows, width]
-    input.  The terms of an input together write every element of its gradient."""
-
-    @staticmethod
-    def forward(ctx, terms, *xs):
-        xs = [x.contiguous() for x in xs]
-        loss = torch.empty((), dtype=torch.float32, device=xs[0].device)
-        grads = [torch.empty_like(x) for x in xs]
-        st = stream_ptr()
-        for k, t in enumerate(terms):
-            x, g = xs[t[1]], grads[t[1]]
-            if t[0] == "bce":
-                _, _, off, n, stride, target = t
-                op = L.BceOp(logits=x.data_ptr() + 4 * off, grad=g.data_ptr() + 4 * off, loss=loss.data_ptr(), n=n,
-                             target=float(target), gscale=1.0, accumulate=1 if k else 0, stride=stride)
-            else:
-                _, _, col0, ncls, rows, n_lab, labels, rpl = t
-                ld = x.numel() // rows
-                op = L.CeOp(logits=x.data_ptr() + 4 * col0, labels=None if labels is None else labels.data_ptr(),
-                            grad=g.data_ptr() + 4 * col0, loss=loss.data_ptr(), B=rows, n_lab=n_lab, C=ncls, ld=ld, gld=ld,
-                            gscale=1.0, accumulate=1 if k else 0, rows_per_label=rpl)
-            L.run_one(op, st)
-        ctx.save_for_backward(*grads)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gout):
-        return (None, *[_scaled(g, gout) for g in ctx.saved_tensors])
-
-
+# columns 1..C: the class logits): its BCE term strides over column 0, its class term over the other columns.
 def _check_labels(labels, rows, what):
     if not (torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.int64 and labels.dim() == 1
             and labels.shape[0] == rows):
@@ -209,24 +183,6 @@ def _check_head(head, what):
     return head.shape[0], head.numel() // W, W
 
 
-class _CeFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, categ, labels):
-        x = categ if (categ.stride(1) == 1 and categ.stride(0) >= categ.shape[1]) else categ.contiguous()
-        B, ncls = x.shape
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        grad = torch.empty((B, ncls), dtype=torch.float32, device=x.device)
-        L.run_one(L.CeOp(logits=x.data_ptr(), labels=labels.data_ptr(), grad=grad.data_ptr(), loss=loss.data_ptr(), B=B,
-                         n_lab=B, C=ncls, ld=x.stride(0), gld=ncls, gscale=1.0, accumulate=0), stream_ptr())
-        ctx.save_for_backward(grad)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gout):
-        (grad,) = ctx.saved_tensors
-        return _scaled(grad, gout), None
-
-
 def categorical_cross_entropy(categ: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     """nn.CrossEntropyLoss()(categ, labels): categ [B, C] fp32 (a view of a categorical head is read in place), labels
     int64 [B] on the device; one launch, fixed summation order."""
@@ -234,7 +190,11 @@ def categorical_cross_entropy(categ: torch.Tensor, labels: torch.Tensor) -> torc
         raise RuntimeError("categorical_cross_entropy runs only on the GPU through libgode.so")
     if categ.dtype != torch.float32 or categ.dim() != 2:
         raise RuntimeError("categorical_cross_entropy: float32 class logits [B, C] are expected")
-    return _CeFn.apply(categ, _check_labels(labels, categ.shape[0], "categorical_cross_entropy"))
+    labels = _check_labels(labels, categ.shape[0], "categorical_cross_entropy")
+    B, C = categ.shape
+    # rows stride(0) apart are read where they lie; the gradient is compact [B, C] either way
+    in_place = categ.stride(1) == 1 and categ.stride(0) >= C
+    return _LossFn.apply([_ce(0, 0, C, B, B, labels, 1, categ.stride(0) if in_place else C, C)], in_place, categ)
 
 
 def bce_ce_head(head, target: float, labels) -> torch.Tensor:
@@ -242,7 +202,7 @@ def bce_ce_head(head, target: float, labels) -> torch.Tensor:
     patch head's positions all take their video's label, each term is the mean over all positions."""
     B, R, W = _check_head(head, "bce_ce_head")
     labels = _check_labels(labels, B, "bce_ce_head")
-    return _TermsFn.apply([("bce", 0, 0, R, W, target), ("ce", 0, 1, W - 1, R, R, labels, R // B)], head)
+    return _LossFn.apply([_bce(0, 0, R, W, target), _ce(0, 1, W - 1, R, R, labels, R // B, W)], False, head)
 
 
 def bce_ce_head_pair(head, target: float, labels, logits_b, target_b: float) -> torch.Tensor:
@@ -252,8 +212,8 @@ def bce_ce_head_pair(head, target: float, labels, logits_b, target_b: float) -> 
     if not logits_b.is_cuda:
         raise RuntimeError("bce_ce_head_pair runs only on the GPU through libgode.so")
     labels = _check_labels(labels, B, "bce_ce_head_pair")
-    return _TermsFn.apply([("bce", 0, 0, R, W, target), ("bce", 1, 0, logits_b.numel(), 1, target_b),
-                           ("ce", 0, 1, W - 1, R, R, labels, R // B)], head, logits_b)
+    return _LossFn.apply([_bce(0, 0, R, W, target), _bce(1, 0, logits_b.numel(), 1, target_b),
+                          _ce(0, 1, W - 1, R, R, labels, R // B, W)], False, head, logits_b)
 
 
 def bce_ce_head_halves(joint, target_first: float, target_second: float, labels_first) -> torch.Tensor:
@@ -264,8 +224,8 @@ def bce_ce_head_halves(joint, target_first: float, target_second: float, labels_
         raise RuntimeError("bce_ce_head_halves: an even leading dimension is expected")
     B, R = n2 // 2, R2 // 2
     labels = _check_labels(labels_first, B, "bce_ce_head_halves")
-    return _TermsFn.apply([("bce", 0, 0, R, W, target_first), ("bce", 0, R * W, R, W, target_second),
-                           ("ce", 0, 1, W - 1, R2, R, labels, R // B)], joint)
+    return _LossFn.apply([_bce(0, 0, R, W, target_first), _bce(0, R * W, R, W, target_second),
+                          _ce(0, 1, W - 1, R2, R, labels, R // B, W)], False, joint)
 
 
 def bce_ce_heads(head_a, target_a: float, labels_a, head_b, target_b: float) -> torch.Tensor:
@@ -275,57 +235,13 @@ def bce_ce_heads(head_a, target_a: float, labels_a, head_b, target_b: float) -> 
     if Wb != W:
         raise RuntimeError("bce_ce_heads: both heads must have the same width")
     labels = _check_labels(labels_a, B, "bce_ce_heads")
-    return _TermsFn.apply([("bce", 0, 0, R, W, target_a), ("bce", 1, 0, Rb, W, target_b),
-                           ("ce", 0, 1, W - 1, R, R, labels, R // B), ("ce", 1, 1, W - 1, Rb, 0, None, 1)], head_a, head_b)
+    return _LossFn.apply([_bce(0, 0, R, W, target_a), _bce(1, 0, Rb, W, target_b),
+                          _ce(0, 1, W - 1, R, R, labels, R // B, W), _ce(1, 1, W - 1, Rb, 0, None, 1, W)], False,
+                         head_a, head_b)
 
 
 # Wasserstein loss (torchgan.losses, mnist_moco_ode_wgan.py:13,97-98): generator -reduce(fgz), discriminator
-# reduce(fgz - fx), no clipping, no gradient penalty.  The terms of one loss accumulate into one device scalar.
-_REDUCTIONS = {"mean": 0, "sum": 1}
-
-
-class _WganFn(torch.autograd.Function):
-    """sum_k sign_k * reduce(fake_k [- real_k]) in one autograd node.  terms: per term (sign, layout) with layout 1 (one
-    tensor: fake), 2 (two tensors: real, fake) or 0 (one joint [real; fake] tensor); xs holds the tensors in order."""
-
-    @staticmethod
-    def forward(ctx, reduction, terms, *xs):
-        red = _REDUCTIONS[reduction]
-        loss = torch.empty((), dtype=torch.float32, device=xs[0].device)
-        st = stream_ptr()
-        grads, j = [], 0
-        for k, (sign, layout) in enumerate(terms):
-            if layout == 0:
-                x = xs[j].contiguous()
-                g = torch.empty_like(x)
-                n = x.numel() // 2
-                op = L.WganOp(real=x.data_ptr(), fake=x.data_ptr() + 4 * n, grad_real=g.data_ptr(),
-                              grad_fake=g.data_ptr() + 4 * n, n=n)
-                grads.append(g)
-                j += 1
-            elif layout == 1:
-                x = xs[j].contiguous()
-                g = torch.empty_like(x)
-                op = L.WganOp(fake=x.data_ptr(), grad_fake=g.data_ptr(), n=x.numel())
-                grads.append(g)
-                j += 1
-            else:
-                r, f = xs[j].contiguous(), xs[j + 1].contiguous()
-                gr, gf = torch.empty_like(r), torch.empty_like(f)
-                op = L.WganOp(real=r.data_ptr(), fake=f.data_ptr(), grad_real=gr.data_ptr(), grad_fake=gf.data_ptr(),
-                              n=f.numel())
-                grads += [gr, gf]
-                j += 2
-            op.loss, op.sign, op.gscale, op.reduction, op.accumulate = loss.data_ptr(), float(sign), 1.0, red, 1 if k else 0
-            L.run_one(op, st)
-        ctx.save_for_backward(*grads)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gout):
-        return (None, None) + tuple(_scaled(g, gout) for g in ctx.saved_tensors)
-
-
+# reduce(fgz - fx), no clipping, no gradient penalty.
 def _wgan_check(*xs):
     for x in xs:
         if not x.is_cuda:
@@ -335,14 +251,15 @@ def _wgan_check(*xs):
 def wasserstein_generator_loss(fgz: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
     """torchgan's wasserstein_generator_loss: reduce(-fgz)."""
     _wgan_check(fgz)
-    return _WganFn.apply(reduction, ((-1.0, 1),), fgz)
+    return _LossFn.apply([_wgan(-1.0, reduction, fgz.numel(), (0, 0))], False, fgz)
 
 
 def wasserstein_generator_loss_pair(fgz_a: torch.Tensor, fgz_b: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
     """wasserstein_generator_loss(a) + wasserstein_generator_loss(b) as one node (each term reduced on its own, the two
     added in fp32: mnist_moco_ode_wgan.py:174)."""
     _wgan_check(fgz_a, fgz_b)
-    return _WganFn.apply(reduction, ((-1.0, 1), (-1.0, 1)), fgz_a, fgz_b)
+    return _LossFn.apply([_wgan(-1.0, reduction, fgz_a.numel(), (0, 0)), _wgan(-1.0, reduction, fgz_b.numel(), (1, 0))],
+                         False, fgz_a, fgz_b)
 
 
 def wasserstein_discriminator_loss(fx: torch.Tensor, fgz: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
@@ -350,7 +267,7 @@ def wasserstein_discriminator_loss(fx: torch.Tensor, fgz: torch.Tensor, reductio
     _wgan_check(fx, fgz)
     if fx.shape != fgz.shape:
         raise RuntimeError(f"wasserstein_discriminator_loss: fx {tuple(fx.shape)} and fgz {tuple(fgz.shape)} differ in shape")
-    return _WganFn.apply(reduction, ((1.0, 2),), fx, fgz)
+    return _LossFn.apply([_wgan(1.0, reduction, fgz.numel(), (1, 0), real=(0, 0))], False, fx, fgz)
 
 
 def wasserstein_discriminator_loss_halves(joint: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
@@ -358,7 +275,8 @@ def wasserstein_discriminator_loss_halves(joint: torch.Tensor, reduction: str = 
     _wgan_check(joint)
     if joint.shape[0] % 2:
         raise RuntimeError("wasserstein_discriminator_loss_halves: a tensor with an even leading dimension is expected")
-    return _WganFn.apply(reduction, ((1.0, 0),), joint)
+    n = joint.numel() // 2
+    return _LossFn.apply([_wgan(1.0, reduction, n, (0, n), real=(0, 0))], False, joint)
 
 
 def _wgan_args(reduction, override_train_ops, clip=None):
