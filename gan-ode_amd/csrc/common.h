@@ -51,8 +51,6 @@ __device__ __forceinline__ void buf_dma16(const BufRsrc& b, float* lds, int voff
 #endif
 }
 
-static inline bool gode_strides_are_channels_last(const int64_t* s) { return s[0] == 0 && s[1] == 0 && s[2] == 0 && s[3] == 0 && s[4] == 0; }
-
 // Division by a run-time invariant (Granlund-Montgomery, branch-free, exact for all 32-bit n): the host builds the
 // magic once per launch, the kernels pay a v_mul_hi + 3 ALU ops instead of a ~30-instruction software divide.
 struct FastDiv { uint32_t mul, sh1, sh2, d; };

@@ -55,6 +55,9 @@ struct IgemmGeom {
 
 GODE_HD int gode_ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// element strides {N,D,H,W,C} left all zero: the tensor is dense channels-last
+static inline bool gode_strides_are_channels_last(const int64_t* s) { return s[0] == 0 && s[1] == 0 && s[2] == 0 && s[3] == 0 && s[4] == 0; }
+
 // Builds the phase table.  Returns 0 on success.
 inline int gode_build_igemm_geom(const gode_conv_geom& g, int dir, IgemmGeom* out) {
   IgemmGeom& G = *out;

@@ -8,7 +8,7 @@
 // Data flow per workgroup (256 threads = 4 waves, BMxBN output tile, K slabs of 32), three staging paths:
 //   LDS-DMA (igemm_fast_kernel MODE 2; every heavy, transform-free GEMM): global --global_load_lds_dwordx4--> LDS
 //     [row][32], 16-byte chunks XOR-swizzled through the source address, two buffers, one barrier per slab;
-//   registers (MODE 0/1 and the generic igemm_kernel; BN/activation of the previous layer fused into the load, odd
+//   registers (MODE 0 and the generic igemm_kernel; BN/activation of the previous layer fused into the load, odd
 //     channel counts, strided sources): float4 (or scalar) gathers -> registers -> ds_write_b128 -> LDS [row][36];
 //   then ds_read_b128 fragments -> 32x32x2 MFMA, 2x2 (2x1, 1x1) tiles per wave.
 // MFMA k-index trick: lane half h supplies k = 4h+j in step j, so one ds_read_b128 feeds four MFMAs.
@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "conv_geom.h"
+#include "igemm_plan.h"
 
 int gode_launch_conv_patch_fprop(const gode_igemm_op* op, const int64_t* gs, hipStream_t st);   // conv_patch.hip
 
@@ -288,14 +289,11 @@ __global__ void __launch_bounds__(WM* WN * 64) igemm_kernel(const IgemmArgs a) {
   }
 }
 
-#define IGEMM_MAX_LIVE_TAPS 64   // MODE 3 tap table (+1 slot read past the end)
-
 // ---------------------------------------------------------------------------------------------------------------
 // FAST variant for the layers that carry the FLOPs: vector gather, Cg % 32 == 0 (so a 32-wide K slab never straddles
 // a tap and the tap decode is wave-uniform scalar work), K % 32 == 0.  The loop body is one basic block: loads are
 // unconditional (clamped address + mask), the BN/activation transform is branch-free, and the staging work of slab
 // s+1 is placed between the MFMA groups of slab s so that it issues in the shadow of the matrix pipe.
-// MODE 1 : registers, two LDS buffers, one barrier per slab, staging interleaved with this wave's own MFMAs.
 // MODE 0 : registers, one LDS buffer (half the LDS => twice the resident workgroups), two barriers per slab; the
 //           staging of one workgroup is covered by the MFMAs of the others on the SIMD.  Default when XF.
 // MODE 2 (LDS-DMA): the slab is written to LDS by `global_load_lds_dwordx4` (no VGPR round trip, no ds_write pass);
@@ -307,7 +305,7 @@ __global__ void __launch_bounds__(WM* WN * 64) igemm_kernel(const IgemmArgs a) {
 //           the bookkeeping costs the plain MODE 2 loop 5-12 % when compiled in.
 template <int WM, int WN, int TM, int TN, int MODE, bool XF>
 __global__ void __launch_bounds__(WM* WN * 64) igemm_fast_kernel(const IgemmArgs a) {
-  constexpr bool DB = MODE == 1, GL = MODE >= 2, SK = MODE == 3;
+  constexpr bool GL = MODE >= 2, SK = MODE == 3;
   static_assert(!(GL && XF), "the LDS-DMA path cannot transform on load");
   constexpr int NT = WM * WN * 64, BM = WM * TM * 32, BN = WN * TN * 32, LDK = GL ? 32 : 36;
   constexpr int RPP = NT / 8;
@@ -315,7 +313,7 @@ __global__ void __launch_bounds__(WM* WN * 64) igemm_fast_kernel(const IgemmArgs
   static_assert(BM % RPP == 0 && BN % RPP == 0, "tile/loader mismatch");
   static_assert(!GL || RPP % 16 == 0, "swizzle key must not depend on the loader pass");
   constexpr int BUF = (BM + BN) * LDK;
-  constexpr int NBUF = (DB || GL) ? 2 : 1;
+  constexpr int NBUF = GL ? 2 : 1;
   __shared__ __attribute__((aligned(16))) float smem[NBUF * BUF + BM * 5 + (MODE == 3 ? 4 + IGEMM_MAX_LIVE_TAPS : 0)];
   int* rowinfo = reinterpret_cast<int*>(smem + NBUF * BUF);
   int* outoff = rowinfo + BM * 4;
@@ -603,26 +601,8 @@ __global__ void __launch_bounds__(WM* WN * 64) igemm_fast_kernel(const IgemmArgs
     __syncthreads();                          // the epilogue reuses the buffers
   } else if (nslab > 0) {
   fetch(0);
-  if (DB) {
-    stageA(0);
-    stageB(0);
-    __syncthreads();
-    for (int s = 0; s + 1 < nslab; ++s) {
-      const int buf = s & 1;
-      fetch(s + 1);
-      mma_group(buf, 0);
-      mma_group(buf, 1);
-      stageA(buf ^ 1);
-      mma_group(buf, 2);
-      stageB(buf ^ 1);
-      mma_group(buf, 3);
-      __syncthreads();
-    }
-    const int buf = (nslab - 1) & 1;
-    mma_group(buf, 0); mma_group(buf, 1); mma_group(buf, 2); mma_group(buf, 3);
-    __syncthreads();
 #ifdef GODE_ABLATION_BUILD   // timing-only bodies (WRONG results); never defined for libgode.so (gan-ode_amd/build.py)
-  } else if (a.stagger == -1) {        // ABLATION (timing only, wrong results): MFMA + LDS reads, no staging, no barriers
+  if (a.stagger == -1) {        // ABLATION (timing only, wrong results): MFMA + LDS reads, no staging, no barriers
     stageA(0); stageB(0);
     __syncthreads();
     for (int s = 0; s + 1 < nslab; ++s) { mma_group(0, 0); mma_group(0, 1); mma_group(0, 2); mma_group(0, 3); }
@@ -635,8 +615,9 @@ __global__ void __launch_bounds__(WM* WN * 64) igemm_fast_kernel(const IgemmArgs
     __syncthreads();
     for (int s = 0; s + 1 < nslab; ++s) { __syncthreads(); fetch(s + 1); mma_group(0, 0); mma_group(0, 1); mma_group(0, 2); mma_group(0, 3); __syncthreads(); }
     asm volatile("" :: "v"(ra[0][0]), "v"(rb[0][0]));
+  } else
 #endif
-  } else {
+  {
     for (int s = 0; s + 1 < nslab; ++s) {
       stageA(0);
       stageB(0);
@@ -728,7 +709,6 @@ __global__ void __launch_bounds__(WM* WN * 64) igemm_fast_kernel(const IgemmArgs
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-#define SPLITK_ROWS 16
 // split-K finish: sums the partial tiles in fixed order, applies the epilogue and produces the BatchNorm partial sums
 // (one stats row per SPLITK_ROWS output positions, so that even a 512-position output spreads over 32 workgroups).  Threads own columns, so every sum has a fixed order.
 __global__ void __launch_bounds__(256) igemm_splitk_reduce_kernel(const float* work, float* out, float* stats, int positions,
@@ -857,7 +837,6 @@ __global__ void __launch_bounds__(256) conv_dot_kernel(const DotArgs d) {
 // (float4 of channels each, all taps in a loop, shuffle reduction at the end), 64/(Cg/4) positions per
 // wave-iteration, grid-stride, one grid row per stride phase, the phase's weight panel (<= 16 KB) in LDS.
 // MNIST head 44 -> 28 us; UCF head 224 -> ~65 us.
-#define PW_MAXW 4096
 struct PwArgs { IgemmArgs a; FastDiv dMw[GODE_MAX_PHASES], dMh[GODE_MAX_PHASES], dMd[GODE_MAX_PHASES]; int32_t lpp; };
 
 // ONE_TAP (1x1x1 layers, e.g. the MNIST head): the lane's weights live in registers, no LDS, no tap loop (28 us vs 34 us
@@ -979,419 +958,90 @@ __global__ void __launch_bounds__(256) conv_smallk_kernel(const PwArgs d) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-enum { TILE_128x128 = 1, TILE_128x64 = 2, TILE_128x32 = 3, TILE_64x64 = 4, TILE_128x128_W8 = 5, TILE_256x128 = 6 };
-
-static int tile_bm(int tile) { return tile == TILE_64x64 ? 64 : (tile == TILE_256x128 ? 256 : 128); }
-static int tile_bn(int tile) { return (tile == TILE_128x128 || tile == TILE_128x128_W8 || tile == TILE_256x128) ? 128 : tile == TILE_128x32 ? 32 : 64; }
-
-static int pick_tile(const IgemmGeom& G, int requested) {
-  requested %= 10;   // +10: double-LDS-buffer variant of the same tile (tuning knob; default is single-buffer)
-  if (requested >= TILE_128x128 && requested <= TILE_256x128) return requested;
-  if (G.Ncols <= 32) return TILE_128x32;
-  if (G.Ncols <= 64) return TILE_128x64;
-  int64_t blocks = 0;
-  for (int i = 0; i < G.nphase; ++i) blocks += (int64_t)gode_ceil_div(G.ph[i].M, 128) * gode_ceil_div(G.Ncols, 128);
-  return blocks >= 192 ? TILE_128x128 : TILE_64x64;
-}
-
-// split-K plan: purely a function of the geometry (so gode_igemm_stats_rows / gode_igemm_work_size agree with the
-// launch).  Used when the FAST kernel applies and the natural grid would leave most of the 256 CUs idle.
-struct SplitPlan { int ksplit, slabs_per_split, positions; };
-
-static bool fast_geometry(const IgemmGeom& G) {
-  bool ok = G.Cg % 32 == 0;
-  for (int i = 0; i < G.nphase; ++i) ok = ok && G.ph[i].K >= 32 && G.ph[i].K % 32 == 0 && G.ph[i].Kp == G.ph[i].K;
-  return ok;
-}
-
-static bool strides_allow_vec(const gode_igemm_op* op, const IgemmGeom& G) {
-  if (gode_strides_are_channels_last(op->gs)) return G.Cg % 4 == 0;
-  return op->gs[4] == 1 && G.Cg % 4 == 0 && op->gs[0] % 4 == 0 && op->gs[1] % 4 == 0 && op->gs[2] % 4 == 0 &&
-         op->gs[3] % 4 == 0;
-}
-
-static SplitPlan plan_split(const gode_igemm_op* op, const IgemmGeom& G, int tile) {
-  const gode_conv_geom& g = op->g;
-  SplitPlan sp; sp.ksplit = 1; sp.slabs_per_split = 0; sp.positions = g.N * G.Xd * G.Xh * G.Xw;
-  if (!fast_geometry(G) || G.Ncols <= 4 || !strides_allow_vec(op, G) || op->tile >= 10) return sp;
-  const int bm = tile == 4 ? 64 : 128, bn = (tile == 1 || tile == 5) ? 128 : (tile == 3 ? 32 : 64);
-  int64_t blocks = 0; int max_slabs = 0, min_slabs = 1 << 30;
-  for (int i = 0; i < G.nphase; ++i) {
-    blocks += (int64_t)gode_ceil_div(G.ph[i].M, bm) * gode_ceil_div(G.Ncols, bn);
-    const int ns = G.ph[i].K >> 5;
-    if (ns > max_slabs) max_slabs = ns;
-    if (ns < min_slabs) min_slabs = ns;
-  }
-  if (blocks >= 64 || min_slabs < 8) return sp;   // only grids that would leave >3/4 of the CUs idle
-  int k = (int)((512 + blocks - 1) / blocks);
-  if (k > min_slabs / 4) k = min_slabs / 4;
-  if (k > 32) k = 32;
-  if (k < 2) return sp;
-  sp.slabs_per_split = gode_ceil_div(max_slabs, k);
-  sp.ksplit = gode_ceil_div(max_slabs, sp.slabs_per_split);
-  return sp;
-}
-
-static int pick_tile_split_aware(const gode_conv_geom& g, const IgemmGeom& G, int requested) {
-  const int t = pick_tile(G, requested);
-  if (requested % 10 != 0 || !fast_geometry(G) || G.Ncols <= 4) return t;
-  // with split-K available a starved grid is better served by the big tile (unless there are very few rows)
-  int maxM = 0;
-  for (int i = 0; i < G.nphase; ++i) if (G.ph[i].M > maxM) maxM = G.ph[i].M;
-  int64_t blocks = 0;
-  for (int i = 0; i < G.nphase; ++i) blocks += (int64_t)gode_ceil_div(G.ph[i].M, 128) * gode_ceil_div(G.Ncols, 128);
-  if (t == TILE_64x64 && maxM > 64 && blocks < 64) return G.Ncols <= 64 ? TILE_128x64 : TILE_128x128;
-  (void)g;
-  return t;
-}
-
-// Tile and K-split of a FAST-path GEMM from a small cost model instead of thresholds.  All workgroups of a launch
-// carry equal work and the dispatcher deals them evenly, so the launch lasts as long as the busiest CU:
-//   time = ceil(workgroups / 256) * (fixed + slabs * cycles_per_slab(tile) / efficiency) [+ split-K reduce]
-// with the MFMA cycles of one 32-deep slab (64 per 32x32x2 instruction), the measured pipe efficiencies of the tiles
-// (two or more resident workgroups per CU overlap each other's barriers; a lone one cannot) and ~4k cycles of
-// prologue + epilogue.  Checked against measurements: ConvT 128->64 (4096 x 128x64) 314 us model / 297 us measured;
-// UCF video-D layer-2 dgrad 128x128 578 / 514 us, for which the model prefers 128x64 (436 us).
-// MODE 3 of the FAST kernel (live taps only) pays for its slower loop when the temporal taps that fall off the tensor's
-// ends are > 15 % of the K loop (temporal stride 1: Do of the Di planes' taps are live)
-static bool igemm_wants_tapskip(const gode_igemm_op* op, const IgemmGeom& G) {
-  if (!(op->dir == GODE_DGRAD && op->groups != 2 && !G.fullk && op->g.sd == 1 && G.ph[0].Td > 1 && 100 * op->g.Do < 85 * op->g.Di))
-    return false;
-  for (int i = 0; i < G.nphase; ++i) if (G.ph[i].Td * G.ph[i].Th * G.ph[i].Tw >= IGEMM_MAX_LIVE_TAPS) return false;
-  return true;
-}
-
-static void choose_fast(const gode_igemm_op* op, const IgemmGeom& G, int* tile_out, SplitPlan* sp_out, double* cycles_out = nullptr) {
-  const gode_conv_geom& g = op->g;
-  const int positions = g.N * G.Xd * G.Xh * G.Xw;
-  const double out_bytes = 4.0 * positions * G.Ncols;
-  int max_slabs = 0, min_slabs = 1 << 30;
-  bool even_phases = true;        // phases of unequal size leave early-exit workgroups in the grid: measured, a K split
-  for (int i = 0; i < G.nphase; ++i) {   // then gains nothing (video-D layer 3 dgrad: 101 us split 3 ways vs 64 us unsplit)
-    const int ns = G.ph[i].K >> 5;
-    if (ns > max_slabs) max_slabs = ns;
-    if (ns < min_slabs) min_slabs = ns;
-    even_phases = even_phases && G.ph[i].M == G.ph[0].M;
-  }
-  // 256x128 (8 waves, one workgroup per CU, 25 % less operand traffic per MFMA) last: 2-3 % ahead of 128x128 on the full
-  // decoder grids and 5 % on the MNIST video-D layer-2 input gradient (scripts/sweep_tiles.py), behind it on grids that
-  // do not fill whole rounds of 256 such tiles
-  static const int tiles[5] = {TILE_128x128, TILE_128x64, TILE_64x64, TILE_128x32, TILE_256x128};
-  static const int ksplits[10] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
-  const bool live_taps = igemm_wants_tapskip(op, G);
-  double best = 1e300;
-  int best_tile = G.Ncols <= 32 ? TILE_128x32 : TILE_128x64, best_k = 1;
-  for (int ti = 0; ti < 5; ++ti) {
-    const int t = tiles[ti], bm = tile_bm(t), bn = tile_bn(t);
-    if (bn >= 2 * G.Ncols && bn > 32) continue;              // more than half of every tile would be padding
-    if (t == TILE_128x32 && G.Ncols > 32) continue;
-    if (t == TILE_256x128 && (live_taps || op->groups == 2)) continue;     // (measured on plain launches only)
-    const double cps = t == TILE_256x128 ? 8192.0 : (t == TILE_128x128 ? 4096.0 : (t == TILE_128x64 ? 2048.0 : 1024.0));
-    const int resident = t == TILE_256x128 ? 1 : (t == TILE_128x128 ? 2 : (t == TILE_128x64 ? 3 : 4));
-    const double eff2 = t == TILE_64x64 ? 0.70 : (t == TILE_128x32 ? 0.62 : (t == TILE_256x128 ? 0.785 : 0.76));   // (64x64 re-measured with the round-3 loop: 0.62 before)
-    int64_t tiles_n = 0;
-    for (int i = 0; i < G.nphase; ++i) tiles_n += (int64_t)gode_ceil_div(G.ph[i].M, bm) * gode_ceil_div(G.Ncols, bn);
-    if (t == TILE_256x128 && tiles_n < 192) continue;        // one workgroup per CU: needs a grid that covers the chip
-    for (int ki = 0; ki < 10; ++ki) {
-      const int k = ksplits[ki];
-      // (uneven phases: no split once the unsplit grid already covers half the chip -- see above; tiny grids, e.g. the
-      // image discriminator's 7x7 <- 3x3 input gradient with 25 tiles, still gain from one: 29.5 -> ~20 us)
-      if (k > 1 && (min_slabs / k < 4 || out_bytes * k > 192e6 || min_slabs != max_slabs || (!even_phases && tiles_n >= 128))) break;
-      // the 256x128 tile only unsplit (measured with K splits: never ahead); live-tap launches split only grids that do
-      // not fill the chip (UCF video-D layer 2 input gradient at N = 16: 269 us unsplit, 318 us split 2 ways)
-      if (k > 1 && (t == TILE_256x128 || (live_taps && tiles_n >= 256))) break;
-      const int64_t blocks = tiles_n * k;
-      // live-tap launches: tiles of the end planes are short, so the hardware's in-order dispatch evens the CUs out and
-      // the whole-rounds quantisation does not apply to the big tile (measured, UCF video-D layer 2 input gradient at
-      // N=32, 640 tiles of 128x128 vs 1280 of 128x64: 10 % apart although 640 is 2.5 rounds; at N=16 the smaller tile
-      // with a K split stays ahead by 5 %)
-      const double per_cu = (live_taps && t == TILE_128x128 && k == 1 && blocks >= 512) ? blocks / 256.0 : (double)((blocks + 255) / 256);
-      const int slabs = gode_ceil_div(max_slabs, k);
-      const double eff = ((per_cu >= 2 && resident >= 2) || t == TILE_256x128) ? eff2 : 0.8 * eff2;    // (8 waves cover their own barriers)
-      double cyc = per_cu * (4000.0 + slabs * cps / eff);
-      if (k > 1) cyc += 2.4e9 * (2.5e-6 + (k + 1) * out_bytes / 3e12);
-      if (cyc < best * 0.97) { best = cyc; best_tile = t; best_k = k; }   // 3 % hysteresis toward the earlier (larger) choice
-    }
-  }
-  if (cycles_out) *cycles_out = best;
-  if (live_taps) {
-    // Live-tap launches whose 128x128 grid does not cover the chip (UCF video-D layer 3 input gradient: 224 / 112 tiles): the
-    // tiles of the end planes are a quarter as long as those of the middle planes and all of them are resident at once, so the
-    // launch lasts as long as the CU that drew the long ones -- the estimate above (equal tiles) is 20-30 % off there.  Small
-    // tiles even that out: 4-5 workgroups of 64x64 per CU (scripts/sweep_tiles.py, N = 32 / 16: 371 -> 288 us unsplit, 209 ->
-    // 179 us split 3 ways; every other live-tap shape of the configs keeps the model's choice within 2 %).
-    int64_t t128 = 0, t64 = 0;
-    for (int i = 0; i < G.nphase; ++i) {
-      t128 += (int64_t)gode_ceil_div(G.ph[i].M, 128) * gode_ceil_div(G.Ncols, 128);
-      t64 += (int64_t)gode_ceil_div(G.ph[i].M, 64) * gode_ceil_div(G.Ncols, 64);
-    }
-    if (t128 < 256 && G.Ncols >= 64 && min_slabs == max_slabs) {
-      int k = (int)((1152 + t64 / 2) / t64);
-      if (k < 1) k = 1;
-      while (k > 1 && (min_slabs / k < 8 || out_bytes * k > 192e6)) --k;
-      best_tile = TILE_64x64; best_k = k;
-    }
-  }
-  *tile_out = best_tile;
-  sp_out->positions = positions;
-  sp_out->ksplit = 1; sp_out->slabs_per_split = 0;
-  if (best_k > 1) {
-    sp_out->slabs_per_split = gode_ceil_div(max_slabs, best_k);
-    sp_out->ksplit = gode_ceil_div(max_slabs, sp_out->slabs_per_split);
-  }
-}
-
-// The border-split table of an op that asks for it (gode_igemm_op.border), or false: FPROP, fullk, image groups, live-tap
-// (MODE 3) launches and shapes that do not split keep the plain table.
-static bool border_table(const gode_igemm_op* op, const IgemmGeom& G, IgemmGeom* B) {
-  if (!op->border || op->dir != GODE_DGRAD || op->groups == 2 || G.fullk || igemm_wants_tapskip(op, G)) return false;
-  return gode_build_igemm_geom_border(op->g, op->dir, B) == 0 && B->border != 0;
-}
-
-// Cost of a FAST launch over a border-split table.  Its tiles differ in length (interior / edge / corner sub-phases: K, K/2,
-// K/4 on a k4 s2 layer), the grid holds only live tiles and the longest come first, so the in-order dispatcher evens the
-// CUs out and the launch lasts the summed work over the 256 CUs -- once there are clearly more tiles than workgroup slots
-// and three or more workgroups per CU.  Measured on the three decoder layers at 512 rows (profiles/border_split_layers.md):
-//   128x64 tiles (1024 / 2048 / 4096 of them on 768 slots): 0.826 / 0.929 / 1.004 of the plain launch with the same tile
-//   where the summed work is 0.771 / 0.884 / 0.944 of it -- a loss of 1.071 / 1.050 / 1.064 against the sum: BORDER_LOSS;
-//   a tail term (a share of one longest tile) fitted to the same launches came out at 0.01: the shortest tiles go last;
-//   128x128 (512 tiles on 512 slots, 1024 on 512) and 256x128 (256 / 512 tiles on 256 slots): within 1 % of plain -- all
-//   tiles are resident in one or two rounds and some CU draws only long ones.  Those tiles are not offered.
-// Same per-tile constants as choose_fast.  Never a K split.
-#define BORDER_LOSS 1.06
-static void choose_border(const gode_igemm_op* op, const IgemmGeom& B, int* tile_out, double* cycles_out) {
-  (void)op;
-  static const int tiles[4] = {TILE_128x128, TILE_128x64, TILE_64x64, TILE_256x128};
-  double best = 1e300; int best_tile = TILE_128x64;
-  for (int ti = 0; ti < 4; ++ti) {
-    const int t = tiles[ti], bm = tile_bm(t), bn = tile_bn(t);
-    if (bn >= 2 * B.Ncols && bn > 32) continue;
-    if (t != TILE_128x64 && t != TILE_64x64) continue;      // (three or more workgroups per CU: see above)
-    const double cps = t == TILE_256x128 ? 8192.0 : (t == TILE_128x128 ? 4096.0 : (t == TILE_128x64 ? 2048.0 : 1024.0));
-    const int resident = t == TILE_256x128 ? 1 : (t == TILE_128x128 ? 2 : (t == TILE_128x64 ? 3 : 4));
-    const double eff2 = t == TILE_64x64 ? 0.70 : (t == TILE_256x128 ? 0.785 : 0.76);
-    int64_t ntiles = 0; int max_slabs = 0;
-    for (int i = 0; i < B.nphase; ++i) {
-      ntiles += (int64_t)gode_ceil_div(B.ph[i].M, bm) * gode_ceil_div(B.Ncols, bn);
-      if ((B.ph[i].K >> 5) > max_slabs) max_slabs = B.ph[i].K >> 5;
-    }
-    if (3 * ntiles < 4 * 256 * (int64_t)resident) continue;     // (measured down to 4/3 tiles per slot)
-    const double eff = (resident >= 2 || t == TILE_256x128) ? eff2 : 0.8 * eff2;
-    double work = 0;
-    for (int i = 0; i < B.nphase; ++i)
-      work += (double)gode_ceil_div(B.ph[i].M, bm) * gode_ceil_div(B.Ncols, bn) * (4000.0 + (B.ph[i].K >> 5) * cps / eff);
-    const double cyc = BORDER_LOSS * work / 256.0;
-    if (cyc < best) { best = cyc; best_tile = t; }
-  }
-  *tile_out = best_tile; *cycles_out = best;
-}
-
-static int prepare(const gode_igemm_op* op, IgemmArgs* A, int* tile, int* max_mblk, int* rows, SplitPlan* sp, int* rows0 = nullptr,
-                   double* cycles = nullptr) {
-  int rc = gode_build_igemm_geom(op->g, op->dir, &A->G);
-  if (rc) return rc;
-  A->ntab = 0;
-  if (cycles) *cycles = -1.0;
-  IgemmGeom B;
-  const bool can_border = border_table(op, A->G, &B);
-  const bool grouped = op->groups == 2;
-  if (grouped) {
-    // two image groups with SEPARATE BatchNorm partial statistics (one discriminator pass over [real; fake]): the
-    // single FPROP phase becomes two phases over the two halves of the batch, so no tile straddles the groups and
-    // each group's partial-statistics rows are contiguous
-    if (op->dir != GODE_FPROP || op->g.N % 2 != 0 || A->G.nphase != 1) return GODE_E_ARG;
-    A->G.ph[1] = A->G.ph[0];
-    A->G.ph[0].M /= 2; A->G.ph[1].M = A->G.ph[0].M; A->G.ph[1].img0 = op->g.N / 2;
-    A->G.nphase = 2;
-  } else if (op->groups != 0 && op->groups != 1) return GODE_E_ARG;
-  static const char* menv = getenv("GODE_IGEMM_MODEL");
-  static const bool sweeping = getenv("GODE_IGEMM_SWEEP") != nullptr;     // calibration runs: GODE_IGEMM_FORCE="tile,k" is re-read per call
-  const char* fenv = sweeping ? getenv("GODE_IGEMM_FORCE") : nullptr;
-  int ftile = 0, fk = 0;
-  if (fenv && sscanf(fenv, "%d,%d", &ftile, &fk) == 2 && op->tile == 0 && fast_geometry(A->G) && A->G.Ncols > 4 &&
-      strides_allow_vec(op, A->G)) {
-    int max_slabs = 0;
-    for (int i = 0; i < A->G.nphase; ++i) if ((A->G.ph[i].K >> 5) > max_slabs) max_slabs = A->G.ph[i].K >> 5;
-    *tile = ftile;
-    sp->positions = op->g.N * A->G.Xd * A->G.Xh * A->G.Xw; sp->ksplit = 1; sp->slabs_per_split = 0;
-    if (fk > 1) { sp->slabs_per_split = gode_ceil_div(max_slabs, fk); sp->ksplit = gode_ceil_div(max_slabs, sp->slabs_per_split); }
-    if (can_border && fk <= 1) A->G = B;     // (calibration runs time the border form with the forced tile)
-  } else if (op->tile == 0 && fast_geometry(A->G) && A->G.Ncols > 4 && strides_allow_vec(op, A->G) && (!menv || atoi(menv) != 0)) {
-    double cyc = -1.0;
-    choose_fast(op, A->G, tile, sp, &cyc);
-    if (can_border && fast_geometry(B) && sp->ksplit == 1) {
-      // per layer: the border form only where the model prices it below the plain launch (3 % hysteresis toward plain).
-      // A launch that splits K keeps doing so: a K split adds its partial sums in another order, and an op with the flag
-      // must give the raw outputs of the op without it bit for bit
-      int tb; double cb;
-      choose_border(op, B, &tb, &cb);
-      if (cb < 0.97 * cyc) { A->G = B; *tile = tb; sp->ksplit = 1; sp->slabs_per_split = 0; cyc = cb; }
-    }
-    if (cycles) *cycles = cyc;
-  } else {
-    *tile = pick_tile_split_aware(op->g, A->G, op->tile);
-    *sp = plan_split(op, A->G, *tile);
-    // a REQUESTED tile takes the border form unless a plan splits K; tile = 0 off the modelled path (generic kernel, odd
-    // channel counts) stays plain: nothing measured says it would pay there
-    if (can_border && sp->ksplit == 1 && op->tile != 0) {
-      const int tb = pick_tile_split_aware(op->g, B, op->tile);
-      const SplitPlan sb = plan_split(op, B, tb);
-      if (sb.ksplit == 1) { A->G = B; *tile = tb; *sp = sb; }
-    }
-  }
-  if (grouped && sp->ksplit > 1 && (sp->positions / 2) % SPLITK_ROWS != 0) {
-    // the split-K finish emits one statistics row per SPLITK_ROWS output positions: the groups must not share a row
-    sp->ksplit = 1; sp->slabs_per_split = 0;
-  }
-  const int bm = tile_bm(*tile);
-  int r0 = 0, mx = 0;
-  for (int i = 0; i < A->G.nphase; ++i) {
-    A->G.ph[i].row0 = r0;
-    const int mb = gode_ceil_div(A->G.ph[i].M, bm);
-    r0 += mb;
-    if (mb > mx) mx = mb;
-  }
-  *max_mblk = mx;
-  *rows = sp->ksplit > 1 ? gode_ceil_div(sp->positions, SPLITK_ROWS) : r0;
-  if (rows0) *rows0 = !grouped ? *rows : (sp->ksplit > 1 ? *rows / 2 : A->G.ph[1].row0);
-  return 0;
-}
-
 // rows of the partial statistics that belong to image group 0 (grouped FPROP; == gode_igemm_stats_rows otherwise)
 extern "C" int gode_igemm_stats_rows0(const gode_igemm_op* op) {
-  IgemmArgs A; int tile, mx, rows, rows0; SplitPlan sp;
-  int rc = prepare(op, &A, &tile, &mx, &rows, &sp, &rows0);
-  return rc ? rc : rows0;
+  IgemmPlan P;
+  const int rc = igemm_make_plan(op, &P);
+  return rc ? rc : P.rows0;
 }
 
 // The cost model's estimate (GPU cycles) for this op's launch, or -1 when the op does not take the modelled FAST path.
 // A caller that can run a batch as one launch or as two launches over its parts (ConvStack with split_images) compares.
 extern "C" double gode_igemm_model_cycles(const gode_igemm_op* op) {
-  if (!op || op->groups == 2 || op->tile != 0) return -1.0;
-  IgemmArgs A;
-  if (gode_build_igemm_geom(op->g, op->dir, &A.G)) return -1.0;
-  static const char* menv = getenv("GODE_IGEMM_MODEL");
-  if (!fast_geometry(A.G) || A.G.Ncols <= 4 || !strides_allow_vec(op, A.G) || (menv && atoi(menv) == 0)) return -1.0;
-  int tile; SplitPlan sp; double cyc = -1.0;
-  IgemmGeom B;
-  choose_fast(op, A.G, &tile, &sp, &cyc);
-  if (sp.ksplit == 1 && border_table(op, A.G, &B) && fast_geometry(B)) {      // (the same choice as prepare's)
-    double cb;
-    choose_border(op, B, &tile, &cb);
-    if (cb < 0.97 * cyc) cyc = cb;
-  }
-  return cyc;
+  IgemmPlan P;
+  return igemm_make_plan(op, &P) ? -1.0 : P.cycles;
 }
 
 extern "C" int gode_igemm_stats_segments(const gode_igemm_op* op, int32_t split_images, int32_t* seg) {
   if (!op || !seg || op->groups == 2 || op->border || split_images <= 0 || split_images >= op->g.N) return GODE_E_ARG;
-  IgemmArgs A; int tile, mx, rows; SplitPlan sp;
-  int rc = prepare(op, &A, &tile, &mx, &rows, &sp);
+  IgemmPlan P;
+  const int rc = igemm_make_plan(op, &P);
   if (rc) return rc;
-  if (sp.ksplit > 1) {
+  if (P.ksplit > 1) {
     // split-K finish: one statistics row per SPLITK_ROWS output positions, positions in image-major order
-    const int64_t per_img = (int64_t)A.G.Xd * A.G.Xh * A.G.Xw;
+    const int64_t per_img = (int64_t)P.G.Xd * P.G.Xh * P.G.Xw;
     const int64_t b = (int64_t)split_images * per_img;
     if (b % SPLITK_ROWS != 0) return GODE_E_SHAPE;
-    seg[0] = 0; seg[1] = (int32_t)(b / SPLITK_ROWS); seg[2] = rows;
+    seg[0] = 0; seg[1] = (int32_t)(b / SPLITK_ROWS); seg[2] = P.stats_rows;
     return 1;
   }
-  const int bm = tile_bm(tile);
-  for (int i = 0; i < A.G.nphase; ++i) {
-    const PhaseGeom& P = A.G.ph[i];
-    const int64_t per_img = (int64_t)P.Md * P.Mh * P.Mw;       // rows of a phase are image-major
+  const int bm = tile_bm(P.tile);
+  for (int i = 0; i < P.G.nphase; ++i) {
+    const PhaseGeom& Ph = P.G.ph[i];
+    const int64_t per_img = (int64_t)Ph.Md * Ph.Mh * Ph.Mw;       // rows of a phase are image-major
     const int64_t b = (int64_t)split_images * per_img;
-    if (P.M != (int64_t)op->g.N * per_img) return GODE_E_SHAPE;
+    if (Ph.M != (int64_t)op->g.N * per_img) return GODE_E_SHAPE;
     if (b % bm != 0) return GODE_E_SHAPE;                        // a tile would hold rows of both parts
-    seg[3 * i] = P.row0; seg[3 * i + 1] = P.row0 + (int32_t)(b / bm); seg[3 * i + 2] = P.row0 + gode_ceil_div(P.M, bm);
+    seg[3 * i] = Ph.row0; seg[3 * i + 1] = Ph.row0 + (int32_t)(b / bm); seg[3 * i + 2] = Ph.row0 + gode_ceil_div(Ph.M, bm);
   }
-  return A.G.nphase;
+  return P.G.nphase;
 }
 
 extern "C" int gode_igemm_stats_rows(const gode_igemm_op* op) {
-  IgemmArgs A; int tile, mx, rows; SplitPlan sp;
-  int rc = prepare(op, &A, &tile, &mx, &rows, &sp);
-  return rc ? rc : rows;
+  IgemmPlan P;
+  const int rc = igemm_make_plan(op, &P);
+  return rc ? rc : P.stats_rows;
 }
 
 extern "C" int64_t gode_igemm_work_size(const gode_igemm_op* op) {
-  IgemmArgs A; int tile, mx, rows; SplitPlan sp;
-  int rc = prepare(op, &A, &tile, &mx, &rows, &sp);
+  IgemmPlan P;
+  const int rc = igemm_make_plan(op, &P);
   if (rc) return rc;
-  return sp.ksplit > 1 ? (int64_t)sp.ksplit * sp.positions * A.G.Ncols : 0;
+  return P.ksplit > 1 ? (int64_t)P.ksplit * P.positions * P.G.Ncols : 0;
 }
 
-template <int WM, int WN, int TM, int TN>
-static int launch(IgemmArgs& A, bool vec, int max_mblk, bool double_buf, const SplitPlan& sp, hipStream_t st) {
-  constexpr int BN = WN * TN * 32;
-  dim3 grid(max_mblk, gode_ceil_div(A.G.Ncols, BN), A.G.nphase), block(WM * WN * 64);
-  static const bool generic_forced = getenv("GODE_IGEMM_GENERIC") != nullptr;     // read once per process
-  bool fast = vec && fast_geometry(A.G) && (sp.ksplit > 1 || !generic_forced);
-  if (sp.ksplit > 1 && (!fast || A.work == nullptr)) return GODE_E_ARG;   // the plan needs the FAST path + workspace
-  A.ksplit = sp.ksplit; A.slabs_per_split = sp.slabs_per_split;
+// One tiled-GEMM launch of a plan.  `vec`: the pointers allow what the plan's strides do; without it the generic kernel runs
+// the same tile (a plan that splits K cannot be served then).
+template <int TILE>
+static int launch(IgemmArgs& A, const IgemmPlan& P, bool vec, hipStream_t st) {
+  constexpr IgemmTile T = IGEMM_TILES[TILE];
+  constexpr int WM = T.WM, WN = T.WN, TM = T.TM, TN = T.TN;
+  dim3 grid(P.max_mblk, gode_ceil_div(A.G.Ncols, T.bn), A.G.nphase), block(WM * WN * 64);
+  const bool fast = vec && P.fast;
+  if (P.ksplit > 1 && (!fast || A.work == nullptr)) return GODE_E_ARG;   // the plan needs the FAST path + workspace
   if (fast) {
-    const int MB = max_mblk, NB = (int)grid.y, NC = NB * A.G.nphase;
-    A.MB = MB; A.NB = NB; A.xcd_mode = 0;
     static const char* senv = getenv("GODE_IGEMM_STAGGER");
     A.stagger = senv ? atoi(senv) : 0;
 #ifndef GODE_ABLATION_BUILD
     if (A.stagger < 0) A.stagger = 0;   // the negative (ablation) selectors only exist in -DGODE_ABLATION_BUILD builds
 #endif
-    static const char* xenv = getenv("GODE_IGEMM_XCD");
-    const int force = xenv ? atoi(xenv) : -1;
-    const int64_t wbytes = gode_pack_floats(A.G) * 4;
-    const bool ok1 = (NC % 8 == 0) || (NC < 8 && 8 % NC == 0 && MB % (8 / NC) == 0);
-    const bool ok2 = MB % 8 == 0;
-    // measured L2-miss (fabric) fetch per launch on the three decoder layers, forward / backward-data, raw FETCH_SIZE MB:
-    // mode 0: 45/95/411, 76/139/161;  mode 1: 203/230/338, 197/222/161;  mode 2: 68/73/46, 76/93/161;
-    // mode 3: 68/33/36, 60/89/154 -- at equal launch times (+-1.5 %), so the choice is made on traffic alone
-    // Mode 3 makes every XCD read the whole weight pack once; when 8 copies of it outweigh the gathered tensor 3:1
-    // (ConvT 512->256 forward: 8 x 8.4 MB vs 16.8 MB) the plain order, which spreads the panels, fetches less.
-    const int64_t images = (int64_t)A.out_numel / ((int64_t)A.G.Xd * A.G.Xh * A.G.Xw * A.G.Ncols);
-    const int64_t in_bytes = images * A.G.Gd * A.G.Gh * A.G.Gw * A.G.Cg * 4;
-    int mode = ok2 ? (wbytes * 8 < 3 * in_bytes ? 3 : 0) : 0;
-    // depth-major rows with dead-tap skipping: the tiles of the end planes are light, so a contiguous run per XCD would
-    // leave the XCDs that own them idle -- interleave the m-blocks over the XCDs instead
-    // -- and NOT the plain order either: it hands an XCD m-blocks 8 apart, i.e. (at 16 tiles per depth plane) only
-    // planes of one weight: UCF video-D layer 2 at N = 32 runs 600 us in the plain order, 845 us with contiguous runs,
-    // 470 us interleaved (scripts/exp/xcd_sweep.py; no other shape of either config moves by more than 2 %)
-    if (A.dmajor > 0) mode = ok2 ? 2 : (ok1 ? 1 : 0);
-    if (force == 0) mode = 0;
-    if (force == 1 && ok1) mode = 1;
-    if (force == 2 && ok2) mode = 2;
-    if (force == 3 && ok2) mode = 3;
-    A.xcd_mode = mode;
-    dim3 g1(MB * NC * sp.ksplit);
-    if (A.G.border) {
-      if (sp.ksplit > 1 || A.tapskip) return GODE_E_ARG;     // (prepare never plans either on a border-split table)
-      constexpr int BM = WM * TM * 32;
-      A.ntab = A.G.nphase; A.tile0[0] = 0;
-      for (int i = 0; i < A.G.nphase; ++i) A.tile0[i + 1] = A.tile0[i] + gode_ceil_div(A.G.ph[i].M, BM) * NB;
-      for (int i = A.G.nphase + 1; i <= GODE_MAX_PHASES; ++i) A.tile0[i] = A.tile0[A.G.nphase];
-      g1 = dim3(A.tile0[A.G.nphase]);
-    }
+    const dim3 g1(P.ntab > 0 ? P.tile0[P.ntab] : P.MB * P.NB * A.G.nphase * P.ksplit);
+    // LDS-DMA staging unless the previous layer's BatchNorm/activation is fused into the load or an operand is beyond the
+    // 2 GiB a raw buffer's offsets span: then register staging (MODE 0)
     const bool has_xf = A.scale != nullptr || A.act != GODE_ACT_NONE;
-    static const char* genv = getenv("GODE_IGEMM_GLDS");
-    // default; GODE_IGEMM_GLDS=0 selects register staging (as do operands beyond the 2 GiB a raw buffer's offsets span)
-    const bool glds = (genv ? atoi(genv) != 0 : true) && A.src_bytes != 0 && A.w_bytes != 0;
-    if (!has_xf && glds && !double_buf) {
-      if (A.tapskip) hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 3, false>), g1, block, 0, st, A);
-      else hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 2, false>), g1, block, 0, st, A);
-    } else if (double_buf) {
-      if (has_xf) hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 1, true>), g1, block, 0, st, A);
-      else hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 1, false>), g1, block, 0, st, A);
-    } else {
-      if (has_xf) hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 0, true>), g1, block, 0, st, A);
-      else hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 0, false>), g1, block, 0, st, A);
-    }
-    if (sp.ksplit > 1) {
+    const bool glds = !has_xf && A.src_bytes != 0 && A.w_bytes != 0;
+    if (glds && A.tapskip) hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 3, false>), g1, block, 0, st, A);
+    else if (glds) hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 2, false>), g1, block, 0, st, A);
+    else if (has_xf) hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 0, true>), g1, block, 0, st, A);
+    else hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 0, false>), g1, block, 0, st, A);
+    if (P.ksplit > 1) {
       GODE_LAUNCH_CHECK();
       if (A.G.Ncols % 4 == 0 && ((uintptr_t)A.work % 16) == 0 && ((uintptr_t)A.out % 16) == 0)
-        hipLaunchKernelGGL(igemm_splitk_reduce_vec_kernel, dim3(gode_ceil_div(sp.positions, SPLITK_ROWS), gode_ceil_div(A.G.Ncols, 64)),
-                           dim3(256), 0, st, A.work, A.out, A.stats, sp.positions, A.G.Ncols, sp.ksplit, A.epilogue);
+        hipLaunchKernelGGL(igemm_splitk_reduce_vec_kernel, dim3(gode_ceil_div(P.positions, SPLITK_ROWS), gode_ceil_div(A.G.Ncols, 64)),
+                           dim3(256), 0, st, A.work, A.out, A.stats, P.positions, A.G.Ncols, P.ksplit, A.epilogue);
       else
-        hipLaunchKernelGGL(igemm_splitk_reduce_kernel, dim3(gode_ceil_div(sp.positions, SPLITK_ROWS)), dim3(256), 0, st, A.work, A.out,
-                           A.stats, sp.positions, A.G.Ncols, sp.ksplit, A.epilogue);
+        hipLaunchKernelGGL(igemm_splitk_reduce_kernel, dim3(gode_ceil_div(P.positions, SPLITK_ROWS)), dim3(256), 0, st, A.work, A.out,
+                           A.stats, P.positions, A.G.Ncols, P.ksplit, A.epilogue);
     }
   }
   else if (vec) hipLaunchKernelGGL((igemm_kernel<WM, WN, TM, TN, true>), grid, block, 0, st, A);
@@ -1400,15 +1050,22 @@ static int launch(IgemmArgs& A, bool vec, int max_mblk, bool double_buf, const S
   return 0;
 }
 
+static PwArgs pw_args(const IgemmArgs& A, int lanes_per_position) {
+  PwArgs D; D.a = A; D.lpp = lanes_per_position;
+  for (int i = 0; i < A.G.nphase; ++i) {
+    D.dMw[i] = make_fastdiv((uint32_t)A.G.ph[i].Mw); D.dMh[i] = make_fastdiv((uint32_t)A.G.ph[i].Mh);
+    D.dMd[i] = make_fastdiv((uint32_t)A.G.ph[i].Md);
+  }
+  return D;
+}
+
 extern "C" int gode_igemm(const gode_igemm_op* op, void* stream) {
   if (!op || !op->src || !op->wpack || !op->out) return GODE_E_ARG;
-  IgemmArgs A;
-  int tile, max_mblk, rows;
-  SplitPlan sp;
-  int rc = prepare(op, &A, &tile, &max_mblk, &rows, &sp);
+  IgemmPlan P;
+  int rc = igemm_make_plan(op, &P);
   if (rc) return rc;
-  if (max_mblk == 0) return 0;
-  const IgemmGeom& G = A.G;
+  if (P.max_mblk == 0) return 0;
+  const IgemmGeom& G = P.G;
   int64_t gs[5];
   if (gode_strides_are_channels_last(op->gs)) {
     gs[4] = 1; gs[3] = G.Cg; gs[2] = (int64_t)G.Gw * gs[3]; gs[1] = (int64_t)G.Gh * gs[2]; gs[0] = (int64_t)G.Gd * gs[1];
@@ -1421,91 +1078,59 @@ extern "C" int gode_igemm(const gode_igemm_op* op, void* stream) {
   int64_t outn = (int64_t)op->g.N * G.Xd * G.Xh * G.Xw * G.Ncols;
   for (int i = 0; i < 5; ++i) if (gs[i] < 0) return GODE_E_ARG;
   if (span >= (1ll << 31) || outn >= (1ll << 31)) return GODE_E_SHAPE;
-  if (op->src && op->wpack && op->out && ((uintptr_t)op->wpack % 16) == 0) {      // first layers with 1-4 input channels: conv_patch.hip
-    const int pr = gode_launch_conv_patch_fprop(op, gs, (hipStream_t)stream);
+  if (((uintptr_t)op->wpack % 16) != 0 || (op->scale == nullptr) != (op->shift == nullptr)) return GODE_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (P.family == IGEMM_PATCH_FPROP) {      // conv_patch.hip; it declines the shapes it has no kernel for
+    const int pr = gode_launch_conv_patch_fprop(op, gs, st);
     if (pr != 0) return pr < 0 ? pr : 0;
   }
+  IgemmArgs A;
+  A.G = G;
   A.src = op->src; A.w = op->wpack; A.out = op->out; A.scale = op->scale; A.shift = op->shift; A.stats = op->stats;
   A.gsN = (int)gs[0]; A.gsD = (int)gs[1]; A.gsH = (int)gs[2]; A.gsW = (int)gs[3]; A.gsC = (int)gs[4];
   A.act = op->act; A.epilogue = op->epilogue;
   A.stagger = 0;
-  // input gradient of a convolution with temporal taps: depth-major tiles, so that the taps falling off the tensor's ends
-  // are dead for whole tiles (skipped in the FAST kernel's K loop)
-  A.dmajor = 0;
-  A.tapskip = !G.border && igemm_wants_tapskip(op, G);
-  // Depth-major rows: every tile sees one or two planes (a small plane) or a slice of one (a plane of >= 128 rows, which
-  // would fill tiles by itself in image-major order too -- but depth-major with the interleaved XCD order below is 4-6 %
-  // faster there as well: UCF video-D layer 1 input gradient 833 -> 800 us at N = 32, 405 -> 381 at N = 16).
-  if (A.tapskip) A.dmajor = op->g.N;
-  A.stats_rows = rows;
+  A.tapskip = P.tapskip; A.dmajor = P.dmajor; A.stats_rows = P.stats_rows;
+  A.ksplit = P.ksplit; A.slabs_per_split = P.slabs_per_split;
+  A.MB = P.MB; A.NB = P.NB; A.xcd_mode = P.xcd_mode; A.ntab = P.ntab;
+  for (int i = 0; i <= GODE_MAX_PHASES; ++i) A.tile0[i] = P.tile0[i];
   A.src_bytes = span * 4 < (1ll << 31) ? (uint32_t)(span * 4) : 0u;
   A.w_bytes = gode_pack_floats(G) * 4 < (1ll << 31) ? (uint32_t)(gode_pack_floats(G) * 4) : 0u;
-  A.work = op->work; A.out_numel = (int32_t)outn; A.ksplit = 1; A.slabs_per_split = 0; A.MB = 0; A.NB = 0; A.xcd_mode = 0;
-  if ((op->scale == nullptr) != (op->shift == nullptr)) return GODE_E_ARG;
-  const bool vec = gs[4] == 1 && (G.Cg % 4) == 0 && (gs[0] % 4) == 0 && (gs[1] % 4) == 0 && (gs[2] % 4) == 0 &&
-                   (gs[3] % 4) == 0 && ((uintptr_t)op->src % 16) == 0 &&
+  A.work = op->work; A.out_numel = (int32_t)outn;
+  // what the plan could not see: the pointers' alignment.  It only ever takes the op from its family to the tiled GEMM, and
+  // there from the vector kernels to the generic one -- tile and K split stay the plan's
+  const bool vec = P.vec && ((uintptr_t)op->src % 16) == 0 &&
                    (op->scale == nullptr || ((uintptr_t)op->scale % 16 == 0 && (uintptr_t)op->shift % 16 == 0));
-  if (((uintptr_t)op->wpack % 16) != 0) return GODE_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  if (op->groups != 2) {      // (the thin-output streaming kernels below know nothing of image groups; grouped ops carry BN stats)
-    int maxM = 0, minK = 1 << 30; bool kp_ok = true;
-    for (int i = 0; i < G.nphase; ++i) {
-      if (G.ph[i].M > maxM) maxM = G.ph[i].M;
-      if (G.ph[i].K < minK) minK = G.ph[i].K;
-      kp_ok = kp_ok && G.ph[i].Kp == G.ph[i].K;
-    }
+  int maxM = 0, minK = 1 << 30;
+  for (int i = 0; i < G.nphase; ++i) {
+    if (G.ph[i].M > maxM) maxM = G.ph[i].M;
+    if (G.ph[i].K < minK) minK = G.ph[i].K;
+  }
+  if (P.family == IGEMM_POINTWISE && vec) {
     const int lpp = G.Cg / 4;
-    int maxK = 0;
-    for (int i = 0; i < G.nphase; ++i) if (G.ph[i].Kp > maxK) maxK = G.ph[i].Kp;
     const bool one_tap = G.nphase == 1 && G.ph[0].K == G.Cg;
-    // the multi-tap form needs many positions to beat the padded MFMA path (measured: M = 25 k slower, M >= 65 k faster)
-    if (vec && kp_ok && G.Ncols <= 4 && G.Ncols * maxK <= PW_MAXW && op->stats == nullptr && op->tile == 0 &&
-        maxM >= (one_tap ? 4096 : 65536) && (lpp == 4 || lpp == 8 || lpp == 16 || lpp == 32 || lpp == 64)) {
-      PwArgs D; D.a = A; D.lpp = lpp;
-      for (int i = 0; i < G.nphase; ++i) {
-        D.dMw[i] = make_fastdiv((uint32_t)G.ph[i].Mw); D.dMh[i] = make_fastdiv((uint32_t)G.ph[i].Mh);
-        D.dMd[i] = make_fastdiv((uint32_t)G.ph[i].Md);
-      }
-      int64_t blocks = ((int64_t)maxM + (64 / lpp) * 4 * 8 - 1) / ((64 / lpp) * 4 * 8);     // ~8 position groups per wave
-      if (blocks > (one_tap ? 4096 : 2048)) blocks = one_tap ? 4096 : 2048;
-      if (one_tap) hipLaunchKernelGGL(conv_pointwise_kernel<true>, dim3((int)blocks, 1), dim3(256), 0, st, D);
-      else hipLaunchKernelGGL(conv_pointwise_kernel<false>, dim3((int)blocks, G.nphase), dim3(256), 0, st, D);
-      GODE_LAUNCH_CHECK();
-      return 0;
-    }
-    {
-      const int nl = G.Ncols / 4;
-      // K <= 4 only: at K = 8 / 16 (first discriminator layers) the per-lane gather chain made it no faster than the
-      // padded MFMA path (24.9 vs 22 us, 15.7 vs 10 us); at K = 1 it is 27 us against 63 us
-      if (G.nphase == 1 && G.ph[0].K <= 4 && G.Ncols % 4 == 0 && G.Ncols <= 128 && op->stats == nullptr && op->tile == 0 &&
-          maxM >= 2048 && (nl == 4 || nl == 8 || nl == 16 || nl == 32) && ((uintptr_t)op->out % 16) == 0) {
-        PwArgs D; D.a = A; D.lpp = nl;
-        D.dMw[0] = make_fastdiv((uint32_t)G.ph[0].Mw); D.dMh[0] = make_fastdiv((uint32_t)G.ph[0].Mh); D.dMd[0] = make_fastdiv((uint32_t)G.ph[0].Md);
-        int64_t blocks = ((int64_t)maxM + (64 / nl) * 4 * 4 - 1) / ((64 / nl) * 4 * 4);     // ~4 position groups per wave
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(conv_smallk_kernel, dim3((int)blocks), dim3(256), 0, st, D);
-        GODE_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-    if (vec && kp_ok && G.Ncols <= 4 && op->stats == nullptr && maxM <= 16384 && minK >= 512 && op->tile == 0) {
-      DotArgs D; D.a = A; D.dCg = make_fastdiv((uint32_t)G.Cg);
-      D.per_block = (maxM <= 256 && minK >= 4096) ? 1 : 4;
-      hipLaunchKernelGGL(conv_dot_kernel, dim3(D.per_block == 1 ? maxM : gode_ceil_div(maxM, 4), G.nphase), dim3(256), 0, st, D);
-      GODE_LAUNCH_CHECK();
-      return 0;
-    }
+    const PwArgs D = pw_args(A, lpp);
+    int64_t blocks = ((int64_t)maxM + (64 / lpp) * 4 * 8 - 1) / ((64 / lpp) * 4 * 8);     // ~8 position groups per wave
+    if (blocks > (one_tap ? 4096 : 2048)) blocks = one_tap ? 4096 : 2048;
+    if (one_tap) hipLaunchKernelGGL(conv_pointwise_kernel<true>, dim3((int)blocks, 1), dim3(256), 0, st, D);
+    else hipLaunchKernelGGL(conv_pointwise_kernel<false>, dim3((int)blocks, G.nphase), dim3(256), 0, st, D);
+  } else if (P.family == IGEMM_SMALLK && ((uintptr_t)op->out % 16) == 0) {
+    const int nl = G.Ncols / 4;
+    const PwArgs D = pw_args(A, nl);
+    int64_t blocks = ((int64_t)maxM + (64 / nl) * 4 * 4 - 1) / ((64 / nl) * 4 * 4);     // ~4 position groups per wave
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(conv_smallk_kernel, dim3((int)blocks), dim3(256), 0, st, D);
+  } else if (P.family == IGEMM_DOT && vec) {
+    DotArgs D; D.a = A; D.dCg = make_fastdiv((uint32_t)G.Cg);
+    D.per_block = (maxM <= 256 && minK >= 4096) ? 1 : 4;
+    hipLaunchKernelGGL(conv_dot_kernel, dim3(D.per_block == 1 ? maxM : gode_ceil_div(maxM, 4), G.nphase), dim3(256), 0, st, D);
+  } else {      // the tiled GEMM: one launcher per entry of IGEMM_TILES (the plan's tile exists)
+    static int (*const launchers[IGEMM_TILE_IDS])(IgemmArgs&, const IgemmPlan&, bool, hipStream_t) = {
+        nullptr, launch<TILE_128x128>, launch<TILE_128x64>, launch<TILE_128x32>, launch<TILE_64x64>, nullptr, launch<TILE_256x128>};
+    return launchers[P.tile](A, P, vec, st);
   }
-  const bool sb = op->tile >= 10;   // request the double-buffered FAST variant
-  switch (tile) {
-    case TILE_128x128: return launch<2, 2, 2, 2>(A, vec, max_mblk, sb, sp, st);
-    case TILE_128x64: return launch<2, 2, 2, 1>(A, vec, max_mblk, sb, sp, st);
-    case TILE_128x32: return launch<4, 1, 1, 1>(A, vec, max_mblk, sb, sp, st);
-    case TILE_64x64: return launch<2, 2, 1, 1>(A, vec, max_mblk, sb, sp, st);
-    case TILE_128x128_W8: return launch<4, 2, 1, 2>(A, vec, max_mblk, sb, sp, st);
-    case TILE_256x128: return launch<4, 2, 2, 2>(A, vec, max_mblk, sb, sp, st);
-  }
-  return GODE_E_ARG;
+  GODE_LAUNCH_CHECK();
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,381 @@
+// igemm_plan.h -- how one implicit-GEMM op (gode_igemm_op) is launched, decided once: the phase table (plain, grouped or
+// border-split), tile, K split, live-tap mode, workgroup->XCD order and the kernel family that serves it.  Plain host
+// arithmetic on the op's geometry -- no pointer is dereferenced, no HIP -- so it builds with g++ and is pinned on the CPU
+// (tests/hostcheck/plan_check.cpp against tests/golden/igemm_plans.txt).  igemm.hip turns a plan into launches; the
+// queries of include/gode.h (gode_igemm_stats_rows / _rows0 / _stats_segments / _work_size / _model_cycles) read it.
+#pragma once
+#include <stdio.h>
+#include <stdlib.h>
+#include "conv_geom.h"
+
+#define IGEMM_MAX_LIVE_TAPS 64   // MODE 3 tap table (+1 slot read past the end)
+#define SPLITK_ROWS 16           // output positions per workgroup (and per statistics row) of the split-K finish
+#define PW_MAXW 4096             // floats of weights the pointwise kernel keeps in LDS
+
+// The tiles, indexed by tile id (gode_igemm_op.tile; 0 = auto, 5 is not a tile).  BM x BN outputs per workgroup of WM x WN
+// waves with TM x TN 32x32 MFMA tiles each (the kernels' template parameters); for the cost model the MFMA cycles of one
+// 32-deep K slab (64 per 32x32x2 instruction), the workgroups resident per CU, and the measured pipe efficiency with two
+// or more of them resident (scripts/sweep_tiles.py; 64x64 re-measured with the round-3 loop: 0.62 before).
+enum { TILE_128x128 = 1, TILE_128x64 = 2, TILE_128x32 = 3, TILE_64x64 = 4, TILE_256x128 = 6, IGEMM_TILE_IDS = 7 };
+struct IgemmTile { int bm, bn, WM, WN, TM, TN; double cps; int resident; double eff2; };
+constexpr IgemmTile igemm_tile(int WM, int WN, int TM, int TN, double cps, int resident, double eff2) {
+  return IgemmTile{WM * TM * 32, WN * TN * 32, WM, WN, TM, TN, cps, resident, eff2};
+}
+static constexpr IgemmTile IGEMM_TILES[IGEMM_TILE_IDS] = {
+    igemm_tile(0, 0, 0, 0, 0.0, 0, 0.0),
+    igemm_tile(2, 2, 2, 2, 4096.0, 2, 0.76),      // 128x128
+    igemm_tile(2, 2, 2, 1, 2048.0, 3, 0.76),      // 128x64
+    igemm_tile(4, 1, 1, 1, 1024.0, 4, 0.62),      // 128x32
+    igemm_tile(2, 2, 1, 1, 1024.0, 4, 0.70),      // 64x64
+    igemm_tile(0, 0, 0, 0, 0.0, 0, 0.0),
+    igemm_tile(4, 2, 2, 2, 8192.0, 1, 0.785)};    // 256x128, 8 waves
+
+static bool tile_exists(int tile) { return tile > 0 && tile < IGEMM_TILE_IDS && IGEMM_TILES[tile].bm != 0; }
+static int tile_bm(int tile) { return IGEMM_TILES[tile].bm; }
+static int tile_bn(int tile) { return IGEMM_TILES[tile].bn; }
+static int64_t count_tiles(const IgemmGeom& G, int tile) {      // workgroups of a launch of G with this tile
+  int64_t n = 0;
+  for (int i = 0; i < G.nphase; ++i) n += (int64_t)gode_ceil_div(G.ph[i].M, tile_bm(tile)) * gode_ceil_div(G.Ncols, tile_bn(tile));
+  return n;
+}
+
+// split-K plan: purely a function of the geometry (so gode_igemm_stats_rows / gode_igemm_work_size agree with the
+// launch).  Used when the FAST kernel applies and the natural grid would leave most of the 256 CUs idle.
+struct SplitPlan { int ksplit, slabs_per_split, positions; };
+static SplitPlan split_k(const gode_igemm_op* op, const IgemmGeom& G, int max_slabs, int k) {     // k <= 1: no split
+  SplitPlan sp = {1, 0, op->g.N * G.Xd * G.Xh * G.Xw};
+  if (k > 1) { sp.slabs_per_split = gode_ceil_div(max_slabs, k); sp.ksplit = gode_ceil_div(max_slabs, sp.slabs_per_split); }
+  return sp;
+}
+static void slab_range(const IgemmGeom& G, int* min_slabs, int* max_slabs) {     // 32-deep K slabs of the shortest / longest phase
+  *min_slabs = 1 << 30; *max_slabs = 0;
+  for (int i = 0; i < G.nphase; ++i) {
+    const int ns = G.ph[i].K >> 5;
+    if (ns > *max_slabs) *max_slabs = ns;
+    if (ns < *min_slabs) *min_slabs = ns;
+  }
+}
+
+static bool fast_geometry(const IgemmGeom& G) {
+  bool ok = G.Cg % 32 == 0;
+  for (int i = 0; i < G.nphase; ++i) ok = ok && G.ph[i].K >= 32 && G.ph[i].K % 32 == 0 && G.ph[i].Kp == G.ph[i].K;
+  return ok;
+}
+
+static bool strides_allow_vec(const gode_igemm_op* op, const IgemmGeom& G) {
+  if (gode_strides_are_channels_last(op->gs)) return G.Cg % 4 == 0;
+  return op->gs[4] == 1 && G.Cg % 4 == 0 && op->gs[0] % 4 == 0 && op->gs[1] % 4 == 0 && op->gs[2] % 4 == 0 &&
+         op->gs[3] % 4 == 0;
+}
+
+static SplitPlan plan_split(const gode_igemm_op* op, const IgemmGeom& G, int tile) {
+  const SplitPlan sp = split_k(op, G, 0, 1);
+  if (!fast_geometry(G) || G.Ncols <= 4 || !strides_allow_vec(op, G)) return sp;
+  // known oddity, kept so that no plan changes: a requested 256x128 tile has its grid counted in 128x64 blocks
+  const int64_t blocks = count_tiles(G, tile == TILE_256x128 ? TILE_128x64 : tile);
+  int max_slabs, min_slabs;
+  slab_range(G, &min_slabs, &max_slabs);
+  if (blocks >= 64 || min_slabs < 8) return sp;   // only grids that would leave >3/4 of the CUs idle
+  int k = (int)((512 + blocks - 1) / blocks);
+  if (k > min_slabs / 4) k = min_slabs / 4;
+  if (k > 32) k = 32;
+  return split_k(op, G, max_slabs, k);
+}
+
+// The tile off the modelled path: the requested one, or thresholds on the output columns and the grid.
+static int pick_tile(const IgemmGeom& G, int requested) {
+  if (requested != 0) return requested;
+  if (G.Ncols <= 32) return TILE_128x32;
+  if (G.Ncols <= 64) return TILE_128x64;
+  const int64_t blocks = count_tiles(G, TILE_128x128);
+  if (blocks >= 192) return TILE_128x128;
+  // with split-K available a starved grid is better served by the big tile (unless there are very few rows)
+  int maxM = 0;
+  for (int i = 0; i < G.nphase; ++i) if (G.ph[i].M > maxM) maxM = G.ph[i].M;
+  return fast_geometry(G) && maxM > tile_bm(TILE_64x64) && blocks < 64 ? TILE_128x128 : TILE_64x64;
+}
+
+// MODE 3 of the FAST kernel (live taps only) pays for its slower loop when the temporal taps that fall off the tensor's
+// ends are > 15 % of the K loop (temporal stride 1: Do of the Di planes' taps are live)
+static bool igemm_wants_tapskip(const gode_igemm_op* op, const IgemmGeom& G) {
+  if (!(op->dir == GODE_DGRAD && op->groups != 2 && !G.fullk && op->g.sd == 1 && G.ph[0].Td > 1 && 100 * op->g.Do < 85 * op->g.Di))
+    return false;
+  for (int i = 0; i < G.nphase; ++i) if (G.ph[i].Td * G.ph[i].Th * G.ph[i].Tw >= IGEMM_MAX_LIVE_TAPS) return false;
+  return true;
+}
+
+// Tile and K-split of a FAST-path GEMM from a small cost model instead of thresholds.  All workgroups of a launch
+// carry equal work and the dispatcher deals them evenly, so the launch lasts as long as the busiest CU:
+//   time = ceil(workgroups / 256) * (fixed + slabs * cycles_per_slab(tile) / efficiency) [+ split-K reduce]
+// with the MFMA cycles of one 32-deep slab (64 per 32x32x2 instruction), the measured pipe efficiencies of the tiles
+// (two or more resident workgroups per CU overlap each other's barriers; a lone one cannot) and ~4k cycles of
+// prologue + epilogue.  Checked against measurements: ConvT 128->64 (4096 x 128x64) 314 us model / 297 us measured;
+// UCF video-D layer-2 dgrad 128x128 578 / 514 us, for which the model prefers 128x64 (436 us).
+static void choose_fast(const gode_igemm_op* op, const IgemmGeom& G, int* tile_out, SplitPlan* sp_out, double* cycles_out) {
+  const gode_conv_geom& g = op->g;
+  const int positions = g.N * G.Xd * G.Xh * G.Xw;
+  const double out_bytes = 4.0 * positions * G.Ncols;
+  int max_slabs, min_slabs;
+  slab_range(G, &min_slabs, &max_slabs);
+  bool even_phases = true;        // phases of unequal size leave early-exit workgroups in the grid: measured, a K split
+  for (int i = 0; i < G.nphase; ++i)     // then gains nothing (video-D layer 3 dgrad: 101 us split 3 ways vs 64 us unsplit)
+    even_phases = even_phases && G.ph[i].M == G.ph[0].M;
+  // 256x128 (8 waves, one workgroup per CU, 25 % less operand traffic per MFMA) last: 2-3 % ahead of 128x128 on the full
+  // decoder grids and 5 % on the MNIST video-D layer-2 input gradient (scripts/sweep_tiles.py), behind it on grids that
+  // do not fill whole rounds of 256 such tiles
+  static const int tiles[5] = {TILE_128x128, TILE_128x64, TILE_64x64, TILE_128x32, TILE_256x128};
+  static const int ksplits[10] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
+  const bool live_taps = igemm_wants_tapskip(op, G);
+  double best = 1e300;
+  int best_tile = G.Ncols <= 32 ? TILE_128x32 : TILE_128x64, best_k = 1;
+  for (int ti = 0; ti < 5; ++ti) {
+    const int t = tiles[ti], bn = tile_bn(t);
+    if (bn >= 2 * G.Ncols && bn > 32) continue;              // more than half of every tile would be padding
+    if (t == TILE_128x32 && G.Ncols > 32) continue;
+    if (t == TILE_256x128 && (live_taps || op->groups == 2)) continue;     // (measured on plain launches only)
+    const double cps = IGEMM_TILES[t].cps, eff2 = IGEMM_TILES[t].eff2;
+    const int resident = IGEMM_TILES[t].resident;
+    const int64_t tiles_n = count_tiles(G, t);
+    if (t == TILE_256x128 && tiles_n < 192) continue;        // one workgroup per CU: needs a grid that covers the chip
+    for (int ki = 0; ki < 10; ++ki) {
+      const int k = ksplits[ki];
+      // (uneven phases: no split once the unsplit grid already covers half the chip -- see above; tiny grids, e.g. the
+      // image discriminator's 7x7 <- 3x3 input gradient with 25 tiles, still gain from one: 29.5 -> ~20 us)
+      if (k > 1 && (min_slabs / k < 4 || out_bytes * k > 192e6 || min_slabs != max_slabs || (!even_phases && tiles_n >= 128))) break;
+      // the 256x128 tile only unsplit (measured with K splits: never ahead); live-tap launches split only grids that do
+      // not fill the chip (UCF video-D layer 2 input gradient at N = 16: 269 us unsplit, 318 us split 2 ways)
+      if (k > 1 && (t == TILE_256x128 || (live_taps && tiles_n >= 256))) break;
+      const int64_t blocks = tiles_n * k;
+      // live-tap launches: tiles of the end planes are short, so the hardware's in-order dispatch evens the CUs out and
+      // the whole-rounds quantisation does not apply to the big tile (measured, UCF video-D layer 2 input gradient at
+      // N=32, 640 tiles of 128x128 vs 1280 of 128x64: 10 % apart although 640 is 2.5 rounds; at N=16 the smaller tile
+      // with a K split stays ahead by 5 %)
+      const double per_cu = (live_taps && t == TILE_128x128 && k == 1 && blocks >= 512) ? blocks / 256.0 : (double)((blocks + 255) / 256);
+      const int slabs = gode_ceil_div(max_slabs, k);
+      const double eff = ((per_cu >= 2 && resident >= 2) || t == TILE_256x128) ? eff2 : 0.8 * eff2;    // (8 waves cover their own barriers)
+      double cyc = per_cu * (4000.0 + slabs * cps / eff);
+      if (k > 1) cyc += 2.4e9 * (2.5e-6 + (k + 1) * out_bytes / 3e12);
+      if (cyc < best * 0.97) { best = cyc; best_tile = t; best_k = k; }   // 3 % hysteresis toward the earlier (larger) choice
+    }
+  }
+  *cycles_out = best;
+  if (live_taps) {
+    // Live-tap launches whose 128x128 grid does not cover the chip (UCF video-D layer 3 input gradient: 224 / 112 tiles): the
+    // tiles of the end planes are a quarter as long as those of the middle planes and all of them are resident at once, so the
+    // launch lasts as long as the CU that drew the long ones -- the estimate above (equal tiles) is 20-30 % off there.  Small
+    // tiles even that out: 4-5 workgroups of 64x64 per CU (scripts/sweep_tiles.py, N = 32 / 16: 371 -> 288 us unsplit, 209 ->
+    // 179 us split 3 ways; every other live-tap shape of the configs keeps the model's choice within 2 %).
+    const int64_t t128 = count_tiles(G, TILE_128x128), t64 = count_tiles(G, TILE_64x64);
+    if (t128 < 256 && G.Ncols >= 64 && min_slabs == max_slabs) {
+      int k = (int)((1152 + t64 / 2) / t64);
+      if (k < 1) k = 1;
+      while (k > 1 && (min_slabs / k < 8 || out_bytes * k > 192e6)) --k;
+      best_tile = TILE_64x64; best_k = k;
+    }
+  }
+  *tile_out = best_tile;
+  *sp_out = split_k(op, G, max_slabs, best_k);
+}
+
+// The border-split table of an op that asks for it (gode_igemm_op.border), or false: FPROP, fullk, image groups, live-tap
+// (MODE 3) launches and shapes that do not split keep the plain table.
+static bool border_table(const gode_igemm_op* op, const IgemmGeom& G, IgemmGeom* B) {
+  if (!op->border || op->dir != GODE_DGRAD || op->groups == 2 || G.fullk || igemm_wants_tapskip(op, G)) return false;
+  return gode_build_igemm_geom_border(op->g, op->dir, B) == 0 && B->border != 0;
+}
+
+// Cost of a FAST launch over a border-split table.  Its tiles differ in length (interior / edge / corner sub-phases: K, K/2,
+// K/4 on a k4 s2 layer), the grid holds only live tiles and the longest come first, so the in-order dispatcher evens the
+// CUs out and the launch lasts the summed work over the 256 CUs -- once there are clearly more tiles than workgroup slots
+// and three or more workgroups per CU.  Measured on the three decoder layers at 512 rows (profiles/border_split_layers.md):
+//   128x64 tiles (1024 / 2048 / 4096 of them on 768 slots): 0.826 / 0.929 / 1.004 of the plain launch with the same tile
+//   where the summed work is 0.771 / 0.884 / 0.944 of it -- a loss of 1.071 / 1.050 / 1.064 against the sum: BORDER_LOSS;
+//   a tail term (a share of one longest tile) fitted to the same launches came out at 0.01: the shortest tiles go last;
+//   128x128 (512 tiles on 512 slots, 1024 on 512) and 256x128 (256 / 512 tiles on 256 slots): within 1 % of plain -- all
+//   tiles are resident in one or two rounds and some CU draws only long ones.  Those tiles are not offered.
+// Same per-tile constants as choose_fast.  Never a K split.
+#define BORDER_LOSS 1.06
+static void choose_border(const IgemmGeom& B, int* tile_out, double* cycles_out) {
+  static const int tiles[2] = {TILE_128x64, TILE_64x64};     // (three or more workgroups per CU: see above)
+  double best = 1e300; int best_tile = TILE_128x64;
+  for (int ti = 0; ti < 2; ++ti) {
+    const int t = tiles[ti], bm = tile_bm(t), bn = tile_bn(t);
+    if (bn >= 2 * B.Ncols && bn > 32) continue;
+    const double cps = IGEMM_TILES[t].cps, eff = IGEMM_TILES[t].eff2;
+    const int resident = IGEMM_TILES[t].resident;
+    if (3 * count_tiles(B, t) < 4 * 256 * (int64_t)resident) continue;     // (measured down to 4/3 tiles per slot)
+    double work = 0;
+    for (int i = 0; i < B.nphase; ++i)
+      work += (double)gode_ceil_div(B.ph[i].M, bm) * gode_ceil_div(B.Ncols, bn) * (4000.0 + (B.ph[i].K >> 5) * cps / eff);
+    const double cyc = BORDER_LOSS * work / 256.0;
+    if (cyc < best) { best = cyc; best_tile = t; }
+  }
+  *tile_out = best_tile; *cycles_out = best;
+}
+
+// Which kernel of igemm.hip / conv_patch.hip serves the op.  The thin-output streaming kernels and the patch kernel need
+// aligned pointers besides: gode_igemm falls back to the tiled GEMM of the same plan when they are not (or when
+// conv_patch.hip declines the shape).
+enum { IGEMM_GEMM = 0, IGEMM_PATCH_FPROP = 1, IGEMM_POINTWISE = 2, IGEMM_SMALLK = 3, IGEMM_DOT = 4 };
+
+struct IgemmPlan {
+  IgemmGeom G;                                 // the phase table in use (plain, two image groups, or border-split), row0 filled in
+  int32_t family;
+  int32_t tile;                                // index into IGEMM_TILES
+  int32_t vec, fast;                           // strides allow float4 gathers; ... and the FAST kernel (every phase's K in whole slabs)
+  int32_t ksplit, slabs_per_split, positions;  // split-K: ksplit copies of the grid, partial tiles of `positions` rows each
+  int32_t max_mblk, stats_rows, rows0;         // rows of the partial statistics; those of image group 0
+  int32_t tapskip, dmajor;                     // FAST kernel MODE 3; depth-major rows with this many images
+  int32_t xcd_mode, MB, NB;                    // FAST kernel's 1-D grid order (igemm_block_id)
+  int32_t ntab, tile0[GODE_MAX_PHASES + 1];    // border-split table: first workgroup of each sub-phase, tile0[ntab] = grid
+  double cycles;                               // the cost model's estimate, or -1 off the modelled path (and for image groups)
+};
+
+// The kernels beside the tiled GEMM (tile = 0 and no statistics only; image groups carry statistics).
+static int thin_family(const gode_igemm_op* op, const IgemmGeom& G, bool vec) {
+  if (op->tile != 0 || op->stats != nullptr || op->groups == 2) return IGEMM_GEMM;
+  // first layers with 1-4 input channels: offered to conv_patch.hip (which takes 32 / 64 / 128 output channels and its own
+  // list of tap shapes); none of the shapes below
+  if (op->dir == GODE_FPROP && !op->scale && !op->shift && op->act == GODE_ACT_NONE && op->epilogue == GODE_EPI_RAW && op->g.Ci <= 4 &&
+      op->g.Co >= 32 && G.ph[0].K >= 8)
+    return IGEMM_PATCH_FPROP;
+  int maxM = 0, minK = 1 << 30, maxK = 0; bool kp_ok = true;
+  for (int i = 0; i < G.nphase; ++i) {
+    if (G.ph[i].M > maxM) maxM = G.ph[i].M;
+    if (G.ph[i].K < minK) minK = G.ph[i].K;
+    if (G.ph[i].Kp > maxK) maxK = G.ph[i].Kp;
+    kp_ok = kp_ok && G.ph[i].Kp == G.ph[i].K;
+  }
+  const int lpp = G.Cg / 4, nl = G.Ncols / 4;
+  const bool one_tap = G.nphase == 1 && G.ph[0].K == G.Cg;
+  // the multi-tap form needs many positions to beat the padded MFMA path (measured: M = 25 k slower, M >= 65 k faster)
+  if (vec && kp_ok && G.Ncols <= 4 && G.Ncols * maxK <= PW_MAXW && maxM >= (one_tap ? 4096 : 65536) &&
+      (lpp == 4 || lpp == 8 || lpp == 16 || lpp == 32 || lpp == 64))
+    return IGEMM_POINTWISE;
+  // K <= 4 only: at K = 8 / 16 (first discriminator layers) the per-lane gather chain made it no faster than the
+  // padded MFMA path (24.9 vs 22 us, 15.7 vs 10 us); at K = 1 it is 27 us against 63 us
+  if (G.nphase == 1 && G.ph[0].K <= 4 && G.Ncols % 4 == 0 && G.Ncols <= 128 && maxM >= 2048 && (nl == 4 || nl == 8 || nl == 16 || nl == 32))
+    return IGEMM_SMALLK;
+  if (vec && kp_ok && G.Ncols <= 4 && maxM <= 16384 && minK >= 512) return IGEMM_DOT;
+  return IGEMM_GEMM;
+}
+
+// Order of the FAST kernel's 1-D grid over the 8 XCDs (igemm_block_id), and the tile table of a border-split launch.
+static void plan_grid_order(const gode_igemm_op* op, IgemmPlan* P) {
+  const IgemmGeom& G = P->G;
+  P->MB = 0; P->NB = 0; P->xcd_mode = 0; P->ntab = 0;
+  for (int i = 0; i <= GODE_MAX_PHASES; ++i) P->tile0[i] = 0;
+  if (!P->fast) return;
+  const int MB = P->max_mblk, NB = gode_ceil_div(G.Ncols, tile_bn(P->tile)), NC = NB * G.nphase;
+  P->MB = MB; P->NB = NB;
+  static const char* xenv = getenv("GODE_IGEMM_XCD");
+  const int force = xenv ? atoi(xenv) : -1;
+  const int64_t wbytes = gode_pack_floats(G) * 4;
+  const bool ok1 = (NC % 8 == 0) || (NC < 8 && 8 % NC == 0 && MB % (8 / NC) == 0);
+  const bool ok2 = MB % 8 == 0;
+  // measured L2-miss (fabric) fetch per launch on the three decoder layers, forward / backward-data, raw FETCH_SIZE MB:
+  // mode 0: 45/95/411, 76/139/161;  mode 1: 203/230/338, 197/222/161;  mode 2: 68/73/46, 76/93/161;
+  // mode 3: 68/33/36, 60/89/154 -- at equal launch times (+-1.5 %), so the choice is made on traffic alone
+  // Mode 3 makes every XCD read the whole weight pack once; when 8 copies of it outweigh the gathered tensor 3:1
+  // (ConvT 512->256 forward: 8 x 8.4 MB vs 16.8 MB) the plain order, which spreads the panels, fetches less.
+  const int64_t in_bytes = (int64_t)op->g.N * G.Gd * G.Gh * G.Gw * G.Cg * 4;
+  int mode = ok2 ? (wbytes * 8 < 3 * in_bytes ? 3 : 0) : 0;
+  // depth-major rows with dead-tap skipping: the tiles of the end planes are light, so a contiguous run per XCD would
+  // leave the XCDs that own them idle -- interleave the m-blocks over the XCDs instead
+  // -- and NOT the plain order either: it hands an XCD m-blocks 8 apart, i.e. (at 16 tiles per depth plane) only
+  // planes of one weight: UCF video-D layer 2 at N = 32 runs 600 us in the plain order, 845 us with contiguous runs,
+  // 470 us interleaved (scripts/exp/xcd_sweep.py; no other shape of either config moves by more than 2 %)
+  if (P->dmajor > 0) mode = ok2 ? 2 : (ok1 ? 1 : 0);
+  if (force == 0) mode = 0;
+  if (force == 1 && ok1) mode = 1;
+  if (force == 2 && ok2) mode = 2;
+  if (force == 3 && ok2) mode = 3;
+  P->xcd_mode = mode;
+  if (G.border) {       // (never with a K split or live taps: see igemm_make_plan and border_table)
+    P->ntab = G.nphase;
+    for (int i = 0; i < G.nphase; ++i) P->tile0[i + 1] = P->tile0[i] + gode_ceil_div(G.ph[i].M, tile_bm(P->tile)) * NB;
+    for (int i = G.nphase + 1; i <= GODE_MAX_PHASES; ++i) P->tile0[i] = P->tile0[G.nphase];
+  }
+}
+
+static int igemm_make_plan(const gode_igemm_op* op, IgemmPlan* P) {
+  if (!op || (op->tile != 0 && !tile_exists(op->tile))) return GODE_E_ARG;
+  IgemmGeom& G = P->G;
+  int rc = gode_build_igemm_geom(op->g, op->dir, &G);
+  if (rc) return rc;
+  // input gradient of a convolution with temporal taps: depth-major tiles, so that the taps falling off the tensor's ends
+  // are dead for whole tiles (skipped in the FAST kernel's K loop).  Every tile sees one or two planes (a small plane) or
+  // a slice of one (a plane of >= 128 rows, which would fill tiles by itself in image-major order too -- but depth-major
+  // with the interleaved XCD order is 4-6 % faster there as well: UCF video-D layer 1 input gradient 833 -> 800 us at
+  // N = 32, 405 -> 381 at N = 16).
+  P->tapskip = igemm_wants_tapskip(op, G);
+  P->dmajor = P->tapskip ? op->g.N : 0;
+  IgemmGeom B;
+  const bool can_border = border_table(op, G, &B);
+  const bool grouped = op->groups == 2;
+  if (grouped) {
+    // two image groups with SEPARATE BatchNorm partial statistics (one discriminator pass over [real; fake]): the
+    // single FPROP phase becomes two phases over the two halves of the batch, so no tile straddles the groups and
+    // each group's partial-statistics rows are contiguous
+    if (op->dir != GODE_FPROP || op->g.N % 2 != 0 || G.nphase != 1) return GODE_E_ARG;
+    G.ph[1] = G.ph[0];
+    G.ph[0].M /= 2; G.ph[1].M = G.ph[0].M; G.ph[1].img0 = op->g.N / 2;
+    G.nphase = 2;
+  } else if (op->groups != 0 && op->groups != 1) return GODE_E_ARG;
+  P->vec = strides_allow_vec(op, G);
+  int tile; SplitPlan sp; double cyc = -1.0;
+  bool take_border = false;
+  if (op->tile == 0 && fast_geometry(G) && G.Ncols > 4 && P->vec) {
+    choose_fast(op, G, &tile, &sp, &cyc);
+    if (can_border && fast_geometry(B) && sp.ksplit == 1) {
+      // per layer: the border form only where the model prices it below the plain launch (3 % hysteresis toward plain).
+      // A launch that splits K keeps doing so: a K split adds its partial sums in another order, and an op with the flag
+      // must give the raw outputs of the op without it bit for bit
+      int tb; double cb;
+      choose_border(B, &tb, &cb);
+      if (cb < 0.97 * cyc) { take_border = true; tile = tb; cyc = cb; }
+    }
+    // calibration runs (scripts/sweep_tiles.py): GODE_IGEMM_SWEEP enables GODE_IGEMM_FORCE="tile,k", re-read per call
+    static const bool sweeping = getenv("GODE_IGEMM_SWEEP") != nullptr;
+    const char* fenv = sweeping ? getenv("GODE_IGEMM_FORCE") : nullptr;
+    int fk = 0, min_slabs, max_slabs;
+    if (fenv && sscanf(fenv, "%d,%d", &tile, &fk) == 2) {
+      if (!tile_exists(tile)) return GODE_E_ARG;
+      slab_range(G, &min_slabs, &max_slabs);
+      sp = split_k(op, G, max_slabs, fk);
+      take_border = can_border && fk <= 1;     // (they time the border form with the forced tile)
+    }
+  } else {
+    tile = pick_tile(G, op->tile);
+    sp = plan_split(op, G, tile);
+    // a REQUESTED tile takes the border form unless a plan splits K; tile = 0 off the modelled path (generic kernel, odd
+    // channel counts) stays plain: nothing measured says it would pay there
+    if (can_border && sp.ksplit == 1 && op->tile != 0) {
+      const int tb = pick_tile(B, op->tile);
+      const SplitPlan sb = plan_split(op, B, tb);
+      if (sb.ksplit == 1) { take_border = true; tile = tb; sp = sb; }
+    }
+  }
+  if (take_border) G = B;
+  if (grouped && sp.ksplit > 1 && (sp.positions / 2) % SPLITK_ROWS != 0) {
+    // the split-K finish emits one statistics row per SPLITK_ROWS output positions: the groups must not share a row
+    sp.ksplit = 1; sp.slabs_per_split = 0;
+  }
+  const int bm = tile_bm(tile);
+  int r0 = 0, mx = 0;
+  for (int i = 0; i < G.nphase; ++i) {
+    G.ph[i].row0 = r0;
+    const int mb = gode_ceil_div(G.ph[i].M, bm);
+    r0 += mb;
+    if (mb > mx) mx = mb;
+  }
+  P->tile = tile; P->ksplit = sp.ksplit; P->slabs_per_split = sp.slabs_per_split; P->positions = sp.positions;
+  P->max_mblk = mx;
+  P->stats_rows = sp.ksplit > 1 ? gode_ceil_div(sp.positions, SPLITK_ROWS) : r0;
+  P->rows0 = !grouped ? P->stats_rows : (sp.ksplit > 1 ? P->stats_rows / 2 : G.ph[1].row0);
+  P->cycles = grouped ? -1.0 : cyc;        // (its reader splits a batch into two launches; a grouped pass is never split)
+  P->fast = P->vec && fast_geometry(G);
+  P->family = thin_family(op, G, P->vec);
+  plan_grid_order(op, P);
+  return 0;
+}

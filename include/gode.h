@@ -54,7 +54,7 @@ typedef struct gode_conv_geom {
  * gode_bn_finalize, which reads each channel's rows contiguously. */
 typedef struct gode_igemm_op {
   gode_conv_geom g;
-  int32_t dir, act, epilogue, tile; /* tile: 0 auto */
+  int32_t dir, act, epilogue, tile; /* tile: 0 auto; 1 128x128, 2 128x64, 3 128x32, 4 64x64, 6 256x128; else GODE_E_ARG */
   const float* src;
   const float* wpack;
   float* out;

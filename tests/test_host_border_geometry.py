@@ -91,3 +91,19 @@ def test_model_chooses_per_layer_and_never_prices_the_flag_above_plain():
         plain = lib.gode_igemm_model_cycles(C.byref(L.IgemmOp(g=g, dir=L.DGRAD, tile=0)))
         flag = lib.gode_igemm_model_cycles(C.byref(L.IgemmOp(g=g, dir=L.DGRAD, tile=0, border=1)))
         assert 0 < flag <= plain
+
+
+@pytest.mark.parametrize("tile", [5, 7, 12, -1])
+def test_a_tile_that_does_not_exist_is_refused(tile):
+    """Only 0 (auto) and the tiles 1, 2, 3, 4 and 6 exist: anything else is an argument error in every query (the model
+    estimate is -1 for any requested tile, existing or not)."""
+    lib = L.lib()
+    g = _convt(512, 64, 96, 4)
+    for kw in (dict(dir=L.DGRAD), dict(dir=L.DGRAD, border=1), dict(dir=L.FPROP), dict(dir=L.FPROP, groups=2)):
+        op = L.IgemmOp(g=g, tile=tile, **kw)
+        assert lib.gode_igemm_stats_rows(C.byref(op)) == -1
+        assert lib.gode_igemm_stats_rows0(C.byref(op)) == -1
+        assert lib.gode_igemm_work_size(C.byref(op)) == -1
+        assert lib.gode_igemm_model_cycles(C.byref(op)) == -1.0
+    assert lib.gode_igemm_model_cycles(C.byref(L.IgemmOp(g=g, dir=L.DGRAD, tile=2))) == -1.0
+    assert lib.gode_igemm_model_cycles(C.byref(L.IgemmOp(g=g, dir=L.DGRAD, tile=0))) > 0
