@@ -288,6 +288,7 @@ _PROTOS = {
     "gode_igemm_stats_rows0": ([ptr], cint),
     "gode_igemm_stats_segments": ([ptr, i32, ptr], cint),
     "gode_igemm_model_cycles": ([ptr], C.c_double),
+    "gode_igemm_family": ([ptr], cint),
     "gode_igemm_work_size": ([ptr], i64),
     "gode_pack_size": ([ptr, cint], i64),
     "gode_pack_weights": ([ptr, cint, ptr, ptr, ptr, i32, ptr], cint),

@@ -905,6 +905,86 @@ __global__ void __launch_bounds__(256) conv_pointwise_kernel(const PwArgs d) {
   }
 }
 
+// lane i takes x of lane i + N (row_down) / i - N (row_up) of its row of 16 lanes as a DPP operand, 0 past the row's end
+template <int N> __device__ __forceinline__ float row_down(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x100 + N, 0xf, 0xf, true));
+}
+template <int N> __device__ __forceinline__ float row_up(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x110 + N, 0xf, 0xf, true));
+}
+
+// The one-tap form with ONE output column and <= 16 lanes per position (the MNIST head, 64 -> 1): the body above is bound
+// by instruction issue there (~200 per KiB of input: 30.9 us, 3.3 TB/s on the sampling step's 103 MB), not by HBM; this one
+// issues ~90 per KiB (18.9 us, 5.5 TB/s: profiles/sampling_small_kernels.md).  A wave takes PW1_U consecutive position
+// groups per iteration: their loads are issued together, the position is decoded once and stepped, one accumulator per
+// group is reduced over the LPP lanes of a position with DPP row shifts -- lane i adds lane i + o, o = LPP/2 ... 1, which
+// on the first lane of a position is the xor butterfly's sum, pair for pair -- and the first PW1_U lanes of a position
+// then take one group's sum each, so the tanh sequence and the store run once per iteration.  Same values bit for bit.
+#define PW1_U 4
+template <int LPP>
+__global__ void __launch_bounds__(256) conv_pointwise1_kernel(const PwArgs d) {
+  static_assert(LPP >= PW1_U && LPP <= 16, "a position's lanes lie in one DPP row and hold one result per group");
+  constexpr int PPW = 64 / LPP;
+  const IgemmArgs& a = d.a;
+  const PhaseGeom& P = a.G.ph[0];
+  const int lane = threadIdx.x & 63, sub = lane / LPP, q = lane % LPP, ch = q * 4;
+  const float neg = a.act == GODE_ACT_RELU ? 0.f : (a.act == GODE_ACT_LRELU ? 0.2f : 1.f);
+  f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+  if (a.scale) { sc = *reinterpret_cast<const f32x4*>(a.scale + ch); sh = *reinterpret_cast<const f32x4*>(a.shift + ch); }
+  const f32x4 w = *reinterpret_cast<const f32x4*>(a.w + P.w_off + ch);
+  const bool stepping = PPW <= P.Mw;          // a step of PPW positions carries at most once per coordinate
+  const int64_t wave_id = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+  for (int64_t m0 = wave_id * (PPW * PW1_U); m0 < P.M; m0 += nwaves * (PPW * PW1_U)) {
+    uint32_t qw = 0, qh = 0, qd = 0, img = 0;
+    uint32_t rw = 0, rh = 0, rd = 0, ri = 0;    // lane q < PW1_U: the position of group q, whose result it stores
+    bool st = false;
+    bool ok[PW1_U];
+    f32x4 v[PW1_U];
+#pragma unroll
+    for (int g = 0; g < PW1_U; ++g) {
+      const int64_t m = m0 + g * PPW + sub;
+      const bool live = m < P.M;
+      if (g == 0 || !stepping) {
+        const uint32_t mm = live ? (uint32_t)m : 0u;
+        const uint32_t t1 = fdiv(mm, d.dMw[0]); qw = mm - t1 * P.Mw;
+        const uint32_t t2 = fdiv(t1, d.dMh[0]); qh = t1 - t2 * P.Mh;
+        img = fdiv(t2, d.dMd[0]); qd = t2 - img * P.Md;
+      } else {
+        qw += PPW;
+        const bool cw = qw >= (uint32_t)P.Mw; qw -= cw ? P.Mw : 0; qh += cw;
+        const bool chh = qh >= (uint32_t)P.Mh; qh = chh ? 0u : qh; qd += chh;
+        const bool cd = qd >= (uint32_t)P.Md; qd = cd ? 0u : qd; img += cd;
+      }
+      const int id = (int)qd * a.G.Sd + P.Od, ih = (int)qh * a.G.Sh + P.Oh, iw = (int)qw * a.G.Sw + P.Ow;
+      ok[g] = live && (unsigned)id < (unsigned)a.G.Gd && (unsigned)ih < (unsigned)a.G.Gh && (unsigned)iw < (unsigned)a.G.Gw;
+      // (a position outside the source or past the end reads the first position's channels, and its sum is dropped)
+      const int so = ok[g] ? (int)img * a.gsN + id * a.gsD + ih * a.gsH + iw * a.gsW : 0;
+      v[g] = *reinterpret_cast<const f32x4*>(a.src + so + ch);
+      if (q == g) { st = live; rw = qw; rh = qh; rd = qd; ri = img; }
+    }
+    float acc[PW1_U];
+#pragma unroll
+    for (int g = 0; g < PW1_U; ++g) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { const float u = v[g][e] * sc[e] + sh[e]; v[g][e] = fmaxf(u, u * neg); }
+      // v[0]*w[0] + v[1]*w[1] + v[2]*w[2] + v[3]*w[3] as the body above contracts it, spelled out so that it cannot change
+      acc[g] = 0.f;
+      acc[g] += fmaf(v[g][3], w[3], fmaf(v[g][2], w[2], fmaf(v[g][1], w[1], v[g][0] * w[0])));
+      acc[g] = ok[g] ? acc[g] : 0.f;
+      if (LPP > 8) acc[g] += row_down<8>(acc[g]);
+      if (LPP > 4) acc[g] += row_down<4>(acc[g]);
+      acc[g] += row_down<2>(acc[g]);
+      acc[g] += row_down<1>(acc[g]);
+    }
+    // lane q of the position takes group q's sum from the position's first lane (every lane runs the shifts)
+    static_assert(PW1_U == 4, "one shift per group below");
+    const float r1 = row_up<1>(acc[1]), r2 = row_up<2>(acc[2]), r3 = row_up<3>(acc[3]);
+    const float res = q == 1 ? r1 : (q == 2 ? r2 : (q == 3 ? r3 : acc[0]));
+    const int oo = (((int)ri * a.G.Xd + (int)rd * a.G.OSd + P.Pd) * a.G.Xh + (int)rh * a.G.OSh + P.Ph) * a.G.Xw + (int)rw * a.G.OSw + P.Pw;
+    if (q < PW1_U && st) a.out[oo] = a.epilogue == GODE_EPI_TANH ? tanhf(res) : res;
+  }
+}
+
 // Tiny-K layers (K = taps x channels, one phase; dispatched for K <= 4): the backward-data of the generator head (Conv
 // 1 -> 64, k1: K = 1) writes 64x more than it reads, so it is an output-bound HBM pass: the weight matrix sits in LDS as
 // [k][column], Ncols/4 lanes share a position (each gathers the K inputs itself -- same addresses, one broadcast -- and
@@ -970,6 +1050,13 @@ extern "C" int gode_igemm_stats_rows0(const gode_igemm_op* op) {
 extern "C" double gode_igemm_model_cycles(const gode_igemm_op* op) {
   IgemmPlan P;
   return igemm_make_plan(op, &P) ? -1.0 : P.cycles;
+}
+
+// which kernel family the plan gives the op (IGEMM_GEMM ... IGEMM_DOT), host-side
+extern "C" int gode_igemm_family(const gode_igemm_op* op) {
+  IgemmPlan P;
+  const int rc = igemm_make_plan(op, &P);
+  return rc ? rc : P.family;
 }
 
 extern "C" int gode_igemm_stats_segments(const gode_igemm_op* op, int32_t split_images, int32_t* seg) {
@@ -1112,7 +1199,15 @@ extern "C" int gode_igemm(const gode_igemm_op* op, void* stream) {
     const PwArgs D = pw_args(A, lpp);
     int64_t blocks = ((int64_t)maxM + (64 / lpp) * 4 * 8 - 1) / ((64 / lpp) * 4 * 8);     // ~8 position groups per wave
     if (blocks > (one_tap ? 4096 : 2048)) blocks = one_tap ? 4096 : 2048;
-    if (one_tap) hipLaunchKernelGGL(conv_pointwise_kernel<true>, dim3((int)blocks, 1), dim3(256), 0, st, D);
+    if (one_tap && G.Ncols == 1 && lpp <= 16) {
+      // every wave resident at once (<= 8 per SIMD on 1024 SIMDs) and the same number of iterations for all, within one
+      const int64_t its = ((int64_t)maxM + (64 / lpp) * PW1_U - 1) / ((64 / lpp) * PW1_U), per_wave = (its + 8191) / 8192;
+      const dim3 g1((unsigned)((its + 4 * per_wave - 1) / (4 * per_wave)));
+      if (lpp == 16) hipLaunchKernelGGL(conv_pointwise1_kernel<16>, g1, dim3(256), 0, st, D);
+      else if (lpp == 8) hipLaunchKernelGGL(conv_pointwise1_kernel<8>, g1, dim3(256), 0, st, D);
+      else hipLaunchKernelGGL(conv_pointwise1_kernel<4>, g1, dim3(256), 0, st, D);
+    }
+    else if (one_tap) hipLaunchKernelGGL(conv_pointwise_kernel<true>, dim3((int)blocks, 1), dim3(256), 0, st, D);
     else hipLaunchKernelGGL(conv_pointwise_kernel<false>, dim3((int)blocks, G.nphase), dim3(256), 0, st, D);
   } else if (P.family == IGEMM_SMALLK && ((uintptr_t)op->out % 16) == 0) {
     const int nl = G.Ncols / 4;

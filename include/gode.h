@@ -91,6 +91,9 @@ int gode_igemm_stats_segments(const gode_igemm_op* op, int32_t split_images, int
 /* The launch-time estimate (GPU cycles) of the tile / split-K cost model for this op, or -1 when the op does not take the
  * modelled path.  Host-side, no GPU work: such a caller compares one launch over the whole batch with two over its parts. */
 double gode_igemm_model_cycles(const gode_igemm_op* op);
+/* The kernel family the launch plan gives the op: 0 tiled GEMM, 1 LDS-patch FPROP, 2 pointwise (thin-output streaming),
+ * 3 tiny-K, 4 dot.  Host-side, no GPU work; unaligned pointers can still take a launch from its family to the tiled GEMM. */
+int gode_igemm_family(const gode_igemm_op* op);
 /* floats needed for the packed weights of (geom, dir) */
 int64_t gode_pack_size(const gode_conv_geom* g, int dir);
 /* canonical W[co][ci][taps] -> packed panels.  co_perm (nullable, length g->Co): internal y-side channel c is

@@ -1,0 +1,19 @@
+"""The headline workload alone, for a kernel trace: build_mnist(), 220 calls of gen.sample_videos(32) under no_grad, seeded as
+bench.py seeds its timed loop.   rocprofv3 --kernel-trace --output-format csv -- python scripts/sample_only.py
+(profiles/sampling_small_kernels.md averages the trace per kernel and grid size after dropping each kernel's first 10 %.)"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import gan_ode_amd as G  # noqa: E402
+
+torch.manual_seed(1234); np.random.seed(1234)
+gen, _, _ = G.build_mnist()
+gen.cuda()
+with torch.no_grad():
+    for _ in range(220):
+        gen.sample_videos(32)
+torch.cuda.synchronize()
