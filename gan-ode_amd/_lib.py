@@ -12,6 +12,7 @@ i32, i64, f32, ptr = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 cint, u32, u64 = C.c_int, C.c_uint32, C.c_uint64
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH_OUT = 0, 1, 2, 3
+ACT_TANH, ACT_SIGMOID = 4, 5   # gode_fc_act / gode_fc_act_bwd only
 EPI_RAW, EPI_TANH = 0, 1
 FPROP, DGRAD = 0, 1
 PACK_BORDER = 0x100          # or'ed into a pack's dir: the pack an IgemmOp with border=1 reads
@@ -24,6 +25,7 @@ OP_GRU_FWD, OP_GRU_BWD = 19, 20
 OP_DNOISE = 21
 OP_CATEG, OP_CE = 22, 23
 OP_CHSTATS, OP_CBN_EMBED, OP_CBN_EMBED_BWD, OP_CBN_APPLY, OP_CBN_BWD, OP_GRES_OUT, OP_GRES_OUT_BWD, OP_SN_FWD, OP_SN_BWD = range(24, 33)
+OP_FC_ACT, OP_FC_ACT_BWD, OP_BCE_PROB = 33, 34, 35
 REC_ADAM_NOISE = -1          # gode_sizeof index of the gode_adam_noise_tensor table record
 ODE_NPARAM = 2672
 ODERNN_NPARAM = 2176
@@ -263,6 +265,23 @@ class SnBwdOp(_Op):
     KIND, FN = OP_SN_BWD, "gode_sn_bwd"
 
 
+class FcActOp(_Op):
+    _fields_ = [("y", ptr), ("b", ptr), ("out", ptr), ("M", i64), ("C", i32), ("act", i32), ("key", i64), ("layer", i32),
+                ("p", f32)]
+    KIND, FN = OP_FC_ACT, "gode_fc_act"
+
+
+class FcActBwdOp(_Op):
+    _fields_ = [("g_out", ptr), ("out", ptr), ("g_y", ptr), ("db", ptr), ("work", ptr), ("M", i64), ("C", i32), ("act", i32),
+                ("key", i64), ("layer", i32), ("p", f32), ("accumulate", i32), ("pad_", i32)]
+    KIND, FN = OP_FC_ACT_BWD, "gode_fc_act_bwd"
+
+
+class BceProbOp(_Op):
+    _fields_ = [("p", ptr), ("t", ptr), ("grad", ptr), ("loss", ptr), ("n", i64), ("gscale", f32), ("accumulate", i32)]
+    KIND, FN = OP_BCE_PROB, "gode_bce_prob"
+
+
 class AdamNoiseTensor(C.Structure):
     _fields_ = [("p", ptr), ("g", ptr), ("m", ptr), ("v", ptr), ("n", i64), ("noise_off", i64)]
 
@@ -312,6 +331,8 @@ _PROTOS = {
     "gode_chstats_rows": ([i64], cint),
     "gode_cbn_bwd_work_size": ([i32, i32, i32, i32], i64),
     "gode_gres_out_bwd_work_size": ([i32, i32, i32, i32, i32, i32], i64),
+    "gode_fc_act_bwd_work_size": ([i64, i32], i64),
+    "gode_dropout_mask": ([ptr, i64, u64, u32, f32, ptr], cint),
     "gode_scale": ([ptr, ptr, i64, f32, cint, ptr], cint),
     "gode_adam_multi": ([ptr, i32, i64, f32, f32, f32, f32, f32, f32, i32, ptr], cint),
     "gode_adam_multi_dev": ([ptr, i32, i64, f32, f32, f32, f32, f32, ptr, ptr], cint),

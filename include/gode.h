@@ -25,7 +25,8 @@ extern "C" {
 
 enum { GODE_OK = 0, GODE_E_ARG = -1, GODE_E_SHAPE = -2, GODE_E_KIND = -3 };
 enum { GODE_ACT_NONE = 0, GODE_ACT_RELU = 1, GODE_ACT_LRELU = 2,              /* LeakyReLU slope is 0.2 */
-       GODE_ACT_TANH_OUT = 3 /* bn_bwd only: y holds tanh OUTPUT, g *= 1-y^2 */ };
+       GODE_ACT_TANH_OUT = 3 /* bn_bwd only: y holds tanh OUTPUT, g *= 1-y^2 */,
+       GODE_ACT_TANH = 4, GODE_ACT_SIGMOID = 5 /* gode_fc_act / gode_fc_act_bwd only */ };
 enum { GODE_EPI_RAW = 0, GODE_EPI_TANH = 1 };
 enum { GODE_FPROP = 0, GODE_DGRAD = 1 };
 /* or'ed into the `dir` of gode_pack_size / gode_pack_weights / gode_pack_op: the pack an igemm op with border != 0 reads */
@@ -669,6 +670,47 @@ typedef struct gode_sn_bwd_op {
 } gode_sn_bwd_op;
 int gode_sn_bwd(const gode_sn_bwd_op* op, void* stream);
 
+/* ---- stage 2: the fully-connected MNIST GAN (stage2/test_ODE_training_with_MNIST_GAN.ipynb: Generator 100-256-512-1024-784
+ * with LeakyReLU(0.2) / tanh, Discriminator 784-1024-512-256-1 with LeakyReLU(0.2) + F.dropout(x, 0.3) / sigmoid, nn.BCELoss) --
+ * the passes around the products, which are gode_igemm (FPROP / DGRAD of the geometry {N = M, Ci, Co, everything else 1}) and
+ * gode_wgrad on row-major blocks [M][C].  M * C < 2^31, any C >= 1 (16-byte vectors when C % 4 == 0 and the pointers allow).
+ *
+ * The dropout stream: element e = m*C + c of a layer's [M][C] block takes output lane e & 3 of Philox4x32-10 with key
+ * (key low word, key high word) and counter (q low word, 0, 0x40000000 | layer, q high word), q = e >> 2; the word x becomes
+ * u = ((x >> 9) + 0.5) * 2^-23 as for the noise streams above, and the element is KEPT iff u >= p, compared in fp32; kept values
+ * are multiplied by fp32(1 / (1 - p)).  layer < 256.  The stream word has bit 31 clear (the instance noise sets it) and bit 30
+ * set (a parameter-noise stream is a small index), so the three families never share a counter; independent of the grid and of
+ * the vector width.  No mask is stored: the backward recomputes the bits.
+ *
+ *   out[m][c] = drop(act(y[m][c] + b[c]))     act: GODE_ACT_NONE / _LRELU / _TANH / _SIGMOID;  b nullable;  p == 0: no dropout;
+ *                                             out may alias y. */
+typedef struct gode_fc_act_op {
+  const float* y; const float* b; float* out; int64_t M; int32_t C, act;
+  int64_t key; int32_t layer; float p;
+} gode_fc_act_op;
+int gode_fc_act(const gode_fc_act_op* op, void* stream);
+/* its backward from g_out[M][C] and the forward's out[M][C]:  g_y = g_out * keep / (1 - p) * act', with act' taken from the
+ * activation's output a (= out, or out * (1 - p) behind a dropout): a > 0 ? 1 : 0.2 for LeakyReLU, 1 - a^2 for tanh,
+ * a (1 - a) for sigmoid.  g_y may alias g_out.  db (nullable, [C]): the column sums of g_y, stored or (accumulate != 0) added;
+ * they are reduced in a fixed order without atomics -- row lanes, then chunks of 128 rows through work (>=
+ * gode_fc_act_bwd_work_size floats; 0 for M <= 128: work may be NULL) -- so two runs give the same bits. */
+typedef struct gode_fc_act_bwd_op {
+  const float* g_out; const float* out; float* g_y; float* db; float* work; int64_t M; int32_t C, act;
+  int64_t key; int32_t layer; float p; int32_t accumulate, pad_;
+} gode_fc_act_bwd_op;
+int gode_fc_act_bwd(const gode_fc_act_bwd_op* op, void* stream);
+int64_t gode_fc_act_bwd_work_size(int64_t M, int32_t C);
+/* the keep values alone: out[e] = 1 or 0 for elements e < n of (key, layer, p) */
+int gode_dropout_mask(float* out, int64_t n, uint64_t key, uint32_t layer, float p, void* stream);
+/* nn.BCELoss() on probabilities p[n] against targets t[n], mean reduction, torch's clamps:
+ *   loss (+)= mean(-(t * max(log p, -100) + (1 - t) * max(log(1 - p), -100)))
+ *   grad[i] = gscale * (p - t) / max(p (1 - p), 1e-12) / n          (grad nullable)
+ * summed in double in one workgroup in a fixed order.  loss is one device float; accumulate != 0 adds to it. */
+typedef struct gode_bce_prob_op {
+  const float* p; const float* t; float* grad; float* loss; int64_t n; float gscale; int32_t accumulate;
+} gode_bce_prob_op;
+int gode_bce_prob(const gode_bce_prob_op* op, void* stream);
+
 /* out[i] = a[i]*alpha (+ out[i] if accumulate); small utility for gradient bucket handling */
 int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulate, void* stream);
 
@@ -706,7 +748,10 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
   X(GRES_OUT,      29, gode_gres_out_op,      gode_gres_out)      \
   X(GRES_OUT_BWD,  30, gode_gres_out_bwd_op,  gode_gres_out_bwd)  \
   X(SN_FWD,        31, gode_sn_op,            gode_sn_fwd)        \
-  X(SN_BWD,        32, gode_sn_bwd_op,        gode_sn_bwd)
+  X(SN_BWD,        32, gode_sn_bwd_op,        gode_sn_bwd)        \
+  X(FC_ACT,        33, gode_fc_act_op,        gode_fc_act)        \
+  X(FC_ACT_BWD,    34, gode_fc_act_bwd_op,    gode_fc_act_bwd)    \
+  X(BCE_PROB,      35, gode_bce_prob_op,      gode_bce_prob)
 /* GODE_OP_PACK stays outside the table: it has no (op*, stream) entry point, gode_run sends every run of consecutive pack
  * ops out as batched launches instead. */
 #define GODE_ENUM_ROW_(name, value, op_t, fn) GODE_OP_##name = value,
