@@ -13,6 +13,7 @@ cint, u32, u64 = C.c_int, C.c_uint32, C.c_uint64
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH_OUT = 0, 1, 2, 3
 ACT_TANH, ACT_SIGMOID = 4, 5   # gode_fc_act / gode_fc_act_bwd only
+ACT_LRELU01 = 6                # LeakyReLU(0.1): the convolution stack's ops (not gode_fc_act / gode_cbn_*)
 EPI_RAW, EPI_TANH = 0, 1
 FPROP, DGRAD = 0, 1
 PACK_BORDER = 0x100          # or'ed into a pack's dir: the pack an IgemmOp with border=1 reads
@@ -26,6 +27,7 @@ OP_DNOISE = 21
 OP_CATEG, OP_CE = 22, 23
 OP_CHSTATS, OP_CBN_EMBED, OP_CBN_EMBED_BWD, OP_CBN_APPLY, OP_CBN_BWD, OP_GRES_OUT, OP_GRES_OUT_BWD, OP_SN_FWD, OP_SN_BWD = range(24, 33)
 OP_FC_ACT, OP_FC_ACT_BWD, OP_BCE_PROB = 33, 34, 35
+OP_BCE_T = 36
 REC_ADAM_NOISE = -1          # gode_sizeof index of the gode_adam_noise_tensor table record
 ODE_NPARAM = 2672
 ODERNN_NPARAM = 2176
@@ -280,6 +282,11 @@ class FcActBwdOp(_Op):
 class BceProbOp(_Op):
     _fields_ = [("p", ptr), ("t", ptr), ("grad", ptr), ("loss", ptr), ("n", i64), ("gscale", f32), ("accumulate", i32)]
     KIND, FN = OP_BCE_PROB, "gode_bce_prob"
+
+
+class BceTOp(_Op):
+    _fields_ = [("logits", ptr), ("target", ptr), ("grad", ptr), ("loss", ptr), ("n", i64), ("gscale", f32), ("accumulate", i32)]
+    KIND, FN = OP_BCE_T, "gode_bce_logits_t"
 
 
 class AdamNoiseTensor(C.Structure):

@@ -13,15 +13,21 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// slope of the activation on the negative side (1: the identity); act(t) == fmaxf(t, t * slope), the slopes lie in [0, 1]
+__host__ __device__ __forceinline__ float gode_act_neg_slope(int act) {
+  return act == GODE_ACT_RELU ? 0.f : (act == GODE_ACT_LRELU ? 0.2f : (act == GODE_ACT_LRELU01 ? 0.1f : 1.f));
+}
 __device__ __forceinline__ float gode_act(float v, int act) {
   if (act == GODE_ACT_RELU) return v > 0.f ? v : 0.f;
   if (act == GODE_ACT_LRELU) return v > 0.f ? v : 0.2f * v;
+  if (act == GODE_ACT_LRELU01) return v > 0.f ? v : 0.1f * v;
   return v;
 }
 // derivative of act evaluated at pre-activation z
 __device__ __forceinline__ float gode_act_grad(float z, int act) {
   if (act == GODE_ACT_RELU) return z > 0.f ? 1.f : 0.f;
   if (act == GODE_ACT_LRELU) return z > 0.f ? 1.f : 0.2f;
+  if (act == GODE_ACT_LRELU01) return z > 0.f ? 1.f : 0.1f;
   return 1.f;
 }
 

@@ -21,7 +21,7 @@ __device__ __forceinline__ uint32_t dnoise_call(const gode_dnoise_op& a) {
 __global__ void __launch_bounds__(256) dnoise_apply_kernel(const gode_dnoise_op a, NoiseArgs na) {
   const int64_t n4 = a.M * a.C / 4;
   const int64_t n4_0 = a.M0 > 0 ? a.M0 * a.C / 4 : n4;          // float4s of the first group
-  const float neg = a.act == GODE_ACT_RELU ? 0.f : (a.act == GODE_ACT_LRELU ? 0.2f : 1.f);
+  const float neg = gode_act_neg_slope(a.act);
   const uint32_t call0 = dnoise_call(a);
   const uint64_t q_off = (uint64_t)a.e_off >> 2;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {

@@ -98,7 +98,7 @@ extern "C" int gode_bn_finalize(const gode_bn_finalize_op* op, void* stream) {
 
 __global__ void __launch_bounds__(256) bn_apply_kernel(const gode_bn_apply_op a) {
   const int64_t n4 = a.M * a.C / 4;
-  const float neg = a.act == GODE_ACT_RELU ? 0.f : (a.act == GODE_ACT_LRELU ? 0.2f : 1.f);
+  const float neg = gode_act_neg_slope(a.act);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const int c = (int)((i * 4) % a.C) + ((a.M0 > 0 && i * 4 >= a.M0 * a.C) ? a.C : 0);   // second image group: + C
     f32x4 v = *reinterpret_cast<const f32x4*>(a.y + i * 4);
@@ -478,20 +478,22 @@ extern "C" int gode_bn_bwd(const gode_bn_bwd_op* op, void* stream) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// BCE with logits against a constant target, mean reduction (single block: n is a few thousand at most)
-__global__ void __launch_bounds__(256) bce_kernel(const gode_bce_op a) {
+// BCE with logits, mean reduction (single block: n is a few thousand at most).  One body for both ops: the target is the
+// op's constant (tt == NULL) or element i of a tensor, so a constant-valued tensor gives gode_bce_logits' bits.
+__device__ __forceinline__ void bce_body(const float* logits, const float* tt, float target, float* grad, float* loss,
+                                         int64_t n, float gscale, int accumulate, int64_t ld) {
   __shared__ double red[256];
   const int tid = threadIdx.x;
   double s = 0.0;
-  const float inv = 1.f / (float)a.n;
-  const int64_t ld = a.stride > 1 ? a.stride : 1;      // (column 0 of a categorical head: one logit per row)
-  for (int64_t i = tid; i < a.n; i += 256) {
-    const float x = a.logits[i * ld];
-    const float l = fmaxf(x, 0.f) - x * a.target + log1pf(expf(-fabsf(x)));
+  const float inv = 1.f / (float)n;
+  for (int64_t i = tid; i < n; i += 256) {
+    const float x = logits[i * ld];
+    const float t = tt ? tt[i] : target;
+    const float l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
     s += (double)l;
-    if (a.grad) {
+    if (grad) {
       const float sig = 1.f / (1.f + expf(-x));
-      a.grad[i * ld] = a.gscale * (sig - a.target) * inv;
+      grad[i * ld] = gscale * (sig - t) * inv;
     }
   }
   red[tid] = s;
@@ -500,15 +502,29 @@ __global__ void __launch_bounds__(256) bce_kernel(const gode_bce_op a) {
     if (tid < k) red[tid] += red[tid + k];
     __syncthreads();
   }
-  if (tid == 0 && a.loss) {
-    const float v = (float)(red[0] / (double)a.n);
-    *a.loss = a.accumulate ? *a.loss + v : v;
+  if (tid == 0 && loss) {
+    const float v = (float)(red[0] / (double)n);
+    *loss = accumulate ? *loss + v : v;
   }
+}
+__global__ void __launch_bounds__(256) bce_kernel(const gode_bce_op a) {
+  // (stride: column 0 of a categorical head, one logit per row)
+  bce_body(a.logits, nullptr, a.target, a.grad, a.loss, a.n, a.gscale, a.accumulate, a.stride > 1 ? a.stride : 1);
+}
+__global__ void __launch_bounds__(256) bce_t_kernel(const gode_bce_t_op a) {
+  bce_body(a.logits, a.target, 0.f, a.grad, a.loss, a.n, a.gscale, a.accumulate, 1);
 }
 
 extern "C" int gode_bce_logits(const gode_bce_op* op, void* stream) {
   if (!op || !op->logits || op->n <= 0) return GODE_E_ARG;
   hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *op);
+  GODE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gode_bce_logits_t(const gode_bce_t_op* op, void* stream) {
+  if (!op || !op->logits || !op->target || op->n <= 0) return GODE_E_ARG;
+  hipLaunchKernelGGL(bce_t_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *op);
   GODE_LAUNCH_CHECK();
   return 0;
 }

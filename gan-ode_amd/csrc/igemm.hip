@@ -401,7 +401,7 @@ __global__ void __launch_bounds__(WM* WN * 64) igemm_fast_kernel(const IgemmArgs
     wrow[i] = a.w + P.w_off + (int64_t)(wok[i] ? n : Ncols - 1) * P.Kp + kchunk + (SK ? 0 : s_begin * 32);
   }
   const bool xf = a.scale != nullptr;
-  const float neg = a.act == GODE_ACT_RELU ? 0.f : (a.act == GODE_ACT_LRELU ? 0.2f : 1.f);
+  const float neg = gode_act_neg_slope(a.act);
 
   // wave-uniform tap odometer for the slab being fetched (starts at this workgroup's first slab)
   int c0, jd, jh, jw;
@@ -790,7 +790,7 @@ __global__ void __launch_bounds__(256) conv_dot_kernel(const DotArgs d) {
   const int qd = t % P.Md; const int img = t / P.Md;
   const int base = img * a.gsN;
   const int bd = qd * a.G.Sd + P.Od, bh = qh * a.G.Sh + P.Oh, bw = qw * a.G.Sw + P.Ow;
-  const float neg = a.act == GODE_ACT_RELU ? 0.f : (a.act == GODE_ACT_LRELU ? 0.2f : 1.f);
+  const float neg = gode_act_neg_slope(a.act);
   const bool xf = a.scale != nullptr;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   const float* wp = a.w + P.w_off;
@@ -854,7 +854,7 @@ __global__ void __launch_bounds__(256) conv_pointwise_kernel(const PwArgs d) {
   }
   const int lane = threadIdx.x & 63, lpp = d.lpp, ppw = 64 / lpp;
   const int sub = lane / lpp, ch = (lane - sub * lpp) * 4;
-  const float neg = a.act == GODE_ACT_RELU ? 0.f : (a.act == GODE_ACT_LRELU ? 0.2f : 1.f);
+  const float neg = gode_act_neg_slope(a.act);
   f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
   if (a.scale) { sc = *reinterpret_cast<const f32x4*>(a.scale + ch); sh = *reinterpret_cast<const f32x4*>(a.shift + ch); }
   const int ntap = ONE_TAP ? 1 : P.Td * P.Th * P.Tw;
@@ -928,7 +928,7 @@ __global__ void __launch_bounds__(256) conv_pointwise1_kernel(const PwArgs d) {
   const IgemmArgs& a = d.a;
   const PhaseGeom& P = a.G.ph[0];
   const int lane = threadIdx.x & 63, sub = lane / LPP, q = lane % LPP, ch = q * 4;
-  const float neg = a.act == GODE_ACT_RELU ? 0.f : (a.act == GODE_ACT_LRELU ? 0.2f : 1.f);
+  const float neg = gode_act_neg_slope(a.act);
   f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
   if (a.scale) { sc = *reinterpret_cast<const f32x4*>(a.scale + ch); sh = *reinterpret_cast<const f32x4*>(a.shift + ch); }
   const f32x4 w = *reinterpret_cast<const f32x4*>(a.w + P.w_off + ch);
@@ -1001,7 +1001,7 @@ __global__ void __launch_bounds__(256) conv_smallk_kernel(const PwArgs d) {
   __syncthreads();
   const int lane = threadIdx.x & 63, lpp = d.lpp, ppw = 64 / lpp;
   const int sub = lane / lpp, c4 = (lane - sub * lpp) * 4;
-  const float neg = a.act == GODE_ACT_RELU ? 0.f : (a.act == GODE_ACT_LRELU ? 0.2f : 1.f);
+  const float neg = gode_act_neg_slope(a.act);
   const bool xf = a.scale != nullptr;
   const int64_t wave_id = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
   for (int64_t m0 = wave_id * ppw; m0 < P.M; m0 += nwaves * ppw) {

@@ -206,7 +206,7 @@ __global__ void __launch_bounds__(WM* WN * 64) wgrad_fast_kernel(const WgradArgs
     if (!a.xform_on_y && xok) { xsc = *reinterpret_cast<const f32x4*>(a.scale + xci); xsh = *reinterpret_cast<const f32x4*>(a.shift + xci); }
     if (a.xform_on_y && yok) { ysc = *reinterpret_cast<const f32x4*>(a.scale + co0); ysh = *reinterpret_cast<const f32x4*>(a.shift + co0); }
   }
-  const float nslope = a.act == GODE_ACT_RELU ? 0.f : (a.act == GODE_ACT_LRELU ? 0.2f : 1.f);
+  const float nslope = gode_act_neg_slope(a.act);
   const float xneg = a.xform_on_y ? 1.f : nslope, yneg = a.xform_on_y ? nslope : 1.f;
   const float* yptr = a.y + (yok ? co0 : 0);
   const float* xptr = a.x + xci;
@@ -421,7 +421,7 @@ __global__ void __launch_bounds__(256) wgrad_thin_kernel(const WgradArgs a, int 
   const int tid = threadIdx.x, cl = tid % CL, ml = tid / CL;
   const int Kt = a.Kt;
   __shared__ __attribute__((aligned(16))) float red[4][256][4];   // 16 KB: taps are combined four at a time
-  const float nslope = a.act == GODE_ACT_RELU ? 0.f : (a.act == GODE_ACT_LRELU ? 0.2f : 1.f);
+  const float nslope = gode_act_neg_slope(a.act);
   const float xneg = a.xform_on_y ? 1.f : nslope, yneg = a.xform_on_y ? nslope : 1.f;
   const int m0 = blockIdx.x * chunk_thin;
   const int m1 = m0 + chunk_thin < a.M ? m0 + chunk_thin : a.M;
@@ -588,7 +588,7 @@ __global__ void __launch_bounds__(256) wgrad_patch_kernel(const WpArgs p) {
     b_colj[k] = j;
   }
   const int y_off = patch + fh * CO + rb * 32 + fr;
-  const float yneg = a.act == GODE_ACT_RELU ? 0.f : (a.act == GODE_ACT_LRELU ? 0.2f : 1.f);
+  const float yneg = gode_act_neg_slope(a.act);
   const bool yxf = a.scale != nullptr;               // (host: only with xform_on_y)
   constexpr int NYC = (32 * YC + 255) / 256;         // float4 chunks of the Y slab per thread (256 % YC == 0)
   const int yc4 = tid % YC, ypos0 = tid / YC;        // chunk i of this thread: position ypos0 + i * (256 / YC), same channels

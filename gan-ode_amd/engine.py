@@ -730,6 +730,8 @@ class ConvStack:
                     bn_work = max(bn_work, lib.gode_bn_bwd_work_size(M, Cc))
                     if need_param_grad:
                         patch["dgamma"].append((l - 1, b, False))
+                elif sp.act == L.ACT_NONE:
+                    continue      # neither BatchNorm nor activation behind layer l - 1: g[l - 1] already is its output gradient
                 else:
                     b = L.BnBwdOp(g=dptr(self.g[l - 1]), y=dptr(self.y[l - 1]), M=M, C=Cc, act=sp.act)
                 patch.setdefault("bnb", []).append(b)

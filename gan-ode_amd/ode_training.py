@@ -196,8 +196,9 @@ class GANODETrainer(object):
     modules=(gen, dis_img, dis_vid): optional.  The regulariser evaluates g_loss two more times than the reference
     does; with `modules` the buffers of these networks (BatchNorm running statistics) are put back afterwards, without
     it they see two extra momentum updates per penalised step (eval-mode sampling only).  The closures must draw their
-    randomness from torch's CPU generator and NumPy's global state, as the generators of this package do: the
-    regulariser rewinds these two.
+    randomness from torch's CPU generator, NumPy's global state (as the generators of this package do) or the CUDA
+    generator of the parameters' device (torch.randn(..., device=device), as the CIFAR notebook's closures do): the
+    regulariser rewinds these three.
     """
 
     def __init__(self, g_params, dImg_params, dVid_params, g_loss, dImg_loss, dVid_loss, lr=0.02, reg=0.01, method='rk4',
@@ -254,12 +255,24 @@ class GANODETrainer(object):
 
     # -- the regulariser ---------------------------------------------------------------------------------------------------
     def _penalty_pair(self, params):
-        """q+ and q- = grad_params g_loss at thetaG +- eps * v, v = grad_thetaG g_loss; the generator's parameters, the two
-        host generators (left as after ONE g_loss call) and, with `modules`, all buffers are as before on return.
+        """q+ and q- = grad_params g_loss at thetaG +- eps * v, v = grad_thetaG g_loss; the generator's parameters, the
+        random generators (torch's CPU one, NumPy's and the CUDA one of the parameters' device: left as after ONE g_loss call)
+        and, with `modules`, all buffers are as before on return.
         Returns (q+, q-, 1/eps as a device float or None, 1/eps as a Python float or None)."""
-        rng = (torch.get_rng_state(), np.random.get_state())
+        cuda_dev = self.g_params[0].device if self._on_gpu(self.g_params) else None
+
+        def rng_state():
+            return (torch.get_rng_state(), np.random.get_state(),
+                    torch.cuda.get_rng_state(cuda_dev) if cuda_dev is not None else None)
+
+        def rewind(state):
+            torch.set_rng_state(state[0]); np.random.set_state(state[1])
+            if cuda_dev is not None:
+                torch.cuda.set_rng_state(state[2], cuda_dev)
+
+        rng = rng_state()
         v = torch.autograd.grad(self.g_loss(), self.g_params, allow_unused=True)
-        rng_after = (torch.get_rng_state(), np.random.get_state())
+        rng_after = rng_state()
         self._save_buffers()
         gpu = self._on_gpu(self.g_params)
         if gpu:
@@ -277,7 +290,7 @@ class GANODETrainer(object):
             inv_host = 1.0 / eps if eps > 0 else 0.0
         q = []
         for k, sign in enumerate((1.0, -1.0)):
-            torch.set_rng_state(rng[0]); np.random.set_state(rng[1])
+            rewind(rng)
             if gpu:
                 G.axpy("shift%d" % k, G.params, G.saved, vv, sign, a_dev=G.fd)
                 G._bump()
@@ -294,7 +307,7 @@ class GANODETrainer(object):
             with torch.no_grad():
                 for p, s in zip(self.g_params, saved):
                     p.copy_(s)
-        torch.set_rng_state(rng_after[0]); np.random.set_state(rng_after[1])
+        rewind(rng_after)
         self._restore_buffers()
         return q[0], q[1], (G.fd[1:2] if gpu else None), inv_host
 

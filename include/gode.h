@@ -26,7 +26,9 @@ extern "C" {
 enum { GODE_OK = 0, GODE_E_ARG = -1, GODE_E_SHAPE = -2, GODE_E_KIND = -3 };
 enum { GODE_ACT_NONE = 0, GODE_ACT_RELU = 1, GODE_ACT_LRELU = 2,              /* LeakyReLU slope is 0.2 */
        GODE_ACT_TANH_OUT = 3 /* bn_bwd only: y holds tanh OUTPUT, g *= 1-y^2 */,
-       GODE_ACT_TANH = 4, GODE_ACT_SIGMOID = 5 /* gode_fc_act / gode_fc_act_bwd only */ };
+       GODE_ACT_TANH = 4, GODE_ACT_SIGMOID = 5 /* gode_fc_act / gode_fc_act_bwd only */,
+       GODE_ACT_LRELU01 = 6 /* LeakyReLU with slope 0.1: wherever the convolution stack takes GODE_ACT_LRELU (gode_igemm, gode_wgrad,
+                               gode_bn_apply, gode_bn_bwd, gode_dnoise); not gode_fc_act / gode_cbn_* */ };
 enum { GODE_EPI_RAW = 0, GODE_EPI_TANH = 1 };
 enum { GODE_FPROP = 0, GODE_DGRAD = 1 };
 /* or'ed into the `dir` of gode_pack_size / gode_pack_weights / gode_pack_op: the pack an igemm op with border != 0 reads */
@@ -711,6 +713,17 @@ typedef struct gode_bce_prob_op {
 } gode_bce_prob_op;
 int gode_bce_prob(const gode_bce_prob_op* op, void* stream);
 
+/* ---- stage 2: the CIFAR DCGAN (stage2/test_ODE_training_with_cifar_GAN.ipynb) runs on the convolution stack above with
+ * GODE_ACT_LRELU01; its criterion is nn.BCEWithLogitsLoss() against a target TENSOR: gode_bce_logits with target[n] in place of
+ * the constant --
+ *   loss (+)= mean(max(x,0) - x*t[i] + log1p(exp(-|x|))),   g[i] = gscale*(sigmoid(x[i]) - t[i])/n          (grad nullable)
+ * the same device code, so a tensor that holds one value gives gode_bce_logits' loss and gradient bit for bit.  Summed in double
+ * by one workgroup in a fixed order (no atomics: two runs give the same bits).  loss is one device float; accumulate != 0 adds. */
+typedef struct gode_bce_t_op {
+  const float* logits; const float* target; float* grad; float* loss; int64_t n; float gscale; int32_t accumulate;
+} gode_bce_t_op;
+int gode_bce_logits_t(const gode_bce_t_op* op, void* stream);
+
 /* out[i] = a[i]*alpha (+ out[i] if accumulate); small utility for gradient bucket handling */
 int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulate, void* stream);
 
@@ -751,7 +764,8 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
   X(SN_BWD,        32, gode_sn_bwd_op,        gode_sn_bwd)        \
   X(FC_ACT,        33, gode_fc_act_op,        gode_fc_act)        \
   X(FC_ACT_BWD,    34, gode_fc_act_bwd_op,    gode_fc_act_bwd)    \
-  X(BCE_PROB,      35, gode_bce_prob_op,      gode_bce_prob)
+  X(BCE_PROB,      35, gode_bce_prob_op,      gode_bce_prob)      \
+  X(BCE_T,         36, gode_bce_t_op,         gode_bce_logits_t)
 /* GODE_OP_PACK stays outside the table: it has no (op*, stream) entry point, gode_run sends every run of consecutive pack
  * ops out as batched launches instead. */
 #define GODE_ENUM_ROW_(name, value, op_t, fn) GODE_OP_##name = value,
