@@ -16,7 +16,7 @@ ACT_TANH, ACT_SIGMOID = 4, 5   # gode_fc_act / gode_fc_act_bwd only
 ACT_LRELU01 = 6                # LeakyReLU(0.1): the convolution stack's ops (not gode_fc_act / gode_cbn_*)
 EPI_RAW, EPI_TANH = 0, 1
 FPROP, DGRAD = 0, 1
-PACK_BORDER = 0x100          # or'ed into a pack's dir: the pack an IgemmOp with border=1 reads
+PACK_BORDER = 0x100          # or'ed into a pack's dir: the pack an IgemmOp with border=1 / 2 reads
 OP_IGEMM, OP_WGRAD, OP_BN_FINALIZE, OP_BN_BWD, OP_ODE_FWD, OP_ODE_BWD, OP_BCE, OP_ADAM, OP_PACK = range(1, 10)
 OP_ODERNN_FWD, OP_ODERNN_BWD, OP_BN_APPLY, OP_COL2IM = 10, 11, 12, 13
 OP_SDE_FWD, OP_SDE_BWD = 14, 15
@@ -315,6 +315,8 @@ _PROTOS = {
     "gode_igemm_stats_segments": ([ptr, i32, ptr], cint),
     "gode_igemm_model_cycles": ([ptr], C.c_double),
     "gode_igemm_family": ([ptr], cint),
+    "gode_igemm_dead_taps": ([ptr], C.c_double),
+    "gode_igemm_launch_info": ([ptr, ptr], cint),
     "gode_igemm_work_size": ([ptr], i64),
     "gode_pack_size": ([ptr, cint], i64),
     "gode_pack_weights": ([ptr, cint, ptr, ptr, ptr, i32, ptr], cint),

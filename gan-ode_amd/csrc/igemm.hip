@@ -40,8 +40,9 @@ struct IgemmArgs {
   int32_t stats_rows;   // number of partial-statistics rows of the launch (the stats buffer is [2][ncols][stats_rows])
   uint32_t src_bytes, w_bytes;   // LDS-DMA kernels address both operands as raw buffers (32-bit byte offsets): their extents
   // FAST kernel on a border-split table (G.border): its sub-phases differ in rows AND in K, so the 1-D grid holds exactly the
-  // live tiles, sub-phase after sub-phase (longest K first): tile0[i] = first workgroup of sub-phase i, tile0[nphase] = grid
-  int32_t ntab;
+  // live tiles, entry after entry (longest K first; an entry is `interleave` sub-phases: igemm_border_block): tile0[i] =
+  // first workgroup of entry i, tile0[ntab] = grid
+  int32_t ntab, interleave;
   int32_t tile0[GODE_MAX_PHASES + 1];
 };
 
@@ -52,18 +53,9 @@ struct IgemmArgs {
 // shared by neighbouring output rows hit the same L2; the default), 0 is the plain order.  Every mode is a bijection
 // of [0, MB*NB*nphase).
 __device__ __forceinline__ void igemm_block_id(const IgemmArgs& a, int& mblk, int& nblk, int& phase, int& split) {
-  if (a.ntab > 0) {
-    // border-split table: find the sub-phase (uniform scan of <= 16 entries); inside it runs of 8 m-blocks go one to each
-    // XCD with all their n-blocks back to back (the gathered rows are fetched once per XCD, as xcd_mode 2), the last
-    // (< 8) m-blocks in the plain order.  A bijection of the sub-phase's tiles whatever its m-block count.
-    const int id = blockIdx.x;
-    int p = 0;
-    while (p + 1 < a.ntab && id >= a.tile0[p + 1]) ++p;
-    const int t = id - a.tile0[p], NB = a.NB, mb = (a.tile0[p + 1] - a.tile0[p]) / NB;
-    const int grp = t / (8 * NB), r = t - grp * 8 * NB, rest = mb - grp * 8;
-    if (rest >= 8) { mblk = grp * 8 + (r & 7); nblk = r >> 3; }
-    else { mblk = grp * 8 + r % rest; nblk = r / rest; }
-    phase = p; split = 0;
+  if (a.ntab > 0) {      // border-split table: igemm_plan.h
+    igemm_border_block(blockIdx.x, a.ntab, a.tile0, a.NB, a.interleave, mblk, nblk, phase);
+    split = 0;
     return;
   }
   const int MB = a.MB, NC = a.NB * a.G.nphase;
@@ -1059,6 +1051,30 @@ extern "C" int gode_igemm_family(const gode_igemm_op* op) {
   return rc ? rc : P.family;
 }
 
+// what the border-split table of the op would leave out, as a share of the plain table's multiply-adds (0: no such table)
+extern "C" double gode_igemm_dead_taps(const gode_igemm_op* op) {
+  if (!op) return 0.0;
+  gode_igemm_op flagged = *op;
+  flagged.border = 1;
+  IgemmGeom G, B;
+  if (gode_build_igemm_geom(op->g, op->dir, &G) || !border_table(&flagged, G, &B)) return 0.0;
+  double plain = 0, live = 0;
+  for (int i = 0; i < G.nphase; ++i) plain += (double)G.ph[i].M * G.ph[i].K;
+  for (int i = 0; i < B.nphase; ++i) live += (double)B.ph[i].M * B.ph[i].K;
+  return plain > 0 ? 1.0 - live / plain : 0.0;
+}
+
+extern "C" int gode_igemm_launch_info(const gode_igemm_op* op, int32_t* info) {
+  if (!info) return GODE_E_ARG;
+  IgemmPlan P;
+  const int rc = igemm_make_plan(op, &P);
+  if (rc) return rc;
+  info[0] = P.G.border != 0; info[1] = P.tile;
+  info[2] = P.ntab > 0 ? P.tile0[P.ntab] : (int32_t)count_tiles(P.G, P.tile) * P.ksplit;
+  info[3] = 256 * IGEMM_TILES[P.tile].resident;
+  return 0;
+}
+
 extern "C" int gode_igemm_stats_segments(const gode_igemm_op* op, int32_t split_images, int32_t* seg) {
   if (!op || !seg || op->groups == 2 || op->border || split_images <= 0 || split_images >= op->g.N) return GODE_E_ARG;
   IgemmPlan P;
@@ -1179,7 +1195,7 @@ extern "C" int gode_igemm(const gode_igemm_op* op, void* stream) {
   A.stagger = 0;
   A.tapskip = P.tapskip; A.dmajor = P.dmajor; A.stats_rows = P.stats_rows;
   A.ksplit = P.ksplit; A.slabs_per_split = P.slabs_per_split;
-  A.MB = P.MB; A.NB = P.NB; A.xcd_mode = P.xcd_mode; A.ntab = P.ntab;
+  A.MB = P.MB; A.NB = P.NB; A.xcd_mode = P.xcd_mode; A.ntab = P.ntab; A.interleave = P.interleave;
   for (int i = 0; i <= GODE_MAX_PHASES; ++i) A.tile0[i] = P.tile0[i];
   A.src_bytes = span * 4 < (1ll << 31) ? (uint32_t)(span * 4) : 0u;
   A.w_bytes = gode_pack_floats(G) * 4 < (1ll << 31) ? (uint32_t)(gode_pack_floats(G) * 4) : 0u;

@@ -227,7 +227,8 @@ struct IgemmPlan {
   int32_t max_mblk, stats_rows, rows0;         // rows of the partial statistics; those of image group 0
   int32_t tapskip, dmajor;                     // FAST kernel MODE 3; depth-major rows with this many images
   int32_t xcd_mode, MB, NB;                    // FAST kernel's 1-D grid order (igemm_block_id)
-  int32_t ntab, tile0[GODE_MAX_PHASES + 1];    // border-split table: first workgroup of each sub-phase, tile0[ntab] = grid
+  int32_t ntab, tile0[GODE_MAX_PHASES + 1];    // border-split table: first workgroup of each entry, tile0[ntab] = grid
+  int32_t interleave;                          // sub-phases per entry: 1 sub-phase after sub-phase, > 1 phase-interleaved, 0 no table
   double cycles;                               // the cost model's estimate, or -1 off the modelled path (and for image groups)
 };
 
@@ -260,10 +261,56 @@ static int thin_family(const gode_igemm_op* op, const IgemmGeom& G, bool vec) {
   return IGEMM_GEMM;
 }
 
+// Workgroup `id` of a border-split launch -> (sub-phase, m-block, n-block); shared by the FAST kernel (igemm_block_id) and
+// the host check that enumerates the whole map (tests/hostcheck/border_grid_check.cpp).  The 1-D grid holds exactly the live
+// tiles, entry after entry (longest K first).  An entry is `np` consecutive sub-phases of the table with the same number
+// of m-blocks and tile0[e] its first workgroup.  Inside an entry runs of 8 m-blocks go one to each XCD (workgroups are
+// dealt round-robin to the 8 XCDs in id order) with all their (sub-phase, n-block) combos back to back, as xcd_mode 2 does:
+// the gathered rows are fetched once per XCD; the last (< 8) m-blocks in the plain order.  A bijection of the entry's
+// tiles whatever its m-block count.  np = 1: sub-phase after sub-phase.  np > 1 (gode_igemm_op.border == 2): the entry is
+// one border class (interior, h-edge, w-edge, corner) of ALL stride phases, which gather the same input rows.
+GODE_HD void igemm_border_block(int id, int ntab, const int32_t* tile0, int NB, int np, int& mblk, int& nblk, int& phase) {
+  int e = 0;
+  while (e + 1 < ntab && id >= tile0[e + 1]) ++e;     // (uniform scan of <= 16 entries)
+  const int NC = NB * np, t = id - tile0[e], mb = (tile0[e + 1] - tile0[e]) / NC;
+  const int grp = t / (8 * NC), r = t - grp * 8 * NC, rest = mb - grp * 8;
+  int combo;
+  if (rest >= 8) { mblk = grp * 8 + (r & 7); combo = r >> 3; }
+  else { mblk = grp * 8 + r % rest; combo = r / rest; }
+  nblk = combo % NB; phase = e * np + combo / NB;
+}
+
+// The border classes of a border-split table, for the phase-interleaved grid: sub-phases with the same extents and taps
+// (hence the same K and the same number of m-blocks) form a class.  Writes the table order that lays the classes out one
+// after the other (classes by first appearance, so K stays descending; members in table order) and returns the members per
+// class -- or 0 when some class does not hold exactly one sub-phase of every stride phase (k3 s2 p1: the phases differ in
+// taps and extents; temporal taps off both ends: two depth runs per phase), which keeps the order as it is.
+static int border_classes(const IgemmGeom& B, int order[GODE_MAX_PHASES]) {
+  const int nsp = B.OSd * B.OSh * B.OSw;       // stride phases
+  if (!B.border || nsp < 2 || B.nphase % nsp != 0) return 0;
+  const int ncls = B.nphase / nsp;
+  int rep[GODE_MAX_PHASES], count[GODE_MAX_PHASES], seen[GODE_MAX_PHASES], nc = 0;
+  for (int i = 0; i < B.nphase; ++i) {
+    const PhaseGeom& s = B.ph[i];
+    int c = 0;
+    for (; c < nc; ++c) {
+      const PhaseGeom& r = B.ph[rep[c]];
+      if (r.Md == s.Md && r.Mh == s.Mh && r.Mw == s.Mw && r.Td == s.Td && r.Th == s.Th && r.Tw == s.Tw) break;
+    }
+    if (c == nc) { if (nc == ncls) return 0; rep[nc] = i; count[nc] = 0; seen[nc] = 0; ++nc; }
+    const int residue = ((s.Pd % B.OSd) * B.OSh + s.Ph % B.OSh) * B.OSw + s.Pw % B.OSw;
+    if (count[c] == nsp || (seen[c] >> residue & 1)) return 0;
+    seen[c] |= 1 << residue;
+    order[c * nsp + count[c]++] = i;
+  }
+  for (int c = 0; c < nc; ++c) if (count[c] != nsp) return 0;
+  return nc == ncls ? nsp : 0;
+}
+
 // Order of the FAST kernel's 1-D grid over the 8 XCDs (igemm_block_id), and the tile table of a border-split launch.
 static void plan_grid_order(const gode_igemm_op* op, IgemmPlan* P) {
-  const IgemmGeom& G = P->G;
-  P->MB = 0; P->NB = 0; P->xcd_mode = 0; P->ntab = 0;
+  IgemmGeom& G = P->G;
+  P->MB = 0; P->NB = 0; P->xcd_mode = 0; P->ntab = 0; P->interleave = 0;
   for (int i = 0; i <= GODE_MAX_PHASES; ++i) P->tile0[i] = 0;
   if (!P->fast) return;
   const int MB = P->max_mblk, NB = gode_ceil_div(G.Ncols, tile_bn(P->tile)), NC = NB * G.nphase;
@@ -292,9 +339,20 @@ static void plan_grid_order(const gode_igemm_op* op, IgemmPlan* P) {
   if (force == 3 && ok2) mode = 3;
   P->xcd_mode = mode;
   if (G.border) {       // (never with a K split or live taps: see igemm_make_plan and border_table)
-    P->ntab = G.nphase;
-    for (int i = 0; i < G.nphase; ++i) P->tile0[i + 1] = P->tile0[i] + gode_ceil_div(G.ph[i].M, tile_bm(P->tile)) * NB;
-    for (int i = G.nphase + 1; i <= GODE_MAX_PHASES; ++i) P->tile0[i] = P->tile0[G.nphase];
+    int order[GODE_MAX_PHASES];
+    static const char* oenv = getenv("GODE_IGEMM_BORDER_ORDER");      // calibration runs: 0 keeps sub-phase after sub-phase
+    const int np = op->border == 2 && !(oenv && atoi(oenv) == 0) ? border_classes(G, order) : 0;
+    if (np > 0) {
+      // phase-interleaved: the table is re-laid class by class.  row0 was given in the table's own order and travels with
+      // the sub-phase, so the launch writes the statistics rows of the op with border == 1
+      const IgemmGeom T = G;
+      for (int i = 0; i < G.nphase; ++i) G.ph[i] = T.ph[order[i]];
+    }
+    P->interleave = np > 0 ? np : 1;
+    P->ntab = G.nphase / P->interleave;
+    for (int e = 0; e < P->ntab; ++e)
+      P->tile0[e + 1] = P->tile0[e] + gode_ceil_div(G.ph[e * P->interleave].M, tile_bm(P->tile)) * NB * P->interleave;
+    for (int i = P->ntab + 1; i <= GODE_MAX_PHASES; ++i) P->tile0[i] = P->tile0[P->ntab];
   }
 }
 
@@ -331,9 +389,10 @@ static int igemm_make_plan(const gode_igemm_op* op, IgemmPlan* P) {
       // per layer: the border form only where the model prices it below the plain launch (3 % hysteresis toward plain).
       // A launch that splits K keeps doing so: a K split adds its partial sums in another order, and an op with the flag
       // must give the raw outputs of the op without it bit for bit
+      // border == 2: the caller decides per layer, from measurements -- taken whenever choose_border offers a tile
       int tb; double cb;
       choose_border(B, &tb, &cb);
-      if (cb < 0.97 * cyc) { take_border = true; tile = tb; cyc = cb; }
+      if (op->border == 2 ? cb < 1e300 : cb < 0.97 * cyc) { take_border = true; tile = tb; cyc = cb; }
     }
     // calibration runs (scripts/sweep_tiles.py): GODE_IGEMM_SWEEP enables GODE_IGEMM_FORCE="tile,k", re-read per call
     static const bool sweeping = getenv("GODE_IGEMM_SWEEP") != nullptr;
@@ -350,7 +409,8 @@ static int igemm_make_plan(const gode_igemm_op* op, IgemmPlan* P) {
     sp = plan_split(op, G, tile);
     // a REQUESTED tile takes the border form unless a plan splits K; tile = 0 off the modelled path (generic kernel, odd
     // channel counts) stays plain: nothing measured says it would pay there
-    if (can_border && sp.ksplit == 1 && op->tile != 0) {
+    // (border == 2: on the FAST kernel only -- its grid order is what the value asks for)
+    if (can_border && sp.ksplit == 1 && op->tile != 0 && (op->border != 2 || (P->vec && fast_geometry(G) && fast_geometry(B)))) {
       const int tb = pick_tile(B, op->tile);
       const SplitPlan sb = plan_split(op, B, tb);
       if (sb.ksplit == 1) { take_border = true; tile = tb; sp = sb; }

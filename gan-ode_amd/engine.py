@@ -20,6 +20,29 @@ import torch
 
 from . import _lib as L
 
+# A transposed-convolution layer takes gode_igemm_op.border = 2 (border-split table without the cost model's comparison,
+# phase-interleaved grid) when at least BORDER_TAKE_DEAD_TAPS of its multiply-adds gather padding (gode_igemm_dead_taps) and
+# its border-split grid holds at least BORDER_TAKE_TILES_PER_SLOT tiles per workgroup slot of the chip.  Measured
+# (profiles/border_order_layers.md; the k4 s2 p1 decoder layers on 4x4 / 8x8 / 16x16 have 0.234 / 0.121 / 0.062 dead taps):
+#   512 rows: 8x8 (2.67 tiles per slot) 4.6 % and 16x16 (5.33) 3.9 % faster than the launch they had; 4x4 (1.33; the model
+#     takes the table by itself, so the value only changes the grid order) 7 % faster launched back to back but unchanged in
+#     the sampling loop's kernel trace (203.4 -> 202.9 us): not taken;
+#   256 rows: 8x8 (1.33) 5 % SLOWER than its plain 256x128 launch; 16x16 (2.67) 1.1 % faster; 4x4: no tile on offer.
+# 0.06: the smallest share measured -- nothing below it was, so nothing below it is taken.  2.0: between 1.33 and 2.67.
+BORDER_TAKE_DEAD_TAPS = 0.06
+BORDER_TAKE_TILES_PER_SLOT = 2.0
+
+
+def border_value(g) -> int:
+    """gode_igemm_op.border for the forward GEMM of a transposed-convolution layer (conv-orientation geometry g) that has a
+    border-split form: 1 leaves the form to the launch's cost model, 2 takes the table with the phase-interleaved grid."""
+    lib = L.lib()
+    if lib.gode_igemm_dead_taps(C.byref(L.IgemmOp(g=g, dir=L.DGRAD, tile=0))) < BORDER_TAKE_DEAD_TAPS:
+        return 1
+    info = (C.c_int32 * 4)()      # {border table in use, tile, tiles, workgroup slots}
+    L.check(lib.gode_igemm_launch_info(C.byref(L.IgemmOp(g=g, dir=L.DGRAD, tile=0, border=2)), info))
+    return 2 if info[0] and info[2] >= BORDER_TAKE_TILES_PER_SLOT * info[3] else 1
+
 
 def make_geom(N, Ci, Co, xi, yo, k, s, p) -> L.ConvGeom:
     """xi / yo / k / s / p are (d, h, w) triples in conv orientation."""
@@ -149,8 +172,9 @@ class ConvStack:
         # does, with or without a backward behind it: a no-grad pass must give the frames of the pass a backward follows bit
         # for bit, and the two forms group the BatchNorm partial sums differently.  GODE_BORDER_SPLIT=0: none.
         self._border = self._border_layers() if os.environ.get("GODE_BORDER_SPLIT", "1") != "0" else {}
+        self._border_flag = {l: border_value(specs[l].geom) for l in self._border}
         for l, s in enumerate(specs):
-            bord = l in self._border       # its pack: the plain pack + the edge / corner panels, under a key of its own
+            bord = self._border_flag.get(l, 0)      # its pack: the plain pack + the edge / corner panels, under a key of its own
             n = lib.gode_pack_size(C.byref(s.geom), s.fwd_dir | (L.PACK_BORDER if bord else 0))
             if n <= 0:
                 raise RuntimeError(f"bad geometry for pack ({n})")
@@ -158,7 +182,7 @@ class ConvStack:
             C_out = s.out_dims()[4]
             two = self._two_f[l] = bool(self.split) and 0 < l < self.nl - 1 and self._two_launches(s.geom, s.fwd_dir)
             if s.has_bn:
-                probe = L.IgemmOp(g=s.geom, dir=s.fwd_dir, tile=0, groups=groups, border=1 if bord else 0)
+                probe = L.IgemmOp(g=s.geom, dir=s.fwd_dir, tile=0, groups=groups, border=bord)
                 if two:     # the parts' partial sums: two arrays [2][ncols][rows of the part], one after the other
                     ra, rb = (lib.gode_igemm_stats_rows(C.byref(L.IgemmOp(g=self._part_geom(s.geom, n), dir=s.fwd_dir, tile=0)))
                               for n in (self.split, s.geom.N - self.split))
@@ -471,7 +495,7 @@ class ConvStack:
                     # (wpack_f[l] is the border-form pack and stat_rows[l] the flagged op's row count: see __init__)
                     packs[-1] = (l, "border", L.PackOp(g=s.geom, dir=L.DGRAD | L.PACK_BORDER, co_canon=0, w=dptr(p.weight),
                                                        wpack=dptr(self.wpack_f[l]), co_perm=dptr(s.co_perm)))
-                    op.border = 1
+                    op.border = self._border_flag[l]
                 ops.append(op)
             if l == 0:
                 patch["first"] = op

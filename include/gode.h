@@ -76,7 +76,16 @@ typedef struct gode_igemm_op {
    * taps, so no MFMA multiplies zero padding.  `wpack` must then be packed with dir = GODE_DGRAD | GODE_PACK_BORDER (that
    * pack extends the plain one, so the launch is free to stay plain when its cost model says so).  Raw outputs are bit-identical to
    * border == 0; the partial-statistics rows are grouped differently: gode_igemm_stats_rows / _rows0 / _work_size /
-   * _model_cycles all follow the flag.  0: as before. */
+   * _model_cycles all follow the flag.  0: as before.
+   * border == 2: the caller has measured the layer and decides.  The launch takes the border-split table whenever the op has
+   * one, every sub-phase runs on the MFMA kernel's fast path (channels and every K in whole 32-deep slabs, vector strides) and K is not
+   * split -- with the tile of the border cost model (tile == 0; the plain plan when that model offers none: fewer than 4/3
+   * tiles per workgroup slot), or the requested one -- without comparing the two forms' modelled cost.  Its grid is
+   * phase-interleaved where the table allows: the sub-phases of one border class (interior, h-edge, w-edge, corner) of all
+   * stride phases, which gather the same input rows, run back to back on one XCD per m-block, classes in descending K;
+   * tables whose classes do not hold one sub-phase of every stride phase (k3 s2 p1, temporal taps off both ends) keep the
+   * order of border == 1.  Same pack as border == 1; at equal tile raw outputs AND partial-statistics rows are bit-identical
+   * to border == 1.  Any other nonzero value: as 1. */
   int32_t border;
 } gode_igemm_op;
 int gode_igemm(const gode_igemm_op* op, void* stream);
@@ -97,6 +106,12 @@ double gode_igemm_model_cycles(const gode_igemm_op* op);
 /* The kernel family the launch plan gives the op: 0 tiled GEMM, 1 LDS-patch FPROP, 2 pointwise (thin-output streaming),
  * 3 tiny-K, 4 dot.  Host-side, no GPU work; unaligned pointers can still take a launch from its family to the tiled GEMM. */
 int gode_igemm_family(const gode_igemm_op* op);
+/* Share of the op's multiply-adds that gather zero padding at the tensor's borders: 1 - (sum of M*K over the border-split
+ * table) / (sum of M*K over the plain table); 0 when the op has no border-split table (gode_igemm_op.border).  Host-side. */
+double gode_igemm_dead_taps(const gode_igemm_op* op);
+/* The shape of the op's launch plan: info = {1 if it runs the border-split table, tile id, tiles of the GEMM launch,
+ * workgroups the chip holds at once with that tile (256 CUs x resident workgroups per CU)}.  Host-side; 0 or an error. */
+int gode_igemm_launch_info(const gode_igemm_op* op, int32_t* info);
 /* floats needed for the packed weights of (geom, dir) */
 int64_t gode_pack_size(const gode_conv_geom* g, int dir);
 /* canonical W[co][ci][taps] -> packed panels.  co_perm (nullable, length g->Co): internal y-side channel c is
