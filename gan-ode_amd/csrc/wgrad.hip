@@ -9,9 +9,8 @@
 // The reduction is cut into `splits` slabs (grid.z), each writing its own [Co][taps*Ci] partial; a second kernel
 // sums the partials in fixed order and scatters into PyTorch's canonical W[co][ci][taps] layout (deterministic,
 // no float atomics).  The BN+activation of the producing layer is fused into whichever operand is an activation.
-#include <stdlib.h>
 #include "common.h"
-#include "conv_geom.h"
+#include "wgrad_plan.h"
 
 struct WgradArgs {
   gode_conv_geom g;
@@ -412,7 +411,6 @@ __global__ void __launch_bounds__(WM* WN * 64) wgrad_fast_kernel(const WgradArgs
 // generator's 64->1 output layer).  An MFMA tile would be >90% padding; instead every thread keeps 4 output channels
 // x Kt taps in registers, strides over positions, and the workgroup combines its position lanes through LDS.  Output:
 // one [Co][Kt] slab per workgroup in the same layout the split-K reduce consumes.
-#define THIN_MAXKT 16
 __global__ void __launch_bounds__(256) wgrad_thin_kernel(const WgradArgs a, int chunk_thin) {
   const gode_conv_geom& g = a.g;
   const int C4 = g.Co >> 2;                 // float4 channel lanes (Co % 4 == 0, C4 <= 256)
@@ -531,8 +529,6 @@ __global__ void __launch_bounds__(256) wgrad_thin_kernel(const WgradArgs a, int 
 // operand is read straight out of that patch: column j = (row r, kw, ci) of position q sits at r*PL + (q*sw + kw)*Ci + ci,
 // so the per-lane part of the address is fixed and the position part is an immediate.  No im2col tile exists anywhere.
 // The padded row length PL = kw*Ci (mod 32) lets the 32 column lanes of a ds_read_b32 fall into distinct banks.
-#define WP_MAXB 4          // 32x32 output blocks per wave
-#define WP_MAXE 16         // patch elements staged per thread and slab
 struct WpArgs {
   WgradArgs w;
   int32_t RB, CB;          // 32-row blocks of Co, 32-column blocks of Kt
@@ -737,7 +733,6 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* work, fl
 // few outputs, many slabs (thin path, up to 1024 slabs): 16 outputs x 16 slab lanes per workgroup -- each lane's chain
 // is splits/16 loads, 8 in flight (64 x 4 lanes meant 256 serial loads per thread: ~30 us of pure latency);
 // fixed-order combine through LDS
-#define RS_OUT 16
 #define RS_LANES 16
 __global__ void __launch_bounds__(256) wgrad_reduce_small_kernel(const float* work, float* dw, int Co, int Ci, int taps,
                                                                  int splits, const int32_t* co_perm, int accumulate) {
@@ -765,211 +760,62 @@ __global__ void __launch_bounds__(256) wgrad_reduce_small_kernel(const float* wo
   }
 }
 
+
 // ---------------------------------------------------------------------------------------------------------------
-// 3: 256 output channels x 128 weight columns, 8 waves (FAST kernel only): 25 % fewer operand bytes per MFMA than 128 x 128.
-// Measured: decoder layers 332 -> 310 and 313 -> 304 us, MNIST video-D layers 2 / 3 at N = 64 119 -> 112 and 144 -> 135 us;
-// a 0.6-GFLOP problem (image-D layer 2) loses 15 %, hence the size floor.
-static int wg_tile(const gode_conv_geom& g) {
-  const int64_t macs = (int64_t)g.N * g.Do * g.Ho * g.Wo * g.Co * g.Ci * g.kd * g.kh * g.kw;
-  static const char* tenv = getenv("GODE_WGRAD_TILE");       // tuning knob (scripts/exp/sweep_wgrad.py): 2 = 128x128, 3 = 256x128, 4 = 128x256
-  if (tenv) {
-    const int t = atoi(tenv);
-    if (t == 2 && g.Co > 64) return 2;
-    if (t == 3 && g.Co % 256 == 0 && g.Ci % 4 == 0) return 3;
-    if (t == 4 && g.Co % 128 == 0 && g.Ci % 4 == 0 && (g.kd * g.kh * g.kw * g.Ci) % 256 == 0) return 4;
-  }
-  if (g.Co % 256 == 0 && g.Ci % 4 == 0 && macs >= (1ll << 31)) return 3;
-  // 128 x 256, 8 waves: the decoder's last stride-2 layer (326 -> 321 us); with only two column tiles (MNIST video-D
-  // layer 1, Kt = 512) it needs 128 position splits and loses 12 %
-  if (g.Co == 128 && g.Ci % 4 == 0 && (g.kd * g.kh * g.kw * g.Ci) % 256 == 0 && g.kd * g.kh * g.kw * g.Ci >= 1024 && macs >= (1ll << 31)) return 4;
-  return g.Co <= 32 ? 0 : (g.Co <= 64 ? 1 : 2);
-}
-static int wg_bi(int t) { return t == 0 ? 32 : (t == 1 ? 64 : (t == 3 ? 256 : 128)); }
-static int wg_bj(int t) { return t == 4 ? 256 : 128; }
+extern "C" int gode_wgrad_auto_splits(const gode_conv_geom* g) { return wgrad_auto_splits(*g); }
+extern "C" int64_t gode_wgrad_work_size(const gode_wgrad_op* op) { return wgrad_work_size(op); }
 
-// Position splits of the weight-gradient GEMM.  All workgroups carry equal work, so the launch time is the busiest
-// CU's share: the grid (tiles x splits) should be a multiple of the 256 CUs and give each CU >= 2 resident workgroups
-// (measured on the decoder layers: 512 workgroups 96-105 TFLOP/s, 640 workgroups 84-88, 256 workgroups 90-99).  More
-// splits also cost one more [Co][Kt] slab to write and reduce, ~114 positions' worth of GEMM time each.
-extern "C" int gode_wgrad_auto_splits(const gode_conv_geom* g) {
-  const int taps = g->kd * g->kh * g->kw, Kt = taps * g->Ci;
-  const int64_t M = (int64_t)g->N * g->Do * g->Ho * g->Wo;
-  const int wt = wg_tile(*g);
-  const bool w8 = wt >= 3;          // 8-wave tiles: one workgroup per CU (96 KB of LDS), its waves cover each other's barriers
-  const int64_t tiles = (int64_t)gode_ceil_div(g->Co, wg_bi(wt)) * gode_ceil_div(Kt, wg_bj(wt));
-  int64_t cap = (M + 63) / 64;
-  if (cap > 256) cap = 256;
-  if (cap < 1) cap = 1;
-  int best = 1; double best_cost = 1e300;
-  for (int64_t s = 1; s <= cap; ++s) {
-    const double blocks = (double)(tiles * s);
-    const double rounds = (double)((tiles * s + 255) / 256);
-    const double balance = blocks / (rounds * 256.0);                 // busiest CU's share vs the mean
-    const double overlap = (blocks >= 512.0 || w8) ? 1.0 : 0.92;      // a lone 4-wave workgroup per CU cannot hide its barriers
-    const double cost = (1.0 + 114.0 * (double)s / (double)M) / (balance * overlap);
-    if (cost < best_cost - 1e-12) { best_cost = cost; best = (int)s; }
-  }
-  return best;
-}
-
-static bool wg_thin(const gode_conv_geom& g) {
-  const int Kt = g.kd * g.kh * g.kw * g.Ci;
-  return Kt <= THIN_MAXKT && g.Co % 4 == 0 && (256 % ((g.Co / 4) < 64 ? (g.Co / 4) : 64)) == 0;
-}
-static int wg_thin_blocks(const gode_conv_geom& g) {
-  const int64_t M = (int64_t)g.N * g.Do * g.Ho * g.Wo;
-  int64_t b = (M + 63) / 64;       // ~4 positions per thread (the per-position gather chain is serial), up to 1024 workgroups
-  return (int)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
-}
-// PATCH path eligibility and launch shape (a function of the op's geometry and transform only, so that the work-size
-// query and the launch agree)
-static bool wg_patch(const gode_wgrad_op* op, WpArgs* P) {
-  const gode_conv_geom& g = op->g;
-  const int Kt = g.kd * g.kh * g.kw * g.Ci;
-  // (Kt <= 16 stays on the THIN path: measured on the MNIST first layers, 33 / 36 us there against 44 / 84 us here)
-  if (op->splits > 0 || g.Ci > 4 || Kt <= THIN_MAXKT || (g.Co != 32 && g.Co != 64 && g.Co != 128) || g.Wo < 16) return false;
-  if (op->scale && !op->xform_on_y) return false;
-  const int RB = g.Co / 32, CB = (Kt + 31) / 32;
-  if ((CB + 4 / RB - 1) / (4 / RB) > WP_MAXB) return false;
-  const int PR = g.kd * g.kh, LW = 31 * g.sw + g.kw;
-  if (PR > 255 || LW > 32767 || PR * LW * g.Ci > 256 * WP_MAXE) return false;
-  int PL = LW * g.Ci;
-  while (PL % 32 != (g.kw * g.Ci) % 32) ++PL;
-  if (2 * (PR * PL + 32 * g.Co + 4) * 4 > 64 * 1024 || 256 % (g.Co / 4) != 0 || PR > 30) return false;
-  // the kernel packs tap-validity masks into one word: depth taps in bits 0..4, row taps from bit 5 (e_key's 5-bit fields)
-  if (g.kd > 5 || g.kh > 27) return false;
-  const int nseg = (g.Wo + 31) / 32;
-  const int64_t segs = (int64_t)g.N * g.Do * g.Ho * nseg;
-  if (segs >= (1ll << 31)) return false;
-  if (P) {
-    P->RB = RB; P->CB = CB; P->PR = PR; P->PL = PL; P->LW = LW; P->nseg = nseg; P->dseg = make_fastdiv((uint32_t)nseg); P->segs = (int)segs;
-    int wgs = (int)(segs / 2 < 1 ? 1 : segs / 2);            // >= 2 segments per workgroup, two workgroups per CU at most
-    if (wgs > 512) wgs = 512;
-    P->segs_per_wg = (int)((segs + wgs - 1) / wgs);
-  }
-  return true;
-}
-static int wg_patch_blocks(const gode_wgrad_op* op) {
-  WpArgs P;
-  if (!wg_patch(op, &P)) return 0;
-  return (P.segs + P.segs_per_wg - 1) / P.segs_per_wg;
-}
-
-static int wg_splits(const gode_wgrad_op* op) {
-  if (const int pb = wg_patch_blocks(op)) return pb;
-  if (op->splits <= 0 && wg_thin(op->g)) return wg_thin_blocks(op->g);
-  return op->splits > 0 ? op->splits : gode_wgrad_auto_splits(&op->g);
-}
-
-extern "C" int64_t gode_wgrad_work_size(const gode_wgrad_op* op) {
-  const int taps = op->g.kd * op->g.kh * op->g.kw;
-  return (int64_t)wg_splits(op) * op->g.Co * taps * op->g.Ci;
-}
-
-static bool wg_generic_forced() {
-  static const bool f = getenv("GODE_WGRAD_GENERIC") != nullptr;     // read once per process
-  return f;
-}
-template <int WM, int WN, int TM, int TN>
-static int wg_launch(const WgradArgs& A, bool vx, bool vy, int splits, hipStream_t st) {
-  constexpr int BI = WM * TM * 32, BJ = WN * TN * 32;
-  dim3 grid(gode_ceil_div(A.Kt, BJ), gode_ceil_div(A.g.Co, BI), splits), block(WM * WN * 64);
-  static const char* genv = getenv("GODE_WGRAD_GLDS");
-  const bool glds = (genv ? atoi(genv) != 0 : true) && A.scale == nullptr && A.act == GODE_ACT_NONE && A.x_bytes != 0;
-  if (vx && vy && !wg_generic_forced()) {
-    if (glds) hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, true>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, false>), grid, block, 0, st, A);
-  }
-  else if (vx && vy) hipLaunchKernelGGL((wgrad_kernel<WM, WN, TM, TN, true, true>), grid, block, 0, st, A);
-  else if (vx) hipLaunchKernelGGL((wgrad_kernel<WM, WN, TM, TN, true, false>), grid, block, 0, st, A);
-  else if (vy) hipLaunchKernelGGL((wgrad_kernel<WM, WN, TM, TN, false, true>), grid, block, 0, st, A);
-  else hipLaunchKernelGGL((wgrad_kernel<WM, WN, TM, TN, false, false>), grid, block, 0, st, A);
-  GODE_LAUNCH_CHECK();
-  return 0;
-}
+// a tile of WGRAD_TILES as the kernels' template arguments
+#define WG_TILE_ARGS(t) WGRAD_TILES[t].WM, WGRAD_TILES[t].WN, WGRAD_TILES[t].TM, WGRAD_TILES[t].TN
 
 extern "C" int gode_wgrad(const gode_wgrad_op* op, void* stream) {
   if (!op || !op->x || !op->y || !op->work || !op->dw) return GODE_E_ARG;
+  WgradPlan P;
+  const int rc = wgrad_make_plan(op, &P);
+  if (rc) return rc;
   const gode_conv_geom& g = op->g;
-  IgemmGeom chk;
-  int rc = gode_build_igemm_geom(g, GODE_FPROP, &chk);  // validates the conv relation
-  if (rc) return rc;
-  WgradArgs A;
-  A.g = g; A.x = op->x; A.y = op->y; A.scale = op->scale; A.shift = op->shift; A.work = op->work;
-  int64_t xs[5];
-  if (gode_strides_are_channels_last(op->xs)) {
-    xs[4] = 1; xs[3] = g.Ci; xs[2] = (int64_t)g.Wi * xs[3]; xs[1] = (int64_t)g.Hi * xs[2]; xs[0] = (int64_t)g.Di * xs[1];
-  } else {
-    for (int i = 0; i < 5; ++i) xs[i] = op->xs[i];
-  }
-  int64_t span = 1 + (int64_t)(g.N - 1) * xs[0] + (int64_t)(g.Di - 1) * xs[1] + (int64_t)(g.Hi - 1) * xs[2] +
-                 (int64_t)(g.Wi - 1) * xs[3] + (int64_t)(g.Ci - 1) * xs[4];
-  const int64_t M = (int64_t)g.N * g.Do * g.Ho * g.Wo;
-  if (span >= (1ll << 31) || M * g.Co >= (1ll << 31)) return GODE_E_SHAPE;
-  A.xsN = (int)xs[0]; A.xsD = (int)xs[1]; A.xsH = (int)xs[2]; A.xsW = (int)xs[3]; A.xsC = (int)xs[4];
-  A.act = op->act; A.xform_on_y = op->xform_on_y;
-  A.x_bytes = (span * 4 < (1ll << 31) && M * g.Co * 4 < (1ll << 31)) ? (uint32_t)(span * 4) : 0u;
-  A.M = (int)M; A.taps = g.kd * g.kh * g.kw; A.Kt = A.taps * g.Ci;
-  A.dWo = make_fastdiv(g.Wo); A.dHo = make_fastdiv(g.Ho); A.dDo = make_fastdiv(g.Do);
-  const int splits = wg_splits(op);
-  A.chunk = (int)(((M + splits - 1) / splits + 31) / 32 * 32);
-  const bool vx = xs[4] == 1 && g.Ci % 4 == 0 && xs[0] % 4 == 0 && xs[1] % 4 == 0 && xs[2] % 4 == 0 && xs[3] % 4 == 0 &&
-                  (uintptr_t)op->x % 16 == 0;
-  const bool vy = g.Co % 4 == 0 && (uintptr_t)op->y % 16 == 0;
-  hipStream_t st = (hipStream_t)stream;
-  const int t = wg_tile(g);
+  const WgradPatch& w = P.work.patch;
+  const int splits = P.work.splits;
   WpArgs WP;
-  const bool patch = wg_patch(op, &WP);
-  if (patch) {
-    WP.w = A;
-    WP.yvec = (uintptr_t)op->y % 16 == 0;
-    const size_t lds = (size_t)2 * (WP.PR * WP.PL + 32 * g.Co + 4) * sizeof(float);
-    const int nbw = (WP.CB + 4 / WP.RB - 1) / (4 / WP.RB);      // column blocks per wave
-    void (*kern)(const WpArgs) = nullptr;
-#define WP_PICK(N, C) if (nbw == N && g.Co == C) kern = wgrad_patch_kernel<N, C>;
-    WP_PICK(1, 32) WP_PICK(2, 32) WP_PICK(3, 32) WP_PICK(4, 32)
-    WP_PICK(1, 64) WP_PICK(2, 64) WP_PICK(3, 64) WP_PICK(4, 64)
-    WP_PICK(1, 128) WP_PICK(2, 128) WP_PICK(3, 128) WP_PICK(4, 128)
-#undef WP_PICK
-    if (!kern) return GODE_E_SHAPE;
-    hipLaunchKernelGGL(kern, dim3(splits), dim3(256), lds, st, WP);
-    GODE_LAUNCH_CHECK();
-    rc = 0;
-  } else if (op->splits <= 0 && wg_thin(g) && vy) {
-    const int chunk_thin = (int)((M + splits - 1) / splits);
-    hipLaunchKernelGGL(wgrad_thin_kernel, dim3(splits), dim3(256), 0, st, A, chunk_thin);
-    GODE_LAUNCH_CHECK();
-    rc = 0;
-  } else if (t == 0) rc = wg_launch<1, 4, 1, 1>(A, vx, vy, splits, st);
-  else if (t == 1) rc = wg_launch<2, 2, 1, 2>(A, vx, vy, splits, st);
-  else if (t >= 3 && vx && vy && !wg_generic_forced()) {
-    dim3 grid(gode_ceil_div(A.Kt, wg_bj(t)), gode_ceil_div(g.Co, wg_bi(t)), splits), block(512);
-    const bool glds = A.scale == nullptr && A.act == GODE_ACT_NONE && A.x_bytes != 0;
-    if (t == 3) {
-      if (glds) hipLaunchKernelGGL((wgrad_fast_kernel<4, 2, 2, 2, true>), grid, block, 0, st, A);
-      else hipLaunchKernelGGL((wgrad_fast_kernel<4, 2, 2, 2, false>), grid, block, 0, st, A);
-    } else {
-      if (glds) hipLaunchKernelGGL((wgrad_fast_kernel<2, 4, 2, 2, true>), grid, block, 0, st, A);
-      else hipLaunchKernelGGL((wgrad_fast_kernel<2, 4, 2, 2, false>), grid, block, 0, st, A);
-    }
-    GODE_LAUNCH_CHECK();
-    rc = 0;
+  WgradArgs& A = WP.w;
+  A.g = g; A.x = op->x; A.y = op->y; A.scale = op->scale; A.shift = op->shift; A.work = op->work;
+  A.xsN = P.xs[0]; A.xsD = P.xs[1]; A.xsH = P.xs[2]; A.xsW = P.xs[3]; A.xsC = P.xs[4];
+  A.act = op->act; A.xform_on_y = op->xform_on_y;
+  A.M = P.M; A.chunk = P.chunk; A.Kt = P.Kt; A.taps = P.taps;
+  A.dWo = make_fastdiv(g.Wo); A.dHo = make_fastdiv(g.Ho); A.dDo = make_fastdiv(g.Do);
+  A.x_bytes = P.x_bytes;
+  if (P.path == WG_PATCH) {
+    WP.RB = w.RB; WP.CB = w.CB; WP.PR = w.PR; WP.PL = w.PL; WP.LW = w.LW; WP.nseg = w.nseg; WP.dseg = make_fastdiv((uint32_t)w.nseg);
+    WP.segs = w.segs; WP.segs_per_wg = w.segs_per_wg; WP.yvec = P.vy;
   }
-  else rc = wg_launch<2, 2, 2, 2>(A, vx, vy, splits, st);
-  if (rc) return rc;
-  const int64_t total = (int64_t)g.Co * A.Kt;
-  if ((total <= 8192 || (patch && total <= 32768)) && splits >= 16) {   // (patch path: hundreds of slabs of a [Co][Kt] of a few thousand)
-    hipLaunchKernelGGL(wgrad_reduce_small_kernel, dim3((int)((total + RS_OUT - 1) / RS_OUT)), dim3(256), 0, st, op->work, op->dw, g.Co,
-                       g.Ci, A.taps, splits, op->co_perm, op->accumulate);
-    GODE_LAUNCH_CHECK();
-    return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(P.grid_x, P.grid_y, P.grid_z), block(P.block);
+  // the one place that names a kernel: a case per entry of wgrad_plan.h's kernel lists
+#define WG_CASE_FAST(t, gl) case wgrad_fast_key(t, gl): hipLaunchKernelGGL((wgrad_fast_kernel<WG_TILE_ARGS(t), gl != 0>), grid, block, 0, st, A); break;
+#define WG_CASE_GENERIC(t, vx, vy) case wgrad_generic_key(t, vx, vy): hipLaunchKernelGGL((wgrad_kernel<WG_TILE_ARGS(t), vx != 0, vy != 0>), grid, block, 0, st, A); break;
+#define WG_CASE_PATCH(n, c) case wgrad_patch_key(n, c): hipLaunchKernelGGL((wgrad_patch_kernel<n, c>), grid, block, P.lds_bytes, st, WP); break;
+  switch (wgrad_kernel_key(P, g.Co)) {
+    WGRAD_FAST_KERNELS(WG_CASE_FAST)
+    WGRAD_GENERIC_KERNELS(WG_CASE_GENERIC)
+    WGRAD_PATCH_KERNELS(WG_CASE_PATCH)
+    case wgrad_thin_key(): hipLaunchKernelGGL(wgrad_thin_kernel, grid, block, 0, st, A, P.chunk_thin); break;
+    default: return GODE_E_SHAPE;
   }
-  const bool v4 = A.Kt % 4 == 0 && (uintptr_t)op->work % 16 == 0;
-  int blocks = (int)((total / (v4 ? 4 : 1) + 255) / 256); if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-  if (v4) hipLaunchKernelGGL((wgrad_reduce_kernel<true>), dim3(blocks), dim3(256), 0, st, op->work, op->dw, g.Co, g.Ci,
-                             A.taps, splits, op->co_perm, op->accumulate);
-  else hipLaunchKernelGGL((wgrad_reduce_kernel<false>), dim3(blocks), dim3(256), 0, st, op->work, op->dw, g.Co, g.Ci,
-                          A.taps, splits, op->co_perm, op->accumulate);
+#undef WG_CASE_FAST
+#undef WG_CASE_GENERIC
+#undef WG_CASE_PATCH
+  GODE_LAUNCH_CHECK();
+  const dim3 rgrid(P.reduce_blocks), rblock(256);
+  switch (P.reduce) {
+    case WG_REDUCE_SMALL:
+      hipLaunchKernelGGL(wgrad_reduce_small_kernel, rgrid, rblock, 0, st, op->work, op->dw, g.Co, g.Ci, P.taps, splits, op->co_perm, op->accumulate);
+      break;
+    case WG_REDUCE_VEC4:
+      hipLaunchKernelGGL((wgrad_reduce_kernel<true>), rgrid, rblock, 0, st, op->work, op->dw, g.Co, g.Ci, P.taps, splits, op->co_perm, op->accumulate);
+      break;
+    default:
+      hipLaunchKernelGGL((wgrad_reduce_kernel<false>), rgrid, rblock, 0, st, op->work, op->dw, g.Co, g.Ci, P.taps, splits, op->co_perm, op->accumulate);
+  }
   GODE_LAUNCH_CHECK();
   return 0;
 }
