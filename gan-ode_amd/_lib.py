@@ -36,6 +36,17 @@ CDE_NPARAM = 7536
 CDE_MAX_N = 4096
 GRU_NPARAM = 1632
 SN_BWD_BLOCKS = 64
+# `method` of gode_ode_fwd_op / gode_ode_bwd_op (include/gode.h), by torchdiffeq's solver name
+ODE_METHODS = {"rk4": 0, "dopri5": 1, "euler": 2, "midpoint": 3}
+
+
+def ode_method_code(name):
+    """torchdiffeq solver name -> the ops' `method` code; any solver libgode has no kernel for is an error."""
+    try:
+        return ODE_METHODS[name]
+    except (KeyError, TypeError):
+        raise NotImplementedError(f"ode_method {name!r}: libgode implements " + ", ".join(repr(k) for k in ODE_METHODS)
+                                  + " ('rk4' is the reference's call)") from None
 
 
 class ConvGeom(C.Structure):

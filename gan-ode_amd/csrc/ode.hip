@@ -97,7 +97,10 @@ int gode_launch_ode_bwd_valu(const gode_ode_bwd_op* op, hipStream_t st);
 // per wave, short dependent chains: 14 / 33 us forward / adjoint at the config size N = 32 against 21 / 53 us) and the
 // MFMA-chain kernels of this file (16 trajectories per wave: 67 vs 43 TFLOP/s forward at N = 2^20).  Default: VALU up
 // to 8192 trajectories, MFMA above; GODE_ODE_MFMA=1 / =0 forces one (the A/B of profiles/r02_ode_kernels.txt).
-static bool ode_use_mfma(int N) {
+// The MFMA-chain kernels step with Kutta 3/8 only: methods 2 (euler) and 3 (midpoint) run on the VALU kernels at every
+// N, whatever GODE_ODE_MFMA says.
+static bool ode_use_mfma(int N, int method) {
+  if (method == 2 || method == 3) return false;
   static const char* e = getenv("GODE_ODE_MFMA");
   if (e) return atoi(e) != 0;
   return N > 8192;
@@ -110,13 +113,13 @@ extern "C" int gode_ode_fwd(const gode_ode_fwd_op* op, void* stream) {
     if (op->prenet && (!op->p.Wa || !op->p.ba || !op->p.Wb || !op->p.bb)) return GODE_E_ARG;
     return gode_ode_fwd_multi(op, 1, stream);       // odernn_valu.hip (VALU kernels; MFMA fallback inside)
   }
-  if (op && op->method != 0) return GODE_E_ARG;
+  if (op && op->method != 0 && op->method != 2 && op->method != 3) return GODE_E_ARG;   // fixed grid: rk4, euler, midpoint
   if (!op || !op->x || !op->z || !op->dt || op->N <= 0 || op->T < 1 || op->substeps < 1) return GODE_E_ARG;
   if (op->grid_dt && (!op->emit_at || !op->emit_w || op->G < 1)) return GODE_E_ARG;
   if (op->zcols < 68 || op->zcols % 4 != 0) return GODE_E_ARG;
   if (!op->p.W1 || !op->p.b1 || !op->p.W2 || !op->p.b2) return GODE_E_ARG;
   if (op->prenet && (!op->p.Wa || !op->p.ba || !op->p.Wb || !op->p.bb)) return GODE_E_ARG;
-  if (!ode_use_mfma(op->N)) return gode_launch_ode_fwd_valu(op, (hipStream_t)stream);
+  if (!ode_use_mfma(op->N, op->method)) return gode_launch_ode_fwd_valu(op, (hipStream_t)stream);
   hipLaunchKernelGGL(ode_fwd_kernel, dim3((op->N + 15) / 16), dim3(op->content ? 256 : 64), 0, (hipStream_t)stream, *op);
   GODE_LAUNCH_CHECK();
   return 0;
@@ -261,7 +264,7 @@ extern "C" int gode_ode_bwd(const gode_ode_bwd_op* op, void* stream) {
   const bool adaptive = op && op->method == 1 && op->substeps == 0;
   if (!op || !op->traj || !op->gz || !op->work || !op->grads || op->N <= 0 || op->T < 1) return GODE_E_ARG;
   if (adaptive ? (!op->tout || !(op->rtol > 0.f) || !(op->atol >= 0.f)) : (!op->dt || op->substeps < 1)) return GODE_E_ARG;
-  if (op->method != 0 && op->method != 1) return GODE_E_ARG;
+  if (op->method < 0 || op->method > 3) return GODE_E_ARG;
   if (op->zcols < 16 || op->zcols % 4 != 0) return GODE_E_ARG;
   if (!op->p.W1 || !op->p.b1 || !op->p.W2 || !op->p.b2) return GODE_E_ARG;
   if (op->prenet && (!op->x || !op->p.Wa || !op->p.ba || !op->p.Wb || !op->p.bb)) return GODE_E_ARG;
@@ -269,7 +272,7 @@ extern "C" int gode_ode_bwd(const gode_ode_bwd_op* op, void* stream) {
   const int nblk = (op->N + 15) / 16;
   hipStream_t st = (hipStream_t)stream;
   if (adaptive) return gode_ode_bwd_multi(op, 1, stream);      // odernn_valu.hip (reduces into grads itself)
-  if (!ode_use_mfma(op->N)) {
+  if (!ode_use_mfma(op->N, op->method)) {
     const int rc = gode_launch_ode_bwd_valu(op, st);
     if (rc) return rc;
   } else {

@@ -1,5 +1,5 @@
-// ode_valu.hip -- the fixed-grid RK4 solve and its adjoint on the VECTOR ALU with DPP row rotations (the default since
-// round 2; the MFMA-chain kernels of ode.hip remain selectable with GODE_ODE_MFMA=1 for the A/B in profiles/).
+// ode_valu.hip -- the fixed-grid solve (rk4, euler, midpoint) and its adjoint on the VECTOR ALU with DPP row rotations (the
+// default since round 2; the rk4-only MFMA-chain kernels of ode.hip remain selectable with GODE_ODE_MFMA=1 for the A/B in profiles/).
 //
 // Reference arithmetic: as ode.hip (models/mocogan_ode.py:6-17,123-148; torchdiffeq fixed-grid rk4 = Kutta 3/8 and its
 // continuous adjoint, restated in oracle/ode_ref.py).
@@ -20,10 +20,19 @@
 //     barriers + an LDS round trip per outer product, eight per RK4 step).
 // Which lane a rotation delivers is read off the hardware once per kernel (the lane index is rotated the same way), so
 // the weight arrangement cannot disagree with the DPP semantics.
+//
+// Both kernels are compiled once per fixed-grid method (the `method` codes of gode.h): METHOD_RK4 (torchdiffeq's rk4 =
+// Kutta 3/8), METHOD_EULER, METHOD_MIDPOINT.  The method picks ONE step function per kernel (`step` below) at compile
+// time; every grid mode -- output times with `substeps`, the grid_dt / emit_at / emit_w grid, the adjoint's bstep_off /
+// bstep_dt -- calls that function, and nothing inside a time loop branches on the method.
+#include <type_traits>
 #include "common.h"
 #include "ode_common.h"
 #include "valu_common.h"
 
+enum { METHOD_RK4 = 0, METHOD_EULER = 2, METHOD_MIDPOINT = 3 };
+
+template <int METHOD>
 __global__ void __launch_bounds__(256) ode_fwd_valu_kernel(const gode_ode_fwd_op a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, tl = lane >> 4;
@@ -52,17 +61,26 @@ __global__ void __launch_bounds__(256) ode_fwd_valu_kernel(const gode_ode_fwd_op
     else if (t == tsel) a.z[(int64_t)n * a.zcols + i] = y;
   };
   emit(0);
-  const float third = 1.0f / 3.0f;
+  // y(t) -> y(t + dt)
+  auto step = [&](float y0, float dt) -> float {
+    if constexpr (METHOD == METHOD_EULER) {
+      return y0 + dt * f(y0);
+    } else if constexpr (METHOD == METHOD_MIDPOINT) {
+      return y0 + dt * f(y0 + (0.5f * dt) * f(y0));
+    } else {
+      const float third = 1.0f / 3.0f;
+      const float k1 = f(y0);
+      const float k2 = f(y0 + dt * k1 * third);
+      const float k3 = f(y0 + dt * (k2 - k1 * third));
+      const float k4 = f(y0 + dt * (k1 - k2 + k3));
+      return y0 + (k1 + 3.f * (k2 + k3) + k4) * dt * 0.125f;
+    }
+  };
   if (a.grid_dt != nullptr) {
     int jo = 1;
     for (int s = 0; s < a.G; ++s) {
-      const float dt = a.grid_dt[s];
       const float y0 = y;
-      const float k1 = f(y);
-      const float k2 = f(y + dt * k1 * third);
-      const float k3 = f(y + dt * (k2 - k1 * third));
-      const float k4 = f(y + dt * (k1 - k2 + k3));
-      const float y1 = y0 + (k1 + 3.f * (k2 + k3) + k4) * dt * 0.125f;
+      const float y1 = step(y0, a.grid_dt[s]);
       while (jo < T && a.emit_at[jo] == s) {
         const float w = a.emit_w[jo];
         y = w == 1.f ? y1 : (w == 0.f ? y0 : y0 + w * (y1 - y0));
@@ -75,19 +93,14 @@ __global__ void __launch_bounds__(256) ode_fwd_valu_kernel(const gode_ode_fwd_op
   }
   for (int j = 0; j + 1 < T; ++j) {
     const float dt = a.dt[j] / (float)a.substeps;
-    for (int ss = 0; ss < a.substeps; ++ss) {
-      const float k1 = f(y);
-      const float k2 = f(y + dt * k1 * third);
-      const float k3 = f(y + dt * (k2 - k1 * third));
-      const float k4 = f(y + dt * (k1 - k2 + k3));
-      y = y + (k1 + 3.f * (k2 + k3) + k4) * dt * 0.125f;
-    }
+    for (int ss = 0; ss < a.substeps; ++ss) y = step(y, dt);
     emit(j + 1);
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // adjoint backward
+template <int METHOD>
 __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op a) {
   __shared__ float R[4][GODE_ODE_NPARAM];     // per-wave image of the gradient vector (combined once, at the end)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -124,26 +137,55 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
   };
   float adj = upstream(T - 1);
   float ky, ka;
-  // one stage of the reversed augmented dynamics at (ys, as); c = RK weight * dt/8 for the parameter integrals
-  auto stage = [&](float ys, float as, float c) {
+  // one stage of the reversed augmented dynamics at (ys, as); c = the stage's b-weight * dt for the parameter integrals
+  // (weighted = std::false_type: a stage of weight 0, whose outer products are not formed)
+  auto stage = [&](float ys, float as, float c, auto weighted) {
     const float h = fast_tanh(mv16(w1, ys, b1));
     const float fv = mv16(w2, h, b2);
     const float v = mv16(w2t, as, 0.f);
     const float du = v * (1.f - h * h);
     ka = mv16(w1t, du, 0.f);
     ky = -fv;
-    const float ca = c * as, cdu = c * du;
-    gb2 += ca; gb1 += cdu;
-    outer16(gW2, ca, h);
-    outer16(gW1, cdu, ys);
+    if constexpr (decltype(weighted)::value) {
+      const float ca = c * as, cdu = c * du;
+      gb2 += ca; gb1 += cdu;
+      outer16(gW2, ca, h);
+      outer16(gW1, cdu, ys);
+    }
+  };
+  // (y, adj)(t) -> (y, adj)(t - dt); the parameter integrals advance with the same tableau's b-weights
+  const std::true_type b_weighted;
+  const std::false_type b_zero;
+  auto step = [&](float& y, float& adj, float dt) {
+    if constexpr (METHOD == METHOD_EULER) {
+      stage(y, adj, dt, b_weighted);
+      y = y + dt * ky;
+      adj = adj + dt * ka;
+    } else if constexpr (METHOD == METHOD_MIDPOINT) {
+      const float half = 0.5f * dt;
+      stage(y, adj, 0.f, b_zero);
+      stage(y + half * ky, adj + half * ka, dt, b_weighted);
+      y = y + dt * ky;
+      adj = adj + dt * ka;
+    } else {
+      const float third = 1.0f / 3.0f;
+      stage(y, adj, dt * 0.125f, b_weighted);
+      const float ky1 = ky, ka1 = ka;
+      stage(y + dt * ky1 * third, adj + dt * ka1 * third, 3.f * dt * 0.125f, b_weighted);
+      const float ky2 = ky, ka2 = ka;
+      stage(y + dt * (ky2 - ky1 * third), adj + dt * (ka2 - ka1 * third), 3.f * dt * 0.125f, b_weighted);
+      const float ky3 = ky, ka3 = ka;
+      stage(y + dt * (ky1 - ky2 + ky3), adj + dt * (ka1 - ka2 + ka3), dt * 0.125f, b_weighted);
+      y = y + (ky1 + 3.f * (ky2 + ky3) + ky) * dt * 0.125f;
+      adj = adj + (ka1 + 3.f * (ka2 + ka3) + ka) * dt * 0.125f;
+    }
   };
 
 #ifdef GODE_ODE_STAMPS
   st1 = __builtin_amdgcn_s_memtime();
 #endif
-  const float third = 1.0f / 3.0f;
-  // the stored state and the upstream gradient of the NEXT interval are requested before the four stages of the
-  // current one, so the (dependent, ~1 us each at N = 32) loads land under ~600 cycles of arithmetic
+  // the stored state and the upstream gradient of the NEXT interval are requested before the stages of the
+  // current one, so the (dependent, ~1 us each at N = 32) loads land under the arithmetic (rk4: ~600 cycles)
   float y_next = (valid && T > 1) ? a.traj[((int64_t)n * T + (T - 1)) * 16 + i] : 0.f;
   for (int it = T - 1; it >= 1; --it) {
     float y = y_next;
@@ -152,18 +194,7 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
     const int s0 = a.bstep_off ? a.bstep_off[it - 1] : 0;
     const int ns = a.bstep_off ? a.bstep_off[it] - s0 : a.substeps;
     const float dt_eq = a.dt[it - 1] / (float)a.substeps;
-    for (int ss = 0; ss < ns; ++ss) {
-      const float dt = a.bstep_off ? a.bstep_dt[s0 + ss] : dt_eq;
-      stage(y, adj, dt * 0.125f);
-      const float ky1 = ky, ka1 = ka;
-      stage(y + dt * ky1 * third, adj + dt * ka1 * third, 3.f * dt * 0.125f);
-      const float ky2 = ky, ka2 = ka;
-      stage(y + dt * (ky2 - ky1 * third), adj + dt * (ka2 - ka1 * third), 3.f * dt * 0.125f);
-      const float ky3 = ky, ka3 = ka;
-      stage(y + dt * (ky1 - ky2 + ky3), adj + dt * (ka1 - ka2 + ka3), dt * 0.125f);
-      y = y + (ky1 + 3.f * (ky2 + ky3) + ky) * dt * 0.125f;
-      adj = adj + (ka1 + 3.f * (ka2 + ka3) + ka) * dt * 0.125f;
-    }
+    for (int ss = 0; ss < ns; ++ss) step(y, adj, a.bstep_off ? a.bstep_dt[s0 + ss] : dt_eq);
     adj = adj + up;
   }
 
@@ -241,13 +272,21 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
 #endif
 }
 
+// op->method picks the instantiation: 2 = euler, 3 = midpoint, anything else the rk4 kernels (0, and the adjoint's
+// method 1 with substeps > 0: a dopri5 forward with a fixed Kutta-3/8 adjoint); the callers have checked the range
 int gode_launch_ode_fwd_valu(const gode_ode_fwd_op* op, hipStream_t st) {
-  hipLaunchKernelGGL(ode_fwd_valu_kernel, dim3((op->N + 15) / 16), dim3(256), 0, st, *op);
+  const dim3 grid((op->N + 15) / 16), block(256);
+  if (op->method == METHOD_EULER) hipLaunchKernelGGL(ode_fwd_valu_kernel<METHOD_EULER>, grid, block, 0, st, *op);
+  else if (op->method == METHOD_MIDPOINT) hipLaunchKernelGGL(ode_fwd_valu_kernel<METHOD_MIDPOINT>, grid, block, 0, st, *op);
+  else hipLaunchKernelGGL(ode_fwd_valu_kernel<METHOD_RK4>, grid, block, 0, st, *op);
   GODE_LAUNCH_CHECK();
   return 0;
 }
 int gode_launch_ode_bwd_valu(const gode_ode_bwd_op* op, hipStream_t st) {
-  hipLaunchKernelGGL(ode_bwd_valu_kernel, dim3((op->N + 15) / 16), dim3(256), 0, st, *op);
+  const dim3 grid((op->N + 15) / 16), block(256);
+  if (op->method == METHOD_EULER) hipLaunchKernelGGL(ode_bwd_valu_kernel<METHOD_EULER>, grid, block, 0, st, *op);
+  else if (op->method == METHOD_MIDPOINT) hipLaunchKernelGGL(ode_bwd_valu_kernel<METHOD_MIDPOINT>, grid, block, 0, st, *op);
+  else hipLaunchKernelGGL(ode_bwd_valu_kernel<METHOD_RK4>, grid, block, 0, st, *op);
   GODE_LAUNCH_CHECK();
   return 0;
 }

@@ -25,6 +25,12 @@ from .engine import ConvStack, LayerParams, LayerSpec, conv_out, dptr, make_geom
 Z_COLS = 96  # latent row: [motion 16 | content 50 | zero pad 30]: K % 32 == 0 puts the first decoder GEMM on the FAST path
 Z_CATEG0 = 66        # dim_z_category = C > 0: the one-hot lives in the first C pad columns (gode_categ_onehot)
 MAX_CATEG = Z_COLS - Z_CATEG0
+ODE_METHODS = L.ODE_METHODS      # gen.ode_method -> the latent ops' `method` code
+
+
+def ode_method_code(name):
+    """The `method` code of gen.ode_method = name on the plain Neural-ODE generators (NotImplementedError: no kernel)."""
+    return L.ode_method_code(name)
 
 
 def _require_gpu(t: torch.Tensor, what: str):
@@ -329,6 +335,7 @@ class _GenPlan:
         ptrs = tuple(dptr(p) for p in ps) + (self.gen.ode_step_size, self.gen.ode_method, self.gen.ode_rtol,
                                              self.gen.ode_atol)
         if ptrs != self._ode_ptrs:
+            method = ode_method_code(self.gen.ode_method)
             self._ode_ptrs = ptrs
             op = L.OdeParams(*ptrs[:8])
             prenet = 0 if ps[0] is None else 1
@@ -356,10 +363,10 @@ class _GenPlan:
                 self.bwd_op.tout = dptr(self._tout)
                 self._nsteps_bwd = torch.zeros((self.n + 63) // 64, dtype=torch.int32, device=self.device)
                 self.bwd_op.nsteps = dptr(self._nsteps_bwd)
-            elif self.gen.ode_method != "rk4":
-                raise NotImplementedError(f"ode_method {self.gen.ode_method!r}: libgode implements 'rk4' (the reference's "
-                                          "call) and 'dopri5'")
-            elif self.gen.ode_step_size is not None and self.T > 1:
+            else:
+                # the fixed-grid solvers (rk4: the reference's call; euler, midpoint): one grid, whichever steps on it
+                self.fwd_op.method = self.bwd_op.method = method
+            if self.gen.ode_method != "dopri5" and self.gen.ode_step_size is not None and self.T > 1:
                 gd = self._grid = self._solver_grid(float(self.gen.ode_step_size))
                 self.fwd_op.G = gd["G"]
                 self.fwd_op.grid_dt, self.fwd_op.emit_at, self.fwd_op.emit_w = dptr(gd["grid_dt"]), dptr(gd["emit_at"]), dptr(gd["emit_w"])
@@ -614,7 +621,8 @@ class VideoGenerator(nn.Module):
     mnist = False
     _plan_cls = None   # set below (_GenPlan)
     _categorical_ok = True     # dim_z_category > 0 is served (the other motion latents switch it off)
-    # the reference passes method='rk4' (models/mocogan_ode.py:50,144); 'dopri5' is what BASELINE configs[3] words
+    # the reference passes method='rk4' (models/mocogan_ode.py:50,144); 'dopri5' is what BASELINE configs[3] words;
+    # 'euler' and 'midpoint' are torchdiffeq's other two fixed-grid solvers, on rk4's grid (ODE_METHODS: all served names)
     ode_method = "rk4"
     # adjoint_substeps (dopri5 only): 0 = the adjoint is integrated adaptively with the same controller and
     # torchdiffeq's mixed norm, as odeint_adjoint does; k > 0 = k fixed Kutta-3/8 steps per output interval

@@ -244,7 +244,10 @@ typedef struct gode_ode_fwd_op {
   /* method 1: torchdiffeq's dopri5 (adaptive Dormand-Prince 5(4), controller and 4th-order dense output as in
    * gode_odernn_fwd) over the T output times tout[T] (increasing, tout[0] = start); the error norm is taken jointly
    * over the trajectories of a workgroup (<= 64; torchdiffeq: over the whole batch).  nsteps[ceil(N/64)] (nullable)
-   * receives the number of trial steps.  method 0: fixed-grid rk4 (above). */
+   * receives the number of trial steps.  method 0: fixed-grid rk4 (above).
+   * method 2: torchdiffeq's euler, y1 = y0 + dt f(y0); method 3: its midpoint, y1 = y0 + dt f(y0 + (dt/2) f(y0)).  Both
+   * walk the grids of method 0 (dt / substeps, or grid_dt / emit_at / emit_w) and take the same arguments; they run on
+   * the vector-ALU kernels at every N.  Any other code: GODE_E_ARG. */
   int32_t method, pad2_; float rtol, atol; const float* tout; int32_t* nsteps;
   /* method 1 with N > 32: >= gode_odernn_sync_size(N) words through which the workgroups exchange the whole-batch error norm
    * (see the ODE-RNN ops below; NULL or more than GODE_ODERNN_SYNC_MAX_N trajectories per launch: one norm per
@@ -274,7 +277,10 @@ typedef struct gode_ode_bwd_op {
    * of the one adjoint call is integrated backwards over the output times tout[T] with dopri5 (rtol, atol), mixed norm
    * (max over the RMS norms of y, a and each ODEFunc parameter tensor, joint over a workgroup's <= 64 trajectories);
    * the theta state is carried across the output intervals, the solver restarts on each.  method 1 with substeps > 0:
-   * the same adjoint discretised with `substeps` fixed Kutta-3/8 steps per interval (round-1 behaviour; dt required). */
+   * the same adjoint discretised with `substeps` fixed Kutta-3/8 steps per interval (round-1 behaviour; dt required).
+   * method 2 (euler) / 3 (midpoint): the adjoint of method 0 with the reverse-time steps of (y, a, g_theta) taken by that
+   * method (the parameter integrals get its b-weights: euler's one stage 1; midpoint's first stage 0, its second 1);
+   * same arguments as method 0 (dt, substeps >= 1, bstep_off / bstep_dt).  Any other code: GODE_E_ARG. */
   int32_t method, pad_; float rtol, atol; const float* tout;
   int32_t* nsteps;   /* nullable, adaptive adjoint only: trial steps of the adjoint call (nsteps[0]; without `sync` and N > 32:
                         [ceil(N/64)], one per workgroup); a negative entry reports a call that stalled (trial-step limit /
