@@ -12,9 +12,9 @@
 #include <stdint.h>
 #include "common.h"
 #include "conv_geom.h"
+#include "igemm_plan.h"      // conv_patch_plan: which shapes run here, and CP_MAXCOL (patch columns staged per thread and row)
 
 #define CP_TAB 128          // slabs whose corners are decoded at a time (LDS table)
-#define CP_MAXCOL 2         // patch columns staged per thread and row
 
 struct CpArgs {
   gode_conv_geom g;
@@ -147,47 +147,26 @@ __global__ void __launch_bounds__(256) conv_patch_fprop_kernel(const CpArgs a) {
   }
 }
 
-// Returns 1 if the op was launched here, 0 if it is not this kernel's shape (the caller goes on), < 0 on errors.
-int gode_launch_conv_patch_fprop(const gode_igemm_op* op, const int64_t* gs, hipStream_t st) {
+// Launches the op with the kernel conv_patch_plan (igemm_plan.h) chose for it: 0, or a hipError_t.
+int gode_launch_conv_patch_fprop(const gode_igemm_op* op, const int64_t* gs, const ConvPatchPlan& C, hipStream_t st) {
   const gode_conv_geom& g = op->g;
-  if (op->dir != GODE_FPROP || op->groups == 2 || op->stats || op->scale || op->shift || op->act != GODE_ACT_NONE ||
-      op->epilogue != GODE_EPI_RAW || op->tile != 0)
-    return 0;
-  const int KC = g.kw * g.Ci, Kt = g.kd * g.kh * KC;
-  if (g.Ci > 4 || (g.Co != 32 && g.Co != 64 && g.Co != 128) || KC % 2 != 0 || Kt < 8 || g.Wo < 16) return 0;
   CpArgs A;
   A.g = g; A.x = op->src; A.w = op->wpack; A.out = op->out;
   A.xsN = (int)gs[0]; A.xsD = (int)gs[1]; A.xsH = (int)gs[2]; A.xsW = (int)gs[3]; A.xsC = (int)gs[4];
-  A.Kp = (Kt + 3) & ~3;
-  A.CB = g.Co / 32; A.SPI = 4 / A.CB;
-  A.LWC = (31 * g.sw + g.kw) * g.Ci;
-  if (A.LWC > CP_MAXCOL * (256 / A.SPI)) return 0;
-  const int PL = A.LWC;        // (the row stride only separates different instructions' reads: no padding needed)
-  A.PL = PL;
-  const int PR = g.kd * g.kh;
-  const size_t lds = (size_t)2 * A.SPI * PR * PL * sizeof(float);
-  if (lds > 60 * 1024) return 0;
-  A.nseg = (g.Wo + 31) / 32;
-  const int64_t segs = (int64_t)g.N * g.Do * g.Ho * A.nseg;
-  if (segs >= (1ll << 31) || (int64_t)g.N * g.Do * g.Ho * g.Wo * g.Co >= (1ll << 31)) return 0;
-  A.segs = (int)segs;
-  const int nit = (A.segs + A.SPI - 1) / A.SPI;
-  int wgs = nit / 4 < 1 ? 1 : nit / 4;               // >= 4 iterations per workgroup, two workgroups per CU at most
-  if (wgs > 512) wgs = 512;
-  A.iters_per_wg = (nit + wgs - 1) / wgs;
-  wgs = (nit + A.iters_per_wg - 1) / A.iters_per_wg;
+  A.Kp = C.Kp; A.CB = C.CB; A.SPI = C.SPI; A.LWC = C.LWC;
+  A.PL = C.LWC;                // (the row stride only separates different instructions' reads: no padding needed)
+  A.nseg = C.nseg; A.segs = C.segs; A.iters_per_wg = C.iters_per_wg;
   A.dseg = make_fastdiv((uint32_t)A.nseg); A.dHo = make_fastdiv((uint32_t)g.Ho); A.dDo = make_fastdiv((uint32_t)g.Do);
   A.dCi = make_fastdiv((uint32_t)g.Ci);
   void (*kern)(const CpArgs) = nullptr;
-  const int KC2 = KC / 2;
-#define CP_PICK(D, H, K2) if (g.kd == D && g.kh == H && KC2 == K2) kern = conv_patch_fprop_kernel<D, H, K2>;
-  CP_PICK(4, 4, 6)      // Conv3d(3, ., 4): UCF video discriminator
-  CP_PICK(1, 4, 6)      // Conv2d(3, ., 4): UCF image discriminator
-  CP_PICK(2, 2, 1)      // Conv3d(1, ., 2): MNIST video discriminator
-  CP_PICK(1, 4, 2)      // Conv2d(1, ., 4): MNIST image discriminator
-#undef CP_PICK
-  if (!kern) return 0;
-  hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), lds, st, A);
+  switch (C.variant) {
+    case CP_K3D_C3: kern = conv_patch_fprop_kernel<4, 4, 6>; break;
+    case CP_K2D_C3: kern = conv_patch_fprop_kernel<1, 4, 6>; break;
+    case CP_K3D_C1: kern = conv_patch_fprop_kernel<2, 2, 1>; break;
+    case CP_K2D_C1: kern = conv_patch_fprop_kernel<1, 4, 2>; break;
+    default: return GODE_E_ARG;
+  }
+  hipLaunchKernelGGL(kern, dim3(C.wgs), dim3(256), (size_t)C.lds, st, A);
   GODE_LAUNCH_CHECK();
-  return 1;
+  return 0;
 }

@@ -19,7 +19,7 @@
 #include "conv_geom.h"
 #include "igemm_plan.h"
 
-int gode_launch_conv_patch_fprop(const gode_igemm_op* op, const int64_t* gs, hipStream_t st);   // conv_patch.hip
+int gode_launch_conv_patch_fprop(const gode_igemm_op* op, const int64_t* gs, const ConvPatchPlan& C, hipStream_t st);   // conv_patch.hip
 
 struct IgemmArgs {
   IgemmGeom G;
@@ -1113,42 +1113,47 @@ extern "C" int64_t gode_igemm_work_size(const gode_igemm_op* op) {
   return P.ksplit > 1 ? (int64_t)P.ksplit * P.positions * P.G.Ncols : 0;
 }
 
-// One tiled-GEMM launch of a plan.  `vec`: the pointers allow what the plan's strides do; without it the generic kernel runs
-// the same tile (a plan that splits K cannot be served then).
+// One tiled-GEMM launch of a plan: the kernel, grid order and split-K finish its launch cell (igemm_plan.h) names.
 template <int TILE>
-static int launch(IgemmArgs& A, const IgemmPlan& P, bool vec, hipStream_t st) {
+static int launch(IgemmArgs& A, const IgemmPlan& P, const IgemmLaunchCell& cell, hipStream_t st) {
   constexpr IgemmTile T = IGEMM_TILES[TILE];
   constexpr int WM = T.WM, WN = T.WN, TM = T.TM, TN = T.TN;
   dim3 grid(P.max_mblk, gode_ceil_div(A.G.Ncols, T.bn), A.G.nphase), block(WM * WN * 64);
-  const bool fast = vec && P.fast;
-  if (P.ksplit > 1 && (!fast || A.work == nullptr)) return GODE_E_ARG;   // the plan needs the FAST path + workspace
-  if (fast) {
+  const bool generic = cell.kernel == IGEMM_K_GENERIC_VEC || cell.kernel == IGEMM_K_GENERIC_SCALAR;
+  int slabs = P.ksplit;
+  if (generic) {
+    IgemmArgs B = A;
+    if (cell.reduce != IGEMM_REDUCE_NONE) {      // a plan that splits K, served unsplit: raw results as the one slab, finished below
+      if (A.work == nullptr) A.work = A.out;
+      B.out = A.work; B.stats = nullptr; B.epilogue = GODE_EPI_RAW;
+      slabs = 1;
+    }
+    if (cell.kernel == IGEMM_K_GENERIC_VEC) hipLaunchKernelGGL((igemm_kernel<WM, WN, TM, TN, true>), grid, block, 0, st, B);
+    else hipLaunchKernelGGL((igemm_kernel<WM, WN, TM, TN, false>), grid, block, 0, st, B);
+  } else {
     static const char* senv = getenv("GODE_IGEMM_STAGGER");
     A.stagger = senv ? atoi(senv) : 0;
 #ifndef GODE_ABLATION_BUILD
     if (A.stagger < 0) A.stagger = 0;   // the negative (ablation) selectors only exist in -DGODE_ABLATION_BUILD builds
 #endif
     const dim3 g1(P.ntab > 0 ? P.tile0[P.ntab] : P.MB * P.NB * A.G.nphase * P.ksplit);
-    // LDS-DMA staging unless the previous layer's BatchNorm/activation is fused into the load or an operand is beyond the
-    // 2 GiB a raw buffer's offsets span: then register staging (MODE 0)
-    const bool has_xf = A.scale != nullptr || A.act != GODE_ACT_NONE;
-    const bool glds = !has_xf && A.src_bytes != 0 && A.w_bytes != 0;
-    if (glds && A.tapskip) hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 3, false>), g1, block, 0, st, A);
-    else if (glds) hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 2, false>), g1, block, 0, st, A);
-    else if (has_xf) hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 0, true>), g1, block, 0, st, A);
-    else hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 0, false>), g1, block, 0, st, A);
-    if (P.ksplit > 1) {
-      GODE_LAUNCH_CHECK();
-      if (A.G.Ncols % 4 == 0 && ((uintptr_t)A.work % 16) == 0 && ((uintptr_t)A.out % 16) == 0)
-        hipLaunchKernelGGL(igemm_splitk_reduce_vec_kernel, dim3(gode_ceil_div(P.positions, SPLITK_ROWS), gode_ceil_div(A.G.Ncols, 64)),
-                           dim3(256), 0, st, A.work, A.out, A.stats, P.positions, A.G.Ncols, P.ksplit, A.epilogue);
-      else
-        hipLaunchKernelGGL(igemm_splitk_reduce_kernel, dim3(gode_ceil_div(P.positions, SPLITK_ROWS)), dim3(256), 0, st, A.work, A.out,
-                           A.stats, P.positions, A.G.Ncols, P.ksplit, A.epilogue);
+    switch (cell.kernel) {
+      case IGEMM_K_FAST_DMA_LIVE: hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 3, false>), g1, block, 0, st, A); break;
+      case IGEMM_K_FAST_DMA: hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 2, false>), g1, block, 0, st, A); break;
+      case IGEMM_K_FAST_REG_XF: hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 0, true>), g1, block, 0, st, A); break;
+      case IGEMM_K_FAST_REG: hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, 0, false>), g1, block, 0, st, A); break;
+      default: return GODE_E_ARG;
     }
   }
-  else if (vec) hipLaunchKernelGGL((igemm_kernel<WM, WN, TM, TN, true>), grid, block, 0, st, A);
-  else hipLaunchKernelGGL((igemm_kernel<WM, WN, TM, TN, false>), grid, block, 0, st, A);
+  if (cell.reduce != IGEMM_REDUCE_NONE) {
+    GODE_LAUNCH_CHECK();
+    if (cell.reduce == IGEMM_REDUCE_VEC)
+      hipLaunchKernelGGL(igemm_splitk_reduce_vec_kernel, dim3(gode_ceil_div(P.positions, SPLITK_ROWS), gode_ceil_div(A.G.Ncols, 64)),
+                         dim3(256), 0, st, A.work, A.out, A.stats, P.positions, A.G.Ncols, slabs, A.epilogue);
+    else
+      hipLaunchKernelGGL(igemm_splitk_reduce_kernel, dim3(gode_ceil_div(P.positions, SPLITK_ROWS)), dim3(256), 0, st, A.work, A.out,
+                         A.stats, P.positions, A.G.Ncols, slabs, A.epilogue);
+  }
   GODE_LAUNCH_CHECK();
   return 0;
 }
@@ -1163,30 +1168,14 @@ static PwArgs pw_args(const IgemmArgs& A, int lanes_per_position) {
 }
 
 extern "C" int gode_igemm(const gode_igemm_op* op, void* stream) {
-  if (!op || !op->src || !op->wpack || !op->out) return GODE_E_ARG;
   IgemmPlan P;
-  int rc = igemm_make_plan(op, &P);
-  if (rc) return rc;
-  if (P.max_mblk == 0) return 0;
-  const IgemmGeom& G = P.G;
+  IgemmLaunchCell cell;
   int64_t gs[5];
-  if (gode_strides_are_channels_last(op->gs)) {
-    gs[4] = 1; gs[3] = G.Cg; gs[2] = (int64_t)G.Gw * gs[3]; gs[1] = (int64_t)G.Gh * gs[2]; gs[0] = (int64_t)G.Gd * gs[1];
-  } else {
-    for (int i = 0; i < 5; ++i) gs[i] = op->gs[i];
-  }
-  // 32-bit offset arithmetic inside the kernel: the gathered span and the output must stay below 2^31 elements
-  int64_t span = 1 + (int64_t)(op->g.N - 1) * gs[0] + (int64_t)(G.Gd - 1) * gs[1] + (int64_t)(G.Gh - 1) * gs[2] +
-                 (int64_t)(G.Gw - 1) * gs[3] + (int64_t)(G.Cg - 1) * gs[4];
-  int64_t outn = (int64_t)op->g.N * G.Xd * G.Xh * G.Xw * G.Ncols;
-  for (int i = 0; i < 5; ++i) if (gs[i] < 0) return GODE_E_ARG;
-  if (span >= (1ll << 31) || outn >= (1ll << 31)) return GODE_E_SHAPE;
-  if (((uintptr_t)op->wpack % 16) != 0 || (op->scale == nullptr) != (op->shift == nullptr)) return GODE_E_ARG;
+  const int rc = igemm_plan_launch(op, &P, gs, &cell);
+  if (rc || cell.kernel == IGEMM_K_NONE) return rc;
+  const IgemmGeom& G = P.G;
   hipStream_t st = (hipStream_t)stream;
-  if (P.family == IGEMM_PATCH_FPROP) {      // conv_patch.hip; it declines the shapes it has no kernel for
-    const int pr = gode_launch_conv_patch_fprop(op, gs, st);
-    if (pr != 0) return pr < 0 ? pr : 0;
-  }
+  if (cell.kernel == IGEMM_K_PATCH) return gode_launch_conv_patch_fprop(op, gs, cell.patch, st);
   IgemmArgs A;
   A.G = G;
   A.src = op->src; A.w = op->wpack; A.out = op->out; A.scale = op->scale; A.shift = op->shift; A.stats = op->stats;
@@ -1197,50 +1186,68 @@ extern "C" int gode_igemm(const gode_igemm_op* op, void* stream) {
   A.ksplit = P.ksplit; A.slabs_per_split = P.slabs_per_split;
   A.MB = P.MB; A.NB = P.NB; A.xcd_mode = P.xcd_mode; A.ntab = P.ntab; A.interleave = P.interleave;
   for (int i = 0; i <= GODE_MAX_PHASES; ++i) A.tile0[i] = P.tile0[i];
-  A.src_bytes = span * 4 < (1ll << 31) ? (uint32_t)(span * 4) : 0u;
-  A.w_bytes = gode_pack_floats(G) * 4 < (1ll << 31) ? (uint32_t)(gode_pack_floats(G) * 4) : 0u;
-  A.work = op->work; A.out_numel = (int32_t)outn;
-  // what the plan could not see: the pointers' alignment.  It only ever takes the op from its family to the tiled GEMM, and
-  // there from the vector kernels to the generic one -- tile and K split stay the plan's
-  const bool vec = P.vec && ((uintptr_t)op->src % 16) == 0 &&
-                   (op->scale == nullptr || ((uintptr_t)op->scale % 16 == 0 && (uintptr_t)op->shift % 16 == 0));
+  A.src_bytes = cell.src_bytes; A.w_bytes = cell.w_bytes;
+  A.work = op->work; A.out_numel = (int32_t)((int64_t)op->g.N * G.Xd * G.Xh * G.Xw * G.Ncols);
   int maxM = 0, minK = 1 << 30;
   for (int i = 0; i < G.nphase; ++i) {
     if (G.ph[i].M > maxM) maxM = G.ph[i].M;
     if (G.ph[i].K < minK) minK = G.ph[i].K;
   }
-  if (P.family == IGEMM_POINTWISE && vec) {
-    const int lpp = G.Cg / 4;
-    const bool one_tap = G.nphase == 1 && G.ph[0].K == G.Cg;
-    const PwArgs D = pw_args(A, lpp);
-    int64_t blocks = ((int64_t)maxM + (64 / lpp) * 4 * 8 - 1) / ((64 / lpp) * 4 * 8);     // ~8 position groups per wave
-    if (blocks > (one_tap ? 4096 : 2048)) blocks = one_tap ? 4096 : 2048;
-    if (one_tap && G.Ncols == 1 && lpp <= 16) {
-      // every wave resident at once (<= 8 per SIMD on 1024 SIMDs) and the same number of iterations for all, within one
-      const int64_t its = ((int64_t)maxM + (64 / lpp) * PW1_U - 1) / ((64 / lpp) * PW1_U), per_wave = (its + 8191) / 8192;
-      const dim3 g1((unsigned)((its + 4 * per_wave - 1) / (4 * per_wave)));
-      if (lpp == 16) hipLaunchKernelGGL(conv_pointwise1_kernel<16>, g1, dim3(256), 0, st, D);
-      else if (lpp == 8) hipLaunchKernelGGL(conv_pointwise1_kernel<8>, g1, dim3(256), 0, st, D);
-      else hipLaunchKernelGGL(conv_pointwise1_kernel<4>, g1, dim3(256), 0, st, D);
+  switch (cell.kernel) {
+    case IGEMM_K_POINTWISE1: case IGEMM_K_POINTWISE_TAP1: case IGEMM_K_POINTWISE_TAPS: {
+      const int lpp = G.Cg / 4;
+      const bool one_tap = cell.kernel != IGEMM_K_POINTWISE_TAPS;
+      const PwArgs D = pw_args(A, lpp);
+      int64_t blocks = ((int64_t)maxM + (64 / lpp) * 4 * 8 - 1) / ((64 / lpp) * 4 * 8);     // ~8 position groups per wave
+      if (blocks > (one_tap ? 4096 : 2048)) blocks = one_tap ? 4096 : 2048;
+      if (cell.kernel == IGEMM_K_POINTWISE1) {
+        // every wave resident at once (<= 8 per SIMD on 1024 SIMDs) and the same number of iterations for all, within one
+        const int64_t its = ((int64_t)maxM + (64 / lpp) * PW1_U - 1) / ((64 / lpp) * PW1_U), per_wave = (its + 8191) / 8192;
+        const dim3 g1((unsigned)((its + 4 * per_wave - 1) / (4 * per_wave)));
+        if (lpp == 16) hipLaunchKernelGGL(conv_pointwise1_kernel<16>, g1, dim3(256), 0, st, D);
+        else if (lpp == 8) hipLaunchKernelGGL(conv_pointwise1_kernel<8>, g1, dim3(256), 0, st, D);
+        else hipLaunchKernelGGL(conv_pointwise1_kernel<4>, g1, dim3(256), 0, st, D);
+      }
+      else if (one_tap) hipLaunchKernelGGL(conv_pointwise_kernel<true>, dim3((int)blocks, 1), dim3(256), 0, st, D);
+      else hipLaunchKernelGGL(conv_pointwise_kernel<false>, dim3((int)blocks, G.nphase), dim3(256), 0, st, D);
+      break;
     }
-    else if (one_tap) hipLaunchKernelGGL(conv_pointwise_kernel<true>, dim3((int)blocks, 1), dim3(256), 0, st, D);
-    else hipLaunchKernelGGL(conv_pointwise_kernel<false>, dim3((int)blocks, G.nphase), dim3(256), 0, st, D);
-  } else if (P.family == IGEMM_SMALLK && ((uintptr_t)op->out % 16) == 0) {
-    const int nl = G.Ncols / 4;
-    const PwArgs D = pw_args(A, nl);
-    int64_t blocks = ((int64_t)maxM + (64 / nl) * 4 * 4 - 1) / ((64 / nl) * 4 * 4);     // ~4 position groups per wave
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(conv_smallk_kernel, dim3((int)blocks), dim3(256), 0, st, D);
-  } else if (P.family == IGEMM_DOT && vec) {
-    DotArgs D; D.a = A; D.dCg = make_fastdiv((uint32_t)G.Cg);
-    D.per_block = (maxM <= 256 && minK >= 4096) ? 1 : 4;
-    hipLaunchKernelGGL(conv_dot_kernel, dim3(D.per_block == 1 ? maxM : gode_ceil_div(maxM, 4), G.nphase), dim3(256), 0, st, D);
-  } else {      // the tiled GEMM: one launcher per entry of IGEMM_TILES (the plan's tile exists)
-    static int (*const launchers[IGEMM_TILE_IDS])(IgemmArgs&, const IgemmPlan&, bool, hipStream_t) = {
-        nullptr, launch<TILE_128x128>, launch<TILE_128x64>, launch<TILE_128x32>, launch<TILE_64x64>, nullptr, launch<TILE_256x128>};
-    return launchers[P.tile](A, P, vec, st);
+    case IGEMM_K_SMALLK: {
+      const int nl = G.Ncols / 4;
+      const PwArgs D = pw_args(A, nl);
+      int64_t blocks = ((int64_t)maxM + (64 / nl) * 4 * 4 - 1) / ((64 / nl) * 4 * 4);     // ~4 position groups per wave
+      if (blocks > 4096) blocks = 4096;
+      hipLaunchKernelGGL(conv_smallk_kernel, dim3((int)blocks), dim3(256), 0, st, D);
+      break;
+    }
+    case IGEMM_K_DOT: {
+      DotArgs D; D.a = A; D.dCg = make_fastdiv((uint32_t)G.Cg);
+      D.per_block = (maxM <= 256 && minK >= 4096) ? 1 : 4;
+      hipLaunchKernelGGL(conv_dot_kernel, dim3(D.per_block == 1 ? maxM : gode_ceil_div(maxM, 4), G.nphase), dim3(256), 0, st, D);
+      break;
+    }
+    default: {      // the tiled GEMM: one launcher per entry of IGEMM_TILES (the plan's tile exists)
+      static int (*const launchers[IGEMM_TILE_IDS])(IgemmArgs&, const IgemmPlan&, const IgemmLaunchCell&, hipStream_t) = {
+          nullptr, launch<TILE_128x128>, launch<TILE_128x64>, launch<TILE_128x32>, launch<TILE_64x64>, nullptr, launch<TILE_256x128>};
+      return launchers[cell.tile](A, P, cell, st);
+    }
   }
   GODE_LAUNCH_CHECK();
+  return 0;
+}
+
+// The launch cell of the op (igemm_plan.h: igemm_launch_cell, the function gode_igemm dispatches on), host-side: what
+// gode_igemm(op) returns before it launches anything, and on 0 cell = {kernel, tile, reduce, ksplit, xcd_mode, table,
+// interleave, tapskip}.  The pointers of the op are looked at (null, alignment), never through.
+extern "C" int gode_igemm_launch_cell(const gode_igemm_op* op, int32_t* cell) {
+  if (!cell) return GODE_E_ARG;
+  IgemmPlan P;
+  IgemmLaunchCell c;
+  int64_t gs[5];
+  const int rc = igemm_plan_launch(op, &P, gs, &c);
+  if (rc) return rc;
+  const int32_t v[IGEMM_CELL_INTS] = {c.kernel, c.tile, c.reduce, c.ksplit, c.xcd_mode, c.table, c.interleave, c.tapskip};
+  for (int i = 0; i < IGEMM_CELL_INTS; ++i) cell[i] = v[i];
   return 0;
 }
 

@@ -213,9 +213,9 @@ static void choose_border(const IgemmGeom& B, int* tile_out, double* cycles_out)
   *tile_out = best_tile; *cycles_out = best;
 }
 
-// Which kernel of igemm.hip / conv_patch.hip serves the op.  The thin-output streaming kernels and the patch kernel need
-// aligned pointers besides: gode_igemm falls back to the tiled GEMM of the same plan when they are not (or when
-// conv_patch.hip declines the shape).
+// Which kernel of igemm.hip / conv_patch.hip serves the op.  The thin-output streaming kernels need aligned pointers besides
+// (the patch kernel gathers scalars and does not): igemm_launch_cell below falls back to the tiled GEMM of the same plan when
+// they are not, or when conv_patch.hip has no kernel for the shape (conv_patch_plan).
 enum { IGEMM_GEMM = 0, IGEMM_PATCH_FPROP = 1, IGEMM_POINTWISE = 2, IGEMM_SMALLK = 3, IGEMM_DOT = 4 };
 
 struct IgemmPlan {
@@ -438,4 +438,145 @@ static int igemm_make_plan(const gode_igemm_op* op, IgemmPlan* P) {
   P->family = thin_family(op, G, P->vec);
   plan_grid_order(op, P);
   return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The launch cell: what gode_igemm actually launches for an op -- the plan plus what the plan cannot see (the pointers'
+// alignment, the fused operand transform, the operands' size, what conv_patch.hip has a kernel for).  gode_igemm and
+// launch<TILE> (igemm.hip) dispatch on it and gode_igemm_launch_cell reports it, so a test that asserts a cell asserts the
+// launch.  Still plain host arithmetic: the pointers are looked at, never through.
+
+#define CP_MAXCOL 2         // conv_patch.hip: patch columns staged per thread and row
+
+// conv_patch.hip's launch of an op, or false when it has no kernel for the shape (the op then runs the tiled GEMM of its plan)
+struct ConvPatchPlan { int32_t Kp, CB, SPI, LWC, PR, nseg, segs, iters_per_wg, wgs, variant; int64_t lds; };
+enum { CP_K3D_C3 = 1, CP_K2D_C3 = 2, CP_K3D_C1 = 3, CP_K2D_C1 = 4 };     // ConvPatchPlan.variant: the kernel instantiations
+static bool conv_patch_plan(const gode_igemm_op* op, ConvPatchPlan* C) {
+  const gode_conv_geom& g = op->g;
+  if (op->dir != GODE_FPROP || op->groups == 2 || op->stats || op->scale || op->shift || op->act != GODE_ACT_NONE ||
+      op->epilogue != GODE_EPI_RAW || op->tile != 0)
+    return false;
+  const int KC = g.kw * g.Ci, Kt = g.kd * g.kh * KC;
+  if (g.Ci > 4 || (g.Co != 32 && g.Co != 64 && g.Co != 128) || KC % 2 != 0 || Kt < 8 || g.Wo < 16) return false;
+  C->Kp = (Kt + 3) & ~3;
+  C->CB = g.Co / 32; C->SPI = 4 / C->CB;
+  C->LWC = (31 * g.sw + g.kw) * g.Ci;
+  if (C->LWC > CP_MAXCOL * (256 / C->SPI)) return false;
+  C->PR = g.kd * g.kh;
+  C->lds = (int64_t)2 * C->SPI * C->PR * C->LWC * (int64_t)sizeof(float);
+  if (C->lds > 60 * 1024) return false;
+  C->nseg = (g.Wo + 31) / 32;
+  const int64_t segs = (int64_t)g.N * g.Do * g.Ho * C->nseg;
+  if (segs >= (1ll << 31) || (int64_t)g.N * g.Do * g.Ho * g.Wo * g.Co >= (1ll << 31)) return false;
+  C->segs = (int)segs;
+  const int nit = (C->segs + C->SPI - 1) / C->SPI;
+  int wgs = nit / 4 < 1 ? 1 : nit / 4;               // >= 4 iterations per workgroup, two workgroups per CU at most
+  if (wgs > 512) wgs = 512;
+  C->iters_per_wg = (nit + wgs - 1) / wgs;
+  C->wgs = (nit + C->iters_per_wg - 1) / C->iters_per_wg;
+  const int KC2 = KC / 2;
+  C->variant = 0;
+  if (g.kd == 4 && g.kh == 4 && KC2 == 6) C->variant = CP_K3D_C3;      // Conv3d(3, ., 4): UCF video discriminator
+  if (g.kd == 1 && g.kh == 4 && KC2 == 6) C->variant = CP_K2D_C3;      // Conv2d(3, ., 4): UCF image discriminator
+  if (g.kd == 2 && g.kh == 2 && KC2 == 1) C->variant = CP_K3D_C1;      // Conv3d(1, ., 2): MNIST video discriminator
+  if (g.kd == 1 && g.kh == 4 && KC2 == 2) C->variant = CP_K2D_C1;      // Conv2d(1, ., 4): MNIST image discriminator
+  return C->variant != 0;
+}
+
+enum { IGEMM_K_NONE = -1,             // nothing to launch (an empty op)
+       IGEMM_K_FAST_DMA = 0,          // igemm_fast_kernel MODE 2: LDS-DMA staging
+       IGEMM_K_FAST_DMA_LIVE = 1,     //                   MODE 3: LDS-DMA over the live taps
+       IGEMM_K_FAST_REG_XF = 2,       //                   MODE 0 with the transform on load
+       IGEMM_K_FAST_REG = 3,          //                   MODE 0 plain (an operand beyond 2 GiB)
+       IGEMM_K_GENERIC_VEC = 4, IGEMM_K_GENERIC_SCALAR = 5,      // igemm_kernel, float4 / scalar gathers
+       IGEMM_K_POINTWISE1 = 6,        // conv_pointwise1_kernel (one tap, one column)
+       IGEMM_K_POINTWISE_TAP1 = 7, IGEMM_K_POINTWISE_TAPS = 8,   // conv_pointwise_kernel<true / false>
+       IGEMM_K_SMALLK = 9, IGEMM_K_DOT = 10, IGEMM_K_PATCH = 11 };
+enum { IGEMM_REDUCE_NONE = 0, IGEMM_REDUCE_VEC = 1, IGEMM_REDUCE_SCALAR = 2 };           // the split-K finish
+enum { IGEMM_TABLE_PLAIN = 0, IGEMM_TABLE_BORDER = 1, IGEMM_TABLE_INTERLEAVED = 2 };     // the phase table of a tiled launch
+
+struct IgemmLaunchCell {
+  int32_t rc;                         // what gode_igemm returns before it launches anything (0: it launches `kernel`)
+  int32_t kernel, tile, reduce;       // tile: 0 off the tiled GEMM
+  int32_t ksplit, xcd_mode, table, interleave, tapskip;    // of the tiled GEMM (xcd_mode: the FAST kernels only); ksplit 1
+                                      // with a reduce: a plan that splits K served unsplit by the generic kernel
+  int32_t vec;                        // pointers and strides allow float4 gathers
+  uint32_t src_bytes, w_bytes;        // extents of the operands as raw buffers, 0 beyond 2 GiB
+  ConvPatchPlan patch;                // kernel == IGEMM_K_PATCH
+};
+#define IGEMM_CELL_INTS 8             // gode_igemm_launch_cell: kernel, tile, reduce, ksplit, xcd_mode, table, interleave, tapskip
+
+static bool igemm_ptr16(const void* p) { return ((uintptr_t)p % 16) == 0; }
+
+// Element strides of the gathered operand and the span they cover, in elements; -1 with a negative stride.
+static int64_t igemm_gather_span(const gode_igemm_op* op, const IgemmGeom& G, int64_t gs[5]) {
+  if (gode_strides_are_channels_last(op->gs)) {
+    gs[4] = 1; gs[3] = G.Cg; gs[2] = (int64_t)G.Gw * gs[3]; gs[1] = (int64_t)G.Gh * gs[2]; gs[0] = (int64_t)G.Gd * gs[1];
+  } else {
+    for (int i = 0; i < 5; ++i) gs[i] = op->gs[i];
+  }
+  for (int i = 0; i < 5; ++i) if (gs[i] < 0) return -1;
+  return 1 + (int64_t)(op->g.N - 1) * gs[0] + (int64_t)(G.Gd - 1) * gs[1] + (int64_t)(G.Gh - 1) * gs[2] + (int64_t)(G.Gw - 1) * gs[3] +
+         (int64_t)(G.Cg - 1) * gs[4];
+}
+
+static IgemmLaunchCell igemm_launch_cell(const gode_igemm_op* op, const IgemmPlan& P, int64_t span) {
+  const IgemmGeom& G = P.G;
+  IgemmLaunchCell c;
+  c.rc = 0; c.kernel = IGEMM_K_NONE; c.tile = 0; c.reduce = IGEMM_REDUCE_NONE;
+  c.ksplit = 1; c.xcd_mode = 0; c.table = IGEMM_TABLE_PLAIN; c.interleave = 0; c.tapskip = 0; c.vec = 0; c.src_bytes = 0; c.w_bytes = 0;
+  if (P.max_mblk == 0) return c;
+  // 32-bit offset arithmetic inside the kernels: the gathered span and the output must stay below 2^31 elements
+  const int64_t outn = (int64_t)op->g.N * G.Xd * G.Xh * G.Xw * G.Ncols;
+  if (span < 0) { c.rc = GODE_E_ARG; return c; }
+  if (span >= (1ll << 31) || outn >= (1ll << 31)) { c.rc = GODE_E_SHAPE; return c; }
+  if (!igemm_ptr16(op->wpack) || (op->scale == nullptr) != (op->shift == nullptr)) { c.rc = GODE_E_ARG; return c; }
+  if (P.family == IGEMM_PATCH_FPROP && conv_patch_plan(op, &c.patch)) { c.kernel = IGEMM_K_PATCH; return c; }
+  c.src_bytes = span * 4 < (1ll << 31) ? (uint32_t)(span * 4) : 0u;
+  c.w_bytes = gode_pack_floats(G) * 4 < (1ll << 31) ? (uint32_t)(gode_pack_floats(G) * 4) : 0u;
+  // what the plan could not see: the pointers' alignment.  It only ever takes the op from its family to the tiled GEMM, and
+  // there from the vector kernels to the generic one -- tile and K split stay the plan's
+  const bool vec = P.vec && igemm_ptr16(op->src) && (op->scale == nullptr || (igemm_ptr16(op->scale) && igemm_ptr16(op->shift)));
+  c.vec = vec;
+  if (P.family == IGEMM_POINTWISE && vec) {
+    const bool one_tap = G.nphase == 1 && G.ph[0].K == G.Cg;
+    c.kernel = one_tap && G.Ncols == 1 && G.Cg / 4 <= 16 ? IGEMM_K_POINTWISE1 : (one_tap ? IGEMM_K_POINTWISE_TAP1 : IGEMM_K_POINTWISE_TAPS);
+    return c;
+  }
+  if (P.family == IGEMM_SMALLK && igemm_ptr16(op->out)) { c.kernel = IGEMM_K_SMALLK; return c; }
+  if (P.family == IGEMM_DOT && vec) { c.kernel = IGEMM_K_DOT; return c; }
+  // the tiled GEMM
+  c.tile = P.tile; c.ksplit = P.ksplit; c.tapskip = P.tapskip; c.interleave = P.interleave;
+  c.table = !G.border ? IGEMM_TABLE_PLAIN : (P.interleave > 1 ? IGEMM_TABLE_INTERLEAVED : IGEMM_TABLE_BORDER);
+  const bool fast = vec && P.fast;
+  if (!fast || (P.ksplit > 1 && op->work == nullptr)) {
+    c.kernel = vec ? IGEMM_K_GENERIC_VEC : IGEMM_K_GENERIC_SCALAR;
+    if (P.ksplit > 1) {
+      // A plan that splits K, without its workspace or off the FAST path.  The statistics rows were sized from the plan (one
+      // per SPLITK_ROWS positions), so the launch keeps that layout: the generic kernel writes the raw, unsplit result as the
+      // one slab -- into work, or into out itself -- and the split-K finish runs over that slab (in place: every element is
+      // read and written by the same thread), applying the epilogue and the statistics.
+      const float* slab = op->work ? op->work : op->out;
+      c.ksplit = 1;
+      c.reduce = G.Ncols % 4 == 0 && igemm_ptr16(slab) && igemm_ptr16(op->out) ? IGEMM_REDUCE_VEC : IGEMM_REDUCE_SCALAR;
+    }
+    return c;
+  }
+  c.xcd_mode = P.xcd_mode;
+  // LDS-DMA staging unless the previous layer's BatchNorm/activation is fused into the load or an operand is beyond the
+  // 2 GiB a raw buffer's offsets span: then register staging (MODE 0)
+  const bool has_xf = op->scale != nullptr || op->act != GODE_ACT_NONE;
+  const bool glds = !has_xf && c.src_bytes != 0 && c.w_bytes != 0;
+  c.kernel = glds ? (P.tapskip ? IGEMM_K_FAST_DMA_LIVE : IGEMM_K_FAST_DMA) : (has_xf ? IGEMM_K_FAST_REG_XF : IGEMM_K_FAST_REG);
+  if (P.ksplit > 1) c.reduce = G.Ncols % 4 == 0 && igemm_ptr16(op->work) && igemm_ptr16(op->out) ? IGEMM_REDUCE_VEC : IGEMM_REDUCE_SCALAR;
+  return c;
+}
+
+// Plan and cell of an op as gode_igemm sees it (the argument checks in its order); gs: the gathered operand's strides.
+static int igemm_plan_launch(const gode_igemm_op* op, IgemmPlan* P, int64_t gs[5], IgemmLaunchCell* cell) {
+  if (!op || !op->src || !op->wpack || !op->out) return GODE_E_ARG;
+  const int rc = igemm_make_plan(op, P);
+  if (rc) return rc;
+  *cell = igemm_launch_cell(op, *P, igemm_gather_span(op, P->G, gs));
+  return cell->rc;
 }

@@ -65,7 +65,11 @@ typedef struct gode_igemm_op {
   const float* shift;
   float* stats;
   int64_t gs[5];
-  float* work; /* nullable; >= gode_igemm_work_size floats enables split-K for launches that would not fill the GPU */
+  /* nullable; >= gode_igemm_work_size(op) floats.  When that size is > 0 the launch plan splits K (it is made from the
+   * geometry alone: it sees no pointer) and the split launch needs `work`, and src, scale and shift on 16-byte boundaries.
+   * Without either the op is served all the same, unsplit on the generic kernel (slower): out, the statistics layout and
+   * gode_igemm_stats_rows / _rows0 stay those of the plan. */
+  float* work;
   /* groups == 2 (FPROP with stats only, N even): the batch is two image groups [0, N/2) and [N/2, N) whose BatchNorm
    * partial statistics must stay separate -- one discriminator pass over [real; fake] keeps the per-pass batch
    * statistics of the reference's two calls (mnist_moco_ode.py:119-124,137-143).  The partial-statistics rows of group 0
@@ -89,7 +93,7 @@ typedef struct gode_igemm_op {
   int32_t border;
 } gode_igemm_op;
 int gode_igemm(const gode_igemm_op* op, void* stream);
-/* floats of workspace the op can use for split-K (0: it never splits).  Deterministic from the op's geometry. */
+/* floats of workspace the op needs to split K (0: it never splits).  Deterministic from the op's geometry. */
 int64_t gode_igemm_work_size(const gode_igemm_op* op);
 /* number of partial-stats rows gode_igemm writes for this op (host-side, no GPU work) */
 int gode_igemm_stats_rows(const gode_igemm_op* op);
@@ -104,8 +108,22 @@ int gode_igemm_stats_segments(const gode_igemm_op* op, int32_t split_images, int
  * modelled path.  Host-side, no GPU work: such a caller compares one launch over the whole batch with two over its parts. */
 double gode_igemm_model_cycles(const gode_igemm_op* op);
 /* The kernel family the launch plan gives the op: 0 tiled GEMM, 1 LDS-patch FPROP, 2 pointwise (thin-output streaming),
- * 3 tiny-K, 4 dot.  Host-side, no GPU work; unaligned pointers can still take a launch from its family to the tiled GEMM. */
+ * 3 tiny-K, 4 dot.  Host-side, no GPU work; unaligned pointers can still take a launch from its family to the tiled GEMM
+ * (src / scale / shift off a 16-byte boundary: pointwise and dot; out: tiny-K; the LDS-patch kernel reads scalars and
+ * stays), and there from the vector kernels to the scalar generic one (a plan that splits K then runs unsplit: see
+ * gode_igemm_op.work). */
 int gode_igemm_family(const gode_igemm_op* op);
+/* The launch cell: what gode_igemm(op) launches, decided by the function the launch itself dispatches on.  Returns what
+ * gode_igemm would return before launching anything (0, GODE_E_ARG, GODE_E_SHAPE); on 0, cell[8] =
+ *   {kernel, tile, reduce, ksplit, xcd_mode, table, interleave, tapskip}
+ * kernel: -1 nothing (empty op); 0 FAST LDS-DMA, 1 FAST LDS-DMA over live taps, 2 FAST register-staged with the transform on
+ *   load, 3 FAST register-staged plain (an operand beyond 2 GiB), 4 generic float4, 5 generic scalar, 6 / 7 / 8 pointwise
+ *   (one tap and one column / one tap / several taps), 9 tiny-K, 10 dot, 11 LDS-patch.
+ * tile: the tile id of a tiled launch (kernels 0-5), else 0.  reduce: the split-K finish, 0 none, 1 float4, 2 scalar
+ *   (with ksplit == 1 on kernels 4 / 5: a plan that splits K served unsplit, the finish run over that one slab).
+ * table: 0 plain, 1 border-split, 2 border-split phase-interleaved (`interleave` sub-phases per entry).  xcd_mode: the
+ * FAST kernels' grid order.  Host-side, no GPU work; the op's pointers are looked at (null, alignment), never through. */
+int gode_igemm_launch_cell(const gode_igemm_op* op, int32_t* cell);
 /* Share of the op's multiply-adds that gather zero padding at the tensor's borders: 1 - (sum of M*K over the border-split
  * table) / (sum of M*K over the plain table); 0 when the op has no border-split table (gode_igemm_op.border).  Host-side. */
 double gode_igemm_dead_taps(const gode_igemm_op* op);

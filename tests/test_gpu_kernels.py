@@ -152,10 +152,11 @@ def test_igemm_fprop_dgrad_wgrad(case):
     assert rel_err(dw.cpu(), wr.grad) < 2e-4
 
 
-@pytest.mark.parametrize("tile", [1, 2, 3, 4])
+@pytest.mark.parametrize("tile", [1, 2, 3, 4, 6])
 def test_igemm_all_tiles_with_fused_bn_relu(tile):
-    """Every tile configuration, with the previous layer's BatchNorm+ReLU fused into the operand load and zero
-    padding applied AFTER the transform."""
+    """Every tile configuration of the GENERIC kernel (24 channels are not whole 32-deep slabs: this geometry never reaches the
+    FAST kernels -- tests/test_gpu_igemm_cells.py does), with the previous layer's BatchNorm+ReLU fused into the operand load
+    and zero padding applied AFTER the transform."""
     N, Ci, Co, hw = 5, 24, 40, 9
     g = make_geom(N, Ci, Co, (1, hw, hw), (1, 5, 5), (1, 3, 3), (1, 2, 2), (0, 1, 1))
     gen = torch.Generator().manual_seed(tile)
