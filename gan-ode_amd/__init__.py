@@ -5,9 +5,9 @@ Python host side that mirrors the reference's class surface.  Importing the pack
 anything does, and there is no fallback path.
 """
 from . import _lib
-from .modules import (CategoricalVideoDiscriminator, CDEFunc, Noise, ODEFunc, PatchImageDiscriminator, SDEFunc, VideoDiscriminator, VideoGenerator,
+from .modules import (CategoricalVideoDiscriminator, CDEFunc, Noise, ODEFunc, ODEFuncTanh, PatchImageDiscriminator, SDEFunc, VideoDiscriminator, VideoGenerator,
                       VideoGeneratorCDE, VideoGeneratorGRU, VideoGeneratorMNIST, VideoGeneratorMNISTODE, VideoGeneratorMNISTODERNN,
-                      VideoGeneratorSDE)
+                      VideoGeneratorMNISTODETanh, VideoGeneratorMNISTTanh, VideoGeneratorSDE, VideoGeneratorTanh)
 from .ode_training import GANODETrainer
 from .gres import ConditionalNorm, GResBlock, SpectralNorm
 from . import dcgan, fcgan
@@ -17,7 +17,7 @@ from .train import (FusedAdam, GanTrainer, WassersteinDiscriminatorLoss, Wassers
                     limit_host_threads, train_step, unit_grad, wasserstein_discriminator_loss,
                     wasserstein_discriminator_loss_halves, wasserstein_generator_loss, wasserstein_generator_loss_pair)
 
-__all__ = ["Noise", "ODEFunc", "PatchImageDiscriminator", "VideoDiscriminator", "CategoricalVideoDiscriminator", "VideoGenerator",
+__all__ = ["Noise", "ODEFunc", "ODEFuncTanh", "VideoGeneratorTanh", "VideoGeneratorMNISTTanh", "VideoGeneratorMNISTODETanh", "PatchImageDiscriminator", "VideoDiscriminator", "CategoricalVideoDiscriminator", "VideoGenerator",
            "VideoGeneratorMNIST", "VideoGeneratorMNISTODE", "VideoGeneratorMNISTODERNN", "SDEFunc", "VideoGeneratorSDE", "CDEFunc", "VideoGeneratorCDE", "VideoGeneratorGRU", "FusedAdam", "GanTrainer", "GANODETrainer", "SpectralNorm", "ConditionalNorm", "GResBlock", "bce_with_logits_const",
            "bce_with_logits_pair", "bce_with_logits_halves", "categorical_cross_entropy", "bce_ce_head", "bce_ce_head_pair",
            "bce_ce_head_halves", "bce_ce_heads", "WassersteinGeneratorLoss", "WassersteinDiscriminatorLoss",

@@ -38,6 +38,10 @@ GRU_NPARAM = 1632
 SN_BWD_BLOCKS = 64
 # `method` of gode_ode_fwd_op / gode_ode_bwd_op (include/gode.h), by torchdiffeq's solver name
 ODE_METHODS = {"rk4": 0, "dopri5": 1, "euler": 2, "midpoint": 3}
+# `rhs` of the same ops: the right-hand side the fixed-grid kernels integrate.  "mlp": f(y) = W2 tanh(W1 y + b1) + b2
+# (models/mocogan_ode.py's ODEFunc); "tanh": f(y) = tanh(W1 y + b1) (models/mocogan_mnist.py's), W2 / b2 unused
+ODE_RHS = {"mlp": 0, "tanh": 1}
+ODE_RHS_TANH_NPARAM = 2400     # rhs 1: the gradient block ends behind b1 (the first 2400 floats of the ODE_NPARAM layout)
 
 
 def ode_method_code(name):
@@ -47,6 +51,11 @@ def ode_method_code(name):
     except (KeyError, TypeError):
         raise NotImplementedError(f"ode_method {name!r}: libgode implements " + ", ".join(repr(k) for k in ODE_METHODS)
                                   + " ('rk4' is the reference's call)") from None
+
+
+def ode_rhs_code(name):
+    """Right-hand side name -> the ops' `rhs` code."""
+    return ODE_RHS[name]
 
 
 class ConvGeom(C.Structure):
@@ -100,7 +109,7 @@ class OdeParams(C.Structure):
 class OdeFwdOp(_Op):
     _fields_ = [("p", OdeParams), ("x", ptr), ("content", ptr), ("dt", ptr), ("sel_t", ptr), ("z", ptr),
                 ("traj", ptr), ("N", i32), ("T", i32), ("substeps", i32), ("prenet", i32), ("zcols", i32), ("G", i32),
-                ("grid_dt", ptr), ("emit_at", ptr), ("emit_w", ptr), ("method", i32), ("pad2_", i32), ("rtol", f32),
+                ("grid_dt", ptr), ("emit_at", ptr), ("emit_w", ptr), ("method", i32), ("rhs", i32), ("rtol", f32),
                 ("atol", f32), ("tout", ptr), ("nsteps", ptr), ("sync", ptr)]
     KIND, FN = OP_ODE_FWD, "gode_ode_fwd"
 
@@ -109,7 +118,7 @@ class OdeBwdOp(_Op):
     _fields_ = [("p", OdeParams), ("x", ptr), ("traj", ptr), ("dt", ptr), ("sel_t", ptr), ("gz", ptr),
                 ("work", ptr), ("grads", ptr), ("N", i32), ("T", i32), ("substeps", i32), ("prenet", i32),
                 ("accumulate", i32), ("zcols", i32), ("bstep_off", ptr), ("bstep_dt", ptr), ("method", i32),
-                ("pad_", i32), ("rtol", f32), ("atol", f32), ("tout", ptr), ("nsteps", ptr), ("sync", ptr)]
+                ("rhs", i32), ("rtol", f32), ("atol", f32), ("tout", ptr), ("nsteps", ptr), ("sync", ptr)]
     KIND, FN = OP_ODE_BWD, "gode_ode_bwd"
 
 

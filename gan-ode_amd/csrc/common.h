@@ -76,9 +76,10 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
 // ---- fixed-order sums of per-workgroup gradient rows (latent_reduce.hip) ---------------------------------------------
 // grads[k - grads_bias] (+)= sum over the nblk rows of work[.][nparam], k in [first, nparam), rows in order.  More than
 // chunk_threshold rows: chunks of `chunk` consecutive rows are first summed in place into their first row, then every
-// chunk-th row is added (both levels in row order).  counts != NULL: nothing is touched when counts[0] < 0.
+// chunk-th row is added (both levels in row order).  counts != NULL: nothing is touched when counts[0] < 0.  ld != 0: the rows
+// are ld >= nparam floats apart (columns from nparam on are then neither read nor written).
 int gode_reduce_rows(float* work, float* grads, int nblk, int nparam, int first, int grads_bias, int accumulate,
-                     const int32_t* counts, int chunk_threshold, int chunk, hipStream_t st);
+                     const int32_t* counts, int chunk_threshold, int chunk, hipStream_t st, int ld = 0);
 
 // Multi-solve launches (up to GODE_MAX_JOBS ops): the ops that share a grads pointer form a group, in array order.
 #define GODE_MAX_JOBS 8

@@ -3,13 +3,14 @@
 #include "common.h"
 
 // second level: grads[k - grads_bias] (+)= sum over the rows b = 0, stride, 2*stride, ... of work[b][k].  Entries below
-// `first` are not touched (no pre-net: that block of grads is then not the caller's memory).
+// `first` are not touched (no pre-net: that block of grads is then not the caller's memory), nor are entries from `nparam`
+// on; rows of `work` are `ld` >= nparam floats apart.
 __global__ void __launch_bounds__(256) latent_reduce_kernel(const float* work, float* grads, int nblk, int stride, int nparam, int first,
-                                                            int grads_bias, int accumulate, const int32_t* counts) {
+                                                            int grads_bias, int accumulate, const int32_t* counts, int ld) {
   const int k = first + blockIdx.x * 256 + threadIdx.x;
   if (k >= nparam || (counts && counts[0] < 0)) return;
   float s = 0.f;
-  for (int b = 0; b < nblk; b += stride) s += work[(int64_t)b * nparam + k];
+  for (int b = 0; b < nblk; b += stride) s += work[(int64_t)b * ld + k];
   grads[k - grads_bias] = accumulate ? grads[k - grads_bias] + s : s;
 }
 // Many workgroups (N >> 1024): a first level sums chunks of `chunk` consecutive partial rows in parallel, in place (the
@@ -17,28 +18,29 @@ __global__ void __launch_bounds__(256) latent_reduce_kernel(const float* work, f
 // the kernel above then adds every chunk-th row.  Fixed order at both levels.  (A single level left 11 workgroups
 // walking 65,536 rows each: 25 of the 28 ms of the N = 2^20 rk4 adjoint.)
 __global__ void __launch_bounds__(256) latent_reduce_chunks_kernel(float* work, int nblk, int chunk, int nparam, int first,
-                                                                   const int32_t* counts) {
+                                                                   const int32_t* counts, int ld) {
   const int k = first + blockIdx.x * 256 + threadIdx.x;
   if (k >= nparam || (counts && counts[0] < 0)) return;
   const int b0 = blockIdx.y * chunk, b1 = b0 + chunk < nblk ? b0 + chunk : nblk;
   float s = 0.f;
 #pragma unroll 8
-  for (int b = b0; b < b1; ++b) s += work[(int64_t)b * nparam + k];
-  work[(int64_t)b0 * nparam + k] = s;
+  for (int b = b0; b < b1; ++b) s += work[(int64_t)b * ld + k];
+  work[(int64_t)b0 * ld + k] = s;
 }
 
 int gode_reduce_rows(float* work, float* grads, int nblk, int nparam, int first, int grads_bias, int accumulate,
-                     const int32_t* counts, int chunk_threshold, int chunk, hipStream_t st) {
+                     const int32_t* counts, int chunk_threshold, int chunk, hipStream_t st, int ld) {
+  if (ld == 0) ld = nparam;
   const int gx = (nparam - first + 255) / 256;
   int stride = 1;
   if (nblk > chunk_threshold) {
     stride = chunk;
     hipLaunchKernelGGL(latent_reduce_chunks_kernel, dim3(gx, (nblk + stride - 1) / stride), dim3(256), 0, st, work, nblk, stride, nparam,
-                       first, counts);
+                       first, counts, ld);
     GODE_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(latent_reduce_kernel, dim3(gx), dim3(256), 0, st, work, grads, nblk, stride, nparam, first, grads_bias, accumulate,
-                     counts);
+                     counts, ld);
   GODE_LAUNCH_CHECK();
   return 0;
 }

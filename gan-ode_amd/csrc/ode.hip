@@ -98,14 +98,18 @@ int gode_launch_ode_bwd_valu(const gode_ode_bwd_op* op, hipStream_t st);
 // MFMA-chain kernels of this file (16 trajectories per wave: 67 vs 43 TFLOP/s forward at N = 2^20).  Default: VALU up
 // to 8192 trajectories, MFMA above; GODE_ODE_MFMA=1 / =0 forces one (the A/B of profiles/r02_ode_kernels.txt).
 // The MFMA-chain kernels step with Kutta 3/8 only: methods 2 (euler) and 3 (midpoint) run on the VALU kernels at every
-// N, whatever GODE_ODE_MFMA says.
-static bool ode_use_mfma(int N, int method) {
-  if (method == 2 || method == 3) return false;
+// N, whatever GODE_ODE_MFMA says, and so does rhs 1 (f(y) = tanh(W1 y + b1)): the MFMA-chain kernels are two-layer rk4 only.
+static bool ode_use_mfma(int N, int method, int rhs) {
+  if (method == 2 || method == 3 || rhs != 0) return false;
   static const char* e = getenv("GODE_ODE_MFMA");
   if (e) return atoi(e) != 0;
   return N > 8192;
 }
+// rhs: 0 or 1, and 1 not with the adaptive solver (method 1: odernn_valu.hip integrates u = W1 y + b1, two-layer algebra)
+static bool ode_rhs_ok(int rhs, int method) { return rhs == 0 || (rhs == 1 && method != 1); }
+
 extern "C" int gode_ode_fwd(const gode_ode_fwd_op* op, void* stream) {
+  if (op && !ode_rhs_ok(op->rhs, op->method)) return GODE_E_ARG;
   if (op && op->method == 1) {
     if (!op->x || !op->z || !op->tout || op->N <= 0 || op->T < 1 || !(op->rtol > 0.f) || !(op->atol >= 0.f)) return GODE_E_ARG;
     if (op->zcols < 68 || op->zcols % 4 != 0) return GODE_E_ARG;
@@ -117,9 +121,9 @@ extern "C" int gode_ode_fwd(const gode_ode_fwd_op* op, void* stream) {
   if (!op || !op->x || !op->z || !op->dt || op->N <= 0 || op->T < 1 || op->substeps < 1) return GODE_E_ARG;
   if (op->grid_dt && (!op->emit_at || !op->emit_w || op->G < 1)) return GODE_E_ARG;
   if (op->zcols < 68 || op->zcols % 4 != 0) return GODE_E_ARG;
-  if (!op->p.W1 || !op->p.b1 || !op->p.W2 || !op->p.b2) return GODE_E_ARG;
+  if (!op->p.W1 || !op->p.b1 || (op->rhs == 0 && (!op->p.W2 || !op->p.b2))) return GODE_E_ARG;
   if (op->prenet && (!op->p.Wa || !op->p.ba || !op->p.Wb || !op->p.bb)) return GODE_E_ARG;
-  if (!ode_use_mfma(op->N, op->method)) return gode_launch_ode_fwd_valu(op, (hipStream_t)stream);
+  if (!ode_use_mfma(op->N, op->method, op->rhs)) return gode_launch_ode_fwd_valu(op, (hipStream_t)stream);
   hipLaunchKernelGGL(ode_fwd_kernel, dim3((op->N + 15) / 16), dim3(op->content ? 256 : 64), 0, (hipStream_t)stream, *op);
   GODE_LAUNCH_CHECK();
   return 0;
@@ -264,15 +268,15 @@ extern "C" int gode_ode_bwd(const gode_ode_bwd_op* op, void* stream) {
   const bool adaptive = op && op->method == 1 && op->substeps == 0;
   if (!op || !op->traj || !op->gz || !op->work || !op->grads || op->N <= 0 || op->T < 1) return GODE_E_ARG;
   if (adaptive ? (!op->tout || !(op->rtol > 0.f) || !(op->atol >= 0.f)) : (!op->dt || op->substeps < 1)) return GODE_E_ARG;
-  if (op->method < 0 || op->method > 3) return GODE_E_ARG;
+  if (op->method < 0 || op->method > 3 || !ode_rhs_ok(op->rhs, op->method)) return GODE_E_ARG;
   if (op->zcols < 16 || op->zcols % 4 != 0) return GODE_E_ARG;
-  if (!op->p.W1 || !op->p.b1 || !op->p.W2 || !op->p.b2) return GODE_E_ARG;
+  if (!op->p.W1 || !op->p.b1 || (op->rhs == 0 && (!op->p.W2 || !op->p.b2))) return GODE_E_ARG;
   if (op->prenet && (!op->x || !op->p.Wa || !op->p.ba || !op->p.Wb || !op->p.bb)) return GODE_E_ARG;
   if ((op->bstep_off == nullptr) != (op->bstep_dt == nullptr)) return GODE_E_ARG;
   const int nblk = (op->N + 15) / 16;
   hipStream_t st = (hipStream_t)stream;
   if (adaptive) return gode_ode_bwd_multi(op, 1, stream);      // odernn_valu.hip (reduces into grads itself)
-  if (!ode_use_mfma(op->N, op->method)) {
+  if (!ode_use_mfma(op->N, op->method, op->rhs)) {
     const int rc = gode_launch_ode_bwd_valu(op, st);
     if (rc) return rc;
   } else {
@@ -283,7 +287,9 @@ extern "C" int gode_ode_bwd(const gode_ode_bwd_op* op, void* stream) {
 }
 
 // rows of `work` -> grads.  Without the pre-net only the ODEFunc block [OFF_W1, NPARAM) exists (`grads` may then point 2128
-// floats before a caller-owned region that holds just that block); two levels above 128 rows
+// floats before a caller-owned region that holds just that block); two levels above 128 rows.  rhs 1: the block ends at
+// OFF_W2 (neither level touches a column from there on, of `work` or of `grads`); the rows keep their stride
 static int ode_bwd_reduce(const gode_ode_bwd_op* op, int nblk, hipStream_t st) {
-  return gode_reduce_rows(op->work, op->grads, nblk, GODE_ODE_NPARAM, op->prenet ? 0 : OFF_W1, 0, op->accumulate, nullptr, 128, 64, st);
+  return gode_reduce_rows(op->work, op->grads, nblk, op->rhs ? OFF_W2 : GODE_ODE_NPARAM, op->prenet ? 0 : OFF_W1, 0, op->accumulate, nullptr,
+                          128, 64, st, GODE_ODE_NPARAM);
 }

@@ -25,33 +25,47 @@
 // Kutta 3/8), METHOD_EULER, METHOD_MIDPOINT.  The method picks ONE step function per kernel (`step` below) at compile
 // time; every grid mode -- output times with `substeps`, the grid_dt / emit_at / emit_w grid, the adjoint's bstep_off /
 // bstep_dt -- calls that function, and nothing inside a time loop branches on the method.
+//
+// The right-hand side is a second compile-time axis (the `rhs` codes of gode.h, RHS_* of valu_common.h): RHS_MLP is
+// f(y) = W2 tanh(W1 y + b1) + b2 (models/mocogan_ode.py:6-17); RHS_TANH is f(y) = tanh(W1 y + b1), the one-layer ODEFunc
+// of models/mocogan_mnist.py:6-16, its weight in the block's W1 slot and its bias in the b1 slot.  An RHS_TANH kernel holds
+// no W2 arrangement and no W2 / b2 accumulator, never dereferences p.W2 / p.b2, and its parameter block -- the LDS copy,
+// the per-wave gradient images, the part of a `work` row it writes -- ends at OFF_W2.
 #include <type_traits>
 #include "common.h"
 #include "ode_common.h"
 #include "valu_common.h"
 
 enum { METHOD_RK4 = 0, METHOD_EULER = 2, METHOD_MIDPOINT = 3 };
+struct NoW16 {};                         // stands where an RHS_TANH kernel has no second matrix
+template <int RHS> using W16If2 = std::conditional_t<RHS == RHS_MLP, W16, NoW16>;
+template <int RHS> constexpr int rhs_nparam = RHS == RHS_MLP ? GODE_ODE_NPARAM : OFF_W2;
 
-template <int METHOD>
+template <int METHOD, int RHS>
 __global__ void __launch_bounds__(256) ode_fwd_valu_kernel(const gode_ode_fwd_op a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, tl = lane >> 4;
   const int n0 = blockIdx.x * 16, n = n0 + wave * 4 + tl;
   const bool valid = n < a.N;
   const int T = a.T;
-  __shared__ float P[GODE_ODE_NPARAM];
+  __shared__ float P[rhs_nparam<RHS>];
   float y = valid ? a.x[n * 16 + i] : 0.f;
-  stage_ode_params<256>(a.p, a.prenet, P);
+  stage_ode_params<256, RHS>(a.p, a.prenet, P);
   if (a.content) broadcast_content(a.content, a.z, a.sel_t, a.N, T, a.zcols, n0, 16, threadIdx.x, 256);
 
   int src[16];
   probe_sources(i, src);
   if (a.prenet) y = prenet_fwd(P, y, i, src);
-  W16 w1, w2;
+  W16 w1;
+  W16If2<RHS> w2;
   load_rows(w1, P + OFF_W1, 16, 0, 0, i, src);
-  load_rows(w2, P + OFF_W2, 16, 0, 0, i, src);
-  const float b1 = P[OFF_B1 + i], b2 = P[OFF_B2 + i];
-  auto f = [&](float yy) { return mv16(w2, fast_tanh(mv16(w1, yy, b1)), b2); };
+  if constexpr (RHS == RHS_MLP) load_rows(w2, P + OFF_W2, 16, 0, 0, i, src);
+  const float b1 = P[OFF_B1 + i], b2 = RHS == RHS_MLP ? P[OFF_B2 + i] : 0.f;
+  auto f = [&](float yy) {
+    const float h = fast_tanh(mv16(w1, yy, b1));
+    if constexpr (RHS == RHS_MLP) return mv16(w2, h, b2);
+    else return h;
+  };
 
   const int tsel = (a.sel_t && valid) ? a.sel_t[n] : -1;
   auto emit = [&](int t) {
@@ -100,9 +114,10 @@ __global__ void __launch_bounds__(256) ode_fwd_valu_kernel(const gode_ode_fwd_op
 
 // ---------------------------------------------------------------------------------------------------------------
 // adjoint backward
-template <int METHOD>
+template <int METHOD, int RHS>
 __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op a) {
-  __shared__ float R[4][GODE_ODE_NPARAM];     // per-wave image of the gradient vector (combined once, at the end)
+  constexpr int NPAR = rhs_nparam<RHS>;       // the block this kernel stages, accumulates and writes out
+  __shared__ float R[4][NPAR];                // per-wave image of the gradient vector (combined once, at the end)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, tl = lane >> 4;
   const int n0 = blockIdx.x * 16, n = n0 + wave * 4 + tl;
@@ -115,19 +130,23 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
   long long st1 = 0, st2 = 0, st3 = 0;
 #endif
 
-  __shared__ float P[GODE_ODE_NPARAM];
-  stage_ode_params<256>(a.p, a.prenet, P);
+  __shared__ float P[NPAR];
+  stage_ode_params<256, RHS>(a.p, a.prenet, P);
   int src[16];
   probe_sources(i, src);
-  W16 w1, w2, w1t, w2t, gW1, gW2;
+  W16 w1, w1t, gW1;
+  W16If2<RHS> w2, w2t, gW2;
   load_rows(w1, P + OFF_W1, 16, 0, 0, i, src);
-  load_rows(w2, P + OFF_W2, 16, 0, 0, i, src);
+  if constexpr (RHS == RHS_MLP) load_rows(w2, P + OFF_W2, 16, 0, 0, i, src);
   load_cols(w1t, P + OFF_W1, 16, 0, 0, i, src);
-  load_cols(w2t, P + OFF_W2, 16, 0, 0, i, src);
+  if constexpr (RHS == RHS_MLP) load_cols(w2t, P + OFF_W2, 16, 0, 0, i, src);
 #pragma unroll
-  for (int r = 0; r < 16; ++r) { gW1.w[r] = 0.f; gW2.w[r] = 0.f; }
-  const float b1 = P[OFF_B1 + i], b2 = P[OFF_B2 + i];
-  float gb1 = 0.f, gb2 = 0.f;
+  for (int r = 0; r < 16; ++r) {
+    gW1.w[r] = 0.f;
+    if constexpr (RHS == RHS_MLP) gW2.w[r] = 0.f;
+  }
+  const float b1 = P[OFF_B1 + i], b2 = RHS == RHS_MLP ? P[OFF_B2 + i] : 0.f;
+  float gb1 = 0.f, gb2 = 0.f;             // (gb2: RHS_MLP only)
 
   const int tsel = (a.sel_t && valid) ? a.sel_t[n] : -1;
   auto upstream = [&](int t) -> float {
@@ -141,16 +160,28 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
   // (weighted = std::false_type: a stage of weight 0, whose outer products are not formed)
   auto stage = [&](float ys, float as, float c, auto weighted) {
     const float h = fast_tanh(mv16(w1, ys, b1));
-    const float fv = mv16(w2, h, b2);
-    const float v = mv16(w2t, as, 0.f);
-    const float du = v * (1.f - h * h);
-    ka = mv16(w1t, du, 0.f);
-    ky = -fv;
-    if constexpr (decltype(weighted)::value) {
-      const float ca = c * as, cdu = c * du;
-      gb2 += ca; gb1 += cdu;
-      outer16(gW2, ca, h);
-      outer16(gW1, cdu, ys);
+    if constexpr (RHS == RHS_MLP) {
+      const float fv = mv16(w2, h, b2);
+      const float v = mv16(w2t, as, 0.f);
+      const float du = v * (1.f - h * h);
+      ka = mv16(w1t, du, 0.f);
+      ky = -fv;
+      if constexpr (decltype(weighted)::value) {
+        const float ca = c * as, cdu = c * du;
+        gb2 += ca; gb1 += cdu;
+        outer16(gW2, ca, h);
+        outer16(gW1, cdu, ys);
+      }
+    } else {
+      // f = h: a^T df/dy = W1^T (a (1 - h^2)), a^T df/db1 = a (1 - h^2), a^T df/dW1 = (a (1 - h^2)) ys^T
+      const float du = as * (1.f - h * h);
+      ka = mv16(w1t, du, 0.f);
+      ky = -h;
+      if constexpr (decltype(weighted)::value) {
+        const float cdu = c * du;
+        gb1 += cdu;
+        outer16(gW1, cdu, ys);
+      }
     }
   };
   // (y, adj)(t) -> (y, adj)(t - dt); the parameter integrals advance with the same tableau's b-weights
@@ -224,9 +255,9 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
     if (tl == 0) R[wave][off + i] = s;
   };
   put_matrix(gW1, OFF_W1, 16, 0, 0);
-  put_matrix(gW2, OFF_W2, 16, 0, 0);
+  if constexpr (RHS == RHS_MLP) put_matrix(gW2, OFF_W2, 16, 0, 0);
   put_vector(gb1, OFF_B1);
-  put_vector(gb2, OFF_B2);
+  if constexpr (RHS == RHS_MLP) put_vector(gb2, OFF_B2);
 
   // ---- pre-net backward; adj = dL/d(pre-net output)
   if (a.prenet) {
@@ -260,7 +291,7 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
     }
   }
   __syncthreads();
-  for (int k = threadIdx.x; k < GODE_ODE_NPARAM; k += 256)
+  for (int k = threadIdx.x; k < NPAR; k += 256)     // (RHS_TANH: floats [OFF_W2, GODE_ODE_NPARAM) of the row stay unwritten)
     part[k] = (k < OFF_W1 && !a.prenet) ? 0.f : (R[0][k] + R[1][k]) + (R[2][k] + R[3][k]);
 #ifdef GODE_ODE_STAMPS
   st3 = __builtin_amdgcn_s_memtime();
@@ -273,20 +304,31 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
 }
 
 // op->method picks the instantiation: 2 = euler, 3 = midpoint, anything else the rk4 kernels (0, and the adjoint's
-// method 1 with substeps > 0: a dopri5 forward with a fixed Kutta-3/8 adjoint); the callers have checked the range
+// method 1 with substeps > 0: a dopri5 forward with a fixed Kutta-3/8 adjoint); op->rhs: 1 = RHS_TANH, else RHS_MLP.  The
+// callers have checked both ranges.
+template <int RHS>
+static void launch_fwd(const gode_ode_fwd_op* op, dim3 grid, dim3 block, hipStream_t st) {
+  if (op->method == METHOD_EULER) hipLaunchKernelGGL((ode_fwd_valu_kernel<METHOD_EULER, RHS>), grid, block, 0, st, *op);
+  else if (op->method == METHOD_MIDPOINT) hipLaunchKernelGGL((ode_fwd_valu_kernel<METHOD_MIDPOINT, RHS>), grid, block, 0, st, *op);
+  else hipLaunchKernelGGL((ode_fwd_valu_kernel<METHOD_RK4, RHS>), grid, block, 0, st, *op);
+}
+template <int RHS>
+static void launch_bwd(const gode_ode_bwd_op* op, dim3 grid, dim3 block, hipStream_t st) {
+  if (op->method == METHOD_EULER) hipLaunchKernelGGL((ode_bwd_valu_kernel<METHOD_EULER, RHS>), grid, block, 0, st, *op);
+  else if (op->method == METHOD_MIDPOINT) hipLaunchKernelGGL((ode_bwd_valu_kernel<METHOD_MIDPOINT, RHS>), grid, block, 0, st, *op);
+  else hipLaunchKernelGGL((ode_bwd_valu_kernel<METHOD_RK4, RHS>), grid, block, 0, st, *op);
+}
 int gode_launch_ode_fwd_valu(const gode_ode_fwd_op* op, hipStream_t st) {
   const dim3 grid((op->N + 15) / 16), block(256);
-  if (op->method == METHOD_EULER) hipLaunchKernelGGL(ode_fwd_valu_kernel<METHOD_EULER>, grid, block, 0, st, *op);
-  else if (op->method == METHOD_MIDPOINT) hipLaunchKernelGGL(ode_fwd_valu_kernel<METHOD_MIDPOINT>, grid, block, 0, st, *op);
-  else hipLaunchKernelGGL(ode_fwd_valu_kernel<METHOD_RK4>, grid, block, 0, st, *op);
+  if (op->rhs == RHS_TANH) launch_fwd<RHS_TANH>(op, grid, block, st);
+  else launch_fwd<RHS_MLP>(op, grid, block, st);
   GODE_LAUNCH_CHECK();
   return 0;
 }
 int gode_launch_ode_bwd_valu(const gode_ode_bwd_op* op, hipStream_t st) {
   const dim3 grid((op->N + 15) / 16), block(256);
-  if (op->method == METHOD_EULER) hipLaunchKernelGGL(ode_bwd_valu_kernel<METHOD_EULER>, grid, block, 0, st, *op);
-  else if (op->method == METHOD_MIDPOINT) hipLaunchKernelGGL(ode_bwd_valu_kernel<METHOD_MIDPOINT>, grid, block, 0, st, *op);
-  else hipLaunchKernelGGL(ode_bwd_valu_kernel<METHOD_RK4>, grid, block, 0, st, *op);
+  if (op->rhs == RHS_TANH) launch_bwd<RHS_TANH>(op, grid, block, st);
+  else launch_bwd<RHS_MLP>(op, grid, block, st);
   GODE_LAUNCH_CHECK();
   return 0;
 }

@@ -1071,8 +1071,8 @@ __global__ void __launch_bounds__(RV_THREADS) ode_dopri5_bwd_valu_kernel(const O
 int gode_launch_ode_dopri5(const gode_ode_fwd_op* op, hipStream_t st);          // odernn.hip (MFMA fallback)
 int gode_launch_ode_dopri5_bwd_mfma(const gode_ode_bwd_op* op, hipStream_t st); // ode.hip (MFMA fallback incl. its reduce)
 
-static bool ode5_fwd_ok(const gode_ode_fwd_op* op) {
-  if (!op || op->method != 1 || !op->x || !op->z || !op->tout || op->N <= 0 || op->T < 1 || !(op->rtol > 0.f) || !(op->atol >= 0.f)) return false;
+static bool ode5_fwd_ok(const gode_ode_fwd_op* op) {     // (rhs: the adaptive kernels integrate the two-layer function only)
+  if (!op || op->method != 1 || op->rhs != 0 || !op->x || !op->z || !op->tout || op->N <= 0 || op->T < 1 || !(op->rtol > 0.f) || !(op->atol >= 0.f)) return false;
   if (op->zcols < 68 || op->zcols % 4 != 0) return false;
   if (!op->p.W1 || !op->p.b1 || !op->p.W2 || !op->p.b2) return false;
   if (op->prenet && (!op->p.Wa || !op->p.ba || !op->p.Wb || !op->p.bb)) return false;
@@ -1080,7 +1080,7 @@ static bool ode5_fwd_ok(const gode_ode_fwd_op* op) {
 }
 
 static bool ode5_bwd_ok(const gode_ode_bwd_op* op) {
-  if (!op || op->method != 1 || op->substeps != 0 || !op->traj || !op->gz || !op->work || !op->grads || !op->tout || op->N <= 0 || op->T < 1 ||
+  if (!op || op->method != 1 || op->rhs != 0 || op->substeps != 0 || !op->traj || !op->gz || !op->work || !op->grads || !op->tout || op->N <= 0 || op->T < 1 ||
       !(op->rtol > 0.f) || !(op->atol >= 0.f) || op->zcols < 16 || op->zcols % 4 != 0)
     return false;
   if (!op->p.W1 || !op->p.b1 || !op->p.W2 || !op->p.b2) return false;

@@ -149,7 +149,10 @@ __device__ __forceinline__ float sum_traj(float v) {
 // All 2,672 parameters (10.7 KB) go to LDS with ONE round of coalesced loads before anything else: the per-lane weight
 // arrangement is then gathered from LDS.  (Gathering it from global memory cost the config-size adjoint launch more
 // than its whole time loop: twelve dependent batches of L2-missing loads in the pre-net backward, 60k of 126k cycles.)
-template <int THREADS>
+// RHS: the `rhs` code of gode.h the calling kernel is compiled for.  RHS_TANH (f(y) = tanh(W1 y + b1)): p.W2 / p.b2 are not
+// dereferenced and the block ends behind b1 (P holds OFF_W2 floats).
+enum { RHS_MLP = 0, RHS_TANH = 1 };
+template <int THREADS, int RHS = RHS_MLP>
 __device__ __forceinline__ void stage_ode_params(const gode_ode_params& p, int prenet, float* P) {
   const int t = threadIdx.x;
   if (prenet) {
@@ -158,8 +161,13 @@ __device__ __forceinline__ void stage_ode_params(const gode_ode_params& p, int p
     if (t < 16) P[OFF_BB + t] = p.bb[t];
   }
   static_assert(THREADS >= 256, "one 16x16 matrix per round");
-  if (THREADS == 256 || t < 256) { P[OFF_W1 + t] = p.W1[t]; P[OFF_W2 + t] = p.W2[t]; }     // (256 threads: no guard)
-  if (t < 16) { P[OFF_B1 + t] = p.b1[t]; P[OFF_B2 + t] = p.b2[t]; }
+  if constexpr (RHS == RHS_TANH) {
+    if (THREADS == 256 || t < 256) P[OFF_W1 + t] = p.W1[t];
+    if (t < 16) P[OFF_B1 + t] = p.b1[t];
+  } else {
+    if (THREADS == 256 || t < 256) { P[OFF_W1 + t] = p.W1[t]; P[OFF_W2 + t] = p.W2[t]; }     // (256 threads: no guard)
+    if (t < 16) { P[OFF_B1 + t] = p.b1[t]; P[OFF_B2 + t] = p.b2[t]; }
+  }
   __syncthreads();
 }
 // pre-net Linear(16,64) -> LReLU -> Linear(64,16) -> LReLU on a staged block whose first four tensors are Wa, ba, Wb, bb:

@@ -153,6 +153,28 @@ class ODEFunc(nn.Module):
         raise RuntimeError("ODEFunc is evaluated inside libgode's fused RK4 kernels (gode_ode_fwd/bwd)")
 
 
+class ODEFuncTanh(nn.Module):
+    """Right-hand side f(t, x) = tanh(W x + b) (models/mocogan_mnist.py:6-16: the ODEFunc(dim) of that file).  Evaluated
+    inside the fused fixed-grid ODE kernels (the ops' rhs = 1), like ODEFunc."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.fn = nn.Sequential(nn.Linear(dim, dim), nn.Tanh())
+
+    def forward(self, t, x):
+        raise RuntimeError("ODEFuncTanh is evaluated inside libgode's fused fixed-grid kernels (gode_ode_fwd/bwd, rhs = 1)")
+
+
+def _is_one_layer(ode_fn):
+    """Is ode_fn (a class or an instance) the one-layer right-hand side?"""
+    return issubclass(ode_fn, ODEFuncTanh) if isinstance(ode_fn, type) else isinstance(ode_fn, ODEFuncTanh)
+
+
+def _ode_fn_tensors(fn):
+    """The tensors of an ODEFunc / ODEFuncTanh in the kernels' order: W1, b1[, W2, b2]."""
+    return [t for m in fn.fn if isinstance(m, nn.Linear) for t in (m.weight, m.bias)]
+
+
 def solver_grid_arrays(T, step_size):
     """torchdiffeq options={'step_size': h} (FixedGridODESolver) for t = linspace(0, 1, T): the solver walks its own
     grid arange(niters)*h + t0 (last point clamped to t_end) and interpolates the requested outputs linearly; the
@@ -239,7 +261,11 @@ class _GenPlan:
 
     zcols = 68                   # row width of a latent-only plan (sample_z_m); plans with a decoder write Z_COLS
     rows_in_traj = True          # sample_z_m's rows: the kernel's trajectory buffer (else the first 16 latent columns)
-    nparam, grad_offs = L.ODE_NPARAM, _ODE_GRAD_OFFS       # the adjoint kernel's gradient block
+    # the adjoint kernel's gradient block.  One-layer right-hand side (ODEFuncTanh, the ops' rhs = 1): the block ends behind
+    # b1 -- six tensors, 2400 floats; the kernels neither read nor write a float of `grads` from there on
+    rhs = property(lambda self: L.ode_rhs_code("tanh" if _is_one_layer(self.gen.ode_fn) else "mlp"))
+    nparam = property(lambda self: L.ODE_RHS_TANH_NPARAM if self.rhs else L.ODE_NPARAM)
+    grad_offs = property(lambda self: _ODE_GRAD_OFFS[:6] if self.rhs else _ODE_GRAD_OFFS)
     # no pre-net: this kernel keeps its offsets (the block's first _PRENET_NPARAM floats stay unwritten); the SDE
     # kernel's block starts at the first tensor present
     grads_from_first_present = False
@@ -306,8 +332,7 @@ class _GenPlan:
             pre = (None, None, None, None)
         else:
             pre = (lin[0].weight, lin[0].bias, lin[2].weight, lin[2].bias)
-        f = g.ode_fn.fn
-        return pre + (f[0].weight, f[0].bias, f[2].weight, f[2].bias)
+        return pre + tuple(_ode_fn_tensors(g.ode_fn))
 
     @classmethod
     def multi_ok(cls, gen, adjoint):
@@ -336,16 +361,22 @@ class _GenPlan:
                                              self.gen.ode_atol)
         if ptrs != self._ode_ptrs:
             method = ode_method_code(self.gen.ode_method)
+            rhs = self.rhs
+            if rhs and method == ODE_METHODS["dopri5"]:
+                raise NotImplementedError("ode_method 'dopri5' with the one-layer right-hand side (ODEFuncTanh): libgode's "
+                                          "adaptive kernels integrate the two-layer ODEFunc only; the one-layer function "
+                                          "is served by 'rk4', 'euler' and 'midpoint'")
             self._ode_ptrs = ptrs
-            op = L.OdeParams(*ptrs[:8])
+            op = L.OdeParams(*ptrs[:len(ps)])       # (one-layer: six tensors -- W2 / b2 stay NULL, never dereferenced)
             prenet = 0 if ps[0] is None else 1
             zbuf, zcols = self._zbuf, self._zcols
             self.fwd_op = L.OdeFwdOp(p=op, x=dptr(self.x), content=dptr(self.content), dt=dptr(self.dt),
                                      sel_t=dptr(self.sel), z=dptr(zbuf), traj=dptr(self.traj), N=self.n,
-                                     T=self.T, substeps=self.gen.ode_substeps, prenet=prenet, zcols=zcols)
+                                     T=self.T, substeps=self.gen.ode_substeps, prenet=prenet, zcols=zcols, rhs=rhs)
             self.bwd_op = L.OdeBwdOp(p=op, x=dptr(self.x), traj=dptr(self.traj), dt=dptr(self.dt),
                                      sel_t=dptr(self.sel), gz=None, work=dptr(self.ode_work), grads=None, N=self.n,
-                                     T=self.T, substeps=self.gen.ode_substeps, prenet=prenet, accumulate=0, zcols=zcols)
+                                     T=self.T, substeps=self.gen.ode_substeps, prenet=prenet, accumulate=0, zcols=zcols,
+                                     rhs=rhs)
             self._grid = None
             if self.gen.ode_method == "dopri5":
                 # torchdiffeq's adaptive solver over the output times; the adjoint call is integrated adaptively too
@@ -621,6 +652,7 @@ class VideoGenerator(nn.Module):
     mnist = False
     _plan_cls = None   # set below (_GenPlan)
     _categorical_ok = True     # dim_z_category > 0 is served (the other motion latents switch it off)
+    _one_layer_ok = True       # ode_fn=ODEFuncTanh is served (the ODE-RNN generator, whose kernels are two-layer, refuses it)
     # the reference passes method='rk4' (models/mocogan_ode.py:50,144); 'dopri5' is what BASELINE configs[3] words;
     # 'euler' and 'midpoint' are torchdiffeq's other two fixed-grid solvers, on rk4's grid (ODE_METHODS: all served names)
     ode_method = "rk4"
@@ -652,9 +684,10 @@ class VideoGenerator(nn.Module):
         self._pool = _Pool()
 
     def _init_ode_parts(self, ode_fn, dim_hidden, linear, dim_z, ngf):
-        if dim_hidden is None:
+        if dim_hidden is None and not (isinstance(ode_fn, type) and _is_one_layer(ode_fn)):
             # the reference passes no dim_hidden here and its ODEFunc then raises TypeError;
-            # keep the failure mode but say why.
+            # keep the failure mode but say why.  (The one-layer ODEFuncTanh takes none: ucf_moco_ode.py:80's call
+            # constructs against models/mocogan_mnist.py.)
             raise TypeError("ODEFunc.__init__() missing 1 required positional argument: 'dim_hidden' "
                             "(pass dim_hidden=16; ucf_moco_ode.py:80 omits it and fails the same way)")
         self.ode_fn = self._make_ode_fn(ode_fn, dim_hidden)
@@ -662,7 +695,22 @@ class VideoGenerator(nn.Module):
 
     def _make_ode_fn(self, ode_fn, dim_hidden):
         """The fused RK4 / adjoint kernels hard-code ODEFunc's 16 -> 16 -> 16 tanh MLP (one MFMA tile per mat-vec):
-        anything else would be integrated with the wrong right-hand side, so it is refused here."""
+        anything else would be integrated with the wrong right-hand side, so it is refused here.  The one exception is the
+        one-layer ODEFuncTanh (tanh(W x + b), models/mocogan_mnist.py): the fixed-grid kernels are compiled for it too."""
+        if isinstance(ode_fn, type) and _is_one_layer(ode_fn):
+            if not self._one_layer_ok:
+                raise NotImplementedError(f"{type(self).__name__} does not serve the one-layer ODEFuncTanh: only the plain "
+                                          "Neural-ODE generators' fixed-grid kernels integrate tanh(W x + b)")
+            if dim_hidden:
+                # models/mocogan_mnist.py:23-24 would call ode_fn(dim=..., dim_hidden=...) on an __init__(self, dim)
+                raise TypeError("ODEFunc.__init__() got an unexpected keyword argument 'dim_hidden' (the one-layer "
+                                "ODEFunc of models/mocogan_mnist.py takes dim only)")
+            fn = ode_fn(dim=self.dim_z_motion)
+            lin = [m for m in fn.fn] if hasattr(fn, "fn") else []
+            if not (len(lin) == 2 and isinstance(lin[0], nn.Linear) and isinstance(lin[1], nn.Tanh)
+                    and tuple(lin[0].weight.shape) == (16, 16) and lin[0].bias is not None):
+                raise NotImplementedError("ode_fn.fn must be Sequential(Linear(16,16), Tanh())")
+            return fn
         hid = dim_hidden if dim_hidden else self.dim_z_motion
         if hid != 16:
             raise NotImplementedError(f"dim_hidden={hid}: libgode's fused ODE kernels are specialised for the "
@@ -737,8 +785,7 @@ class VideoGenerator(nn.Module):
         ode = []
         if not isinstance(self.linear, nn.Identity):
             ode += [self.linear[0].weight, self.linear[0].bias, self.linear[2].weight, self.linear[2].bias]
-        f = self.ode_fn.fn
-        ode += [f[0].weight, f[0].bias, f[2].weight, f[2].bias]
+        ode += _ode_fn_tensors(self.ode_fn)
         return self._decoder_list(), ode
 
     def _apply(self, fn, *a, **k):
@@ -1082,6 +1129,36 @@ class VideoGeneratorMNISTODE(VideoGeneratorMNIST):
         self.linear = self._make_prenet(linear)
 
 
+class _OneLayerDefault:
+    """The constructor of models/mocogan_mnist.py's three generators: ode_fn defaults to that file's one-layer ODEFunc
+    (ODEFuncTanh), built with dim alone when dim_hidden is falsy (:23-26, :60-63, :117-120)."""
+
+    def __init__(self, n_channels, dim_z_content, dim_z_category, dim_z_motion, video_length, ode_fn=ODEFuncTanh,
+                 dim_hidden=None, linear=True, ngf=64):
+        super().__init__(n_channels, dim_z_content, dim_z_category, dim_z_motion, video_length, ode_fn=ode_fn,
+                         dim_hidden=dim_hidden, linear=linear, ngf=ngf)
+
+
+class VideoGeneratorTanh(_OneLayerDefault, VideoGenerator):
+    """models/mocogan_mnist.py:19-53: the 64x64 generator; VideoGenerator(n_channels, 50, 0, 16, 16), the UCF driver's
+    own call (ucf_moco_ode.py:80), constructs here.  Built in the reference's order: recurrent, main, ode_fn, linear."""
+
+
+class VideoGeneratorMNISTTanh(_OneLayerDefault, VideoGeneratorMNIST):
+    """models/mocogan_mnist.py:56-110: recurrent, the 64x64 main, ode_fn, the 28x28 main, linear."""
+
+
+class VideoGeneratorMNISTODETanh(_OneLayerDefault, VideoGeneratorMNISTODE):
+    """models/mocogan_mnist.py:113-147.  Its super().__init__ call hands none of ode_fn / dim_hidden / linear on, so the
+    parent builds its defaults first (a one-layer ODEFunc, the 28x28 main, a pre-net); ode_fn and linear are then built
+    again from the arguments."""
+
+    def _init_ode_parts(self, ode_fn, dim_hidden, linear, dim_z, ngf):
+        VideoGeneratorMNIST._init_ode_parts(self, ODEFuncTanh, None, True, dim_z, ngf)
+        self.ode_fn = self._make_ode_fn(ode_fn, dim_hidden)
+        self.linear = self._make_prenet(linear)
+
+
 _RNN_GRAD_OFFS = [(0, 256, (16, 16)), (256, 16, (16,)), (272, 256, (16, 16)), (528, 16, (16,)),
                   (544, 768, (48, 16)), (1312, 768, (48, 16)), (2080, 48, (48,)), (2128, 48, (48,))]
 
@@ -1144,6 +1221,7 @@ class VideoGeneratorMNISTODERNN(VideoGeneratorMNIST):
     that runs are comparable with the CPU oracle at identical seeds ("ROCm .cuda() semantics")."""
 
     _categorical_ok = False     # dim_z_category > 0 is refused: categorical latents exist for the Neural-ODE generators only
+    _one_layer_ok = False
 
     _plan_cls = _RnnGenPlan
     ode_rtol, ode_atol = 1e-7, 1e-9
@@ -1239,6 +1317,13 @@ class VideoGeneratorGRU(VideoGenerator):
 
     _plan_cls = _GruGenPlan
     _gode_graph_capture = False     # GanTrainer(graph=True) refuses this generator (not captured / verified)
+
+    def __new__(cls, *args, **kwargs):
+        # __init__ keeps the reference's signature (no ode_fn); a caller that hands this class one is told why not
+        if kwargs.get("ode_fn") is not None:
+            raise NotImplementedError("the GRU generator integrates no ODE: it takes no ode_fn (ODEFunc and ODEFuncTanh are "
+                                      "served by the Neural-ODE generators)")
+        return super().__new__(cls)
 
     def __init__(self, n_channels, dim_z_content, dim_z_category, dim_z_motion, video_length, ngf=64):
         if dim_z_category != 0:

@@ -265,8 +265,13 @@ typedef struct gode_ode_fwd_op {
    * receives the number of trial steps.  method 0: fixed-grid rk4 (above).
    * method 2: torchdiffeq's euler, y1 = y0 + dt f(y0); method 3: its midpoint, y1 = y0 + dt f(y0 + (dt/2) f(y0)).  Both
    * walk the grids of method 0 (dt / substeps, or grid_dt / emit_at / emit_w) and take the same arguments; they run on
-   * the vector-ALU kernels at every N.  Any other code: GODE_E_ARG. */
-  int32_t method, pad2_; float rtol, atol; const float* tout; int32_t* nsteps;
+   * the vector-ALU kernels at every N.  Any other code: GODE_E_ARG.
+   * rhs: the right-hand side.  0: f(y) = W2 tanh(W1 y + b1) + b2 (above; what a zero-initialised op asks for).
+   * 1: f(y) = tanh(W1 y + b1), the one-layer ODEFunc of models/mocogan_mnist.py:6-16 -- its weight in p.W1, its bias in
+   * p.b1; p.W2 and p.b2 are never dereferenced (NULL is fine).  Served for methods 0, 2 and 3, on the vector-ALU kernels at
+   * every N; rhs 1 with method 1 (the adaptive kernels integrate u = W1 y + b1, the two-layer function's algebra) and any
+   * rhs other than 0 or 1: GODE_E_ARG, from gode_ode_fwd and gode_ode_fwd_multi alike, before any launch. */
+  int32_t method, rhs; float rtol, atol; const float* tout; int32_t* nsteps;
   /* method 1 with N > 32: >= gode_odernn_sync_size(N) words through which the workgroups exchange the whole-batch error norm
    * (see the ODE-RNN ops below; NULL or more than GODE_ODERNN_SYNC_MAX_N trajectories per launch: one norm per
    * 64-trajectory workgroup, nsteps per such workgroup).  With it nsteps[0] = trial steps of the call (negative: stalled). */
@@ -298,8 +303,14 @@ typedef struct gode_ode_bwd_op {
    * the same adjoint discretised with `substeps` fixed Kutta-3/8 steps per interval (round-1 behaviour; dt required).
    * method 2 (euler) / 3 (midpoint): the adjoint of method 0 with the reverse-time steps of (y, a, g_theta) taken by that
    * method (the parameter integrals get its b-weights: euler's one stage 1; midpoint's first stage 0, its second 1);
-   * same arguments as method 0 (dt, substeps >= 1, bstep_off / bstep_dt).  Any other code: GODE_E_ARG. */
-  int32_t method, pad_; float rtol, atol; const float* tout;
+   * same arguments as method 0 (dt, substeps >= 1, bstep_off / bstep_dt).  Any other code: GODE_E_ARG.
+   * rhs: as in gode_ode_fwd_op.  rhs 1 (f(y) = tanh(W1 y + b1)): p.W2 / p.b2 are never dereferenced, and the gradient
+   * block is the first 2400 floats of the layout above (pre-net block, W1, b1): floats [2400, 2672) of grads are neither
+   * read nor written, on every path (the two-level reduce included) -- grads may end at float 2400.  `work` rows keep
+   * their stride of GODE_ODE_NPARAM floats (gode_ode_bwd_work_size does not depend on rhs).  rhs 1 with method 1
+   * (substeps 0 or not) and any rhs other than 0 or 1: GODE_E_ARG from gode_ode_bwd and gode_ode_bwd_multi, before any
+   * launch. */
+  int32_t method, rhs; float rtol, atol; const float* tout;
   int32_t* nsteps;   /* nullable, adaptive adjoint only: trial steps of the adjoint call (nsteps[0]; without `sync` and N > 32:
                         [ceil(N/64)], one per workgroup); a negative entry reports a call that stalled (trial-step limit /
                         step-size underflow: torchdiffeq asserts there) */
