@@ -339,6 +339,7 @@ _PROTOS = {
     "gode_igemm_launch_info": ([ptr, ptr], cint),
     "gode_igemm_launch_cell": ([ptr, ptr], cint),
     "gode_igemm_work_size": ([ptr], i64),
+    "gode_col2im_launch_kind": ([ptr, ptr], cint),
     "gode_pack_size": ([ptr, cint], i64),
     "gode_pack_weights": ([ptr, cint, ptr, ptr, ptr, i32, ptr], cint),
     "gode_wgrad_work_size": ([ptr], i64),

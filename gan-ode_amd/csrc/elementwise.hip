@@ -4,6 +4,7 @@
 // 202-212), nn.BCEWithLogitsLoss (mnist_moco_ode.py:89), torch.optim.Adam(weight_decay) (mnist_moco_ode.py:86-88).
 #include "common.h"
 #include "philox.h"
+#include "col2im_plan.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // BatchNorm finalize
@@ -248,35 +249,28 @@ __global__ void __launch_bounds__(256) col2im3d_kernel(const gode_col2im_op a) {
 }
 
 extern "C" int gode_col2im(const gode_col2im_op* op, void* stream) {
-  if (!op || !op->cols || !op->out || op->N <= 0 || op->C <= 0 || op->C > 4 || op->kh <= 0 || op->kw <= 0 || op->sh <= 0 ||
-      op->sw <= 0 || op->ph < 0 || op->pw < 0 || op->Hi <= 0 || op->Wi <= 0)
-    return GODE_E_ARG;
-  if (op->Ho != (op->Hi - 1) * op->sh - 2 * op->ph + op->kh || op->Wo != (op->Wi - 1) * op->sw - 2 * op->pw + op->kw) return GODE_E_SHAPE;
-  if (op->epilogue != GODE_EPI_RAW && op->epilogue != GODE_EPI_TANH) return GODE_E_ARG;
-  if (op->kd > 0) {
-    if (op->sd <= 0 || op->pd < 0 || op->Di <= 0 || op->Do != (op->Di - 1) * op->sd - 2 * op->pd + op->kd) return GODE_E_SHAPE;
-    const int64_t voxels = (int64_t)op->N * op->Do * op->Ho * op->Wo;
-    int64_t nb = (voxels + 255) / 256; if (nb > 16384) nb = 16384;
-    if (op->kd == 4 && op->kh == 4 && op->kw == 4 && op->sd == 1 && op->sh == 2 && op->sw == 2 && op->C == 3 && voxels < (1ll << 31)) {
-      hipLaunchKernelGGL((col2im3d_fixed_kernel<4, 4, 4, 1, 2, 2, 3>), dim3((int)nb), dim3(256), 0, (hipStream_t)stream, *op);
-      GODE_LAUNCH_CHECK();
-      return 0;
-    }
-    hipLaunchKernelGGL(col2im3d_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, *op);
-    GODE_LAUNCH_CHECK();
-    return 0;
+  Col2imPlan P;
+  const int rc = col2im_plan(op, &P);            // col2im_plan.h: the kernel, the grid and the row-group kernel's LDS
+  if (rc) return rc;
+  const dim3 grid(P.grid), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  switch (P.kind) {
+    case C2I_ROWS: hipLaunchKernelGGL(col2im_rows_kernel, grid, block, (size_t)P.lds, st, *op, P.R, P.nq); break;
+    case C2I_PIXEL: hipLaunchKernelGGL(col2im_kernel, grid, block, 0, st, *op); break;
+    case C2I_3D_FIXED: hipLaunchKernelGGL((col2im3d_fixed_kernel<4, 4, 4, 1, 2, 2, 3>), grid, block, 0, st, *op); break;
+    default: hipLaunchKernelGGL(col2im3d_kernel, grid, block, 0, st, *op); break;
   }
-  const int KC = op->kh * op->kw * op->C, R = (op->kh + op->sh - 1) / op->sh;
-  const int nq = (op->Ho - 1 + op->ph) / op->sh + 1;             // row groups that contain an output row
-  const int64_t lds = (int64_t)R * op->Wi * KC * sizeof(float);
-  if ((op->Wi * KC) % 4 == 0 && ((uintptr_t)op->cols % 16) == 0 && lds <= 48 * 1024 && (int64_t)op->N * nq < (1ll << 31)) {
-    hipLaunchKernelGGL(col2im_rows_kernel, dim3(op->N * nq), dim3(256), (size_t)lds, (hipStream_t)stream, *op, R, nq);
-    GODE_LAUNCH_CHECK();
-    return 0;
-  }
-  int64_t nb = ((int64_t)op->N * op->Ho * op->Wo + 255) / 256; if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(col2im_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, *op);
   GODE_LAUNCH_CHECK();
+  return 0;
+}
+
+// The plan of the op, host-side: what gode_col2im(op) launches and why (gode.h)
+extern "C" int gode_col2im_launch_kind(const gode_col2im_op* op, int32_t* kind) {
+  if (!kind) return GODE_E_ARG;
+  Col2imPlan P;
+  const int rc = col2im_plan(op, &P);
+  if (rc) return rc;
+  kind[0] = P.kind; kind[1] = P.why;
   return 0;
 }
 
@@ -593,13 +587,18 @@ extern "C" int gode_adam_l2(const gode_adam_op* op, void* stream) {
 // One update rule for both entry points; float4 lanes when the four pointers of a tensor are 16-byte aligned (torch
 // allocations and arena slices of whole float4s are), scalar tail / fallback otherwise.  HBM-bound: 16 B read + 12 B
 // written per parameter.
+// Every multiply-add is spelled as the fused operation it is to be: under -ffp-contract=fast the compiler otherwise picks, per
+// call site, WHICH product of a sum like v*b2 + (1-b2)*gi*gi it fuses -- the float4 body of adam_multi_kernel fused one way, its
+// scalar tail not at all, lanes 2 and 3 of adam_noise_multi_kernel's float4 body another way -- so an element's bits depended
+// on its place in the tensor and on the entry point (tests/test_gpu_elementwise_cells.py: sigma = 0 noise against plain).  The
+// forms below are the ones the float4 body of adam_multi_kernel had, so the bulk of every aligned tensor keeps its bits.
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float b1, float b2, float eps, float wd,
                                           float gscale, float step_size, float bc2_sqrt) {
-  const float gi = g * gscale + wd * p;
-  const float mi = m + (gi - m) * (1.f - b1);
-  const float vi = v * b2 + (1.f - b2) * gi * gi;
+  const float gi = fmaf(wd, p, g * gscale);
+  const float mi = fmaf(1.f - b1, gi - m, m);
+  const float vi = fmaf(b2, v, (1.f - b2) * gi * gi);
   m = mi; v = vi;
-  p = p - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+  p = fmaf(-step_size, mi / (sqrtf(vi) / bc2_sqrt + eps), p);
 }
 __device__ __forceinline__ void adam_tensor(const gode_adam_tensor& t, float b1, float b2, float eps, float wd, float gscale,
                                             float step_size, float bc2_sqrt) {

@@ -209,6 +209,16 @@ typedef struct gode_col2im_op {
   int32_t Di, Do, kd, sd, pd, pad2_;
 } gode_col2im_op;
 int gode_col2im(const gode_col2im_op* op, void* stream);
+/* The launch plan: which kernel gode_col2im(op) launches and why, decided by the function the launch itself dispatches on.
+ * Returns what gode_col2im would return before launching anything (0, GODE_E_ARG, GODE_E_SHAPE); on 0, kind[2] =
+ *   kind[0]: 0 row-group LDS kernel (2-D), 1 per-pixel 2-D, 2 3-D with fixed 4x4x4 taps / strides 1x2x2 / C == 3, 3 3-D generic;
+ *   kind[1]: why a 2-D op left the row-group kernel (0: it did not) -- bit 0 the row length Wi*kh*kw*C is no multiple of 4,
+ *     bit 1 cols is off a 16-byte boundary, bit 2 its R = ceil(kh/sh) input rows exceed 48 KiB of LDS, bit 3 N * row groups
+ *     >= 2^31; for a 3-D op why it left the fixed kernel -- bit 0 taps or strides are not the fixed ones, bit 1 C != 3, bit 2
+ *     N*Do*Ho*Wo >= 2^31.
+ * All four kernels add an output element's taps in the same order ((kd,) kh, kw ascending from 0.f): the kind changes no bit
+ * of a raw output.  Host-side, no GPU work; cols is looked at (null, alignment), never through. */
+int gode_col2im_launch_kind(const gode_col2im_op* op, int32_t* kind);
 
 /* backward of y -> BN -> act given g_a = dL/d(act output), all [M][C] channels-last:
  *   g_z = g_a * act'(scale*y+shift);  dbeta = sum g_z;  dgamma = sum g_z*xhat;
