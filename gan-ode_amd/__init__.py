@@ -10,7 +10,7 @@ from .modules import (CategoricalVideoDiscriminator, CDEFunc, Noise, ODEFunc, OD
                       VideoGeneratorMNISTODETanh, VideoGeneratorMNISTTanh, VideoGeneratorSDE, VideoGeneratorTanh)
 from .ode_training import GANODETrainer
 from .gres import ConditionalNorm, GResBlock, SpectralNorm
-from . import dcgan, fcgan
+from . import data, dcgan, fcgan
 from .train import (FusedAdam, GanTrainer, WassersteinDiscriminatorLoss, WassersteinGeneratorLoss, bce_with_logits_const,
                     bce_with_logits_halves, bce_with_logits_pair, bce_ce_head, bce_ce_head_halves, bce_ce_head_pair,
                     bce_ce_heads, categorical_cross_entropy, build_mnist, build_ucf, freeze_host_gc, host_cpu_quota,

@@ -28,6 +28,8 @@ OP_CATEG, OP_CE = 22, 23
 OP_CHSTATS, OP_CBN_EMBED, OP_CBN_EMBED_BWD, OP_CBN_APPLY, OP_CBN_BWD, OP_GRES_OUT, OP_GRES_OUT_BWD, OP_SN_FWD, OP_SN_BWD = range(24, 33)
 OP_FC_ACT, OP_FC_ACT_BWD, OP_BCE_PROB = 33, 34, 35
 OP_BCE_T = 36
+OP_RESIZE_U8, OP_CLIP_GATHER = 37, 38
+RESIZE_MAX_TAPS = 32          # GODE_RESIZE_MAX_TAPS: the longest tap row gode_resize_u8 takes
 REC_ADAM_NOISE = -1          # gode_sizeof index of the gode_adam_noise_tensor table record
 ODE_NPARAM = 2672
 ODERNN_NPARAM = 2176
@@ -307,6 +309,19 @@ class BceProbOp(_Op):
 class BceTOp(_Op):
     _fields_ = [("logits", ptr), ("target", ptr), ("grad", ptr), ("loss", ptr), ("n", i64), ("gscale", f32), ("accumulate", i32)]
     KIND, FN = OP_BCE_T, "gode_bce_logits_t"
+
+
+class ResizeU8Op(_Op):
+    _fields_ = [("src", ptr), ("dst", ptr), ("dst_f32", ptr), ("y_first", ptr), ("y_count", ptr), ("y_w", ptr), ("x_first", ptr),
+                ("x_count", ptr), ("x_w", ptr), ("ss", i64 * 4), ("F", i32), ("Hin", i32), ("Win", i32), ("C", i32), ("out_h", i32),
+                ("out_w", i32), ("ky", i32), ("kx", i32)]
+    KIND, FN = OP_RESIZE_U8, "gode_resize_u8"
+
+
+class ClipGatherOp(_Op):
+    _fields_ = [("frames", ptr), ("first", ptr), ("out", ptr), ("n_frames", i64), ("frame_elems", i64), ("B", i32), ("T", i32),
+                ("sub", f32), ("inv", f32)]
+    KIND, FN = OP_CLIP_GATHER, "gode_clip_gather"
 
 
 class AdamNoiseTensor(C.Structure):

@@ -784,6 +784,44 @@ typedef struct gode_bce_t_op {
 } gode_bce_t_op;
 int gode_bce_logits_t(const gode_bce_t_op* op, void* stream);
 
+/* ---- device-resident UCF-101 feed (dataset/ucf101new.py:73-98,162-180: Resize((64, 85), BICUBIC) on uint8 frames, crop of
+ * columns 10..73, (x - 128) / 128) -- DESIGN section 21 -------------------------------------------------------------------
+ * Separable resize of uint8 frames through two tap tables (bicubic_taps of gan-ode_amd/data.py: the weights of
+ * torch.nn.functional.interpolate(mode="bicubic", align_corners=False, antialias=...) evaluated in double and rounded once to
+ * fp32; the horizontal table lists the KEPT output columns only, so the crop costs nothing).  Output row i reads input rows
+ * [y_first[i], y_first[i] + y_count[i]) with weights y_w[i*ky ..], output column j reads input columns [x_first[j], x_first[j] +
+ * x_count[j]) with weights x_w[j*kx ..]:
+ *   v = sum_y wy * (sum_x wx * in)      the horizontal sum first, taps ascending, each an fp32 fused-multiply-add chain from 0
+ *   dst     = uint8(round_half_even(clamp(v, 0, 255)))       (torchvision's order for uint8 tensors: clamp, round, cast)
+ *   dst_f32 = v
+ * src: uint8 read through ELEMENT strides ss {frame, row, column, channel} -- the decoder's [F][Hin][Win][C] and the reference's
+ * permuted [F][C][Hin][Win] both go in without a copy.  dst, dst_f32: [F][out_h][out_w][C] contiguous, each nullable, not both.
+ * C is 1 or 3; 1 <= ky, kx <= GODE_RESIZE_MAX_TAPS (antialiased downscales up to 8x).  The tables are DEVICE memory, which the
+ * entry point does not read; the kernel checks every table row it uses instead: a count outside [1, k], or a range that leaves
+ * the input, turns the outputs that row feeds into NaN (dst_f32) / 0 (dst), and nothing outside src is read.  (The Python side
+ * builds the tables and refuses such rows before any upload.)  GODE_E_SHAPE: ky or kx above the maximum, ky rows of fp32
+ * partial sums (ky * out_w * C floats) beyond the kernel's 48 KiB of LDS, or F * bands of 8 rows >= 2^31. */
+#define GODE_RESIZE_MAX_TAPS 32
+typedef struct gode_resize_u8_op {
+  const uint8_t* src; uint8_t* dst; float* dst_f32;
+  const int32_t* y_first; const int32_t* y_count; const float* y_w;
+  const int32_t* x_first; const int32_t* x_count; const float* x_w;
+  int64_t ss[4];
+  int32_t F, Hin, Win, C, out_h, out_w, ky, kx;
+} gode_resize_u8_op;
+int gode_resize_u8(const gode_resize_u8_op* op, void* stream);
+/* Window gather and normalise: out[b][t][e] = (frames[first[b] + t][e] - sub) * inv for t < T, e < frame_elems -- with sub = 128,
+ * inv = 1/128 exactly the reference's (x - 128.0) / 128.0 (the difference is an integer, the divisor a power of two).  frames:
+ * uint8 [n_frames][frame_elems]; first: int64 [B] on the DEVICE, the first stored frame of every clip (T == 1: image batches);
+ * out: fp32 [B][T][frame_elems] contiguous.  A clip whose range [first, first + T) leaves [0, n_frames) is filled with NaN and
+ * nothing outside the buffer is read (the idiom of gode_ce_logits' bad label).  frame_elems % 16 == 0 with frames and out on
+ * 16-byte boundaries: 16-byte loads and stores; otherwise element by element.  Same values either way. */
+typedef struct gode_clip_gather_op {
+  const uint8_t* frames; const int64_t* first; float* out;
+  int64_t n_frames, frame_elems; int32_t B, T; float sub, inv;
+} gode_clip_gather_op;
+int gode_clip_gather(const gode_clip_gather_op* op, void* stream);
+
 /* out[i] = a[i]*alpha (+ out[i] if accumulate); small utility for gradient bucket handling */
 int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulate, void* stream);
 
@@ -825,7 +863,9 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
   X(FC_ACT,        33, gode_fc_act_op,        gode_fc_act)        \
   X(FC_ACT_BWD,    34, gode_fc_act_bwd_op,    gode_fc_act_bwd)    \
   X(BCE_PROB,      35, gode_bce_prob_op,      gode_bce_prob)      \
-  X(BCE_T,         36, gode_bce_t_op,         gode_bce_logits_t)
+  X(BCE_T,         36, gode_bce_t_op,         gode_bce_logits_t)  \
+  X(RESIZE_U8,     37, gode_resize_u8_op,     gode_resize_u8)     \
+  X(CLIP_GATHER,   38, gode_clip_gather_op,   gode_clip_gather)
 /* GODE_OP_PACK stays outside the table: it has no (op*, stream) entry point, gode_run sends every run of consecutive pack
  * ops out as batched launches instead. */
 #define GODE_ENUM_ROW_(name, value, op_t, fn) GODE_OP_##name = value,
