@@ -9,6 +9,11 @@
 // base q*sw*Ci, a per-row scalar and an immediate.  The weights of a wave's 32 output channels live in registers for
 // the whole launch (kd*kh*kw*Ci / 2 VGPRs: one value per MFMA k step).  A workgroup works on 4 / (Co / 32) slabs at a
 // time, one 32x32 output block per wave; patches are double-buffered.  Output: raw [positions][Co], as gode_igemm.
+//
+// Four instantiations <KD, KH, KC2 = kw * Ci / 2>: <4,4,6> and <1,4,6> are the UCF first layers (and any kw * Ci = 12, e.g.
+// Ci = 4 with kw = 3); <2,2,1> and <1,4,2> take one-channel inputs with output rows of >= 16 positions (and Ci = 2 with
+// kw = 2).  The MNIST discriminators' first layers have those tap shapes but rows of 15 / 14 positions: conv_patch_plan
+// declines them and they run the tiled GEMM, so no config reaches the one-channel kernels -- tests/patch_cells.py does.
 #include <stdint.h>
 #include "common.h"
 #include "conv_geom.h"

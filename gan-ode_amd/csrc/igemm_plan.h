@@ -476,10 +476,14 @@ static bool conv_patch_plan(const gode_igemm_op* op, ConvPatchPlan* C) {
   C->wgs = (nit + C->iters_per_wg - 1) / C->iters_per_wg;
   const int KC2 = KC / 2;
   C->variant = 0;
+  // Keyed on (kd, kh, kw * Ci / 2), not on (kw, Ci): CP_K2D_C3 also serves Ci = 4 with kw = 3, CP_K2D_C1 also Ci = 2 with kw = 2.
+  // The two one-channel kernels take the tap shapes of the MNIST discriminators' first layers, but those layers have output
+  // rows of 15 and 14 positions, are declined above (Wo < 16) and run the tiled GEMM; what reaches CP_K3D_C1 / CP_K2D_C1 is
+  // a one-channel input with Wo >= 16, from a caller of the C ABI (tests/patch_cells.py runs all four at every Co).
   if (g.kd == 4 && g.kh == 4 && KC2 == 6) C->variant = CP_K3D_C3;      // Conv3d(3, ., 4): UCF video discriminator
   if (g.kd == 1 && g.kh == 4 && KC2 == 6) C->variant = CP_K2D_C3;      // Conv2d(3, ., 4): UCF image discriminator
-  if (g.kd == 2 && g.kh == 2 && KC2 == 1) C->variant = CP_K3D_C1;      // Conv3d(1, ., 2): MNIST video discriminator
-  if (g.kd == 1 && g.kh == 4 && KC2 == 2) C->variant = CP_K2D_C1;      // Conv2d(1, ., 4): MNIST image discriminator
+  if (g.kd == 2 && g.kh == 2 && KC2 == 1) C->variant = CP_K3D_C1;      // Conv3d(1, ., 2) with Wo >= 16 (no config has one)
+  if (g.kd == 1 && g.kh == 4 && KC2 == 2) C->variant = CP_K2D_C1;      // Conv2d(1, ., 4) with Wo >= 16 (no config has one)
   return C->variant != 0;
 }
 

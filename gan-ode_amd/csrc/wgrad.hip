@@ -589,7 +589,10 @@ __global__ void __launch_bounds__(256) wgrad_patch_kernel(const WpArgs p) {
   constexpr int NYC = (32 * YC + 255) / 256;         // float4 chunks of the Y slab per thread (256 % YC == 0)
   const int yc4 = tid % YC, ypos0 = tid / YC;        // chunk i of this thread: position ypos0 + i * (256 / YC), same channels
   f32x4 ysc = {1, 1, 1, 1}, ysh = {0, 0, 0, 0};
-  if (yxf) { ysc = *reinterpret_cast<const f32x4*>(a.scale + yc4 * 4); ysh = *reinterpret_cast<const f32x4*>(a.shift + yc4 * 4); }
+  if (yxf) {                                         // once per thread, scalar loads: the plan does not look at their alignment
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { ysc[e] = a.scale[yc4 * 4 + e]; ysh[e] = a.shift[yc4 * 4 + e]; }
+  }
 
   f32x16 acc[NBW];
 #pragma unroll
