@@ -372,6 +372,8 @@ _PROTOS = {
     "gode_ode_bwd_multi": ([ptr, i32, ptr], cint),
     "gode_odernn_fwd_multi": ([ptr, i32, ptr], cint),
     "gode_odernn_bwd_multi": ([ptr, i32, ptr], cint),
+    "gode_odernn_fwd_route": ([ptr, i32, ptr], cint),
+    "gode_odernn_bwd_route": ([ptr, i32, ptr], cint),
     "gode_gru_fwd_multi": ([ptr, i32, ptr], cint),
     "gode_gru_bwd_multi": ([ptr, i32, ptr], cint),
     "gode_chstats_rows": ([i64], cint),

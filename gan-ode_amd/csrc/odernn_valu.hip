@@ -342,11 +342,13 @@ static int add_job(JobsV<Op>& J, const Op& op, int nblk, hipStream_t st) {
   J.op[J.count] = op; J.nblk[J.count] = nblk; J.count += 1;
   return 0;
 }
+// an adjoint launch of ONE workgroup in all writes grads itself (JobsV::direct); every other one goes through work rows
+static inline bool jobs_direct(bool adjoint, int jobs, int grid) { return adjoint && jobs == 1 && grid == 1; }
 template <class Op>
 static int launch_jobs(void (*kernel)(const JobsV<Op>), JobsV<Op>& J, bool adjoint, hipStream_t st) {
   int grid = 0;
   for (int k = 0; k < J.count; ++k) grid += J.nblk[k];
-  J.direct = (adjoint && J.count == 1 && grid == 1) ? 1 : 0;     // ONE workgroup in all: it writes grads itself
+  J.direct = jobs_direct(adjoint, J.count, grid) ? 1 : 0;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(RV_THREADS), 0, st, J);
   GODE_LAUNCH_CHECK();
   return 0;
@@ -366,8 +368,9 @@ static int fwd_multi(void (*kernel)(const JobsV<Op>), const Op* ops, int count, 
   return J.count ? launch_jobs(kernel, J, false, st) : 0;
 }
 // adjoints: one launch, then `rows(ops, count, A)` + latent_rows_kernel add the work rows of each group of ops that share a
-// `grads`.  With a fallback op in the call the ops run one after the other in array order (each with its own accumulate flag),
-// the fallback ones on their MFMA kernels.
+// `grads`.  With a fallback op in the call the ops run one after the other in array order, the fallback ones on their MFMA
+// kernels; the group rule of the fused route holds there too: the first op of a group stores or adds as its flag says, every
+// later op of the group adds.
 template <class Op, class Rows>
 static int bwd_launch(void (*kernel)(const JobsV<Op>), const Op* ops, int count, const int32_t* nblk, hipStream_t st, Rows rows) {
   JobsV<Op> J;
@@ -390,15 +393,41 @@ static int bwd_multi(void (*kernel)(const JobsV<Op>), const Op* ops, int count, 
   if (rc) return rc;
   if (!R.any_mfma) return bwd_launch(kernel, ops, count, R.nblk, st, rows);
   for (int k = 0; k < count; ++k) {
-    rc = R.mfma[k] ? fallback(&ops[k], st) : bwd_launch(kernel, &ops[k], 1, &R.nblk[k], st, rows);
+    Op op = ops[k];
+    for (int j = 0; j < k; ++j)
+      if (ops[j].grads == op.grads) op.accumulate = 1;
+    rc = R.mfma[k] ? fallback(&op, st) : bwd_launch(kernel, &op, 1, &R.nblk[k], st, rows);
     if (rc) return rc;
   }
   return 0;
 }
+// What fwd_multi / bwd_multi would do with these ops, from the decisions they dispatch on (route_ops, jobs_direct); host
+// arithmetic only.  route[k]: 0 = op k in the shared VALU launch, 1 = on the MFMA kernels with launches of its own;
+// route[count]: workgroups of the shared VALU launch (0: none); route[count + 1], adjoints: 0 = work rows + latent_rows_kernel,
+// 1 = the one workgroup writes grads itself, 2 = the ops run one at a time (forward: 0).
+template <class Op, class Ok, class Never>
+static int route_report(const Op* ops, int count, bool adjoint, Ok args_ok, Never never_valu, int32_t* route) {
+  RouteV R;
+  const int rc = route_ops(ops, count, args_ok, never_valu, R);
+  if (rc) return rc;
+  if (!route) return GODE_E_ARG;
+  const bool sequential = adjoint && R.any_mfma;
+  int jobs = 0, grid = 0;
+  for (int k = 0; k < count; ++k) {
+    route[k] = R.mfma[k] ? 1 : 0;
+    if (!R.mfma[k] && !sequential) { jobs += 1; grid += R.nblk[k]; }
+  }
+  route[count] = grid;
+  route[count + 1] = !adjoint ? 0 : (sequential ? 2 : (jobs_direct(true, jobs, grid) ? 1 : 0));
+  return 0;
+}
 
+static bool rnn_fwd_never_valu(const gode_odernn_fwd_op&, int) { return false; }
 extern "C" int gode_odernn_fwd_multi(const gode_odernn_fwd_op* ops, int32_t count, void* stream) {
-  return fwd_multi(odernn_fwd_valu_kernel, ops, count, (hipStream_t)stream, rnn_fwd_args_ok,
-                   [](const gode_odernn_fwd_op&, int) { return false; }, gode_launch_odernn_fwd_mfma);
+  return fwd_multi(odernn_fwd_valu_kernel, ops, count, (hipStream_t)stream, rnn_fwd_args_ok, rnn_fwd_never_valu, gode_launch_odernn_fwd_mfma);
+}
+extern "C" int gode_odernn_fwd_route(const gode_odernn_fwd_op* ops, int32_t count, int32_t* route) {
+  return route_report(ops, count, false, rnn_fwd_args_ok, rnn_fwd_never_valu, route);
 }
 
 extern "C" int gode_odernn_fwd(const gode_odernn_fwd_op* op, void* stream) { return gode_odernn_fwd_multi(op, 1, stream); }
@@ -859,10 +888,13 @@ static bool rnn_bwd_args_ok(const gode_odernn_bwd_op* op) {
 extern "C" int64_t gode_odernn_bwd_work_size(int32_t N) { return (int64_t)((N + 15) / 16) * GODE_ODERNN_NPARAM; }
 
 // fixed Kutta-3/8 substeps always run on odernn.hip's kernel
+static bool rnn_bwd_never_valu(const gode_odernn_bwd_op& op, int) { return op.substeps > 0; }
 extern "C" int gode_odernn_bwd_multi(const gode_odernn_bwd_op* ops, int32_t count, void* stream) {
-  return bwd_multi(odernn_bwd_valu_kernel, ops, count, (hipStream_t)stream, rnn_bwd_args_ok,
-                   [](const gode_odernn_bwd_op& op, int) { return op.substeps > 0; }, gode_launch_odernn_bwd_mfma,
+  return bwd_multi(odernn_bwd_valu_kernel, ops, count, (hipStream_t)stream, rnn_bwd_args_ok, rnn_bwd_never_valu, gode_launch_odernn_bwd_mfma,
                    [](const gode_odernn_bwd_op*, int, RowsArgs& A) { A.nparam = GODE_ODERNN_NPARAM; A.first = 0; });
+}
+extern "C" int gode_odernn_bwd_route(const gode_odernn_bwd_op* ops, int32_t count, int32_t* route) {
+  return route_report(ops, count, true, rnn_bwd_args_ok, rnn_bwd_never_valu, route);
 }
 
 extern "C" int gode_odernn_bwd(const gode_odernn_bwd_op* op, void* stream) { return gode_odernn_bwd_multi(op, 1, stream); }

@@ -327,8 +327,8 @@ typedef struct gode_ode_bwd_op {
   int32_t* sync;     /* adaptive adjoint with N > 32: as in gode_ode_fwd_op */
 } gode_ode_bwd_op;
 int gode_ode_bwd(const gode_ode_bwd_op* op, void* stream);
-/* the adaptive adjoints (method 1, substeps 0) of `count` (<= 8) solves in one launch; ops sharing a grads pointer are
- * reduced in array order */
+/* the adaptive adjoints (method 1, substeps 0) of `count` (<= 8) solves in one launch; ops sharing a grads pointer form a
+ * group under the group rule stated at gode_odernn_bwd_multi */
 int gode_ode_bwd_multi(const gode_ode_bwd_op* ops, int32_t count, void* stream);
 int64_t gode_ode_bwd_work_size(int32_t N);
 #define GODE_ODE_NPARAM 2672
@@ -380,9 +380,21 @@ typedef struct gode_odernn_bwd_op {
 } gode_odernn_bwd_op;
 int gode_odernn_bwd(const gode_odernn_bwd_op* op, void* stream);
 int64_t gode_odernn_bwd_work_size(int32_t N);
-/* the adjoints of `count` (<= 8) independent solves (the video and the image path of one generator step) in one launch;
- * every op reduces into its own grads (accumulate as given, ops are reduced in array order) */
+/* the adjoints of `count` (<= 8) independent solves (the video and the image path of one generator step) in one launch.
+ * The group rule (gode_odernn_bwd_multi and gode_ode_bwd_multi, on every route a call can take): the ops of a call that share
+ * a grads pointer form a group, reduced in array order -- the FIRST op of a group stores into grads or adds to it as its
+ * accumulate flag says; every later op of the group adds, whatever its flag. */
 int gode_odernn_bwd_multi(const gode_odernn_bwd_op* ops, int32_t count, void* stream);
+/* Which route gode_odernn_fwd_multi / gode_odernn_bwd_multi would take with these ops: host arithmetic on the decisions the
+ * launchers dispatch on, no pointer dereferenced but `ops` and `route`, no HIP call.  Returns what the launch would return
+ * before launching anything (0, GODE_E_ARG for a refused op or count); on 0, route[count + 2] =
+ *   route[k], k < count:  0 op k runs on the vector-ALU kernel in the call's shared launch; 1 on the MFMA kernels, with
+ *                         launches of its own
+ *   route[count]:         workgroups of the shared vector-ALU launch (0: there is none)
+ *   route[count + 1]:     adjoint: 0 work rows added by latent_rows_kernel; 1 the launch's one workgroup writes grads itself;
+ *                         2 the ops run one at a time in array order (a call with an MFMA op).  Forward: 0. */
+int gode_odernn_fwd_route(const gode_odernn_fwd_op* ops, int32_t count, int32_t* route);
+int gode_odernn_bwd_route(const gode_odernn_bwd_op* ops, int32_t count, int32_t* route);
 #define GODE_ODERNN_NPARAM 2176
 
 /* ---- Neural-SDE motion latent (models/mocogan_sde.py: sdeint_adjoint(SDEFunc, x, linspace(0, 1, T), method='euler',

@@ -342,13 +342,17 @@ def _shared_oracle(lats):
     return g
 
 
-@pytest.mark.parametrize("fallback", [False, True], ids=["dopri5-multi-fused", "dopri5-multi-nosync-op-falls-back"])
-def test_dopri5_multi_matches_single_ops_and_shared_grads_the_oracle_sum(fallback):
+@pytest.mark.parametrize("fallback,pair_flags", [(False, (0, 1)), (True, (0, 1)), (True, (0, 0))],
+                         ids=["dopri5-multi-fused", "dopri5-multi-nosync-op-falls-back", "dopri5-multi-nosync-op-falls-back-flags00"])
+def test_dopri5_multi_matches_single_ops_and_shared_grads_the_oracle_sum(fallback, pair_flags):
     """Ops of mixed shape in one launch: one workgroup (own grads), four workgroups with `sync` and a pre-net, and a
     two-workgroup + one-workgroup pair without pre-net sharing one grads vector (the video and the image path of one
     generator: the first stores, the second adds).  fallback: one more op without `sync` (N = 70), which falls back to
     the per-workgroup kernels alone in the forward and sends every adjoint of the call down the one-op-at-a-time path.
-    Forward outputs and own-grads adjoints are bitwise their single-op calls; the shared vector is the oracle's sum."""
+    Forward outputs and own-grads adjoints are bitwise their single-op calls; the shared vector is the oracle's sum.
+    pair_flags: the shared pair's accumulate flags.  (0, 0) on the one-op-at-a-time path pins the group rule of gode.h from this
+    user of the shared launcher template (tests/test_gpu_odernn_paths.py: multi-sequential-flags00 is the other): the later op
+    of a group adds, whatever its flag."""
     a = Latent(20, 4, 31, False, method=1)
     b = Latent(100, 3, 32, True, method=1, sync=True)
     d = Latent(40, 4, 33, False, method=1, sync=True, sel=True)
@@ -361,7 +365,7 @@ def test_dopri5_multi_matches_single_ops_and_shared_grads_the_oracle_sum(fallbac
     own = [x for x in lats if x not in (d, e)]
     e.bop.grads = d.grads.data_ptr()
     gshared = _shared_oracle([d, e])
-    acc0 = [1 if x is e else 0 for x in lats]
+    acc0 = [pair_flags[1] if x is e else 0 for x in lats]
     for x in lats:
         x.grads.fill_(NAN)
 
