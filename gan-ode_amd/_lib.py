@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgode.so")
@@ -392,6 +393,10 @@ _PROTOS = {
     "gode_ode_step": ([ptr, i32, i64, i32, f32, f32, f32, f32, f32, ptr, ptr], cint),
     "gode_axpy_multi": ([ptr, i32, i64, f32, ptr, ptr, f32, ptr, ptr, ptr], cint),
     "gode_run": ([ptr, ptr, i32, ptr], cint),
+    "gode_lanes_create": ([ptr], cint),
+    "gode_lanes_destroy": ([ptr], cint),
+    "gode_lanes_stream": ([ptr], ptr),
+    "gode_run_lanes": ([ptr, ptr, ptr, i32, i32, i32, i32, ptr], cint),
     "gode_version": (None, cint),
     "gode_sizeof": ([cint], cint),
 }
@@ -442,8 +447,16 @@ def _traced(op, stream, launch):
     TRACE.append((op, e0, e1))
 
 
+# Process-wide count of launches through the three funnels below (Program.run, run_one, call).  A plan that ran its last
+# call through LanesProgram compares the count with the one it saw then: equal means that nothing of libgode -- an
+# optimiser step, another plan, a trainer -- has been queued in between.
+LAUNCHES = 0
+
+
 def call(tag, launch):
     """Entry points that take no op struct (gode_adam_multi, gode_scale): `tag` stands in for the op in TRACE."""
+    global LAUNCHES
+    LAUNCHES += 1
     if TRACE is not None:
         return _traced(tag, None, launch)
     launch()
@@ -460,6 +473,8 @@ class Program:
         self.n = n
 
     def run(self, stream):
+        global LAUNCHES
+        LAUNCHES += 1
         if TRACE is not None:
             for op in self.ops:
                 run_one(op, stream)
@@ -467,7 +482,52 @@ class Program:
         check(lib().gode_run(self.kinds, self.ptrs, self.n, stream), "gode_run")
 
 
+LANES_ORDERED, LANES_OVERLAP = 0, 1
+
+
+class Lanes:
+    """A gode_lanes object (include/gode.h): the side stream of the two-lane runner and its events, library-owned."""
+
+    # An object whose owner is gone goes back here (per device) and serves the next owner; none is destroyed before the
+    # process ends.  torch keeps the side stream's handle past the owner's life -- the pinned staging buffers remember the
+    # streams they were copied on and record an event on each when they are freed -- so a destroyed stream would be used.
+    _free = {}
+
+    def __init__(self, device_index):
+        """Call with `device_index` current (the stream is created on the current device)."""
+        self.device_index = device_index
+        pool = Lanes._free.setdefault(device_index, [])
+        if pool:
+            self.handle = pool.pop()
+        else:
+            self.handle = ptr()
+            check(lib().gode_lanes_create(C.byref(self.handle)), "gode_lanes_create")
+        self.stream_ptr = lib().gode_lanes_stream(self.handle)
+
+    def __del__(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h and not sys.is_finalizing():
+            Lanes._free.setdefault(self.device_index, []).append(h)
+
+
+class LanesProgram(Program):
+    """A program whose ops [0, n_front) run on a Lanes object's side stream (gode_run_lanes); release_after: the last op
+    of the main lane that touches a buffer the front writes."""
+
+    def __init__(self, ops, n_front, release_after):
+        super().__init__(ops)
+        self.n_front, self.release_after = int(n_front), int(release_after)
+
+    def run_lanes(self, lanes, mode, stream):
+        global LAUNCHES
+        LAUNCHES += 1
+        check(lib().gode_run_lanes(lanes.handle, self.kinds, self.ptrs, self.n, self.n_front, self.release_after, mode,
+                                   stream), "gode_run_lanes")
+
+
 def run_one(op, stream):
+    global LAUNCHES
+    LAUNCHES += 1
     if op.KIND == OP_PACK:
         launch = lambda: check(lib().gode_pack_weights(C.byref(op.g), op.dir, op.w, op.wpack, op.co_perm, op.co_canon,  # noqa: E731
                                                        stream), "gode_pack_weights")

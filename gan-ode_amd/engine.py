@@ -62,6 +62,102 @@ def stream_ptr():
     return torch.cuda.current_stream().cuda_stream
 
 
+# -- two-lane sampling (gode_run_lanes): which op of the main lane releases the side lane ---------------------------------
+# The pointer fields through which the ops of a sampling front WRITE (every other pointer field of theirs is read only).
+_FRONT_WRITES = {L.OdeFwdOp: ("z", "traj"), L.IgemmOp: ("out", "stats", "work")}
+
+
+def op_pointers(op):
+    """Every non-null address an op struct holds, nested parameter blocks included."""
+    out = []
+    for name, tp in op._fields_:
+        v = getattr(op, name)
+        if tp is L.ptr:
+            if v:
+                out.append(v)
+        elif isinstance(v, C.Structure):
+            out += op_pointers(v)
+    return out
+
+
+def front_writes(front_ops, uses_work=lambda op: True):
+    """The addresses the front ops write.  uses_work(op): does this GEMM launch touch its split-K workspace (the stack's
+    GEMMs share one, so a front GEMM that does holds the side lane back until the last of them)?  An op kind without a
+    row in _FRONT_WRITES cannot be part of a front: ValueError."""
+    written = set()
+    for op in front_ops:
+        fields = _FRONT_WRITES.get(type(op))
+        if fields is None:
+            raise ValueError(f"{type(op).__name__} has no write set: it cannot run on the side lane")
+        for f in fields:
+            v = getattr(op, f)
+            if v and (f != "work" or uses_work(op)):
+                written.add(v)
+    return written
+
+
+def release_after(ops, n_front, written=None, extents=None):
+    """Index of the last main-lane op (ops[n_front:]) that holds an address inside a buffer the front (ops[:n_front])
+    writes: behind it the next call's front may overwrite those buffers.  No such op: the first main-lane op.  written: the
+    buffers' base addresses; extents: base address -> bytes (a buffer without an entry is matched by its base address alone,
+    so a caller whose ops address the inside of a buffer must give its extent)."""
+    if not 0 < n_front < len(ops):
+        raise ValueError(f"a two-lane program needs ops on both lanes (n_front={n_front} of {len(ops)})")
+    if written is None:
+        written = front_writes(ops[:n_front])
+    spans = [(a, a + max(1, (extents or {}).get(a, 1))) for a in written]
+    last = n_front
+    for i in range(n_front, len(ops)):
+        if any(lo <= p < hi for p in op_pointers(ops[i]) for lo, hi in spans):
+            last = i
+    return last
+
+
+LANE_SINGLE, LANE_ORDERED, LANE_OVERLAP = "single", "ordered", "overlap"
+
+
+def ring_back(i, n, back):
+    """Slot of a ring of n whose next slot is i that was filled `back` fills ago."""
+    return (i - back) % n
+
+
+def lane_gate(prev_lanes, prev_copy_pending, before_prev_copy_pending):
+    """lane_mode's gpu_behind for the default knob: is there a decoder to put this call's front under?  The evidence is
+    whether the staging copies of the previous call and of the call before it have completed (no such call: not pending).
+    With hysteresis, so that a host that is barely ahead does not switch back and forth -- every switch to two lanes starts
+    with an ORDERED call, which costs and hides nothing: a streak of lanes calls (prev_lanes) goes on while the GPU is one
+    call behind, and starts only when it is two behind."""
+    return bool(prev_copy_pending) if prev_lanes else bool(before_prev_copy_pending)
+
+
+def lane_mode(*, enabled, trace, recording, categorical, grad, keep, fixed_grid_ode, splittable, prev_lanes, launches_between,
+              repacked, versions_same, same_stream, gpu_behind=True):
+    """How a sampling call with host inputs runs.  "single": today's one-stream path.  "overlap": the front waits only for
+    the previous call's release; every condition of the second group must hold for it.  "ordered": the front waits for
+    everything queued on the caller's stream so far.
+      enabled        GODE_SAMPLE_LANES / gen.sample_lanes
+      trace          L.TRACE is set (ops are launched and timed one by one)
+      recording      the feed is recording a graph
+      categorical    dim_z_category > 0: the plan's `labels` leave with the caller
+      grad, keep     gradient mode is on / the plan is kept for a backward pass
+      fixed_grid_ode the latent is the fixed-grid ODE plan
+      splittable     the decoder program starts with its layer-0 GEMM
+      prev_lanes     this plan's previous forward was a lanes call
+      launches_between  libgode launches issued since then (Adam, another plan, a trainer)
+      repacked       a stale weight panel was re-packed in this call
+      versions_same  no tensor the front reads changed its version
+      same_stream    the caller's stream is the one the previous call ran on
+      gpu_behind     the previous call's staging copy has not completed yet: the GPU is at least one call behind the
+                     host, so there is a decoder to put the front under.  False (a caller that consumes every result
+                     before the next call): one stream -- two lanes would hide nothing and cost their event edges"""
+    if (not enabled or trace or recording or categorical or grad or keep or not fixed_grid_ode or not splittable
+            or not gpu_behind):
+        return LANE_SINGLE
+    if prev_lanes and launches_between == 0 and not repacked and versions_same and same_stream:
+        return LANE_OVERLAP
+    return LANE_ORDERED
+
+
 @dataclass
 class LayerSpec:
     geom: L.ConvGeom
@@ -248,6 +344,24 @@ class ConvStack:
                 stale.append(op)
         if stale:
             L.Program(stale).run(st)
+        return bool(stale)
+
+    def front_split(self, prog, pre_ops):
+        """The two-lane form of a forward program behind `pre_ops` (the latent solve): -> (ops, n_front, release_after) of
+        an L.LanesProgram, or None when the stack has no such form: layer 0 must be the program's first op, on a plan-owned
+        input, and the stack neither split nor grouped (their ops address parts of a buffer).  Front = pre_ops + the layer-0
+        GEMM.  The stack's own buffers the front writes count with their extents."""
+        first = prog.ops[0] if prog.ops else None
+        if (self.split or self.groups != 1 or self.noisy or self.x_in is None or len(prog.ops) < 2
+                or not isinstance(first, L.IgemmOp) or first.out != dptr(self.y[0])):
+            return None
+        lib = L.lib()
+        ops = list(pre_ops) + list(prog.ops)
+        n_front = len(pre_ops) + 1
+        written = front_writes(ops[:n_front], uses_work=lambda op: lib.gode_igemm_work_size(C.byref(op)) > 0)
+        extents = {t.data_ptr(): t.numel() * t.element_size()
+                   for t in (self.x_in, self.y[0], self.stats[0], self._ig_work) if t is not None}
+        return ops, n_front, release_after(ops, n_front, written, extents)
 
     @staticmethod
     def _ncols(s: LayerSpec):
@@ -570,6 +684,17 @@ class ConvStack:
         """Runs the stack.  x (+ element strides {N,D,H,W,C}) is required when the plan does not own its input; a
         grouped stack takes the second group's tensor as x2.  Returns the freshly allocated last-layer output
         [N,D,H,W,C] (grouped: N = both groups, first group first)."""
+        prog, out, _ = self.begin_forward(training, x, x_strides, x2, x2_strides, noise)
+        st = stream_ptr()
+        if pre_ops_program is not None:
+            pre_ops_program.run(st)
+        prog.run(st)
+        return self.end_forward(out, training)
+
+    def begin_forward(self, training: bool, x=None, x_strides=None, x2=None, x2_strides=None, noise=None):
+        """forward() up to the launch: the program patched for this call and its stale weight panels re-packed on the
+        current stream -> (program, the output tensor, were panels re-packed).  The caller launches the program (forward()
+        itself; the two-lane sampling path of modules._GenPlan) and hands the output to end_forward."""
         self._refresh()
         if training not in self._fwd:
             self._fwd[training] = self._build_fwd(training)
@@ -598,12 +723,10 @@ class ConvStack:
                     for i in range(5):
                         second.gs[i] = int(x2_strides[i])
                 self._x2_user, self._x2_strides = x2.detach(), tuple(int(v) for v in x2_strides)
-        st = stream_ptr()
-        self._run_stale_packs(patch["packs"], st)
-        if pre_ops_program is not None:
-            pre_ops_program.run(st)
-        prog.run(st)
-        self.out = out.detach()      # `out` itself becomes the autograd node's output: holding it would be a cycle
+        return prog, out, self._run_stale_packs(patch["packs"], stream_ptr())
+
+    def end_forward(self, out, training):
+        self.out = out.detach()     # `out` itself becomes the autograd node's output: holding it would be a cycle
         self.generation += 1
         self._fwd_training = training
         return out

@@ -11,8 +11,10 @@ through the HIP kernels and raises if the tensors are not on the GPU or libgode.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
+import os
 from typing import Optional
 
 import numpy as np
@@ -20,12 +22,16 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import ConvStack, LayerParams, LayerSpec, conv_out, dptr, make_geom, stream_ptr
+from .engine import (LANE_ORDERED, LANE_OVERLAP, LANE_SINGLE, ConvStack, LayerParams, LayerSpec, conv_out, dptr, lane_gate,
+                     lane_mode, make_geom, ring_back, stream_ptr)
 
 Z_COLS = 96  # latent row: [motion 16 | content 50 | zero pad 30]: K % 32 == 0 puts the first decoder GEMM on the FAST path
 Z_CATEG0 = 66        # dim_z_category = C > 0: the one-hot lives in the first C pad columns (gode_categ_onehot)
 MAX_CATEG = Z_COLS - Z_CATEG0
 ODE_METHODS = L.ODE_METHODS      # gen.ode_method -> the latent ops' `method` code
+# GODE_SAMPLE_LANES=0 (read once): no-grad sampling calls stay on one stream (_GenPlan._forward_lanes); per generator:
+# gen.sample_lanes = False
+_SAMPLE_LANES_ENV = os.environ.get("GODE_SAMPLE_LANES", "1") != "0"
 
 
 def ode_method_code(name):
@@ -310,6 +316,18 @@ class _GenPlan:
         self._alloc()
         self._ode_ptrs = None
         self.busy = False
+        # two-lane sampling (_forward_lanes): the gode_lanes object and its side stream, the cached two-lane program, what
+        # the previous call saw (None: it was no lanes call), and the calls counted by the path they took
+        self._lanes = self._side = self._lane_prog = self._lane_prev = None
+        self.lane_calls = {LANE_OVERLAP: 0, LANE_ORDERED: 0, LANE_SINGLE: 0}
+        # The one kind of plan that can take the two lanes gets its lanes object now, not at its first lanes call: the side
+        # stream takes its hardware queue when it is created, and measured a stream created behind a
+        # replayed training graph sat on the caller's queue, 17 us per step slower than one stream.  With gen.sample_lanes
+        # off at this point the object is made at the plan's first lanes call after the switch (_lanes_possible).
+        self._lanes_ok = type(self) is _GenPlan and self.stack is not None and not self.ncat and _SAMPLE_LANES_ENV
+        self.lanes_made_late = False
+        if self._lanes_ok and gen.sample_lanes:
+            self._make_lanes()
 
     @staticmethod
     def _x_shape(n_traj, T):
@@ -443,17 +461,118 @@ class _GenPlan:
                 slot["ev"] = torch.cuda.Event()
             slot["ev"].record()
 
-    def forward(self, x_host, content_host, sel_host, training, keep, cls_host=None):
+    def forward(self, x_host, content_host, sel_host, training, keep, cls_host=None, no_grad=False):
         """x_host None: the latent rows of this call were produced ahead of time by VideoGenerator.prefetch_latents (on
-        its own stream); only the decoder runs here, after the latent's event."""
+        its own stream); only the decoder runs here, after the latent's event.  no_grad: the caller's gradient mode is off
+        (inside an autograd Function it always is, so the caller has to say)."""
         if x_host is None:
             torch.cuda.current_stream().wait_event(self._latent_ev)
             out = self.stack.forward(training)
+            self._lane_prev = None
+        elif self._lanes_possible(keep, no_grad):
+            out = self._forward_lanes(x_host, content_host, sel_host, training)
         else:
             self.stage_inputs(x_host, content_host, sel_host, cls_host)
             out = self.stack.forward(training, pre_ops_program=self.fwd_prog)
+            self._lane_prev = None
+            self.lane_calls[LANE_SINGLE] += 1
         self.busy = keep
         return out
+
+    # -- two-lane sampling: the next call's front under this call's decoder ------------------------------------------------
+    # A no-grad sampling call's H2D copy, latent solve and layer-0 GEMM (the front) depend on nothing the previous call
+    # computed, and write only buffers of this plan: _in, the latent rows, y[0], stats[0].  They go to the side stream of a
+    # gode_lanes object, where they wait for the previous call's LAST READER of those buffers (release_after) instead of
+    # its last kernel -- so in a loop of calls they run under the previous decoder's GEMMs.  BatchNorm finalize of layer 0
+    # stays on the caller's stream: it read-modify-writes the module's running statistics, which a state_dict() clone queued
+    # between two calls must see as it does on one stream.  Same kernels on the same inputs: bit-identical.
+    # Only a call that finds the GPU behind the host takes the two lanes (lane_mode's gpu_behind): a caller that consumes
+    # each result before its next call stays on one stream.
+    def _lanes_possible(self, keep, no_grad):
+        """The conditions of lane_mode's first group that are known before the decoder pass is prepared, cheapest first."""
+        gen = self.gen
+        if (not no_grad or keep or not gen.sample_lanes or gen._one_stream or not self._lanes_ok or L.TRACE is not None
+                or gen.ode_method == "dopri5"):
+            return False
+        # lane_mode's gpu_behind (engine.lane_gate), asked before anything dearer so that a call on an idle GPU pays two
+        # event queries and nothing else
+        if gen.sample_lanes != "always" and not lane_gate(self._lane_prev is not None, self._copy_pending(1),
+                                                          self._copy_pending(2)):
+            return False
+        feed = getattr(gen, "_feed", None)
+        if (feed is not None and feed.recording) or torch.cuda.is_current_stream_capturing():
+            return False
+        if self._lanes is None:
+            # the plan was built with gen.sample_lanes off: its side stream takes whatever hardware queue is the least used
+            # NOW, which may be the caller's (see __init__); gen.lane_stats() counts such late objects
+            self._make_lanes()
+            self.lanes_made_late = True
+        return True
+
+    def _copy_pending(self, back):
+        """Has the staging copy of the call `back` calls ago (1: the previous one) not completed yet?"""
+        ev = self._ring[ring_back(self._ring_i, len(self._ring), back)]["ev"]
+        return ev is not None and not ev.query()
+
+    def _make_lanes(self):
+        with torch.cuda.device(self.device):
+            self._lanes = L.Lanes(torch.cuda.current_device())
+        self._side = torch.cuda.ExternalStream(self._lanes.stream_ptr, device=self.device)
+
+    def _front_versions(self):
+        """What tells that a tensor the front reads was written: the ODE function's and the pre-net's parameters, and the
+        layer-0 weight (torch's version counter, FusedAdam's, the storage).  A write through `.data` shows in none of them:
+        VideoGenerator.invalidate_packs is the call that tells."""
+        ts = [t for t in self._params() if t is not None] + [self.stack.params[0].weight]
+        return tuple((t._version, getattr(t, "_gode_ver", 0), t.data_ptr()) for t in ts)
+
+    def _forward_lanes(self, x_host, content_host, sel_host, training):
+        """forward() of a call that _lanes_possible let through: the mode is decided once, behind begin_forward."""
+        self._programs()
+        prev, self._lane_prev = self._lane_prev, None        # (an exception below leaves the next call ORDERED)
+        between = L.LAUNCHES - prev["mark"] if prev is not None else -1
+        prog, out, repacked = self.stack.begin_forward(training)
+        st = stream_ptr()
+        cache = self._lane_prog
+        if cache is None or cache[0] is not prog or cache[1] is not self.fwd_prog:
+            # a rebuilt latent program comes with new grid tensors, uploaded on the caller's stream: no overlap past them
+            split = self.stack.front_split(prog, self.fwd_prog.ops)
+            cache = self._lane_prog = (prog, self.fwd_prog, None if split is None else L.LanesProgram(*split))
+            prev = None
+        lp = cache[2]
+        versions = self._front_versions()
+        mode = lane_mode(enabled=True, trace=False, recording=False, categorical=False, grad=False, keep=False,
+                         fixed_grid_ode=True, splittable=lp is not None, prev_lanes=prev is not None,
+                         launches_between=between, repacked=repacked,
+                         versions_same=prev is not None and prev["versions"] == versions,
+                         same_stream=prev is not None and prev["stream"] == st,
+                         gpu_behind=True)
+        self.lane_calls[mode] += 1
+        if mode == LANE_SINGLE:
+            self.stage_inputs(x_host, content_host, sel_host)
+            self.fwd_prog.run(st)
+            prog.run(st)
+        else:
+            self._stage_on_side(mode == LANE_ORDERED, x_host, content_host, sel_host)
+            lp.run_lanes(self._lanes, L.LANES_OVERLAP if mode == LANE_OVERLAP else L.LANES_ORDERED, st)
+            self._lane_prev = dict(mark=L.LAUNCHES, versions=versions, stream=st)
+        return self.stack.end_forward(out, training)
+
+    def _stage_on_side(self, ordered, x_host, content_host, sel_host):
+        """stage_inputs' ring copy on the side lane.  _in is read by the side lane only, so the copy needs no edge of its own
+        behind a lanes call; behind anything else (ordered) the last reader may sit on the caller's stream."""
+        slot = self._ring[self._ring_i]
+        self._ring_i = (self._ring_i + 1) % len(self._ring)
+        if slot["ev"] is not None:
+            slot["ev"].synchronize()
+        _pack_inputs(slot["buf"], x_host, content_host, sel_host)
+        if ordered:
+            self._side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self._side):
+            self._in.copy_(slot["buf"], non_blocking=True)
+            if slot["ev"] is None:
+                slot["ev"] = torch.cuda.Event()
+            slot["ev"].record()
 
     def _decoder_pass_done(self):
         """The trainer may ask to be told when the LAST decoder backward of a generator step has been queued (the decoder
@@ -610,8 +729,8 @@ class _GenFn(torch.autograd.Function):
     """Whole generator pass (pre-net + RK4 + decoder) as one autograd node; backward = decoder backward + adjoint."""
 
     @staticmethod
-    def forward(ctx, plan, x_host, content_host, sel_host, cls_host, training, keep, n_dec, *params):
-        out = plan.forward(x_host, content_host, sel_host, training, keep, cls_host)
+    def forward(ctx, plan, x_host, content_host, sel_host, cls_host, training, keep, no_grad, n_dec, *params):
+        out = plan.forward(x_host, content_host, sel_host, training, keep, cls_host, no_grad=no_grad)
         ctx.plan, ctx.n_dec, ctx.n_params = plan, n_dec, len(params)
         ctx.lease = _Lease(plan)
         return out
@@ -620,7 +739,7 @@ class _GenFn(torch.autograd.Function):
     def backward(ctx, gout):
         plan = ctx.plan
         ctx.lease.check(type(plan.gen).__name__)
-        return _gen_backward(ctx, plan, gout, 8)
+        return _gen_backward(ctx, plan, gout, 9)
 
 
 class _LatentFn(torch.autograd.Function):
@@ -651,6 +770,11 @@ class VideoGenerator(nn.Module):
 
     mnist = False
     _plan_cls = None   # set below (_GenPlan)
+    # no-grad sampling calls (_GenPlan._forward_lanes): True -- two lanes whenever a call finds the GPU behind the host;
+    # "always" -- also on an idle GPU (tests: the mode then depends on no timing); False -- one stream (A/B runs).  Read
+    # at every call; a plan built while it is False makes its lanes object at its first lanes call after the switch.
+    sample_lanes = True
+    _one_stream = 0            # > 0: inside one_stream()
     _categorical_ok = True     # dim_z_category > 0 is served (the other motion latents switch it off)
     _one_layer_ok = True       # ode_fn=ODEFuncTanh is served (the ODE-RNN generator, whose kernels are two-layer, refuses it)
     # the reference passes method='rk4' (models/mocogan_ode.py:50,144); 'dopri5' is what BASELINE configs[3] words;
@@ -797,13 +921,44 @@ class VideoGenerator(nn.Module):
             self.__dict__.pop("_prefetched", None)
         return r
 
+    def lane_stats(self):
+        """How this generator's no-grad sampling calls ran, summed over its plans: {"overlap", "ordered", "single"} -> calls,
+        and how many plans hold a lanes object (made late: after the plan, on a switch of sample_lanes to a true value).
+        A loop of calls that counts overlaps but gains nothing has its side stream on the caller's hardware queue (the
+        runtime shares a few queues among all streams of the process): two lanes then only cost; sample_lanes = False."""
+        out = {LANE_OVERLAP: 0, LANE_ORDERED: 0, LANE_SINGLE: 0, "lanes_objects": 0, "lanes_objects_made_late": 0}
+        for plans in self._pool.plans.values():
+            for p in plans:
+                for k, v in getattr(p, "lane_calls", {}).items():
+                    out[k] += v
+                out["lanes_objects"] += getattr(p, "_lanes", None) is not None
+                out["lanes_objects_made_late"] += bool(getattr(p, "lanes_made_late", False))
+        return out
+
+    @contextlib.contextmanager
+    def one_stream(self):
+        """Sampling calls inside stay on the caller's stream, as with sample_lanes = False (the trainers' discriminator
+        steps, whose generator calls always follow other launches)."""
+        self._one_stream += 1
+        try:
+            yield
+        finally:
+            self._one_stream -= 1
+
     def invalidate_packs(self):
-        """Call after writing conv weights behind autograd's back (`p.data.copy_()`, `p.data.clamp_()`,
-        `dist.broadcast(p.data)`): such writes bump neither torch's version counter nor FusedAdam's, so the packed
-        weight panels would stay stale.  In-place ops on the parameter itself, optimiser steps, load_state_dict and
-        .to()/.cuda() are tracked automatically."""
+        """Call after writing ANY parameter of the generator behind autograd's back (`p.data.copy_()`, `p.data.clamp_()`,
+        `dist.broadcast(p.data)`): such writes bump neither torch's version counter nor FusedAdam's.  Conv weights: the
+        packed weight panels would stay stale.  The ODE function's and the pre-net's parameters and the first conv weight:
+        a two-lane sampling call (_GenPlan._forward_lanes) would let its front, which reads them, start under the
+        previous call's decoder, ahead of a write queued on the caller's stream in between; after this call the next
+        sampling call of every plan orders its front behind everything queued.  In-place ops on the parameter itself,
+        optimiser steps, load_state_dict and .to()/.cuda() are tracked automatically."""
         for k in [k for k in self._pool.pack_cache if k[0] == "ver"]:
             del self._pool.pack_cache[k]
+        for plans in self._pool.plans.values():
+            for p in plans:
+                if getattr(p, "_lane_prev", None) is not None:
+                    p._lane_prev = None
 
     def _zero_labels(self, n, device):
         """np.zeros(B) -> torch.from_numpy -> .cuda() of the reference (models/mocogan.py:235,279): float64 zeros,
@@ -836,7 +991,8 @@ class VideoGenerator(nn.Module):
         dec, ode = self._param_list()
         # (grad mode is off inside Function.forward, so decide here whether the plan must be kept for a backward)
         keep = torch.is_grad_enabled() and any(p.requires_grad for p in dec + ode)
-        return _GenFn.apply(plan, x, content, sel, cls, self.training, keep, len(dec), *dec, *ode)
+        no_grad = not torch.is_grad_enabled()
+        return _GenFn.apply(plan, x, content, sel, cls, self.training, keep, no_grad, len(dec), *dec, *ode)
 
     # -- latents ahead of time ----------------------------------------------------------------------------------------
     def prefetch_latents(self, calls):
@@ -1655,7 +1811,7 @@ class _CdeGenPlan(_GenPlan):
                                "size underflowed; raise cde_max_steps or loosen cde_rtol / cde_atol")
         return c
 
-    def forward(self, x_host, content_host, sel_host, training, keep, cls_host=None):
+    def forward(self, x_host, content_host, sel_host, training, keep, cls_host=None, no_grad=False):
         if x_host is None:                     # prefetched (checked by _launch_latents)
             return super().forward(None, content_host, sel_host, training, keep)
         self.stage_inputs(x_host, content_host, sel_host, cls_host)

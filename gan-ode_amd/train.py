@@ -1020,6 +1020,11 @@ class GanTrainer:
             model._noise_call = call0
             model._noise_sample_offset = (self.rank * nsh + k) * B
 
+    def _gen_one_stream(self):
+        """The discriminator steps' no-grad generator calls keep the one-stream path (VideoGenerator.one_stream): each
+        follows other launches, so two lanes could hide nothing and would only add their event edges."""
+        return getattr(self.gen, "one_stream", contextlib.nullcontext)()
+
     def d_image_step(self, real_img, _join=True, _defer=False, _pair_videos=0):
         """mnist_moco_ode.py:115-131.  real_img: [B,C,H,W], or a list of such shards (virtual replicas).
         _pair_videos (step() only): the batch size of the d_video_step that follows -- its fake videos are generated here,
@@ -1041,7 +1046,7 @@ class GanTrainer:
             if not self.pair_d:
                 with on_side():
                     pr, _ = self.dis_img(x)
-            with torch.no_grad():                        # generator work stays on the caller's stream
+            with torch.no_grad(), self._gen_one_stream():    # generator work stays on the caller's stream
                 if _pair_videos:
                     self._paired_fake_vid, (fake, _) = self.gen.sample_pair(_pair_videos, B, images_first=True)
                 else:
@@ -1107,7 +1112,7 @@ class GanTrainer:
                 begun = True
             if not self.pair_d:
                 pr = self.dis_vid.forward_head(real) if self.ncat else self.dis_vid(real)[0]
-            with torch.no_grad():
+            with torch.no_grad(), self._gen_one_stream():
                 fake, self._paired_fake_vid = self._paired_fake_vid, None
                 if fake is not None:                     # generated by the d_image_step before (see _pair_videos)
                     fake = fake[0]

@@ -7,7 +7,8 @@
  *
  * Conventions
  *  - plain pointers and sizes only; every pointer is DEVICE memory owned by the caller (PyTorch's allocator);
- *    the library never allocates, frees or keeps memory and has no mutable global state;
+ *    the library never allocates, frees or keeps memory and has no mutable global state (the one object it owns is
+ *    the caller-created lanes object of the two-lane runner: a stream and three events, no device memory);
  *  - every call only ENQUEUES work on `stream` (a hipStream_t passed as void*) and never synchronises;
  *  - return value: 0 ok, <0 argument error (GODE_E_*), >0 a hipError_t from a launch;
  *  - activations are channels-last fp32: [N][D][H][W][C]; weights stay in PyTorch's canonical layout
@@ -887,6 +888,31 @@ typedef struct gode_pack_op {
   gode_conv_geom g; int32_t dir /* may carry GODE_PACK_BORDER */, co_canon; const float* w; float* wpack; const int32_t* co_perm;
 } gode_pack_op;
 int gode_run(const int32_t* kinds, const void* const* ops, int32_t n, void* stream);
+
+/* ---- two-lane runner: the front of a program on a side stream --------------------------------------------------
+ * A program whose first n_front ops depend on nothing the PREVIOUS program on `stream` computed (a sampling call's noise
+ * upload, latent solve and first GEMM) can run them under that program's tail.  A lanes object -- the one piece of state
+ * the library owns: a non-blocking side stream and three events without timing -- carries the ordering from call to call:
+ *   ops [0, n_front) go to the side stream, which then records ev_front; `stream` waits for ev_front and runs ops
+ *   [n_front, n); behind op `release_after` (the last op on `stream` that touches a buffer the side lane writes) `stream`
+ *   records ev_release.
+ *   mode GODE_LANES_OVERLAP: the side lane first waits for the ev_release of the previous call on this object, and for
+ *   nothing else -- the caller vouches that nothing but that call's ops [n_front, release_after] uses what the front
+ *   writes, and that nothing queued since then writes what the front reads.
+ *   mode GODE_LANES_ORDERED: the side lane first waits for an event recorded on `stream` at entry, i.e. for everything
+ *   queued so far.  The first call on an object, and the call after one that failed, is ORDERED whatever `mode` says.
+ * Runs of consecutive pack ops are batched and error codes carry the op index as in the one-stream runner.  Argument errors
+ * (a null object, n_front > n, release_after outside [n_front, n), an unknown mode) return GODE_E_ARG before any HIP call.
+ * A `stream` that is being captured takes all n ops itself, in order: a capture never forks.
+ * The stream handle lets the caller put its own work (the H2D copy of the front's input) on the side lane ahead of a call.
+ * Destroying the object drains the side stream first. */
+typedef struct gode_lanes gode_lanes;
+enum { GODE_LANES_ORDERED = 0, GODE_LANES_OVERLAP = 1 };
+int gode_lanes_create(gode_lanes** out);
+int gode_lanes_destroy(gode_lanes* lanes);
+void* gode_lanes_stream(gode_lanes* lanes);
+int gode_run_lanes(gode_lanes* lanes, const int32_t* kinds, const void* const* ops, int32_t n, int32_t n_front,
+                   int32_t release_after, int32_t mode, void* stream);
 
 int gode_version(void);
 /* size of every op struct as compiled, so the ctypes mirror can assert it matches (index = GODE_OP_*; -1: the
