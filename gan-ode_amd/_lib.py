@@ -30,6 +30,8 @@ OP_CHSTATS, OP_CBN_EMBED, OP_CBN_EMBED_BWD, OP_CBN_APPLY, OP_CBN_BWD, OP_GRES_OU
 OP_FC_ACT, OP_FC_ACT_BWD, OP_BCE_PROB = 33, 34, 35
 OP_BCE_T = 36
 OP_RESIZE_U8, OP_CLIP_GATHER = 37, 38
+OP_BN_RUNNING = 39
+BN_RUNNING_MAX = 8            # GODE_BN_RUNNING_MAX: the layers one gode_bn_running launch takes
 RESIZE_MAX_TAPS = 32          # GODE_RESIZE_MAX_TAPS: the longest tap row gode_resize_u8 takes
 REC_ADAM_NOISE = -1          # gode_sizeof index of the gode_adam_noise_tensor table record
 ODE_NPARAM = 2672
@@ -92,8 +94,18 @@ class BnFinalizeOp(_Op):
                 ("beta", ptr), ("running_mean", ptr), ("running_var", ptr), ("num_batches_tracked", ptr),
                 ("mean", ptr), ("invstd", ptr), ("scale", ptr), ("shift", ptr), ("momentum", f32), ("eps", f32),
                 ("training", i32), ("pad_", i32), ("groups", i32), ("rows0", i32), ("nseg", i32), ("order", i32),
-                ("count1", i64), ("seg", i32 * 24), ("stats1", ptr), ("rows1", i32), ("pad3_", i32)]
+                ("count1", i64), ("seg", i32 * 24), ("stats1", ptr), ("rows1", i32), ("pad3_", i32), ("batch_var", ptr)]
     KIND, FN = OP_BN_FINALIZE, "gode_bn_finalize"
+
+
+class BnRunningLayer(C.Structure):
+    _fields_ = [("mean", ptr), ("var", ptr), ("running_mean", ptr), ("running_var", ptr), ("num_batches_tracked", ptr),
+                ("C", i32), ("pad_", i32)]
+
+
+class BnRunningOp(_Op):
+    _fields_ = [("layer", BnRunningLayer * BN_RUNNING_MAX), ("n", i32), ("momentum", f32)]
+    KIND, FN = OP_BN_RUNNING, "gode_bn_running"
 
 
 class BnBwdOp(_Op):
@@ -397,6 +409,7 @@ _PROTOS = {
     "gode_lanes_destroy": ([ptr], cint),
     "gode_lanes_stream": ([ptr], ptr),
     "gode_run_lanes": ([ptr, ptr, ptr, i32, i32, i32, i32, ptr], cint),
+    "gode_run_pair": ([ptr, ptr, ptr, ptr, i32, i32, i32, ptr], cint),
     "gode_version": (None, cint),
     "gode_sizeof": ([cint], cint),
 }
@@ -504,6 +517,21 @@ class Lanes:
             check(lib().gode_lanes_create(C.byref(self.handle)), "gode_lanes_create")
         self.stream_ptr = lib().gode_lanes_stream(self.handle)
 
+    _shared = {}
+
+    @classmethod
+    def shared(cls, device_index, second):
+        """The device's two lanes objects, shared by every plan: one for first plans, one for the SECOND plan of a pair
+        (gode_run_pair).  Streams are few -- the runtime spreads them over a handful of hardware queues, and one more stream
+        in a process cost its generator step 2-5 % -- and sharing is safe: a call overlaps only when no
+        libgode launch was issued since the same plan's previous call, so two plans never interleave on an object without an
+        ordered call in between, which waits for everything queued and for no state the object carries.  Call with
+        `device_index` current."""
+        key = (device_index, bool(second))
+        if key not in cls._shared:
+            cls._shared[key] = cls(device_index)
+        return cls._shared[key]
+
     def __del__(self):
         h, self.handle = getattr(self, "handle", None), None
         if h and not sys.is_finalizing():
@@ -523,6 +551,21 @@ class LanesProgram(Program):
         LAUNCHES += 1
         check(lib().gode_run_lanes(lanes.handle, self.kinds, self.ptrs, self.n, self.n_front, self.release_after, mode,
                                    stream), "gode_run_lanes")
+
+
+class PairProgram(Program):
+    """A program that runs on a Lanes object's own stream but for its last n_tail ops (gode_run_pair): the next call's
+    program, on the peer object, runs next to it."""
+
+    def __init__(self, ops, n_tail=1):
+        super().__init__(ops)
+        self.n_tail = int(n_tail)
+
+    def run_pair(self, lanes, peer, mode, stream):
+        global LAUNCHES
+        LAUNCHES += 1
+        check(lib().gode_run_pair(lanes.handle, None if peer is None else peer.handle, self.kinds, self.ptrs, self.n,
+                                  self.n_tail, mode, stream), "gode_run_pair")
 
 
 def run_one(op, stream):

@@ -59,6 +59,7 @@ struct gode_lanes {
   hipStream_t side;
   hipEvent_t ev_entry, ev_front, ev_release;
   bool released;      // ev_release holds the record of a call that went through: OVERLAP may wait for it
+  bool entered;       // pair mode: ev_entry holds the record of a pair call's entry, a peer's OVERLAP may wait for it
 };
 
 #define GODE_HIP_TRY(expr)                          \
@@ -121,6 +122,7 @@ extern "C" int gode_run_lanes(gode_lanes* l, const int32_t* kinds, const void* c
     (void)hipGetLastError();
     cap = hipStreamCaptureStatusActive;
   }
+  l->entered = false;                    // (ev_entry is about to hold something other than a pair call's entry)
   if (cap != hipStreamCaptureStatusNone) {
     l->released = false;
     return run_range(kinds, ops, 0, n, stream);
@@ -144,4 +146,38 @@ extern "C" int gode_run_lanes(gode_lanes* l, const int32_t* kinds, const void* c
   rc = run_range(kinds, ops, release_after + 1, n, stream);
   if (rc != 0) l->released = false;
   return rc;
+}
+
+// ---- pair mode: two whole programs in flight, on two lanes objects used in turn ---------------------------------------------
+// Everything but the program's tail (its gode_bn_running op) runs on the object's own stream; the tail runs on the caller's
+// stream behind the lane's last op.  Of the object's events, ev_entry is the caller's stream at this call's entry and ev_front
+// the lane behind its last op.  The lane of call m waits for the entry event of call m-1 (the peer's): the programs of calls
+// m-1 and m then run side by side, while everything the caller queued before call m-1 -- readers of result m-2, the tail of
+// call m-2, both users of the buffers call m writes -- has run.
+extern "C" int gode_run_pair(gode_lanes* l, gode_lanes* peer, const int32_t* kinds, const void* const* ops, int32_t n,
+                             int32_t n_tail, int32_t mode, void* stream) {
+  if (!l || peer == l || n < 2 || !kinds || !ops || n_tail < 1 || n_tail >= n ||
+      (mode != GODE_LANES_ORDERED && mode != GODE_LANES_OVERLAP))
+    return GODE_E_ARG;
+  hipStream_t main = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(main, &cap) != hipSuccess) {
+    (void)hipGetLastError();
+    cap = hipStreamCaptureStatusActive;
+  }
+  l->released = false;                   // (a two-lane call on this object starts ORDERED)
+  l->entered = false;                    // an error below leaves the peer's next call ORDERED
+  if (cap != hipStreamCaptureStatusNone) return run_range(kinds, ops, 0, n, stream);
+  const bool overlap = mode == GODE_LANES_OVERLAP && peer && peer->entered;
+  GODE_HIP_TRY(hipEventRecord(l->ev_entry, main));
+  GODE_HIP_TRY(hipStreamWaitEvent(l->side, overlap ? peer->ev_entry : l->ev_entry, 0));
+  int rc = run_range(kinds, ops, 0, n - n_tail, (void*)l->side);
+  // (also behind an op that failed: whatever the lane did take stays in front of the caller's next command)
+  GODE_HIP_TRY(hipEventRecord(l->ev_front, l->side));
+  GODE_HIP_TRY(hipStreamWaitEvent(main, l->ev_front, 0));
+  if (rc != 0) return rc;
+  rc = run_range(kinds, ops, n - n_tail, n, stream);
+  if (rc != 0) return rc;
+  l->entered = true;
+  return 0;
 }

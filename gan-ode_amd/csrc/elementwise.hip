@@ -8,6 +8,23 @@
 
 // ---------------------------------------------------------------------------------------------------------------
 // BatchNorm finalize
+// The momentum update of the running statistics with its roundings pinned: under -ffp-contract=fast the compiler is free to
+// fuse `(1 - m) * run + m * batch` either way, and it chose differently for the two tensors (the mean: two rounded products
+// and an add; the variance: one rounded product and a fused multiply-add).  These helpers switch contraction OFF and state
+// the one fused operation explicitly, so that choice no longer rests with the compiler.  gode_bn_running applies the same
+// update from a deferred finalize's slots and must give the same bits, so both kernels call these.
+__device__ __forceinline__ float bn_running_mean_update(float run, float momentum, float batch_mean) {
+#pragma clang fp contract(off)
+  const float keep = (1.f - momentum) * run;
+  const float add = momentum * batch_mean;
+  return add + keep;
+}
+__device__ __forceinline__ float bn_running_var_update(float run, float momentum, float unbiased) {
+#pragma clang fp contract(off)
+  const float keep = (1.f - momentum) * run;
+  return __builtin_fmaf(momentum, unbiased, keep);
+}
+
 __global__ void __launch_bounds__(256) bn_finalize_kernel(const gode_bn_finalize_op a) {
   const int c = blockIdx.x, tid = threadIdx.x;
   __shared__ double red[2][256];
@@ -60,12 +77,18 @@ __global__ void __launch_bounds__(256) bn_finalize_kernel(const gode_bn_finalize
         const int o = grp * a.C + c;
         a.mean[o] = (float)mean; a.invstd[o] = invstd;
         a.scale[o] = sc; a.shift[o] = b - (float)mean * sc;
-        if (a.running_mean) {
-          const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
-          a.running_mean[c] = (1.f - a.momentum) * a.running_mean[c] + a.momentum * (float)mean;
-          a.running_var[c] = (1.f - a.momentum) * a.running_var[c] + a.momentum * (float)unbiased;
+        if (a.batch_var) {
+          // deferred form: the unbiased variance goes to the slot (the mean already is in mean[]); gode_bn_running applies
+          // the momentum updates later, the running tensors and num_batches_tracked are not touched here
+          a.batch_var[c] = (float)(n > 1.0 ? var * n / (n - 1.0) : var);
+        } else {
+          if (a.running_mean) {
+            const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
+            a.running_mean[c] = bn_running_mean_update(a.running_mean[c], a.momentum, (float)mean);
+            a.running_var[c] = bn_running_var_update(a.running_var[c], a.momentum, (float)unbiased);
+          }
+          if (c == 0 && a.num_batches_tracked) *a.num_batches_tracked += 1;
         }
-        if (c == 0 && a.num_batches_tracked) *a.num_batches_tracked += 1;
       }
     }
   } else if (tid == 0) {
@@ -92,7 +115,35 @@ extern "C" int gode_bn_finalize(const gode_bn_finalize_op* op, void* stream) {
     for (int i = 0; op->groups == 2 && i < op->nseg; ++i)
       if (!(0 <= op->seg[3 * i] && op->seg[3 * i] <= op->seg[3 * i + 1] && op->seg[3 * i + 1] <= op->seg[3 * i + 2] && op->seg[3 * i + 2] <= op->rows)) return GODE_E_ARG;
   } else if (!op->running_mean || !op->running_var) return GODE_E_ARG;
+  // the deferred form serves one training-mode batch: no groups, no segments, no eval mode
+  if (op->batch_var && (!op->training || op->groups == 2 || op->nseg != 0 || op->stats1)) return GODE_E_ARG;
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(op->C), dim3(256), 0, (hipStream_t)stream, *op);
+  GODE_LAUNCH_CHECK();
+  return 0;
+}
+
+// The momentum updates a run of deferred finalizes left out, all layers of a stack in one launch: one workgroup, layers in
+// order, a thread per channel.  Same operations on the same floats as the in-place form (bn_running_*_update).
+__global__ void __launch_bounds__(256) bn_running_kernel(const gode_bn_running_op a) {
+  for (int l = 0; l < a.n; ++l) {
+    const gode_bn_running_layer& y = a.layer[l];
+    if (y.running_mean)
+      for (int c = threadIdx.x; c < y.C; c += 256) {
+        y.running_mean[c] = bn_running_mean_update(y.running_mean[c], a.momentum, y.mean[c]);
+        y.running_var[c] = bn_running_var_update(y.running_var[c], a.momentum, y.var[c]);
+      }
+    if (threadIdx.x == 0 && y.num_batches_tracked) *y.num_batches_tracked += 1;
+    __syncthreads();     // (two rows may name the same module: its updates then apply in row order)
+  }
+}
+
+extern "C" int gode_bn_running(const gode_bn_running_op* op, void* stream) {
+  if (!op || op->n <= 0 || op->n > GODE_BN_RUNNING_MAX) return GODE_E_ARG;
+  for (int l = 0; l < op->n; ++l) {
+    const gode_bn_running_layer& y = op->layer[l];
+    if (y.C <= 0 || (y.running_mean && (!y.running_var || !y.mean || !y.var))) return GODE_E_ARG;
+  }
+  hipLaunchKernelGGL(bn_running_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *op);
   GODE_LAUNCH_CHECK();
   return 0;
 }

@@ -158,6 +158,34 @@ def lane_mode(*, enabled, trace, recording, categorical, grad, keep, fixed_grid_
     return LANE_ORDERED
 
 
+# -- pair mode (gode_run_pair): two decoder passes in flight on two plans used in turn -------------------------------------
+def pair_turn(prev_turn):
+    """Which of a pair of plans (0: the first, the one every one-stream call uses) takes the next pair call: the other one
+    than the previous pair call's; 0 when the previous forward was no pair call (prev_turn None)."""
+    return 0 if prev_turn is None else 1 - prev_turn
+
+
+def pair_wait(turn, overlap):
+    """Whose entry event the lane of a pair call waits for: the peer's -- recorded at the entry of the previous call, which
+    ran on the peer -- when the call overlaps, its own (recorded at this call's entry) when it is ordered."""
+    return 1 - turn if overlap else turn
+
+
+def pair_schedule(calls):
+    """The bookkeeping of a run of pair calls as modules._GenPlan and the runner do it, for the host tests.  calls[m] =
+    (fresh, may_overlap): fresh -- the previous forward was no pair call (the streak starts afresh at plan 0);
+    may_overlap -- lane_mode's second group holds.  -> [(plan, call whose entry event the lane waits for)], calls counted
+    from 0: m itself for an ordered call, m - 1 for one that overlaps."""
+    out, entry, prev = [], {}, None
+    for m, (fresh, may_overlap) in enumerate(calls):
+        turn = pair_turn(None if fresh else prev)
+        overlap = bool(may_overlap) and not fresh and (1 - turn) in entry     # (the runner: the peer's event holds a record)
+        entry[turn] = m                      # the caller's stream records this object's entry event
+        out.append((turn, entry[pair_wait(turn, overlap)]))
+        prev = turn
+    return out
+
+
 @dataclass
 class LayerSpec:
     geom: L.ConvGeom
@@ -362,6 +390,39 @@ class ConvStack:
         extents = {t.data_ptr(): t.numel() * t.element_size()
                    for t in (self.x_in, self.y[0], self.stats[0], self._ig_work) if t is not None}
         return ops, n_front, release_after(ops, n_front, written, extents)
+
+    def pair_program(self, prog, pre_ops):
+        """The pair-mode form of a training-mode forward program behind `pre_ops`: the same op structs (so the per-call
+        patches reach both), but every BatchNorm finalize in its deferred form -- a copy whose batch_var names a slot of
+        this stack -- and ONE trailing gode_bn_running op that applies all layers' momentum updates.  Nothing in front of
+        that last op touches a tensor another plan of the module touches, so two plans' programs may run side by side.
+        -> the ops, or None when the stack has no such form: front_split's refusals (split, grouped and noisy stacks,
+        caller-owned input), an eval-mode program, more BatchNorm layers than one gode_bn_running launch takes.  The split-K
+        workspace and the statistics are this stack's own; the packed weight panels are shared with the module's other
+        plans and only read here."""
+        if self.split or self.groups != 1 or self.noisy or self.x_in is None or len(prog.ops) < 2:
+            return None
+        fins = [op for op in prog.ops if isinstance(op, L.BnFinalizeOp)]
+        if not fins or len(fins) > L.BN_RUNNING_MAX or any(not f.training or f.groups == 2 or f.nseg or f.stats1 for f in fins):
+            return None
+        if getattr(self, "_bvar", None) is None:
+            self._bvar = {}
+        run = L.BnRunningOp(n=len(fins), momentum=self.momentum)
+        ops, k = list(pre_ops), -1
+        for op in prog.ops:
+            if isinstance(op, L.BnFinalizeOp):
+                k += 1
+                slot = self._bvar.get(k)
+                if slot is None or slot.numel() != op.C:
+                    slot = self._bvar[k] = torch.empty(op.C, dtype=torch.float32, device=self.device)
+                d = L.BnFinalizeOp.from_buffer_copy(op)
+                d.batch_var = slot.data_ptr()
+                y = run.layer[k]
+                y.mean, y.var, y.C = op.mean, slot.data_ptr(), op.C
+                y.running_mean, y.running_var, y.num_batches_tracked = op.running_mean, op.running_var, op.num_batches_tracked
+                op = d
+            ops.append(op)
+        return ops + [run]
 
     @staticmethod
     def _ncols(s: LayerSpec):
@@ -691,10 +752,13 @@ class ConvStack:
         prog.run(st)
         return self.end_forward(out, training)
 
-    def begin_forward(self, training: bool, x=None, x_strides=None, x2=None, x2_strides=None, noise=None):
+    def begin_forward(self, training: bool, x=None, x_strides=None, x2=None, x2_strides=None, noise=None, out_stream=None):
         """forward() up to the launch: the program patched for this call and its stale weight panels re-packed on the
         current stream -> (program, the output tensor, were panels re-packed).  The caller launches the program (forward()
-        itself; the two-lane sampling path of modules._GenPlan) and hands the output to end_forward."""
+        itself; the two-lane sampling path of modules._GenPlan) and hands the output to end_forward.  out_stream: the
+        stream that will WRITE the output when it is not the current one (pair mode): the tensor is then allocated for
+        that stream and the current stream is recorded as a user, so the allocator hands the block out again only when
+        what the caller queued against it has run."""
         self._refresh()
         if training not in self._fwd:
             self._fwd[training] = self._build_fwd(training)
@@ -703,7 +767,13 @@ class ConvStack:
             if noise is None:
                 raise RuntimeError("this plan applies instance noise: forward() needs its noise arguments")
             self._patch_noise(patch, noise, [(x, x_strides), (x2, x2_strides)])
-        out = torch.empty(self.out_dims, dtype=torch.float32, device=self.device)
+        if out_stream is None:
+            out = torch.empty(self.out_dims, dtype=torch.float32, device=self.device)
+        else:
+            cur = torch.cuda.current_stream()
+            with torch.cuda.stream(out_stream):
+                out = torch.empty(self.out_dims, dtype=torch.float32, device=self.device)
+            out.record_stream(cur)
         patch["last"].out = out.data_ptr()
         if "last2" in patch:
             patch["last2"][0].out = out.data_ptr() + patch["last2"][1]

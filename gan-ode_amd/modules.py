@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .engine import (LANE_ORDERED, LANE_OVERLAP, LANE_SINGLE, ConvStack, LayerParams, LayerSpec, conv_out, dptr, lane_gate,
-                     lane_mode, make_geom, ring_back, stream_ptr)
+                     lane_mode, make_geom, pair_turn, stream_ptr)
 
 Z_COLS = 96  # latent row: [motion 16 | content 50 | zero pad 30]: K % 32 == 0 puts the first decoder GEMM on the FAST path
 Z_CATEG0 = 66        # dim_z_category = C > 0: the one-hot lives in the first C pad columns (gode_categ_onehot)
@@ -32,6 +32,9 @@ ODE_METHODS = L.ODE_METHODS      # gen.ode_method -> the latent ops' `method` co
 # GODE_SAMPLE_LANES=0 (read once): no-grad sampling calls stay on one stream (_GenPlan._forward_lanes); per generator:
 # gen.sample_lanes = False
 _SAMPLE_LANES_ENV = os.environ.get("GODE_SAMPLE_LANES", "1") != "0"
+# What gen.sample_lanes = True selects behind its gate: pair mode (_GenPlan._forward_pair) or the two-lane front
+# (_forward_lanes).  DESIGN section 24 holds the measurement that decides it.
+_PAIR_DEFAULT = True
 
 
 def ode_method_code(name):
@@ -279,7 +282,7 @@ class _GenPlan:
     # the adaptive solver's, and its adjoints only when they are adaptive too
     multi, multi_always = ("ode", L.OdeFwdOp, L.OdeBwdOp), False
 
-    def __init__(self, gen: "VideoGenerator", n_traj: int, T: int, select: bool, zbuf=None, x=None):
+    def __init__(self, gen: "VideoGenerator", n_traj: int, T: int, select: bool, zbuf=None, x=None, lanes=None):
         """zbuf: latent rows of a joint pass (_GenJointPlan) -- the plan then is the latent half only (no decoder stack).
         x: the motion noise on the device -- sample_z_m's plan: the latent half alone on its own [n_traj*T, zcols] rows, no
         content, no classes, nothing staged."""
@@ -320,13 +323,25 @@ class _GenPlan:
         # the previous call saw (None: it was no lanes call), and the calls counted by the path they took
         self._lanes = self._side = self._lane_prog = self._lane_prev = None
         self.lane_calls = {LANE_OVERLAP: 0, LANE_ORDERED: 0, LANE_SINGLE: 0}
+        # pair mode (_forward_pair): the second plan of this shape (built when the first streak starts: it doubles the
+        # activation memory), this plan's pair-mode program, what the previous pair call saw (None: the previous forward was
+        # no pair call), the pair calls counted by mode, and the staging-copy events of the last two calls of either plan
+        # (lane_gate's evidence).  A second plan is driven by the first (_owner) and never enters the pool.
+        self._peer = self._pair_prog = self._pair_prev = None
+        self._pair_refused = False
+        self._owner = self
+        self.pair_calls = {LANE_OVERLAP: 0, LANE_ORDERED: 0}
+        self._copies = []
         # The one kind of plan that can take the two lanes gets its lanes object now, not at its first lanes call: the side
         # stream takes its hardware queue when it is created, and measured a stream created behind a
         # replayed training graph sat on the caller's queue, 17 us per step slower than one stream.  With gen.sample_lanes
         # off at this point the object is made at the plan's first lanes call after the switch (_lanes_possible).
         self._lanes_ok = type(self) is _GenPlan and self.stack is not None and not self.ncat and _SAMPLE_LANES_ENV
         self.lanes_made_late = False
-        if self._lanes_ok and gen.sample_lanes:
+        self._peer_lanes = None
+        if lanes is not None:        # a second plan (pair mode): the lanes object its first plan made for it
+            self._make_lanes(lanes)
+        elif self._lanes_ok and gen.sample_lanes:
             self._make_lanes()
 
     @staticmethod
@@ -460,6 +475,11 @@ class _GenPlan:
             if slot["ev"] is None:
                 slot["ev"] = torch.cuda.Event()
             slot["ev"].record()
+            self._note_copy(slot["ev"])
+
+    def _note_copy(self, ev):
+        own = self._owner
+        own._copies = own._copies[-1:] + [ev]
 
     def forward(self, x_host, content_host, sel_host, training, keep, cls_host=None, no_grad=False):
         """x_host None: the latent rows of this call were produced ahead of time by VideoGenerator.prefetch_latents (on
@@ -468,13 +488,19 @@ class _GenPlan:
         if x_host is None:
             torch.cuda.current_stream().wait_event(self._latent_ev)
             out = self.stack.forward(training)
-            self._lane_prev = None
+            self._lane_prev = self._pair_prev = None
         elif self._lanes_possible(keep, no_grad):
-            out = self._forward_lanes(x_host, content_host, sel_host, training)
+            knob = self.gen.sample_lanes
+            if (knob == "pair" or (_PAIR_DEFAULT and knob != "always")) and self._pair_possible(training):
+                self._lane_prev = None
+                out = self._forward_pair(x_host, content_host, sel_host, training)
+            else:
+                self._pair_prev = None
+                out = self._forward_lanes(x_host, content_host, sel_host, training)
         else:
             self.stage_inputs(x_host, content_host, sel_host, cls_host)
             out = self.stack.forward(training, pre_ops_program=self.fwd_prog)
-            self._lane_prev = None
+            self._lane_prev = self._pair_prev = None
             self.lane_calls[LANE_SINGLE] += 1
         self.busy = keep
         return out
@@ -496,8 +522,8 @@ class _GenPlan:
             return False
         # lane_mode's gpu_behind (engine.lane_gate), asked before anything dearer so that a call on an idle GPU pays two
         # event queries and nothing else
-        if gen.sample_lanes != "always" and not lane_gate(self._lane_prev is not None, self._copy_pending(1),
-                                                          self._copy_pending(2)):
+        if gen.sample_lanes not in ("always", "pair") and not lane_gate(
+                self._lane_prev is not None or self._pair_prev is not None, self._copy_pending(1), self._copy_pending(2)):
             return False
         feed = getattr(gen, "_feed", None)
         if (feed is not None and feed.recording) or torch.cuda.is_current_stream_capturing():
@@ -511,12 +537,21 @@ class _GenPlan:
 
     def _copy_pending(self, back):
         """Has the staging copy of the call `back` calls ago (1: the previous one) not completed yet?"""
-        ev = self._ring[ring_back(self._ring_i, len(self._ring), back)]["ev"]
+        ev = self._copies[-back] if len(self._copies) >= back else None
         return ev is not None and not ev.query()
 
-    def _make_lanes(self):
+    def _make_lanes(self, lanes=None):
+        """This plan's lanes object: the device's shared one for first plans (L.Lanes.shared says why sharing is safe) --
+        and, where the knob can select pair mode, the device's shared one for second plans: a second plan is built only
+        when a streak starts, but its stream has to take its hardware queue now, next to this plan's (see __init__;
+        measured in DESIGN section 24: made behind a training iteration it shared a queue, the two passes ran one after
+        the other and the step was 43 us slower than on two lanes).  Two objects per device whatever the number of plans:
+        a process with a trainer's two sampling plans holds as many streams as it did with one object per plan."""
         with torch.cuda.device(self.device):
-            self._lanes = L.Lanes(torch.cuda.current_device())
+            self._lanes = lanes if lanes is not None else L.Lanes.shared(torch.cuda.current_device(), False)
+            knob = self.gen.sample_lanes
+            if lanes is None and (knob == "pair" or (_PAIR_DEFAULT and knob != "always")):
+                self._peer_lanes = L.Lanes.shared(torch.cuda.current_device(), True)
         self._side = torch.cuda.ExternalStream(self._lanes.stream_ptr, device=self.device)
 
     def _front_versions(self):
@@ -573,6 +608,65 @@ class _GenPlan:
             if slot["ev"] is None:
                 slot["ev"] = torch.cuda.Event()
             slot["ev"].record()
+        self._note_copy(slot["ev"])
+
+    # -- pair mode: two whole decoder passes in flight, on two plans used in turn --------------------------------------------
+    # With the BatchNorm finalizes in their deferred form (ConvStack.pair_program) nothing but the trailing gode_bn_running
+    # op touches state that two calls share, so a call's whole program runs on its plan's lanes stream and only that op on
+    # the caller's stream, behind it (gode_run_pair).  The lane of call m starts behind the caller's stream at the entry
+    # of call m-1: the BatchNorm passes and the head of one call then run next to the GEMMs of the other.  Eligible exactly
+    # where the two lanes are; a call that cannot overlap (lane_mode's second group, over every parameter the program reads)
+    # is ordered behind everything queued.  Same kernels on the same inputs, the running statistics updated in call order on
+    # the caller's stream: bit-identical.
+    def _pair_possible(self, training):
+        """Has this plan's stack a pair-mode program for this pass (a training-mode pass of a plain stack)?  What only
+        ConvStack.pair_program can tell (the number of BatchNorm layers) it tells once: _forward_pair then notes the
+        refusal and the plan's calls take the two-lane front from there on."""
+        return training and not self._pair_refused and self.stack._G2 is False and not self.stack.noisy
+
+    def _pair_versions(self):
+        """_front_versions over every tensor the program reads: the whole pass now runs off the caller's stream."""
+        ts = [t for t in self._params() if t is not None]
+        for p in self.stack.params:
+            ts += [t for t in (p.weight, p.gamma, p.beta) if t is not None]
+        return tuple((t._version, getattr(t, "_gode_ver", 0), t.data_ptr()) for t in ts)
+
+    def _forward_pair(self, x_host, content_host, sel_host, training):
+        """forward() of a call that _lanes_possible and _pair_possible let through, on the plan whose turn it is."""
+        prev, self._pair_prev = self._pair_prev, None        # (an exception below leaves the next call ordered, on this plan)
+        turn = pair_turn(None if prev is None else prev["turn"])
+        if turn == 1 and self._peer is None:
+            if self._peer_lanes is None:         # (the knob was switched to "pair" after this plan was built)
+                with torch.cuda.device(self.device):
+                    self._peer_lanes = L.Lanes.shared(torch.cuda.current_device(), True)
+            peer = self._peer = type(self)(self.gen, self.n, self.T, self.select, lanes=self._peer_lanes)
+            peer._owner = self
+        plan = self._peer if turn else self
+        plan._programs()
+        between = L.LAUNCHES - prev["mark"] if prev is not None else -1
+        prog, out, repacked = plan.stack.begin_forward(training, out_stream=plan._side)
+        st = stream_ptr()
+        cache = plan._pair_prog
+        if cache is None or cache[0] is not prog or cache[1] is not plan.fwd_prog:
+            # (a rebuilt latent program comes with new grid tensors, uploaded on the caller's stream: no overlap past them)
+            ops = plan.stack.pair_program(prog, plan.fwd_prog.ops)
+            if ops is None:          # (decided at a plan's first pair call, which runs on the first plan)
+                self._pair_refused = True
+                return self._forward_lanes(x_host, content_host, sel_host, training)
+            cache = plan._pair_prog = (prog, plan.fwd_prog, L.PairProgram(ops, 1))
+            prev = None
+        versions = self._pair_versions()
+        mode = lane_mode(enabled=True, trace=False, recording=False, categorical=False, grad=False, keep=False,
+                         fixed_grid_ode=True, splittable=True, prev_lanes=prev is not None, launches_between=between,
+                         repacked=repacked, versions_same=prev is not None and prev["versions"] == versions,
+                         same_stream=prev is not None and prev["stream"] == st, gpu_behind=True)
+        self.pair_calls[mode] += 1
+        plan._stage_on_side(mode == LANE_ORDERED, x_host, content_host, sel_host)
+        other = self if turn else self._peer
+        cache[2].run_pair(plan._lanes, None if other is None else other._lanes,
+                          L.LANES_OVERLAP if mode == LANE_OVERLAP else L.LANES_ORDERED, st)
+        self._pair_prev = dict(mark=L.LAUNCHES, versions=versions, stream=st, turn=turn)
+        return plan.stack.end_forward(out, training)
 
     def _decoder_pass_done(self):
         """The trainer may ask to be told when the LAST decoder backward of a generator step has been queued (the decoder
@@ -770,9 +864,11 @@ class VideoGenerator(nn.Module):
 
     mnist = False
     _plan_cls = None   # set below (_GenPlan)
-    # no-grad sampling calls (_GenPlan._forward_lanes): True -- two lanes whenever a call finds the GPU behind the host;
-    # "always" -- also on an idle GPU (tests: the mode then depends on no timing); False -- one stream (A/B runs).  Read
-    # at every call; a plan built while it is False makes its lanes object at its first lanes call after the switch.
+    # no-grad sampling calls: True -- whenever a call finds the GPU behind the host, the two-lane front
+    # (_GenPlan._forward_lanes) or, with _PAIR_DEFAULT, pair mode (_GenPlan._forward_pair: two decoder passes in flight on
+    # two plans); "always" -- the two-lane front and "pair" -- pair mode at every call, also on an idle GPU (tests and
+    # traces: the mode then depends on no timing); False -- one stream (A/B runs).  Read at every call; a plan built while it is False makes its lanes object at its first lanes call after
+    # the switch.
     sample_lanes = True
     _one_stream = 0            # > 0: inside one_stream()
     _categorical_ok = True     # dim_z_category > 0 is served (the other motion latents switch it off)
@@ -926,11 +1022,15 @@ class VideoGenerator(nn.Module):
         and how many plans hold a lanes object (made late: after the plan, on a switch of sample_lanes to a true value).
         A loop of calls that counts overlaps but gains nothing has its side stream on the caller's hardware queue (the
         runtime shares a few queues among all streams of the process): two lanes then only cost; sample_lanes = False."""
-        out = {LANE_OVERLAP: 0, LANE_ORDERED: 0, LANE_SINGLE: 0, "lanes_objects": 0, "lanes_objects_made_late": 0}
+        out = {LANE_OVERLAP: 0, LANE_ORDERED: 0, LANE_SINGLE: 0, "lanes_objects": 0, "lanes_objects_made_late": 0,
+               "pair_overlap": 0, "pair_ordered": 0, "pair_plans": 0}
         for plans in self._pool.plans.values():
             for p in plans:
                 for k, v in getattr(p, "lane_calls", {}).items():
                     out[k] += v
+                for k, v in getattr(p, "pair_calls", {}).items():
+                    out["pair_" + k] += v
+                out["pair_plans"] += getattr(p, "_peer", None) is not None
                 out["lanes_objects"] += getattr(p, "_lanes", None) is not None
                 out["lanes_objects_made_late"] += bool(getattr(p, "lanes_made_late", False))
         return out
@@ -959,6 +1059,8 @@ class VideoGenerator(nn.Module):
             for p in plans:
                 if getattr(p, "_lane_prev", None) is not None:
                     p._lane_prev = None
+                if getattr(p, "_pair_prev", None) is not None:
+                    p._pair_prev = None
 
     def _zero_labels(self, n, device):
         """np.zeros(B) -> torch.from_numpy -> .cuda() of the reference (models/mocogan.py:235,279): float64 zeros,

@@ -182,8 +182,28 @@ typedef struct gode_bn_finalize_op {
   /* groups == 2, two-launch form (overrides nseg / rows0): group 1's partial sums are an array of their own,
    * stats1[2][ncols][rows1], written by a second gode_igemm launch over that batch alone; `stats` / `rows` are group 0's. */
   const float* stats1; int32_t rows1, pad3_;
+  /* deferred form (non-null; training mode, one group, no segments -- anything else is GODE_E_ARG): the unbiased batch
+   * variance goes to batch_var[C] as float, the batch mean is mean[] as always, and running_mean / running_var /
+   * num_batches_tracked are neither read nor written -- gode_bn_running applies their updates later.  Nothing then orders
+   * two passes over the same module layer by layer. */
+  float* batch_var;
 } gode_bn_finalize_op;
 int gode_bn_finalize(const gode_bn_finalize_op* op, void* stream);
+
+/* The momentum updates that deferred finalizes left out, for up to GODE_BN_RUNNING_MAX layers in ONE launch (one workgroup,
+ * layers in order):  running_mean = (1 - momentum) * running_mean + momentum * mean,  running_var likewise from var (the slot
+ * a deferred finalize wrote),  num_batches_tracked += 1 -- operation for operation what the in-place finalize does, so the
+ * running tensors hold the same bits either way.  running_mean == NULL: that layer only counts its batch. */
+#define GODE_BN_RUNNING_MAX 8
+typedef struct gode_bn_running_layer {
+  const float* mean; const float* var; float* running_mean; float* running_var; int64_t* num_batches_tracked;
+  int32_t C, pad_;
+} gode_bn_running_layer;
+typedef struct gode_bn_running_op {
+  gode_bn_running_layer layer[8];   /* GODE_BN_RUNNING_MAX rows, the first n used */
+  int32_t n; float momentum;
+} gode_bn_running_op;
+int gode_bn_running(const gode_bn_running_op* op, void* stream);
 
 /* out = act(y*scale[c] + shift[c]) over [M][C] (C % 4 == 0): materialises an activated tensor for consumers that are
  * MFMA-bound and re-read every element several times (the heavy GEMMs run ~10-20 % faster without the transform
@@ -878,7 +898,8 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
   X(BCE_PROB,      35, gode_bce_prob_op,      gode_bce_prob)      \
   X(BCE_T,         36, gode_bce_t_op,         gode_bce_logits_t)  \
   X(RESIZE_U8,     37, gode_resize_u8_op,     gode_resize_u8)     \
-  X(CLIP_GATHER,   38, gode_clip_gather_op,   gode_clip_gather)
+  X(CLIP_GATHER,   38, gode_clip_gather_op,   gode_clip_gather)   \
+  X(BN_RUNNING,    39, gode_bn_running_op,    gode_bn_running)
 /* GODE_OP_PACK stays outside the table: it has no (op*, stream) entry point, gode_run sends every run of consecutive pack
  * ops out as batched launches instead. */
 #define GODE_ENUM_ROW_(name, value, op_t, fn) GODE_OP_##name = value,
@@ -913,6 +934,20 @@ int gode_lanes_destroy(gode_lanes* lanes);
 void* gode_lanes_stream(gode_lanes* lanes);
 int gode_run_lanes(gode_lanes* lanes, const int32_t* kinds, const void* const* ops, int32_t n, int32_t n_front,
                    int32_t release_after, int32_t mode, void* stream);
+/* Pair mode: two whole programs in flight on two lanes objects used in turn.  Ops [0, n - n_tail) run on `lanes`' own stream,
+ * which then records its done event; `stream` waits for that event and runs the last n_tail ops (>= 1: the program's
+ * gode_bn_running, the one op that touches state two programs share).  At entry `stream` records `lanes`' entry event.
+ *   mode GODE_LANES_OVERLAP: the lane first waits for the entry event of `peer` -- the object the PREVIOUS call ran on, so
+ *   for everything queued on `stream` before that call -- and for nothing else: the previous call's program keeps running
+ *   next to this one.  The caller vouches that the two programs share no buffer they write, and that nothing queued on
+ *   `stream` since the previous call's entry writes what this program reads.
+ *   mode GODE_LANES_ORDERED, a null `peer`, or a `peer` whose entry event holds no record: the lane waits for this call's own
+ *   entry event, i.e. for everything queued on `stream` so far.
+ * Whatever is queued on `stream` behind the call is behind the whole program.  A `stream` that is being captured takes all n
+ * ops itself, in order.  Argument errors (a null object, peer == lanes, n_tail outside [1, n), an unknown mode) return
+ * GODE_E_ARG before any HIP call; error codes carry the op index as in gode_run. */
+int gode_run_pair(gode_lanes* lanes, gode_lanes* peer, const int32_t* kinds, const void* const* ops, int32_t n,
+                  int32_t n_tail, int32_t mode, void* stream);
 
 int gode_version(void);
 /* size of every op struct as compiled, so the ctypes mirror can assert it matches (index = GODE_OP_*; -1: the
