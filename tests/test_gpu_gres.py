@@ -342,3 +342,63 @@ def test_standalone_conditional_norm_and_spectral_norm():
     yr.square().sum().backward(); yg.square().sum().backward()
     assert rel_err(lin_g.module.weight_bar.grad.cpu(), lin_r.module.weight_bar.grad) < GTOL
     assert rel_err(lin_g.module.weight_u.cpu(), lin_r.module.weight_u.detach()) < TOL
+
+
+def test_block_with_several_position_chunks():
+    """gres_cells.BLOCK_CASE: the second norm's map is 18 x 16, so gode_cbn_bwd runs five position chunks and the statistics
+    nine rows (the fixtures above stay within one chunk).  Against gres_ref.GResBlock in float64 on the device with the same
+    state: forward, every gradient, the carried state and the eval forward.  tests/test_host_gres_cells.py holds the case's
+    pre-activations away from the ReLU kink; nothing is excluded here."""
+    from gres_cells import BLOCK_CASE as case, block_case_tensors
+    sd, x, cond, gy = block_case_tensors()
+    blk = hip_block(case)
+    blk.load_state_dict(sd)
+    blk.cuda()
+    ref = gres_ref.GResBlock(case["cin"], case["cout"], n_class=case["n_class"], bn=case["bn"], upsample_factor=case["up"],
+                             downsample_factor=case["down"]).double()
+    ref.load_state_dict(sd)
+    ref.cuda()
+    a = _grads(blk, x.cuda(), cond.cuda(), lambda y: y.backward(gy.cuda()))
+    r = _grads(ref, x.cuda().double(), cond.cuda().double(), lambda y: y.backward(gy.cuda().double()))
+    assert a["y"].shape == r["y"].shape and rel_err(a["y"].cpu(), r["y"].cpu()) < TOL
+    zero = "conv0.module.bias"          # in front of a train-mode BatchNorm: exact zeros here, rounding noise in the reference
+    assert set(a) == set(r) and zero in a
+    for k in a:
+        if k == zero:
+            assert float(a[k].abs().max()) == 0.0 and float(r[k].abs().max()) < 1e-9 * float(gy.abs().sum())
+        elif k != "y":
+            err = rel_err(a[k].cpu(), r[k].cpu())
+            print("chunked block", k, err)
+            assert err < GTOL, (k, err)
+    blk.eval(); ref.eval()
+    with torch.no_grad():
+        ye, yr = blk(x.cuda(), cond.cuda()), ref(x.cuda().double(), cond.cuda().double())
+    assert rel_err(ye.cpu(), yr.cpu()) < TOL
+    sa, sr = blk.state_dict(), ref.state_dict()
+    assert list(sa) == list(sr)
+    for k in sa:
+        if k.endswith("num_batches_tracked"):
+            assert int(sa[k]) == int(sr[k]) == 1, k
+        elif k.endswith(("weight_u", "weight_v", "running_mean", "running_var")):
+            err = rel_err(sa[k].cpu(), sr[k].cpu())
+            print("chunked block", k, err)
+            assert err < TOL, (k, err)
+        else:
+            assert torch.equal(sa[k].cpu(), sd[k]), k
+
+
+def test_spectral_norm_two_power_iterations():
+    import gan_ode_amd as G
+    seed_all(8)
+    lin = torch.nn.Linear(12, 9)
+    wbar = lin.weight.data.clone()
+    mod = G.SpectralNorm(lin, power_iterations=2).cuda()
+    assert mod.power_iterations == 2
+    ur, vr = mod.module.weight_u.detach().double().clone(), mod.module.weight_v.detach().double().clone()
+    w = mod.normalized_weight()
+    w64 = wbar.double().cuda()
+    w_one, _ = gres_ref.sn_step(w64, ur, vr)
+    w_ref, _ = gres_ref.sn_step(w64, ur, vr)
+    assert rel_err(w_one.cpu(), w_ref.cpu()) > 10 * TOL             # one iteration is not two: the comparison can tell them apart
+    assert rel_err(w.detach().cpu(), w_ref.cpu()) < TOL
+    assert rel_err(mod.module.weight_u.detach().cpu(), ur.cpu()) < TOL and rel_err(mod.module.weight_v.detach().cpu(), vr.cpu()) < TOL
