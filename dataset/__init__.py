@@ -9,3 +9,4 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gan_ode_amd.data import MNISTRotationImage, MNISTRotationVideo, UCF101Image, UCF101Video  # noqa: E402,F401
+from gan_ode_amd.data import RotMnistOnDevice  # noqa: E402,F401  (from_digits builds the clips on the GPU)

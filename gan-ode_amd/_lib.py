@@ -31,8 +31,10 @@ OP_FC_ACT, OP_FC_ACT_BWD, OP_BCE_PROB = 33, 34, 35
 OP_BCE_T = 36
 OP_RESIZE_U8, OP_CLIP_GATHER = 37, 38
 OP_BN_RUNNING = 39
+OP_ROT_CLIPS = 40
 BN_RUNNING_MAX = 8            # GODE_BN_RUNNING_MAX: the layers one gode_bn_running launch takes
 RESIZE_MAX_TAPS = 32          # GODE_RESIZE_MAX_TAPS: the longest tap row gode_resize_u8 takes
+ROT_MIN_SIZE, ROT_MAX_SIZE = 4, 64   # the image heights and widths gode_rot_clips takes
 REC_ADAM_NOISE = -1          # gode_sizeof index of the gode_adam_noise_tensor table record
 ODE_NPARAM = 2672
 ODERNN_NPARAM = 2176
@@ -335,6 +337,12 @@ class ClipGatherOp(_Op):
     _fields_ = [("frames", ptr), ("first", ptr), ("out", ptr), ("n_frames", i64), ("frame_elems", i64), ("B", i32), ("T", i32),
                 ("sub", f32), ("inv", f32)]
     KIND, FN = OP_CLIP_GATHER, "gode_clip_gather"
+
+
+class RotClipsOp(_Op):
+    _fields_ = [("images", ptr), ("cs", ptr), ("out", ptr), ("raw", ptr), ("n", i32), ("K", i32), ("H", i32), ("W", i32),
+                ("in_u8", i32), ("in_scale", f32), ("in_shift", f32), ("cval", f32)]
+    KIND, FN = OP_ROT_CLIPS, "gode_rot_clips"
 
 
 class AdamNoiseTensor(C.Structure):

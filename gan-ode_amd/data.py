@@ -8,6 +8,10 @@ the discriminators read the [B, T, C, H, W] batch in place through strides (no t
 UCF-101 (dataset/ucf101new.py) gets the same treatment, DESIGN section 21: frames are resized, cropped and quantised ONCE on
 the GPU (gode_resize_u8) into one uint8 store, and every step gathers and normalises its windows there (gode_clip_gather).
 The arithmetic of the resize is fixed by bicubic_taps / resize_crop_reference below.  Video decoding is the caller's.
+
+The file itself is what utils/images.py:101-173 (rotate_data) makes of raw MNIST digits; DESIGN section 25 builds it on the GPU
+(gode_rot_clips: RotMnistOnDevice.from_digits / resample / save_mat, rotate_clips), with rot_angles, rotate_reference and
+normalise_reference as the float64 statement of its arithmetic and read_idx_images / read_idx_labels for the IDX files.
 """
 from __future__ import annotations
 
@@ -65,17 +69,75 @@ class MNISTRotationImage(MNISTRotationVideo):
         return img.float(), self.Y[idx]
 
 
+def _class_labels(labels, n, what):
+    """Class indices int64 [n] from class indices or from the one-hot rows extract_labels builds (utils/images.py:84-94)."""
+    y = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    if y.ndim == 2 and y.shape[1] > 1:
+        y = np.argmax(y == 1, axis=1)              # np.where(y == 1)[0][0] per row (utils/images.py:137)
+    y = y.reshape(-1)
+    if y.shape[0] != n:
+        raise ValueError(f"{what}: {y.shape[0]} labels for {n} clips")
+    return torch.from_numpy(np.ascontiguousarray(y.astype(np.int64)))
+
+
 class RotMnistOnDevice:
     """Device-resident training set with shuffled, drop_last batch streams (what DataLoader(shuffle=True,
-    drop_last=True) + dataGen() deliver in mnist_moco_ode.py:56-71), gathered on the GPU."""
+    drop_last=True) + dataGen() deliver in mnist_moco_ode.py:56-71), gathered on the GPU.
 
-    def __init__(self, path_or_tensor, device="cuda", N=500, T=16, seed=None):
-        X = path_or_tensor if torch.is_tensor(path_or_tensor) else load_rot_mnist(path_or_tensor, True, N, T)[0]
+    The clips come from a `rot-mnist_rand.mat` file or a tensor, or are built on the GPU from raw digits by from_digits
+    (gode_rot_clips); such a set can draw fresh angles with resample() and write the file with save_mat().
+    Y: int64 classes [N] on the device (None when no labels were given)."""
+
+    def __init__(self, path_or_tensor, device="cuda", N=500, T=16, seed=None, labels=None):
+        if torch.is_tensor(path_or_tensor):
+            X = path_or_tensor
+        else:
+            X, Y = load_rot_mnist(path_or_tensor, True, N, T)
+            labels = Y if labels is None else labels
         self.X = X.to(device).contiguous()             # [N, T, 1, 28, 28]
         self.N, self.T = self.X.shape[0], self.X.shape[1]
+        self.Y = None if labels is None else _class_labels(labels, self.N, "RotMnistOnDevice").to(self.X.device)
+        self.digits = self.angles = self.mode = self.angle_rng = None       # set by from_digits
+        self.cval = -0.5
         self.gen = torch.Generator()
         if seed is not None:
             self.gen.manual_seed(seed)
+
+    @classmethod
+    def from_digits(cls, digits_uint8, labels=None, K=16, mode="normal", device="cuda", seed=None, angle_rng=None):
+        """The set rotate_data (utils/images.py:101-173) builds from raw digits, made on the GPU: uint8 [n, H, W] (the bytes of
+        the IDX file, read_idx_images; 4 <= H, W <= 64) -> X [n, K, 1, H, W] in one gode_rot_clips launch.  The digits stay on
+        the device for resample().  labels: class indices [n] or one-hot rows [n, 10].  mode / angle_rng: rot_angles' (the
+        angles of "rand-end" / "rsre" come from NumPy's global stream unless angle_rng is given); seed: the batch streams'."""
+        d = torch.as_tensor(digits_uint8)
+        if d.dtype != torch.uint8 or d.dim() != 3:
+            raise ValueError(f"RotMnistOnDevice.from_digits: uint8 digits [n, H, W] expected, got {d.dtype} {tuple(d.shape)}")
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(f"RotMnistOnDevice.from_digits(device={device!r}): the rotation runs on the GPU; libgode has no "
+                               "CPU or PyTorch fallback")
+        d = d.to(device).contiguous()
+        angles = rot_angles(d.shape[0], K, mode, angle_rng)
+        ds = cls(rotate_clips(d, angles).unsqueeze(2), device=device, seed=seed, labels=labels)
+        ds.digits, ds.angles, ds.mode, ds.angle_rng = d, angles, mode, angle_rng
+        return ds
+
+    def resample(self, mode=None):
+        """Draw new angles (mode: this call's and the later ones'; default the set's) and rebuild X in place: fresh "rand-end" /
+        "rsre" clips per epoch, one launch.  "normal" reproduces X bit for bit."""
+        if self.digits is None:
+            raise RuntimeError("RotMnistOnDevice.resample: the set holds no digits (it was not built by from_digits)")
+        angles = rot_angles(self.N, self.T, self.mode if mode is None else mode, self.angle_rng)
+        rotate_clips(self.digits, angles, cval=self.cval, out=self.X.view(self.N, self.T, *self.X.shape[3:]))
+        self.angles, self.mode = angles, (self.mode if mode is None else mode)
+        return self
+
+    def save_mat(self, path):
+        """The file the reference drivers load (utils/images.py:220): X float64 [n, K, H * W], Y float64 [n, 1]."""
+        from scipy.io import savemat
+        if self.Y is None:
+            raise ValueError("RotMnistOnDevice.save_mat: the set has no labels")
+        savemat(path, {"X": self.X.reshape(self.N, self.T, -1).cpu().double().numpy(),
+                       "Y": self.Y.cpu().double().numpy().reshape(-1, 1)})
 
     def _epochs(self, batch):
         while True:
@@ -83,14 +145,236 @@ class RotMnistOnDevice:
             for i in range(0, self.N - batch + 1, batch):
                 yield perm[i:i + batch]
 
-    def videos(self, batch):
-        for idx in self._epochs(batch):
-            yield self.X[idx.to(self.X.device)]                                  # [B, T, 1, 28, 28]
+    def _labelled(self, x, idx, labels):
+        if not labels:
+            return x
+        if self.Y is None:
+            raise ValueError("RotMnistOnDevice: labels=True on a set without labels")
+        return x, self.Y[idx]
 
-    def images(self, batch):
+    def videos(self, batch, labels=False):
+        """Endless stream of [B, T, 1, 28, 28] batches; labels=True: (batch, int64 [B] classes on the device)."""
+        for idx in self._epochs(batch):
+            idx = idx.to(self.X.device)
+            yield self._labelled(self.X[idx], idx, labels)
+
+    def images(self, batch, labels=False):
+        """Endless stream of [B, 1, 28, 28] batches, one uniform frame per drawn clip; labels as in videos()."""
         for idx in self._epochs(batch):
             frame = torch.randint(0, self.T, (batch,), generator=self.gen)
-            yield self.X[idx.to(self.X.device), frame.to(self.X.device)]         # [B, 1, 28, 28]
+            idx = idx.to(self.X.device)
+            yield self._labelled(self.X[idx, frame.to(self.X.device)], idx, labels)
+
+
+# ======================================================================================================================
+# Rotated-MNIST clips from raw digits (DESIGN section 25)
+# ======================================================================================================================
+def _open_idx(path):
+    import gzip
+    with open(path, "rb") as f:
+        gz = f.read(2) == b"\x1f\x8b"
+    return gzip.open(path, "rb") if gz else open(path, "rb")
+
+
+def _read_idx(path, magic, ndim, count, what):
+    with _open_idx(path) as f:
+        head = f.read(4 + 4 * ndim)
+        if len(head) != 4 + 4 * ndim or int.from_bytes(head[:4], "big") != magic:
+            raise ValueError(f"{what}: {path} is not an IDX file with magic {magic}")
+        dims = [int.from_bytes(head[4 + 4 * i:8 + 4 * i], "big") for i in range(ndim)]
+        if count is not None:
+            if count < 0 or count > dims[0]:
+                raise ValueError(f"{what}: {count} items asked of the {dims[0]} in {path}")
+            dims[0] = int(count)
+        size = int(np.prod(dims))
+        buf = f.read(size)
+    if len(buf) != size:
+        raise ValueError(f"{what}: {path} ends after {len(buf)} of {size} bytes")
+    return np.frombuffer(buf, dtype=np.uint8).reshape(dims).copy()
+
+
+def read_idx_images(path, count=None):
+    """The MNIST image file (train-images-idx3-ubyte, gzipped or not) -> uint8 [n, rows, cols]: the bytes extract_data reads
+    (utils/images.py:64-74) before its rescaling, which gode_rot_clips applies on load.  count: only the first `count`.
+    Nothing is downloaded."""
+    return _read_idx(path, 2051, 3, count, "read_idx_images")
+
+
+def read_idx_labels(path, count=None):
+    """The MNIST label file (train-labels-idx1-ubyte, gzipped or not) -> int64 classes [n] (utils/images.py:84-90; the one-hot
+    rows built there only serve to be turned back into these indices at :137)."""
+    return _read_idx(path, 2049, 1, count, "read_idx_labels").astype(np.int64)
+
+
+ROT_MODES = ("normal", "rand-end", "rsre")
+
+
+def rot_angles(n, K=16, mode="normal", rng=None):
+    """float64 [n, K]: the angles in degrees rotate_data (utils/images.py:107-136) gives each of n digits.
+      normal    linspace(0, 359.99, K) for every digit
+      rand-end  linspace(0, e, K), e = uniform(-269.99, 269.99) pushed 90 degrees away from zero (e < 0: e - 90, else e + 90)
+      rsre      linspace(s, e, K), s = uniform(-89.99, 89.99) drawn first, then e = uniform(-269.99, 269.99)
+    The draws are the reference's np.random.uniform calls in its order, digit by digit, from NumPy's global stream when rng is
+    None (after np.random.seed(s) these are the reference's angles for that seed), else from rng (a RandomState or Generator).
+    Not reproduced: the reference's closing `rnd_idx = np.random.shuffle(np.arange(n))` -- shuffle returns None, so X[None, :]
+    shuffles nothing and only adds an axis that .squeeze() removes; it draws from the stream AFTER all angles."""
+    if mode not in ROT_MODES:
+        raise ValueError(f"rot_angles: mode {mode!r}; the reference has " + ", ".join(repr(m) for m in ROT_MODES))
+    n, K = int(n), int(K)
+    if n < 0 or K < 1:
+        raise ValueError(f"rot_angles: n = {n}, K = {K}")
+    uniform = np.random.uniform if rng is None else rng.uniform
+    out = np.empty((n, K), dtype=np.float64)
+    for k in range(n):
+        if mode == "normal":
+            out[k] = np.linspace(0, 359.99, K)
+        elif mode == "rand-end":
+            end = uniform(-269.99, 269.99)
+            end = end - 90 if end < 0 else end + 90
+            out[k] = np.linspace(0, end, K)
+        else:
+            start = uniform(-89.99, 89.99)
+            end = uniform(-269.99, 269.99)
+            out[k] = np.linspace(start, end, K)
+    return out
+
+
+_SPLINE_POLE = math.sqrt(3.0) - 2.0
+
+
+def _spline_prefilter64(c):
+    """The cubic B-spline recursive filter along the LAST axis of a float64 array (a copy): gain 6, pole sqrt(3) - 2, mirror
+    boundary -- one axis of scipy.ndimage.spline_filter(a, 3, mode='mirror')."""
+    z, n = _SPLINE_POLE, c.shape[-1]
+    c = c * 6.0
+    zn1 = z ** (n - 1)
+    c0 = c[..., 0] + zn1 * c[..., n - 1]
+    zi = z
+    for i in range(1, n - 1):
+        c0 = c0 + zi * (c[..., i] + zn1 * c[..., n - 1 - i])
+        zi *= z
+    c[..., 0] = c0 / (1.0 - zn1 * zn1)
+    for i in range(1, n):
+        c[..., i] += z * c[..., i - 1]
+    c[..., n - 1] = (z * c[..., n - 2] + c[..., n - 1]) * z / (z * z - 1.0)
+    for i in range(n - 2, -1, -1):
+        c[..., i] = z * (c[..., i + 1] - c[..., i])
+    return c
+
+
+def _rot_weights64(t):
+    return ((1.0 - t) ** 3 / 6.0, (3.0 * t ** 3 - 6.0 * t ** 2 + 4.0) / 6.0,
+            (-3.0 * t ** 3 + 3.0 * t ** 2 + 3.0 * t + 1.0) / 6.0, t ** 3 / 6.0)
+
+
+def _mirror(i, n):
+    i = np.abs(i)
+    return np.where(i > n - 1, 2 * (n - 1) - i, i)
+
+
+def rot_source_points(angles, H, W):
+    """float64 (p_y, p_x), each [n, K, H, W]: the input point output pixel (y, x) of every frame reads."""
+    a = np.deg2rad(np.asarray(angles, dtype=np.float64))
+    c, s = np.cos(a)[..., None, None], np.sin(a)[..., None, None]
+    cy, cx = (H - 1) / 2.0, (W - 1) / 2.0
+    dy, dx = np.arange(H, dtype=np.float64)[:, None] - cy, np.arange(W, dtype=np.float64)[None, :] - cx
+    return cy + c * dy + s * dx, cx - s * dy + c * dx
+
+
+def _as_images64(images, what):
+    x = images.detach().cpu().numpy() if torch.is_tensor(images) else np.asarray(images)
+    if x.ndim != 3:
+        raise ValueError(f"{what}: images must be [n, H, W], got {tuple(x.shape)}")
+    if min(x.shape[1:]) < L.ROT_MIN_SIZE:
+        raise ValueError(f"{what}: images of {x.shape[1]} x {x.shape[2]}; each side is at least {L.ROT_MIN_SIZE}")
+    return x.astype(np.float64)
+
+
+def _as_angles64(angles, n, what):
+    a = np.asarray(angles.detach().cpu().numpy() if torch.is_tensor(angles) else angles, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != n or a.shape[1] < 1:
+        raise ValueError(f"{what}: angles must be [n, K] degrees with n = {n} and K >= 1, got {tuple(a.shape)}")
+    return a
+
+
+def rotate_reference(images, angles, cval=-0.5):
+    """[n, H, W] values (NumPy or torch, taken to float64) and angles [n, K] in degrees -> float64 tensor [n, K, H, W]:
+    scipy.ndimage.rotate(image, angle, reshape=False, cval=cval, order=3) restated in float64 -- the prefilter along both
+    axes, the source point of every output pixel, cval outside [0, H - 1] x [0, W - 1], else 4 x 4 cubic B-spline taps with
+    mirrored indices.  The oracle of gode_rot_clips (its `raw` output); agrees with scipy to ~1e-14."""
+    x = _as_images64(images, "rotate_reference")
+    n, H, W = x.shape
+    a = _as_angles64(angles, n, "rotate_reference")
+    coef = _spline_prefilter64(np.swapaxes(_spline_prefilter64(np.swapaxes(x, 1, 2)), 1, 2))      # axis 0, then axis 1
+    py, px = rot_source_points(a, H, W)
+    inside = (py >= 0) & (py <= H - 1) & (px >= 0) & (px <= W - 1)
+    py, px = np.where(inside, py, 0.0), np.where(inside, px, 0.0)
+    fy, fx = np.floor(py), np.floor(px)
+    wy, wx = _rot_weights64(py - fy), _rot_weights64(px - fx)
+    iy, ix = fy.astype(np.int64) - 1, fx.astype(np.int64) - 1
+    digit = np.arange(n)[:, None, None, None]
+    out = np.zeros_like(py)
+    for j in range(4):
+        yj = _mirror(iy + j, H)
+        for i in range(4):
+            out += wy[j] * wx[i] * coef[digit, yj, _mirror(ix + i, W)]
+    return torch.from_numpy(np.where(inside, out, float(cval)))
+
+
+def normalise_reference(frames):
+    """[..., H, W] -> float64 tensor of the same shape: every frame min-max normalised as utils/images.py:166-167 writes it,
+    x / (max - min) first, then minus the minimum of that quotient.  A constant frame divides by zero and comes out
+    non-finite, as in the reference."""
+    x = (frames.detach().cpu().numpy() if torch.is_tensor(frames) else np.asarray(frames)).astype(np.float64)
+    flat = x.reshape(x.shape[:-2] + (-1,))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = flat / (flat.max(-1, keepdims=True) - flat.min(-1, keepdims=True))
+        q = q - q.min(-1, keepdims=True)
+    return torch.from_numpy(q.reshape(x.shape))
+
+
+def rot_table(angles):
+    """float32 tensor [n, K, 2] = (cos, sin) of the angles in degrees: evaluated in float64, rounded once.  Angle 0 gives
+    exactly (1, 0)."""
+    a = np.deg2rad(np.asarray(angles, dtype=np.float64))
+    return torch.from_numpy(np.stack([np.cos(a), np.sin(a)], axis=-1).astype(np.float32))
+
+
+def rotate_clips(images, angles, cval=-0.5, want_raw=False, want_out=True, out=None, in_scale=1.0, in_shift=0.0):
+    """gode_rot_clips: device images [n, H, W] -- uint8 (taken through the reference's (v - 127.5f) / 255.0f on load) or fp32 --
+    and host angles [n, K] in degrees -> fp32 [n, K, H, W] min-max normalised frames (`out`: written there when given); with
+    want_raw (out, raw), raw the rotated frames before normalisation; want_out=False: raw alone.  4 <= H, W <= 64."""
+    from .engine import stream_ptr
+    if not torch.is_tensor(images) or images.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("rotate_clips: uint8 or float32 images expected, got "
+                         f"{images.dtype if torch.is_tensor(images) else type(images).__name__}")
+    if images.dim() != 3 or not images.is_contiguous():
+        raise ValueError(f"rotate_clips: images must be a contiguous [n, H, W] tensor, got {tuple(images.shape)}")
+    n, H, W = images.shape
+    if not (L.ROT_MIN_SIZE <= H <= L.ROT_MAX_SIZE and L.ROT_MIN_SIZE <= W <= L.ROT_MAX_SIZE):
+        raise ValueError(f"rotate_clips: images of {H} x {W}; gode_rot_clips takes sides of {L.ROT_MIN_SIZE} to "
+                         f"{L.ROT_MAX_SIZE}")
+    a = _as_angles64(angles, n, "rotate_clips")
+    K = a.shape[1]
+    if not (want_out or want_raw):
+        raise ValueError("rotate_clips: neither the normalised nor the raw frames are wanted")
+    _require_cuda(images, "rotate_clips: images")
+    shape = (n, K, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=images.device) if want_out else None
+    elif (not want_out or tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()
+          or out.device != images.device):
+        raise ValueError(f"rotate_clips: out must be a contiguous float32 {shape} on {images.device}")
+    raw = torch.empty(shape, dtype=torch.float32, device=images.device) if want_raw else None
+    if n:
+        cs = rot_table(a).to(images.device)
+        op = L.RotClipsOp(images=images.data_ptr(), cs=cs.data_ptr(), out=out.data_ptr() if want_out else None,
+                          raw=raw.data_ptr() if want_raw else None, n=n, K=K, H=H, W=W,
+                          in_u8=int(images.dtype == torch.uint8), in_scale=in_scale, in_shift=in_shift, cval=cval)
+        L.run_one(op, stream_ptr())
+    if want_out and want_raw:
+        return out, raw
+    return out if want_out else raw
 
 
 # ======================================================================================================================

@@ -855,6 +855,33 @@ typedef struct gode_clip_gather_op {
 } gode_clip_gather_op;
 int gode_clip_gather(const gode_clip_gather_op* op, void* stream);
 
+/* ---- Rotated-MNIST clips built on the device (utils/images.py:101-173, rotate_data: every digit through K angles with
+ * scipy.ndimage.rotate(image, angle, reshape=False, cval=-0.5), every frame normalised min-max) -- DESIGN section 25 ---------
+ * images: [n][H][W], uint8 (in_u8 = 1) or fp32 (in_u8 = 0), one channel.  On load a = v * in_scale + in_shift (one fused
+ * multiply-add), where for uint8 v is first taken through the reference's own fp32 expression (byte - 127.5f) / 255.0f
+ * (utils/images.py:71); in_scale = 1, in_shift = 0 changes no value.  cs: fp32 [n][K][2] = (cos, sin) of every frame's angle,
+ * evaluated in double on the host and rounded once.  Per digit:
+ *   1. cubic B-spline prefilter along axis 0, then axis 1: gain 6, pole z = sqrt(3) - 2, the causal pass initialised for a mirror
+ *      boundary (period 2n - 2), the anticausal one from z / (z^2 - 1) * (c[n-1] + z c[n-2])   (scipy.ndimage.spline_filter,
+ *      order 3, mode 'mirror');
+ *   2. output pixel (y, x) of frame k reads p_y = cy + cos (y - cy) + sin (x - cx), p_x = cx - sin (y - cy) + cos (x - cx), with
+ *      cy = (H - 1) / 2, cx = (W - 1) / 2, each two fp32 fused multiply-adds;
+ *   3. p_y outside [0, H - 1] or p_x outside [0, W - 1] (or not a number): cval.  Otherwise f = floor(p), t = p - f, weights
+ *      ((1-t)^3, 3t^3 - 6t^2 + 4, -3t^3 + 3t^2 + 3t + 1, t^3) / 6 per axis on the coefficients f - 1 .. f + 2, indices outside
+ *      [0, n - 1] mirrored (i -> -i, i -> 2(n - 1) - i);
+ *   4. out = x / (max - min) - min / (max - min) over the frame's H * W values, both IEEE divisions (utils/images.py:166-167:
+ *      the quotient first, then minus ITS minimum).  A frame of equal values divides by zero and comes out non-finite, as in the
+ *      reference; it is not special-cased.
+ * out: fp32 [n][K][H][W], the normalised frames; raw: the same shape, the rotated frames before step 4; each nullable, not both;
+ * the values of either do not depend on the presence of the other.  Element offsets are 64-bit.
+ * GODE_E_ARG: a null op / images / cs, both outputs null, n < 1, K < 1, in_u8 not 0 or 1.  GODE_E_SHAPE: H or W outside
+ * [4, 64].  Both are returned before any launch. */
+typedef struct gode_rot_clips_op {
+  const void* images; const float* cs; float* out; float* raw;
+  int32_t n, K, H, W, in_u8; float in_scale, in_shift, cval;
+} gode_rot_clips_op;
+int gode_rot_clips(const gode_rot_clips_op* op, void* stream);
+
 /* out[i] = a[i]*alpha (+ out[i] if accumulate); small utility for gradient bucket handling */
 int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulate, void* stream);
 
@@ -899,7 +926,8 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
   X(BCE_T,         36, gode_bce_t_op,         gode_bce_logits_t)  \
   X(RESIZE_U8,     37, gode_resize_u8_op,     gode_resize_u8)     \
   X(CLIP_GATHER,   38, gode_clip_gather_op,   gode_clip_gather)   \
-  X(BN_RUNNING,    39, gode_bn_running_op,    gode_bn_running)
+  X(BN_RUNNING,    39, gode_bn_running_op,    gode_bn_running)    \
+  X(ROT_CLIPS,     40, gode_rot_clips_op,     gode_rot_clips)
 /* GODE_OP_PACK stays outside the table: it has no (op*, stream) entry point, gode_run sends every run of consecutive pack
  * ops out as batched launches instead. */
 #define GODE_ENUM_ROW_(name, value, op_t, fn) GODE_OP_##name = value,
