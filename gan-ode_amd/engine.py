@@ -62,6 +62,56 @@ def stream_ptr():
     return torch.cuda.current_stream().cuda_stream
 
 
+def tensor_version(t):
+    """What tells that a tensor was written or replaced: torch's version counter, ours (bump_version), the storage."""
+    return (t._version, getattr(t, "_gode_ver", 0), t.data_ptr())
+
+
+def bump_version(t):
+    """t was updated through a raw pointer, which torch's counter does not see: bump our own version."""
+    t._gode_ver = getattr(t, "_gode_ver", 0) + 1
+
+
+class PointerTable:
+    """One launch site's pointer table: a pinned int64 host block and its device twin, re-uploaded only when a row changed
+    (parameters, arena gradients and moments keep their addresses; autograd hands out new gradient tensors, whose
+    addresses the caching allocator mostly repeats from step to step).  rows: an int64 array [n][width], compared by its
+    bytes, or a list of n equal-length int tuples, compared as a tuple (cheaper for a caller that has no array yet)."""
+
+    def __init__(self, device):
+        self.device = device
+        self.host = self.dev = self.ev = self.key = None
+        self.uploads = 0
+
+    @staticmethod
+    def _key(rows):
+        return rows.tobytes() if isinstance(rows, np.ndarray) else tuple(rows)
+
+    def matches(self, rows):
+        """Would upload(rows) return the device table as it stands?"""
+        return self.key is not None and self.key == self._key(rows)
+
+    def upload(self, rows):
+        key = self._key(rows)
+        if key == self.key:
+            return self.dev
+        src = torch.from_numpy(np.asarray(rows, dtype=np.int64))
+        if self.host is None or self.host.shape != src.shape:
+            self.host = torch.empty(src.shape, dtype=torch.int64).pin_memory()
+            self.dev = torch.empty(src.shape, dtype=torch.int64, device=self.device)
+            self.ev = None
+        elif not self.ev.query():
+            self.ev.synchronize()        # (a whole step lies between two uploads of a site: never waits in practice)
+        self.host.copy_(src)
+        self.dev.copy_(self.host, non_blocking=True)
+        if self.ev is None:
+            self.ev = torch.cuda.Event()
+        self.ev.record()
+        self.key = key
+        self.uploads += 1
+        return self.dev
+
+
 # -- two-lane sampling (gode_run_lanes): which op of the main lane releases the side lane ---------------------------------
 # The pointer fields through which the ops of a sampling front WRITE (every other pointer field of theirs is read only).
 _FRONT_WRITES = {L.OdeFwdOp: ("z", "traj"), L.IgemmOp: ("out", "stats", "work")}
@@ -365,8 +415,7 @@ class ConvStack:
         """packs: [(layer, dir, PackOp)].  Re-packs only panels whose weight changed since they were last packed."""
         stale = []
         for l, d, op in packs:
-            w = self.params[l].weight
-            ver = (w._version, getattr(w, "_gode_ver", 0), w.data_ptr())
+            ver = tensor_version(self.params[l].weight)
             if self.pack_cache.get(("ver", l, d)) != ver:
                 self.pack_cache[("ver", l, d)] = ver
                 stale.append(op)

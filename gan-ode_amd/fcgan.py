@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import dptr, make_geom, stream_ptr
+from .engine import dptr, make_geom, stream_ptr, tensor_version
 from .modules import _require_gpu
 
 DROP_P = 0.3
@@ -57,10 +57,6 @@ class _Packs:
 
     def __init__(self):
         self.cache = {}
-
-    @staticmethod
-    def version(w):
-        return (w._version, getattr(w, "_gode_ver", 0), w.data_ptr())
 
     def get(self, l, direction, w, ver, g):
         hit = self.cache.get((l, direction, g.N))
@@ -158,7 +154,7 @@ class _FcNet(nn.Module):
         _check_input(x, self.fc1.in_features, what)
         args, vers = [], []
         for fc in self._layers():
-            vers.append(_Packs.version(fc.weight))      # read off the Parameter: _gode_ver lives on that object
+            vers.append(tensor_version(fc.weight))     # read off the Parameter: _gode_ver lives on that object
             for t in (fc.weight, fc.bias):
                 _require_gpu(t, what + " parameter")
                 if t.dtype != torch.float32 or not t.is_contiguous():

@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .engine import (LANE_ORDERED, LANE_OVERLAP, LANE_SINGLE, ConvStack, LayerParams, LayerSpec, conv_out, dptr, lane_gate,
-                     lane_mode, make_geom, pair_turn, stream_ptr)
+                     lane_mode, make_geom, pair_turn, stream_ptr, tensor_version)
 
 Z_COLS = 96  # latent row: [motion 16 | content 50 | zero pad 30]: K % 32 == 0 puts the first decoder GEMM on the FAST path
 Z_CATEG0 = 66        # dim_z_category = C > 0: the one-hot lives in the first C pad columns (gode_categ_onehot)
@@ -559,7 +559,7 @@ class _GenPlan:
         layer-0 weight (torch's version counter, FusedAdam's, the storage).  A write through `.data` shows in none of them:
         VideoGenerator.invalidate_packs is the call that tells."""
         ts = [t for t in self._params() if t is not None] + [self.stack.params[0].weight]
-        return tuple((t._version, getattr(t, "_gode_ver", 0), t.data_ptr()) for t in ts)
+        return tuple(tensor_version(t) for t in ts)
 
     def _forward_lanes(self, x_host, content_host, sel_host, training):
         """forward() of a call that _lanes_possible let through: the mode is decided once, behind begin_forward."""
@@ -629,7 +629,7 @@ class _GenPlan:
         ts = [t for t in self._params() if t is not None]
         for p in self.stack.params:
             ts += [t for t in (p.weight, p.gamma, p.beta) if t is not None]
-        return tuple((t._version, getattr(t, "_gode_ver", 0), t.data_ptr()) for t in ts)
+        return tuple(tensor_version(t) for t in ts)
 
     def _forward_pair(self, x_host, content_host, sel_host, training):
         """forward() of a call that _lanes_possible and _pair_possible let through, on the plan whose turn it is."""

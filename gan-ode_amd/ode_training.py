@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .engine import PointerTable, bump_version, stream_ptr
 
 METHODS = ("euler", "rk2", "rk4")
 FD_H = float(np.finfo(np.float32).eps) ** (1.0 / 3.0)      # relative central-difference step for precision eps32
@@ -42,31 +43,6 @@ def _f32(x):
     return float(np.float32(x))
 
 
-class _Site:
-    """One launch site's pointer table: a pinned host copy and its device twin, re-uploaded only when a pointer changed
-    (autograd hands out new gradient tensors, whose addresses the caching allocator mostly repeats from step to step)."""
-
-    def __init__(self, n, width, device):
-        self.host = torch.empty((n, width), dtype=torch.int64).pin_memory()
-        self.dev = torch.empty((n, width), dtype=torch.int64, device=device)
-        self.ev = None
-        self.key = None
-
-    def upload(self, rows):
-        key = rows.tobytes()
-        if key == self.key:
-            return self.dev
-        if self.ev is not None and not self.ev.query():
-            self.ev.synchronize()        # (a whole step lies between two uploads of a site: never waits in practice)
-        self.host.copy_(torch.from_numpy(rows))
-        self.dev.copy_(self.host, non_blocking=True)
-        if self.ev is None:
-            self.ev = torch.cuda.Event()
-        self.ev.record()
-        self.key = key
-        return self.dev
-
-
 class _Device:
     """The fused path of one parameter list: layout of the concatenated index space (fixed: parameters do not move),
     pointer tables per launch site, scratch of the penalty.  Everything is allocated on first use and kept."""
@@ -92,10 +68,10 @@ class _Device:
             self._layout_key = key
         return key
 
-    def _site(self, name, width):
+    def _site(self, name):
         s = self.sites.get(name)
         if s is None:
-            s = self.sites[name] = _Site(len(self.params), width, self.device)
+            s = self.sites[name] = PointerTable(self.device)
         return s
 
     @staticmethod
@@ -110,11 +86,10 @@ class _Device:
 
     def _bump(self):
         for p in self.params:
-            p._gode_ver = getattr(p, "_gode_ver", 0) + 1     # updated through a raw pointer: bump our own version
+            bump_version(p)
 
     def step(self, site, coefs, grads, cq=None, q=None, cq_dev=None):
         """p += sum_k coefs[k] * grads[k] + cq * (q[0] - q[1]) [* cq_dev[0]] on every parameter, one launch."""
-        from .engine import stream_ptr
         pk = self._layout()
         rows = np.zeros((len(self.params), 9), dtype=np.int64)
         rows[:, 0], rows[:, 7], rows[:, 8] = pk, self.numel, self.chunk0
@@ -131,7 +106,7 @@ class _Device:
                 for i, p in enumerate(self.params):
                     rows[i, col], t = self._ptr(lst[i], p)
                     keep.append(t)
-        tbl = self._site(site, 9).upload(rows)
+        tbl = self._site(site).upload(rows)
         lib = L.lib()
         L.call("ode_step", lambda: L.check(
             lib.gode_ode_step(tbl.data_ptr(), len(self.params), self.chunks, terms, c[0], c[1], c[2], c[3],
@@ -151,7 +126,6 @@ class _Device:
         """dst = base + a [* a_dev[0]] * v per tensor (v None: copy), one launch; h given: also the two norms and the
         difference step into self.sums / self.fd.  dst's layout is the parameters' (same alignment by construction:
         torch allocations are 512-byte aligned, so `saved` may only add vector lanes, and the chunk count is an upper bound)."""
-        from .engine import stream_ptr
         self._scratch()
         self._layout()
         rows = np.zeros((len(self.params), 5), dtype=np.int64)
@@ -166,7 +140,7 @@ class _Device:
                 keep.append(t)
             rows[i, 4] = chunk
             chunk += int(lib.gode_ode_step_chunks(dst[i].data_ptr(), p.numel()))
-        tbl = self._site(site, 5).upload(rows)
+        tbl = self._site(site).upload(rows)
         want = h is not None
         L.call("axpy_multi", lambda: L.check(
             lib.gode_axpy_multi(tbl.data_ptr(), len(self.params), chunk, _f32(a), a_dev.data_ptr() if a_dev is not None else None,

@@ -14,7 +14,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
-from .engine import stream_ptr
+from .engine import PointerTable, bump_version, stream_ptr
 from .modules import PatchImageDiscriminator, VideoDiscriminator, VideoGenerator, VideoGeneratorMNISTODE
 
 
@@ -333,6 +333,7 @@ class FusedAdam(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       maximize=False, foreach=None, capturable=False, differentiable=False,
                                       fused=None, decoupled_weight_decay=False))
+        self._tables, self._keep = {}, {}         # per param group: its PointerTable, the gradients its last launch reads
         # noise_sigma > 0: add_noise of mnist_moco_ode_noise.py / _wgan.py (p += randn_like(p) * sigma on EVERY parameter,
         # gradient or not, right after the update) fused into the Adam launch.  The normals come from libgode's
         # counter-based stream (gode.h: Philox4x32-10 keyed by noise_seed, counter (element quad, noise step,
@@ -383,24 +384,41 @@ class FusedAdam(torch.optim.Optimizer):
     def step(self, closure=None, grads: Optional[dict] = None, gscale: float = 1.0, feed=None):
         """grads: optional {param: tensor} overriding .grad (views into an all-reduced bucket); gscale multiplies
         every gradient (1/world_size for data parallelism).  All tensors of a param group are updated by ONE launch
-        (gode_adam_multi) driven by a small device table of pointers, uploaded only when a pointer changed.
+        (gode_adam_multi, with noise gode_adam_noise_multi) driven by a small device table of pointers, uploaded only
+        when a pointer changed.
         feed: a HostFeed (graph capture): the step-dependent coefficients are then read from the feed's device block
-        (gode_adam_multi_dev), so the recorded launch stays valid while the step count advances."""
+        (the _dev entry points), so the recorded launch stays valid while the step count advances."""
         assert closure is None
-        import numpy as np
-        lib = L.lib()
         for gi, group in enumerate(self.param_groups):
-            if group.get("noise_sigma", 0.0) > 0.0:
-                self._noisy_step(gi, group, grads, gscale, feed)
+            self._group_step(gi, group, grads, gscale, feed)
+        return None
+
+    def _group_step(self, gi, group, grads, gscale, feed):
+        """One step of a param group.  Plain: a parameter without a gradient is skipped.  With noise every parameter gets
+        its noise exactly once -- those with a gradient as Adam + noise rows, those without (the generator's dead GRU
+        cell) as noise-only rows of the same launch, those on a different Adam step count through gode_adam_l2 +
+        gode_param_noise."""
+        lib = L.lib()
+        b1, b2 = group["betas"]
+        params = group["params"]
+        noisy = group.get("noise_sigma", 0.0) > 0.0
+        offs = [None] * len(params)
+        if noisy:
+            group["noise_step"] += 1
+            nstep, seed, nstream, sigma = group["noise_step"], group["noise_seed"], group["noise_stream"], group["noise_sigma"]
+            before = [p for g in self.param_groups[:gi] for p in g["params"]]      # the stream runs on through the groups
+            offs = self.noise_offsets(before + params)[len(before):]
+        rows, keep, step, max_n, dev = [], [], None, 0, None
+        for p, off in zip(params, offs):
+            g = grads.get(p) if grads is not None else p.grad
+            if g is None and not noisy:
                 continue
-            b1, b2 = group["betas"]
-            rows, keep, step, max_n, dev = [], [], None, 0, None
-            for p in group["params"]:
-                g = grads.get(p) if grads is not None else p.grad
-                if g is None:
-                    continue
-                if not p.is_cuda:
-                    raise RuntimeError("FusedAdam runs only on the GPU through libgode.so")
+            if not p.is_cuda:
+                raise RuntimeError("FusedAdam runs only on the GPU through libgode.so")
+            row = None
+            if g is None:
+                row = (p.data_ptr(), 0, 0, 0, p.numel())         # noise-only row
+            else:
                 if not g.is_contiguous():
                     g = g.contiguous()
                 st = self.state[p]
@@ -419,130 +437,43 @@ class FusedAdam(torch.optim.Optimizer):
                                        v=st["exp_avg_sq"].data_ptr(), n=p.numel(), lr=group["lr"], beta1=b1, beta2=b2,
                                        eps=group["eps"], weight_decay=group["weight_decay"], gscale=gscale,
                                        step=s_now), stream_ptr())
+                    if noisy:
+                        L.call("param_noise", lambda: L.check(
+                            lib.gode_param_noise(p.data_ptr(), p.numel(), seed, nstream, nstep, off, sigma, 1, stream_ptr()),
+                            "gode_param_noise"))
                 else:
-                    rows.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                                 p.numel()))
-                    max_n = max(max_n, p.numel())
+                    row = (p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel())
                 keep.append(g)
-                p._gode_ver = getattr(p, "_gode_ver", 0) + 1     # updated through a raw pointer: bump our own version
-                dev = p.device
-            if rows:
-                tbl = getattr(self, "_tables", None)
-                if tbl is None:
-                    tbl = self._tables = {}
-                n = len(rows)
-                ent = tbl.get(id(group))
-                key = tuple(rows)
-                if ent is None or ent.get("key") != key:
-                    # (the pointers of parameters, arena gradients and moments do not change from step to step: the
-                    # table is uploaded once, not per step)
-                    if feed is not None:
-                        raise RuntimeError("graph capture: the Adam pointer table must exist already (run eager "
-                                           "iterations first)")
-                    if ent is None or ent["host"].shape[0] != n:
-                        ent = tbl[id(group)] = dict(host=torch.empty((n, 5), dtype=torch.int64).pin_memory(),
-                                                    dev=torch.empty((n, 5), dtype=torch.int64, device=dev), ev=None)
-                    if ent["ev"] is not None:
-                        ent["ev"].synchronize()          # the previous upload from this pinned buffer has completed
-                    ent["key"] = key
-                    ent["host"].copy_(torch.from_numpy(np.asarray(rows, dtype=np.int64)))
-                    ent["dev"].copy_(ent["host"], non_blocking=True)
-                    if ent["ev"] is None:
-                        ent["ev"] = torch.cuda.Event()
-                    ent["ev"].record()
-                if feed is not None:
-                    coef = feed.adam_slot(self, gi, group["lr"], b1, b2, step)
-                    L.call("adam_multi", lambda: L.check(
-                        lib.gode_adam_multi_dev(ent["dev"].data_ptr(), n, max_n, b1, b2, group["eps"],
-                                                group["weight_decay"], gscale, coef, stream_ptr()), "gode_adam_multi_dev"))
-                else:
-                    L.call("adam_multi", lambda: L.check(
-                        lib.gode_adam_multi(ent["dev"].data_ptr(), n, max_n, group["lr"], b1, b2, group["eps"],
-                                            group["weight_decay"], gscale, step, stream_ptr()), "gode_adam_multi"))
-                self._keep = keep
-        return None
-
-    def _noisy_step(self, gi, group, grads, gscale, feed):
-        """One Adam + parameter-noise step of a param group: every parameter gets its noise exactly once -- those with a
-        gradient as Adam + noise rows, those without (the generator's dead GRU cell) as noise-only rows of the same
-        launch (gode_adam_noise_multi), those on a different Adam step count through gode_adam_l2 + gode_param_noise."""
-        import numpy as np
-        lib = L.lib()
-        b1, b2 = group["betas"]
-        group["noise_step"] += 1
-        nstep, seed, nstream, sigma = group["noise_step"], group["noise_seed"], group["noise_stream"], group["noise_sigma"]
-        base = sum(sum((p.numel() + 3) // 4 * 4 for p in g["params"]) for g in self.param_groups[:gi])
-        rows, keep, step, max_n, dev = [], [], None, 0, None
-        for p, off in zip(group["params"], self.noise_offsets(group["params"])):
-            off += base
-            if not p.is_cuda:
-                raise RuntimeError("FusedAdam runs only on the GPU through libgode.so")
-            g = grads.get(p) if grads is not None else p.grad
-            if g is None:
-                rows.append((p.data_ptr(), 0, 0, 0, p.numel(), off))        # noise-only row
-            else:
-                if not g.is_contiguous():
-                    g = g.contiguous()
-                st = self.state[p]
-                if not st:
-                    st["step"] = torch.tensor(0.0)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1
-                s_now = int(st["step"].item())
-                if step is None:
-                    step = s_now
-                if s_now != step:       # parameters on different step counts: one Adam launch and one noise launch each
-                    if feed is not None:
-                        raise RuntimeError("graph capture needs all parameters of a group on the same Adam step")
-                    L.run_one(L.AdamOp(p=p.data_ptr(), g=g.data_ptr(), m=st["exp_avg"].data_ptr(),
-                                       v=st["exp_avg_sq"].data_ptr(), n=p.numel(), lr=group["lr"], beta1=b1, beta2=b2,
-                                       eps=group["eps"], weight_decay=group["weight_decay"], gscale=gscale,
-                                       step=s_now), stream_ptr())
-                    L.call("param_noise", lambda p=p, off=off: L.check(
-                        lib.gode_param_noise(p.data_ptr(), p.numel(), seed, nstream, nstep, off, sigma, 1, stream_ptr()),
-                        "gode_param_noise"))
-                else:
-                    rows.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                                 p.numel(), off))
-                keep.append(g)
-            max_n = max(max_n, p.numel())
-            p._gode_ver = getattr(p, "_gode_ver", 0) + 1     # updated through a raw pointer: bump our own version
+            if row is not None:
+                rows.append(row + (off,) if noisy else row)
+                max_n = max(max_n, p.numel())
+            bump_version(p)
             dev = p.device
+        self._keep[gi] = keep            # (the launch reads the .contiguous() copies among them)
         if not rows:
             return
-        step = step if step is not None else max(1, self.current_step(gi))   # (noise-only launch: coefficients unused)
-        tbl = getattr(self, "_tables", None)
+        # (the pointers of parameters, arena gradients and moments do not change from step to step: the table is uploaded
+        # once, not per step)
+        tbl = self._tables.get(gi)
         if tbl is None:
-            tbl = self._tables = {}
-        n = len(rows)
-        ent = tbl.get(id(group))
-        key = tuple(rows)
-        if ent is None or ent.get("key") != key:
-            if feed is not None:
-                raise RuntimeError("graph capture: the Adam pointer table must exist already (run eager iterations first)")
-            if ent is None or tuple(ent["host"].shape) != (n, 6):
-                ent = tbl[id(group)] = dict(host=torch.empty((n, 6), dtype=torch.int64).pin_memory(),
-                                            dev=torch.empty((n, 6), dtype=torch.int64, device=dev), ev=None)
-            if ent["ev"] is not None:
-                ent["ev"].synchronize()
-            ent["key"] = key
-            ent["host"].copy_(torch.from_numpy(np.asarray(rows, dtype=np.int64)))
-            ent["dev"].copy_(ent["host"], non_blocking=True)
-            if ent["ev"] is None:
-                ent["ev"] = torch.cuda.Event()
-            ent["ev"].record()
-        if feed is not None:
-            coef = feed.adam_slot(self, gi, group["lr"], b1, b2, step, noise_step=nstep)
-            L.call("adam_noise_multi", lambda: L.check(
-                lib.gode_adam_noise_multi_dev(ent["dev"].data_ptr(), n, max_n, b1, b2, group["eps"], group["weight_decay"],
-                                              gscale, coef, seed, nstream, sigma, stream_ptr()), "gode_adam_noise_multi_dev"))
+            tbl = self._tables[gi] = PointerTable(dev)
+        if feed is not None and not tbl.matches(rows):
+            raise RuntimeError("graph capture: the Adam pointer table must exist already (run eager iterations first)")
+        table, n = tbl.upload(rows).data_ptr(), len(rows)
+        if step is None:
+            step = max(1, self.current_step(gi))                 # (noise-only launch: coefficients unused)
+        tag = "adam_noise_multi" if noisy else "adam_multi"
+        args = (b1, b2, group["eps"], group["weight_decay"], gscale)
+        if feed is not None:         # the coefficients (and the noise step) come from the feed's device block
+            coef = feed.adam_slot(self, gi, group["lr"], b1, b2, step, noise_step=nstep if noisy else None)
+            name, args = f"gode_{tag}_dev", args + (coef,) + ((seed, nstream, sigma) if noisy else ())
         else:
-            L.call("adam_noise_multi", lambda: L.check(
-                lib.gode_adam_noise_multi(ent["dev"].data_ptr(), n, max_n, group["lr"], b1, b2, group["eps"],
-                                          group["weight_decay"], gscale, step, seed, nstream, nstep, sigma, stream_ptr()),
-                "gode_adam_noise_multi"))
-        self._keep = keep
+            name, args = f"gode_{tag}", (group["lr"],) + args + (step,) + ((seed, nstream, nstep, sigma) if noisy else ())
+        L.call(tag, lambda: L.check(getattr(lib, name)(table, n, max_n, *args, stream_ptr()), name))
+
+    def pointer_table(self, group_index=0):
+        """The PointerTable of a param group's launch (None before the group's first launch)."""
+        return self._tables.get(group_index)
 
     def advance_steps(self, group_index=0):
         """Host-side bookkeeping of one optimiser step that a replayed graph performed on the device: the `step`

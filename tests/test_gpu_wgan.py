@@ -12,6 +12,7 @@ import torch
 
 import wgan_ref as W
 from conftest import assert_weights_after_adam, rel_err, seed_all
+from guarded import guarded_tensors as _guarded_tensors
 
 import gan_ode_amd as G
 import gan_ode_amd._lib as L
@@ -116,19 +117,6 @@ def _adam64(p, g, m, v, step, lr=2e-4, b1=0.5, b2=0.999, eps=1e-8, wd=1e-5):
     v = b2 * v + (1 - b2) * g * g
     denom = np.sqrt(v) / np.sqrt(1 - b2 ** step) + eps
     return p - lr / (1 - b1 ** step) * m / denom, m, v
-
-
-def _guarded_tensors(sizes, gap=9):
-    """tensors carved out of one NaN-filled buffer with NaN gaps around each; even-numbered ones 16-byte aligned (float4
-    path), odd-numbered ones one float off (scalar path)"""
-    total = sum(sizes) + (gap + 4) * (len(sizes) + 1)
-    buf = torch.full((total,), NAN, device="cuda")
-    views, off = [], gap
-    for k, n in enumerate(sizes):
-        off = (off + 3) // 4 * 4 + k % 2
-        views.append(buf[off:off + n])
-        off += n + gap
-    return buf, views
 
 
 def test_fused_adam_noise_against_float64_and_dev_variant_bitwise():
