@@ -142,6 +142,21 @@ def test_a_call_in_gradient_mode_between_pair_calls():
     assert modes == ["pair_ordered", "pair_ordered", "pair_overlap", "grad", "pair_ordered", "pair_ordered", "pair_overlap"]
 
 
+def test_eval_mode_calls_between_pair_calls_hand_the_streak_to_the_two_lane_front_and_back():
+    """An eval-mode pass has no pair form, so under the same knob its calls take the two-lane front: a call of one kind
+    ends the streak of the other and starts its own ordered (the first eval call also builds its program)."""
+    def body(gen, m):
+        outs = _flat(_sample(gen, m) for _ in range(3))
+        gen.eval()
+        outs += _flat(_sample(gen, m) for _ in range(3))
+        gen.train()
+        return outs + _flat(_sample(gen, m) for _ in range(3))
+
+    modes = _both(body)
+    assert modes == (["pair_ordered", "pair_ordered", "pair_overlap", "ordered", "overlap", "overlap",
+                      "pair_ordered", "pair_overlap", "pair_overlap"]), modes
+
+
 def test_the_second_plan_is_built_when_a_streak_starts_and_the_default_stays_single_for_a_lone_caller():
     seed_all(5)
     gen, _, _ = G.build_mnist(ngf=8, ndf=8)
