@@ -5,7 +5,8 @@
   d_{-1} := d_0); derivative b + (2c + 3d s) s with torchcde's interval choice (bucketize - 1, clamped);
 * the vector field tanh(W2 relu(W1 z + b1) + b2).view(16, 2) @ dX/dt and the pre-net f([0, x_0]);
 * replay(): the kernel's arithmetic in float64 on a GIVEN accepted schedule (autograd-transparent), so outputs, states
-  and gradients can be compared exactly with the kernels';
+  and gradients can be compared exactly with the kernels'; with fp32 parameters the same arithmetic in torch's fp32, which
+  measures the rounding error of the restatement itself on that schedule;
 * solve(): a full float64 dopri5 solve with oracle.ode_ref's controller (whole-batch RMS norm).
 """
 import numpy as np
@@ -81,9 +82,9 @@ class Field:
     def __init__(self, P, x, T, round_time=True):
         self.P, self.T, self.round = P, T, round_time
         self.margin = torch.full((x.shape[0],), float("inf"), dtype=torch.float64)   # min |W1 z + b1| seen
-        xd = x.double()
+        xd = x.to(P[0].dtype)                          # float64 leaves: the reference; fp32: its own rounding error
         self.cx = hermite_coeffs(slopes(xd))
-        self.ct = hermite_coeffs(time_slopes(T))
+        self.ct = hermite_coeffs(time_slopes(T).to(P[0].dtype))
 
     def __call__(self, t, z):
         t = float(t)
@@ -103,12 +104,14 @@ def interp_weights(x):
     return (-8 * x4 + 14 * x3 - 5 * x2, 16 * x4 - 32 * x3 + 16 * x2, -2 * x4 + 5 * x3 - 4 * x2 + x, 2 * x4 - 3 * x3 + x2)
 
 
-def replay(P, x, T, sched_t, sched_h, margin=None):
+def replay(P, x, T, sched_t, sched_h, margin=None, round_abscissa=True):
     """The discrete forward on a given accepted schedule: -> (outputs [N, T, 16], states [N, S+1, 16], z0).
+    round_abscissa: the dense output's abscissa from the fp32-rounded times, as the kernel and torchdiffeq on an fp32
+    clock take it; False: from the float64 times, as solve() below (oracle.ode_ref._interp_eval on a float64 clock).
     margin (a dict): margin["relu"] = per trajectory, the smallest |W1 z + b1| of any stage -- where it is within
     rounding of 0, an fp32 and a float64 evaluation may take different ReLU branches (a kink of the exact gradient)."""
     f = Field(P, x, T)
-    z0 = prenet(P, x[:, 0].double())
+    z0 = prenet(P, x[:, 0].to(P[0].dtype))
     y = z0
     outs = [z0]
     states = [z0]
@@ -133,7 +136,10 @@ def replay(P, x, T, sched_t, sched_h, margin=None):
                 if coef:
                     ym = ym + h * coef * k
             while jo < T and jo <= t1:
-                xa = (float(np.float32(jo)) - float(np.float32(t0))) / (float(np.float32(t1)) - float(np.float32(t0)))
+                if round_abscissa:
+                    xa = (float(np.float32(jo)) - float(np.float32(t0))) / (float(np.float32(t1)) - float(np.float32(t0)))
+                else:
+                    xa = (jo - t0) / (t1 - t0)
                 wS, wM, w1, w7 = interp_weights(xa)
                 outs.append(y + wS * (y1 - y) + wM * (ym - y) + h * (w1 * ks[0] + w7 * k7))
                 jo += 1
@@ -145,13 +151,14 @@ def replay(P, x, T, sched_t, sched_h, margin=None):
     return torch.stack(outs, 1), torch.stack(states, 1), z0
 
 
-def solve(P, x, T, rtol=1e-4, atol=1e-6):
-    """float64 dopri5 of oracle.ode_ref with the whole-batch RMS norm -> (outputs [N, T, 16], accepted, trials).  The
+def solve(P, x, T, rtol=1e-4, atol=1e-6, sched=None):
+    """float64 dopri5 of oracle.ode_ref with the whole-batch RMS norm -> (outputs [N, T, 16], accepted, trials); sched (a
+    list) receives the accepted steps as (t0, h) floats, in order (the solve stops with the step that reaches T - 1).  The
     stage times reach the field rounded to fp32, as oracle.ode_ref.dopri5_solve and torchdiffeq pass them to an fp32
     field (the step counts are sensitive to it: 54 / 82 instead of 56 / 90 accepted / trial steps at N = 32, seed 7)."""
     f = Field(P, x, T)
     z0 = prenet(P, x[:, 0].double())
-    calls = {"acc": 0, "trials": 0}
+    calls = {"acc": 0, "trials": 0, "sched": sched}
     out = _dopri5_counted(f, z0, torch.arange(T, dtype=torch.float64), rtol, atol, calls)
     return out.transpose(0, 1), calls["acc"], calls["trials"]
 
@@ -180,6 +187,8 @@ def _dopri5_counted(f, y0, t, rtol, atol, calls):
             calls["trials"] += 1
             if bool(ratio <= 1):
                 calls["acc"] += 1
+                if calls.get("sched") is not None:
+                    calls["sched"].append((float(t0), float(dt)))
                 y_mid = y + sum(k * (c * dt) for k, c in zip(ks, R._DP_CMID))
                 interp = R._interp_fit(y, y1, y_mid, f0, f1, dt)
                 seg0, seg1 = t0, t0 + dt

@@ -8,7 +8,6 @@ import ctypes as C
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import assert_weights_after_adam, rel_err, seed_all
 
@@ -16,6 +15,7 @@ import gan_ode_amd as G
 import gan_ode_amd._lib as L
 from gan_ode_amd.modules import sde_grid_arrays
 from oracle import mocogan_ref as M
+from sde_ref import _ops, _params, _sched_dev, restate
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -24,52 +24,6 @@ DT = 2.5e-2
 
 def stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-def restate(params, x, grid, prenet):
-    """params: [Wa ba Wb bb] (prenet) + [Wf1 bf1 Wf2 bf2 Wg1 bg1 Wg2 bg2]; x [1+S, N, 16] = x0, xi.
-    -> states [N, S+1, 16], outputs [N, T, 16] in the dtype of the parameters."""
-    dt_ = params[-1].dtype
-    Wf1, bf1, Wf2, bf2, Wg1, bg1, Wg2, bg2 = params[-8:]
-    y = x[0].to(dt_)
-    if prenet:
-        Wa, ba, Wb, bb = params[:4]
-        y = F.leaky_relu(F.leaky_relu(y @ Wa.t() + ba, 0.2) @ Wb.t() + bb, 0.2)
-    Y = [y]
-    for k in range(grid["S"]):
-        h = grid["dt"][k].to(dt_)
-        dw = grid["sqrt_dt"][k].to(dt_) * x[1 + k].to(dt_)
-        f = torch.tanh(y @ Wf1.t() + bf1) @ Wf2.t() + bf2
-        g = torch.tanh(y @ Wg1.t() + bg1) @ Wg2.t() + bg2
-        y = y + f * h + g * dw
-        Y.append(y)
-    outs = [Y[0]]
-    for j in range(1, len(grid["emit_at"])):
-        k = int(grid["emit_at"][j])
-        outs.append(grid["w0"][j].to(dt_) * Y[k] + grid["w1"][j].to(dt_) * Y[k + 1])
-    return torch.stack(Y, 1), torch.stack(outs, 1)
-
-
-def _params(prenet, gen=None, scale=0.4):
-    gen = gen or torch.Generator().manual_seed(3)
-    shapes = ([(64, 16), (64,), (16, 64), (16,)] if prenet else []) + [(16, 16), (16,), (16, 16), (16,)] * 2
-    return [torch.randn(s, generator=gen) * scale for s in shapes]
-
-
-def _sched_dev(grid):
-    return {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in grid.items()}
-
-
-def _ops(P, prenet, N, T, sd, x, content, sel, z, states, zcols):
-    ptrs = [p.data_ptr() for p in P]
-    prm = L.SdeParams(*(ptrs if prenet else [None] * 4 + ptrs))
-    common = dict(p=prm, x=x.data_ptr(), sel_t=None if sel is None else sel.data_ptr(), dt=sd["dt"].data_ptr(),
-                  sqrt_dt=sd["sqrt_dt"].data_ptr(), emit_at=sd["emit_at"].data_ptr(), emit_w0=sd["w0"].data_ptr(),
-                  emit_w1=sd["w1"].data_ptr(), N=N, T=T, S=sd["S"], prenet=int(prenet), zcols=zcols)
-    fop = L.SdeFwdOp(content=None if content is None else content.data_ptr(), z=z.data_ptr(), states=states.data_ptr(),
-                     **common)
-    bop = L.SdeBwdOp(states=states.data_ptr(), gz=None, work=None, grads=None, accumulate=0, **common)
-    return fop, bop
 
 
 @pytest.mark.parametrize("N,T", [(32, 16), (20, 5), (33, 2), (300, 3), (8192, 16)])
