@@ -10,7 +10,7 @@ from .modules import (CategoricalVideoDiscriminator, CDEFunc, Noise, ODEFunc, OD
                       VideoGeneratorMNISTODETanh, VideoGeneratorMNISTTanh, VideoGeneratorSDE, VideoGeneratorTanh)
 from .ode_training import GANODETrainer
 from .gres import ConditionalNorm, GResBlock, SpectralNorm
-from . import data, dcgan, fcgan
+from . import data, dcgan, fcgan, video_io
 from .train import (FusedAdam, GanTrainer, WassersteinDiscriminatorLoss, WassersteinGeneratorLoss, bce_with_logits_const,
                     bce_with_logits_halves, bce_with_logits_pair, bce_ce_head, bce_ce_head_halves, bce_ce_head_pair,
                     bce_ce_heads, categorical_cross_entropy, build_mnist, build_ucf, freeze_host_gc, host_cpu_quota,
@@ -22,7 +22,7 @@ __all__ = ["Noise", "ODEFunc", "ODEFuncTanh", "VideoGeneratorTanh", "VideoGenera
            "bce_with_logits_pair", "bce_with_logits_halves", "categorical_cross_entropy", "bce_ce_head", "bce_ce_head_pair",
            "bce_ce_head_halves", "bce_ce_heads", "WassersteinGeneratorLoss", "WassersteinDiscriminatorLoss",
            "wasserstein_generator_loss", "wasserstein_generator_loss_pair", "wasserstein_discriminator_loss",
-           "wasserstein_discriminator_loss_halves", "unit_grad", "fcgan", "dcgan", "build_mnist", "build_ucf", "train_step", "host_cpu_quota", "limit_host_threads", "freeze_host_gc", "_lib"]
+           "wasserstein_discriminator_loss_halves", "unit_grad", "fcgan", "dcgan", "video_io", "build_mnist", "build_ucf", "train_step", "host_cpu_quota", "limit_host_threads", "freeze_host_gc", "_lib"]
 
 # Process-global host tuning is opt-in (nothing happens at import): call limit_host_threads() once at start-up when
 # torch's intra-op pool is larger than the container's CPU quota (see its docstring; bench.py and tests/conftest.py

@@ -32,6 +32,7 @@ OP_BCE_T = 36
 OP_RESIZE_U8, OP_CLIP_GATHER = 37, 38
 OP_BN_RUNNING = 39
 OP_ROT_CLIPS = 40
+OP_VIDEO_GRID = 41
 BN_RUNNING_MAX = 8            # GODE_BN_RUNNING_MAX: the layers one gode_bn_running launch takes
 RESIZE_MAX_TAPS = 32          # GODE_RESIZE_MAX_TAPS: the longest tap row gode_resize_u8 takes
 ROT_MIN_SIZE, ROT_MAX_SIZE = 4, 64   # the image heights and widths gode_rot_clips takes
@@ -345,6 +346,12 @@ class RotClipsOp(_Op):
     KIND, FN = OP_ROT_CLIPS, "gode_rot_clips"
 
 
+class VideoGridOp(_Op):
+    _fields_ = [("src", ptr), ("xs", i64 * 5), ("rgb", ptr), ("idx", ptr), ("B", i32), ("C", i32), ("T", i32), ("H", i32),
+                ("W", i32), ("rows", i32), ("cols", i32), ("mode", i32)]
+    KIND, FN = OP_VIDEO_GRID, "gode_video_grid"
+
+
 class AdamNoiseTensor(C.Structure):
     _fields_ = [("p", ptr), ("g", ptr), ("m", ptr), ("v", ptr), ("n", i64), ("noise_off", i64)]
 
@@ -376,6 +383,9 @@ _PROTOS = {
     "gode_igemm_launch_cell": ([ptr, ptr], cint),
     "gode_igemm_work_size": ([ptr], i64),
     "gode_col2im_launch_kind": ([ptr, ptr], cint),
+    "gode_video_grid_launch_kind": ([ptr, ptr], cint),
+    "gode_gif_lzw_bound": ([i64], i64),
+    "gode_gif_lzw": ([ptr, i64, i32, ptr, i64], i64),
     "gode_pack_size": ([ptr, cint], i64),
     "gode_pack_weights": ([ptr, cint, ptr, ptr, ptr, i32, ptr], cint),
     "gode_wgrad_work_size": ([ptr], i64),

@@ -1,7 +1,15 @@
 // api.hip -- program runner and ABI introspection of libgode.so
 #include "common.h"
+#include "gif_lzw.h"
 
 extern "C" int gode_version(void) { return GODE_VERSION; }
+
+// host-side GIF LZW (gif_lzw.h): its error codes are GODE_E_ARG and GODE_E_SHAPE by value
+static_assert((int)gif_lzw::ERR_ARG == (int)GODE_E_ARG && (int)gif_lzw::ERR_CAP == (int)GODE_E_SHAPE, "gif_lzw error codes");
+extern "C" int64_t gode_gif_lzw_bound(int64_t n) { return gif_lzw::bound(n); }
+extern "C" int64_t gode_gif_lzw(const uint8_t* idx, int64_t n, int32_t min_code_size, uint8_t* out, int64_t cap) {
+  return gif_lzw::encode(idx, n, min_code_size, out, cap);
+}
 
 extern "C" int gode_sizeof(int kind) {
   switch (kind) {

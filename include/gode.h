@@ -882,6 +882,46 @@ typedef struct gode_rot_clips_op {
 } gode_rot_clips_op;
 int gode_rot_clips(const gode_rot_clips_op* op, void* stream);
 
+/* ---- sample grid of a batch of videos, as 8-bit frames (the drivers' genSamples, mnist_moco_ode.py:31-48) -- DESIGN section 26
+ * src: fp32 videos (b, c, t, h, w) read in place through the element strides xs[5] (any view: sample_videos' channels-last
+ * permuted view, a contiguous [B, C, T, H, W] tensor, an expanded one).  Video b fills tile (b / cols, b % cols) of a grid of
+ * rows x cols tiles; C == 1 is broadcast to the three colour channels; a tile with b >= B holds source value 0 (the reference's
+ * zero-initialised `out`).  Per value, in float64 and operation for operation as NumPy evaluates the reference's expression:
+ *   mode 0: v = ((double)x + 1.0) / 2.0 * 255.0     (generator output, UCF reals: [-1, 1])
+ *   mode 1: v = (double)x * 255.0                   (Rot-MNIST reals: [0, 1])
+ * then v < 0 -> 0, v > 255 -> 255 and truncation toward zero to uint8 (the writer's clip(0, 255).astype(uint8)).  A NaN input
+ * is outside the contract: NumPy's own cast of NaN is undefined, and what comes out here is unspecified (nothing faults).
+ * rgb: uint8 [T][rows*H][cols*W][3], the frames.  idx: uint8 [T][rows*H][cols*W], palette indices: C == 1 the gray value itself
+ * (a 256-gray palette); C == 3 the cell of a fixed 6 x 7 x 6 colour cube, in integers: with L = (6, 7, 6),
+ * q_c = (v_c * (L_c - 1) + 127) / 255 and idx = (q_r * 7 + q_g) * 6 + q_b, whose palette entry is level
+ * (k * 255 + (L_c - 1) / 2) / (L_c - 1) per channel (entries 252..255 unused, black).  No dithering.  Each output is nullable,
+ * not both; neither depends on the presence of the other.
+ * Launch: four pixels per thread with 16-byte loads and dword stores when W % 4 == 0, the source has unit stride along w
+ * (C == 1) or is channels-last (C == 3: xs[1] == 1, xs[4] == 3), src is 16-byte aligned with xs[0], xs[2], xs[3] multiples of
+ * 4, and the outputs are 4-byte aligned; one pixel per thread through the strides otherwise.  The values are the same.
+ * gode_video_grid_launch_kind returns what gode_video_grid would return before launching anything and, on 0, kind[0] = 1 for
+ * the four-pixel kernel, 0 for the strided one.
+ * GODE_E_ARG: a null op or src; both outputs null; C not 1 or 3; mode not 0 or 1; B < 1; B > rows * cols.  GODE_E_SHAPE: any
+ * of T, H, W, rows, cols below 1; rows * H or cols * W above 16384.  (rows or cols below 1 is GODE_E_SHAPE, whatever B.)  All
+ * are returned before any launch. */
+typedef struct gode_video_grid_op {
+  const float* src; int64_t xs[5];
+  uint8_t* rgb;
+  uint8_t* idx;
+  int32_t B, C, T, H, W, rows, cols, mode;
+} gode_video_grid_op;
+int gode_video_grid(const gode_video_grid_op* op, void* stream);
+int gode_video_grid_launch_kind(const gode_video_grid_op* op, int32_t* kind);
+
+/* ---- GIF variable-width LZW on the host (csrc/gif_lzw.h; gan_ode_amd.video_io.write_gif frames the result) -----------------
+ * gode_gif_lzw encodes n palette indices (each below 1 << min_code_size, 2 <= min_code_size <= 8) into `out`: a clear code
+ * first, codes from min_code_size + 1 to 12 bits wide, a clear code when the table reaches 4096 entries, the
+ * end-of-information code last, bits packed LSB first.  Returns the byte count; GODE_E_ARG for a null pointer, n < 0, a
+ * min_code_size outside [2, 8] or an index the code size cannot hold; GODE_E_SHAPE when `cap` bytes do not hold the stream.
+ * Nothing is ever written at or behind out + cap.  gode_gif_lzw_bound(n): a cap that always suffices (n < 0: GODE_E_ARG). */
+int64_t gode_gif_lzw_bound(int64_t n);
+int64_t gode_gif_lzw(const uint8_t* idx, int64_t n, int32_t min_code_size, uint8_t* out, int64_t cap);
+
 /* out[i] = a[i]*alpha (+ out[i] if accumulate); small utility for gradient bucket handling */
 int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulate, void* stream);
 
@@ -927,7 +967,8 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
   X(RESIZE_U8,     37, gode_resize_u8_op,     gode_resize_u8)     \
   X(CLIP_GATHER,   38, gode_clip_gather_op,   gode_clip_gather)   \
   X(BN_RUNNING,    39, gode_bn_running_op,    gode_bn_running)    \
-  X(ROT_CLIPS,     40, gode_rot_clips_op,     gode_rot_clips)
+  X(ROT_CLIPS,     40, gode_rot_clips_op,     gode_rot_clips)     \
+  X(VIDEO_GRID,    41, gode_video_grid_op,    gode_video_grid)
 /* GODE_OP_PACK stays outside the table: it has no (op*, stream) entry point, gode_run sends every run of consecutive pack
  * ops out as batched launches instead. */
 #define GODE_ENUM_ROW_(name, value, op_t, fn) GODE_OP_##name = value,
