@@ -33,6 +33,7 @@ OP_RESIZE_U8, OP_CLIP_GATHER = 37, 38
 OP_BN_RUNNING = 39
 OP_ROT_CLIPS = 40
 OP_VIDEO_GRID = 41
+OP_LATENT_DRAW = 42
 BN_RUNNING_MAX = 8            # GODE_BN_RUNNING_MAX: the layers one gode_bn_running launch takes
 RESIZE_MAX_TAPS = 32          # GODE_RESIZE_MAX_TAPS: the longest tap row gode_resize_u8 takes
 ROT_MIN_SIZE, ROT_MAX_SIZE = 4, 64   # the image heights and widths gode_rot_clips takes
@@ -350,6 +351,13 @@ class VideoGridOp(_Op):
     _fields_ = [("src", ptr), ("xs", i64 * 5), ("rgb", ptr), ("idx", ptr), ("B", i32), ("C", i32), ("T", i32), ("H", i32),
                 ("W", i32), ("rows", i32), ("cols", i32), ("mode", i32)]
     KIND, FN = OP_VIDEO_GRID, "gode_video_grid"
+
+
+class LatentDrawOp(_Op):
+    _fields_ = [("x", ptr), ("content", ptr), ("sel_t", ptr), ("cls", ptr), ("call_dev", ptr), ("seed", i64), ("traj0", i64),
+                ("n", i32), ("outer", i32), ("inner", i32), ("T", i32), ("n_all", i32), ("C", i32), ("stream", i32),
+                ("call", i32)]
+    KIND, FN = OP_LATENT_DRAW, "gode_latent_draw"
 
 
 class AdamNoiseTensor(C.Structure):

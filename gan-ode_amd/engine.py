@@ -114,7 +114,8 @@ class PointerTable:
 
 # -- two-lane sampling (gode_run_lanes): which op of the main lane releases the side lane ---------------------------------
 # The pointer fields through which the ops of a sampling front WRITE (every other pointer field of theirs is read only).
-_FRONT_WRITES = {L.OdeFwdOp: ("z", "traj"), L.IgemmOp: ("out", "stats", "work")}
+_FRONT_WRITES = {L.OdeFwdOp: ("z", "traj"), L.IgemmOp: ("out", "stats", "work"),
+                 L.LatentDrawOp: ("x", "content", "sel_t", "cls")}
 
 
 def op_pointers(op):

@@ -263,6 +263,16 @@ _ODE_GRAD_OFFS = [(0, 1024, (64, 16)), (1024, 64, (64,)), (1088, 1024, (16, 64))
 _PRENET_NPARAM = 2128      # the pre-net's four tensors: the head of the ODE and SDE gradient blocks when it is present
 
 
+class _DeviceLatents:
+    """Stands in for the host-drawn inputs of a sampling call whose latents are drawn on the device: the call index of the
+    latent stream (include/gode.h) the plan's draw op takes."""
+
+    __slots__ = ("call",)
+
+    def __init__(self, call):
+        self.call = int(call)
+
+
 class _GenPlan:
     """ODE solve + decoder for `n_traj` trajectories.  full: rows = n_traj*T; select: rows = n_traj (one chosen
     time per trajectory, sample_images).  The subclasses swap the motion latent: each states its buffers (_alloc), its
@@ -293,6 +303,9 @@ class _GenPlan:
         self.ncat = int(getattr(gen, "dim_z_category", 0)) if x is None else 0
         self.labels = None           # int64 classes of the staged call (written by the one-hot op; full mode only)
         self.x, self.content, self.sel, self.cls = x, None, None, None
+        self._in = None              # the input block [x | content | sel | cls] (None: a latent-only plan, x is the caller's)
+        self.draw_op = None          # gode_latent_draw in front of the latent program (gen.latent_rng == "device")
+        self._draw_evs, self._draw_ev_i = [None] * 4, 0
         self._ring = []
         if x is None:
             xs = self._x_shape(n_traj, T)
@@ -391,7 +404,7 @@ class _GenPlan:
     def _programs(self):
         ps = self._params()
         ptrs = tuple(dptr(p) for p in ps) + (self.gen.ode_step_size, self.gen.ode_method, self.gen.ode_rtol,
-                                             self.gen.ode_atol)
+                                             self.gen.ode_atol, self._draws_on_device())
         if ptrs != self._ode_ptrs:
             method = ode_method_code(self.gen.ode_method)
             rhs = self.rhs
@@ -440,23 +453,75 @@ class _GenPlan:
                 # the one-hot columns follow the solve in the same program (the solve's content broadcast zeroes the pad)
                 self.categ_op = L.CategOp(cls=dptr(self.cls), z=dptr(zbuf), labels_out=None, n_traj=self.n,
                                           rows_per=1 if self.select else self.T, C=self.ncat, zcols=zcols, col0=Z_CATEG0)
-            self.fwd_prog = L.Program([self.fwd_op] + ([self.categ_op] if self.ncat else []))
+            self.fwd_prog = self._latent_program([self.fwd_op] + ([self.categ_op] if self.ncat else []))
         self.fwd_op.substeps = self.bwd_op.substeps = self.gen.ode_substeps
         if self.gen.ode_method == "dopri5":
             self.bwd_op.substeps = self.gen.adjoint_substeps
 
+    # -- latents drawn on the device (gen.latent_rng == "device") ---------------------------------------
+    def _draws_on_device(self):
+        # (getattr: the host tests drive _programs on bare plans and stand-in generators)
+        return getattr(self, "_in", None) is not None and getattr(self.gen, "latent_rng", "host") == "device"
+
+    def _latent_program(self, ops):
+        """The latent program: `ops`, behind gode_latent_draw when this plan's input block is drawn on the device.  The op
+        writes the block's four sub-blocks in place; its seed, stream and call are set call by call (_set_draw)."""
+        self.draw_op = None
+        if self._draws_on_device():
+            xs = tuple(self.x.shape)
+            outer, inner = (xs[0], xs[2]) if len(xs) == 3 else (1, xs[1])
+            self.draw_op = L.LatentDrawOp(x=dptr(self.x), content=dptr(self.content), sel_t=dptr(self.sel),
+                                          cls=dptr(self.cls), call_dev=None, seed=0, traj0=0, n=self.n, outer=outer,
+                                          inner=inner, T=self.T, n_all=self.n * self.T * 2 if self.select else 0,
+                                          C=self.ncat, stream=0, call=0)
+            ops = [self.draw_op] + list(ops)
+        return L.Program(ops)
+
+    def _set_draw(self, latents):
+        """Points the draw op at the call `latents` (a _DeviceLatents) stands for.  Under graph capture the call index
+        travels in the trainer's HostFeed block (one word, rewritten before every replay), as the discriminators' does."""
+        op, gen = self.draw_op, self.gen
+        if op is None:
+            raise RuntimeError("latent_rng was switched between a sampling call's draw and its launch")
+        seed = int(gen.latent_seed) & 0xFFFFFFFFFFFFFFFF
+        op.seed = seed - (1 << 64) if seed >= 1 << 63 else seed
+        op.stream = int(gen.latent_stream)
+        feed = getattr(gen, "_feed", None)
+        if feed is not None and feed.recording:
+            op.call_dev, op.call = feed.latent_slot(gen, latents.call, 1), 0
+        else:
+            call = latents.call & 0xFFFFFFFF
+            op.call_dev, op.call = None, call - (1 << 32) if call >= 1 << 31 else call
+
+    def _draw_event(self):
+        """An event for the place where a host-mode call records its staging copy's (lane_gate's evidence)."""
+        i = self._draw_ev_i
+        self._draw_ev_i = (i + 1) % len(self._draw_evs)
+        if self._draw_evs[i] is None:
+            self._draw_evs[i] = torch.cuda.Event()
+        return self._draw_evs[i]
+
     def stage_inputs(self, x_host, content_host, sel_host, cls_host=None):
         """Host-drawn inputs -> the plan's device block, on the current stream (one H2D copy).  cls_host: the trajectories'
-        classes (dim_z_category > 0)."""
+        classes (dim_z_category > 0).  x_host a _DeviceLatents: nothing is staged, the latent program's draw op writes the
+        block."""
         self._programs()
+        device_draw = isinstance(x_host, _DeviceLatents)
         if self.ncat:
-            if cls_host is None:
+            if cls_host is None and not device_draw:
                 raise RuntimeError("a categorical generator plan needs the classes of its trajectories")
             if getattr(self.gen, "_feed", None) is not None and self.gen._feed.recording:
                 raise NotImplementedError("categorical latents are not captured in a graph (GanTrainer(graph=True))")
             if not self.select:      # a fresh tensor per call: it leaves the plan as sample_videos' second result
                 self.labels = torch.empty(self.n, dtype=torch.int64, device=self.device)
             self.categ_op.labels_out = dptr(self.labels) if not self.select else None
+        if device_draw:
+            self._set_draw(x_host)
+            if not torch.cuda.is_current_stream_capturing():
+                ev = self._draw_event()
+                ev.record()
+                self._note_copy(ev)
+            return
         feed = getattr(self.gen, "_feed", None)
         if feed is not None and feed.recording:
             # graph capture (GanTrainer(graph=True)): the inputs travel in the trainer's HostFeed block; the recorded
@@ -595,7 +660,17 @@ class _GenPlan:
 
     def _stage_on_side(self, ordered, x_host, content_host, sel_host):
         """stage_inputs' ring copy on the side lane.  _in is read by the side lane only, so the copy needs no edge of its own
-        behind a lanes call; behind anything else (ordered) the last reader may sit on the caller's stream."""
+        behind a lanes call; behind anything else (ordered) the last reader may sit on the caller's stream.  Latents drawn
+        on the device: the draw op rides in the front of the program; only the event is recorded where the copy's was."""
+        if isinstance(x_host, _DeviceLatents):
+            self._programs()
+            self._set_draw(x_host)
+            if ordered:
+                self._side.wait_stream(torch.cuda.current_stream())
+            ev = self._draw_event()
+            ev.record(self._side)
+            self._note_copy(ev)
+            return
         slot = self._ring[self._ring_i]
         self._ring_i = (self._ring_i + 1) % len(self._ring)
         if slot["ev"] is not None:
@@ -879,10 +954,21 @@ class VideoGenerator(nn.Module):
     # adjoint_substeps (dopri5 only): 0 = the adjoint is integrated adaptively with the same controller and
     # torchdiffeq's mixed norm, as odeint_adjoint does; k > 0 = k fixed Kutta-3/8 steps per output interval
     ode_rtol, ode_atol, adjoint_substeps = 1e-7, 1e-9, 0
+    # Where sample_videos / sample_images / sample_pair / prefetch_latents take their latents from.  "host": the reference's
+    # NumPy / torch CPU draws, uploaded (the RNG contract every fixture rests on).  "device": one gode_latent_draw launch in
+    # front of the latent solve, from the counter-based latent stream of include/gode.h keyed by latent_seed (default:
+    # torch.initial_seed() at construction), latent_stream (0; GanTrainer sets the rank) and latent_call, which every
+    # sampling call advances by one -- no host draw, no upload, the global generators untouched; it matches no torch or
+    # NumPy generator.  Plain attributes, no buffers.  sample_z_m / sample_z_content / sample_z_categ / sample_z_video, the
+    # reference's surface, draw on the host in both modes.
+    latent_rng = "host"
+    latent_stream = 0
+    _latent_call = 0
 
     def __init__(self, n_channels, dim_z_content, dim_z_category, dim_z_motion, video_length, ode_fn=ODEFunc,
                  dim_hidden=None, linear=True, ngf=64):
         super().__init__()
+        self.latent_seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
         if not self._categorical_ok and dim_z_category != 0:
             raise NotImplementedError(f"categorical latents (dim_z_category={dim_z_category}) are implemented for the "
                                       f"Neural-ODE generators only, not for {type(self).__name__}")
@@ -1105,7 +1191,8 @@ class VideoGenerator(nn.Module):
         stream; the calls then only wait for the latents and run the decoder.  For the ODE-RNN generator the solves --
         one workgroup of a 256-CU GPU each, ~100 us of dependent arithmetic -- become ONE launch whose workgroups run side
         by side (gode_odernn_fwd_multi) instead of six launches back to back.  Results are bit-identical to the calls
-        without prefetch."""
+        without prefetch.  latent_rng == "device": nothing is drawn on the host; each announced call takes the next index of
+        the latent stream, in announcement order, and its plan's draw op runs ahead of the solves."""
         _require_gpu(self.main[0].weight, type(self).__name__)
         if self.__dict__.get("_prefetched"):
             raise RuntimeError("prefetch_latents: the previous prefetch has not been consumed "
@@ -1145,7 +1232,7 @@ class VideoGenerator(nn.Module):
             for plan, (select, n, _, _) in zip(plans, queue):
                 # draw and stage call by call: a generator may hand out a reused host buffer (the ODE-RNN noise stack)
                 for sub in (plan.subplans() if isinstance(plan, _GenJointPlan) else (plan,)):
-                    sub.stage_inputs(*self._host_inputs(sub.select, sub.n, T))
+                    sub.stage_inputs(*self._inputs(sub.select, sub.n, T))
                     latent_plans.append(sub)
             self._launch_latents(latent_plans)
             ev = torch.cuda.Event()
@@ -1160,6 +1247,9 @@ class VideoGenerator(nn.Module):
         st = stream_ptr()
         pc = self._plan_cls
         if pc.multi_ok(self, False):
+            draws = [p.draw_op for p in plans if p.draw_op is not None]
+            if draws:                        # the plans' latents, drawn on this stream ahead of the solves that read them
+                L.Program(draws).run(st)
             _run_multi([p.fwd_op for p in plans], pc.multi[1], pc.multi[0] + "_fwd_multi", st)
             if self.dim_z_category:          # the one-hot columns of every solve, behind the solves
                 L.Program([p.categ_op for p in plans]).run(st)
@@ -1194,6 +1284,40 @@ class VideoGenerator(nn.Module):
             raise RuntimeError(f"prefetch_latents promised {name(s0)}({n0}) next, got {name(select)}({n}, video_len={T})")
         q.pop(0)
         return plan
+
+    # -- latents drawn on the device ---------------------------------------------------------------------------------
+    @property
+    def latent_call(self):
+        """The call index the next device-mode sampling call takes (wraps at 2^32)."""
+        return self._latent_call
+
+    @latent_call.setter
+    def latent_call(self, v):
+        self._latent_call = int(v) & 0xFFFFFFFF
+
+    @contextlib.contextmanager
+    def latents_at(self, call):
+        """Device-mode sampling calls inside start from call index `call`; the previous counter comes back on exit (the same
+        sample grid every epoch, without touching any global generator)."""
+        prev = self._latent_call
+        self.latent_call = call
+        try:
+            yield self
+        finally:
+            self._latent_call = prev
+
+    def _inputs(self, select, num_samples, T):
+        """The inputs of one sampling call: _host_inputs' draws, or (latent_rng == "device") the call's index in the latent
+        stream -- the plan's draw op then writes what the host would have staged."""
+        mode = self.latent_rng
+        if mode == "host":
+            return self._host_inputs(select, num_samples, T)
+        if mode != "device":
+            raise ValueError(f"latent_rng={mode!r}: 'host' (the reference's draws) or 'device' (the counter-based stream)")
+        self._check_len(T)
+        call = self._latent_call
+        self._latent_call = (call + 1) & 0xFFFFFFFF
+        return _DeviceLatents(call), None, None
 
     # -- reference API ---------------------------------------------------------------------------------------------
     def _host_inputs(self, select, num_samples, T):
@@ -1248,7 +1372,7 @@ class VideoGenerator(nn.Module):
             if self.dim_z_category:          # the plan is needed here: its `labels` are the call's int64 classes
                 _require_gpu(self.main[0].weight, type(self).__name__)
                 plan = self._pool.get((num_samples, T, False), lambda: self._plan_cls(self, num_samples, T, False))
-            h = self._run(num_samples, T, False, *self._host_inputs(False, num_samples, T), plan=plan)  # [B*T, 1, H, W, C]
+            h = self._run(num_samples, T, False, *self._inputs(False, num_samples, T), plan=plan)  # [B*T, 1, H, W, C]
         H, W = h.size(2), h.size(3)
         h = h.view(num_samples, T, H, W, self.n_channels).permute(0, 4, 1, 2, 3)
         if self.dim_z_category:
@@ -1262,13 +1386,15 @@ class VideoGenerator(nn.Module):
         (trajectories are independent and unselected rows receive no gradient).  With ode_method="dopri5" it is a
         documented deviation: torchdiffeq accepts/rejects steps on an error norm over ALL B*T*2 trajectories, here
         the norm is taken over the selected ones, so the accepted step sequence differs (both solutions are within
-        rtol 1e-7 of the exact flow; tests/test_gpu_modules.py::test_dopri5_method_against_oracle pins the size)."""
+        rtol 1e-7 of the exact flow; tests/test_gpu_modules.py::test_dopri5_method_against_oracle pins the size).
+        latent_rng == "device": the selection and the chosen trajectories' latents come from the latent stream, whose values
+        are a function of the trajectory's index -- only the chosen ones are ever drawn, bit for bit what drawing all gives."""
         T = self.video_length
         plan = self._take_prefetched(True, num_samples, T)
         if plan is not None:
             h = self._run(num_samples, T, True, None, None, None, plan=plan)
         else:
-            h = self._run(num_samples, T, True, *self._host_inputs(True, num_samples, T))
+            h = self._run(num_samples, T, True, *self._inputs(True, num_samples, T))
         return h.view(num_samples, h.size(2), h.size(3), self.n_channels).permute(0, 3, 1, 2), None
 
     def sample_pair(self, n_videos, n_images, images_first=False):
@@ -1288,7 +1414,7 @@ class VideoGenerator(nn.Module):
                     return self.sample_videos(n_videos), im
                 vd = self.sample_videos(n_videos)
                 return vd, self.sample_images(n_images)
-            host = [self._host_inputs(sub.select, sub.n, T) for sub in plan.subplans()]
+            host = [self._inputs(sub.select, sub.n, T) for sub in plan.subplans()]
         dec, ode = self._param_list()
         keep = torch.is_grad_enabled() and any(p.requires_grad for p in dec + ode)
         hv, hi = _GenJointFn.apply(plan, host, self.training, keep, len(dec), *dec, *ode)
@@ -1452,8 +1578,8 @@ class _RnnGenPlan(_GenPlan):
 
     def _programs(self):
         ptrs = tuple(dptr(p) for p in self._params())
-        if ptrs != self._ode_ptrs:
-            self._ode_ptrs = ptrs
+        if ptrs + (self._draws_on_device(),) != self._ode_ptrs:
+            self._ode_ptrs = ptrs + (self._draws_on_device(),)
             op = L.OdeRnnParams(*ptrs)
             self.fwd_op = L.OdeRnnFwdOp(p=op, noise=dptr(self.noise), content=dptr(self.content), sel_t=dptr(self.sel),
                                         z=dptr(self._zbuf), hs=None, hp=dptr(self.hp), nsteps=dptr(self.nsteps),
@@ -1464,7 +1590,7 @@ class _RnnGenPlan(_GenPlan):
                                         substeps=self.gen.adjoint_substeps, accumulate=0, zcols=self._zcols,
                                         rtol=self.gen.ode_rtol, atol=self.gen.ode_atol, sync=dptr(self.sync_b),
                                         nsteps=dptr(self.nsteps_bwd))
-            self.fwd_prog = L.Program([self.fwd_op])
+            self.fwd_prog = self._latent_program([self.fwd_op])
         self.fwd_op.rtol, self.fwd_op.atol = self.gen.ode_rtol, self.gen.ode_atol
         self.bwd_op.rtol, self.bwd_op.atol = self.gen.ode_rtol, self.gen.ode_atol
         self.bwd_op.substeps = self.gen.adjoint_substeps
@@ -1553,15 +1679,15 @@ class _GruGenPlan(_GenPlan):
 
     def _programs(self):
         ptrs = tuple(dptr(p) for p in self._params())
-        if ptrs != self._ode_ptrs:
-            self._ode_ptrs = ptrs
+        if ptrs + (self._draws_on_device(),) != self._ode_ptrs:
+            self._ode_ptrs = ptrs + (self._draws_on_device(),)
             op = L.GruParams(*ptrs)
             self.fwd_op = L.GruFwdOp(p=op, noise=dptr(self.noise), content=dptr(self.content), sel_t=dptr(self.sel),
                                      z=dptr(self._zbuf), hs=dptr(self.hs), N=self.n, T=self.T, zcols=self._zcols)
             self.bwd_op = L.GruBwdOp(p=op, noise=dptr(self.noise), hs=dptr(self.hs), sel_t=dptr(self.sel), gz=None,
                                      work=dptr(self.gru_work), grads=None, N=self.n, T=self.T, accumulate=0,
                                      zcols=self._zcols)
-            self.fwd_prog = L.Program([self.fwd_op])
+            self.fwd_prog = self._latent_program([self.fwd_op])
 
 
 class VideoGeneratorGRU(VideoGenerator):
@@ -1705,8 +1831,8 @@ class _SdeGenPlan(_GenPlan):
     def _programs(self):
         ps = self._params()
         ptrs = tuple(dptr(p) for p in ps)
-        if ptrs != self._ode_ptrs:
-            self._ode_ptrs = ptrs
+        if ptrs + (self._draws_on_device(),) != self._ode_ptrs:
+            self._ode_ptrs = ptrs + (self._draws_on_device(),)
             prenet = 0 if ps[0] is None else 1
             sc = self._sched
             common = dict(p=L.SdeParams(*ptrs), x=dptr(self.x), sel_t=dptr(self.sel), dt=dptr(sc["dt"]),
@@ -1716,7 +1842,7 @@ class _SdeGenPlan(_GenPlan):
             self.fwd_op = L.SdeFwdOp(content=dptr(self.content), z=dptr(self._zbuf), states=dptr(self.states), **common)
             self.bwd_op = L.SdeBwdOp(states=dptr(self.states), gz=None, work=dptr(self.sde_work), grads=None,
                                      accumulate=0, **common)
-            self.fwd_prog = L.Program([self.fwd_op])
+            self.fwd_prog = self._latent_program([self.fwd_op])
 
 
 class VideoGeneratorSDE(VideoGeneratorMNIST):
@@ -1891,7 +2017,7 @@ class _CdeGenPlan(_GenPlan):
 
     def _programs(self):
         ps = self._params()
-        key = tuple(dptr(p) for p in ps) + (self.gen.cde_rtol, self.gen.cde_atol)
+        key = tuple(dptr(p) for p in ps) + (self.gen.cde_rtol, self.gen.cde_atol, self._draws_on_device())
         if key != self._ode_ptrs:
             self._ode_ptrs = key
             common = dict(p=L.CdeParams(*key[:8]), x=dptr(self.x), tslope=dptr(self.tslope), sel_t=dptr(self.sel),
@@ -1900,7 +2026,7 @@ class _CdeGenPlan(_GenPlan):
             self.fwd_op = L.CdeFwdOp(content=dptr(self.content), z=dptr(self._zbuf), sync=dptr(self.sync),
                                      rtol=float(self.gen.cde_rtol), atol=float(self.gen.cde_atol), **common)
             self.bwd_op = L.CdeBwdOp(gz=None, work=dptr(self.cde_work), grads=None, accumulate=0, **common)
-            self.fwd_prog = L.Program([self.fwd_op])
+            self.fwd_prog = self._latent_program([self.fwd_op])
 
     def check_solve(self):
         """Reads the solve's {accepted, trials} (a host synchronisation with the current stream) and raises when the

@@ -547,6 +547,17 @@ class HostFeed:
         self.pinned[self.parity][off:off + 4].view(torch.int32)[0] = int(call) - (1 << 32) if call >= 1 << 31 else int(call)
         return self.dev[off:off + 1].data_ptr()
 
+    def latent_slot(self, gen, call, ncalls):
+        """A device-mode generator's latent call index (raw 32 bits) for one captured sampling call, read by its
+        gode_latent_draw op; every replay writes the generator's current counter and advances it by `ncalls`, as an eager
+        call does.  Such a call has no "noise" entry: nothing of it is drawn on the host."""
+        assert self.recording
+        off = self._reserve(1)
+        self.script.append(("latent", gen, off, ncalls))
+        call = int(call) & 0xFFFFFFFF
+        self.pinned[self.parity][off:off + 4].view(torch.int32)[0] = call - (1 << 32) if call >= 1 << 31 else call
+        return self.dev[off:off + 1].data_ptr()
+
     # -- replay ----------------------------------------------------------------------------------------------------
     def begin(self):
         """Next pinned buffer (waits until the upload that last used it has been consumed)."""
@@ -562,6 +573,11 @@ class HostFeed:
             if ent[0] == "noise":
                 _, gen, select, num_samples, T, off, nfloats = ent
                 gen._fill_host_inputs(buf[off:off + nfloats], select, num_samples, T)
+            elif ent[0] == "latent":
+                _, gen, off, ncalls = ent
+                call = gen.latent_call
+                buf[off:off + 4].view(torch.int32)[0] = call - (1 << 32) if call >= 1 << 31 else call
+                gen.latent_call = call + ncalls
             elif ent[0] == "dnoise":
                 _, model, off, ncalls = ent
                 call = model._noise_call
@@ -726,6 +742,10 @@ class GanTrainer:
                 raise NotImplementedError("GanTrainer(graph=True) does not capture categorical training")
             if self.world > 1:
                 raise NotImplementedError("GanTrainer: categorical training is single-process (no data parallelism)")
+        # latents drawn on the device (gen.latent_rng == "device"): every rank takes its own stream of the generator's seed
+        # (the ranks construct the generator under one torch seed), so the replicas' samples are disjoint
+        if self.world > 1 and getattr(gen, "latent_rng", "host") == "device":
+            gen.latent_stream = self.rank
         # discriminator instance noise (VideoDiscriminator / PatchImageDiscriminator(use_noise=True)): noise_seed, when given,
         # keys both discriminators' streams (default: each module's torch.initial_seed() at construction).  Replicas take
         # rank 0's seeds; each replica and virtual-replica shard draws the noise of its own samples (_noise_shard).

@@ -649,6 +649,41 @@ int gode_dnoise(const gode_dnoise_op* op, void* stream);
 int gode_dnoise_normals(float* out, int64_t n, uint64_t seed, uint32_t noise_stream, uint32_t layer, uint32_t call,
                         int64_t e_off, int32_t raw, void* stream);
 
+/* ---- generator latents drawn on the device (latent_rng = "device" of the generator classes) ----------
+ * The latent stream: key (seed low word, seed high word); element e of a field takes output lane e & 3 of Philox4x32-10 with
+ * counter (q low word, call, tag, q high word), q = e >> 2, tag = 0x60000000 | stream << 8 | field, stream < 2^21, field < 256.
+ * The family is disjoint from the parameter-noise streams (small indices, far below 2^29), from dropout (0x40000000 | layer,
+ * layer < 256: bit 29 clear) and from the instance noise (>= 0x80000000: bit 31 set) -- here bits 30 and 29 are set and
+ * bit 31 is clear.  Words become normals as above: u = ((x >> 9) + 0.5) * 2^-23, lanes 0 / 1 = r0 cos 2 pi u1, r0 sin 2 pi u1
+ * with r0 = sqrt(-2 ln u0), lanes 2 / 3 likewise from (u2, u3).  call = (call_dev ? call_dev[0] : 0) + call in 32-bit
+ * wrap-around arithmetic, as in gode_dnoise_op.
+ * Fields, g being the global index of a trajectory among those the call draws:
+ *   0 content:   element g*50 + j, j < 50 -> normal, content[row][j];
+ *   1 motion:    element g*XW + k, XW = outer*inner, k = o*inner + i -> normal, x[o][row][i] ((outer, inner): ODE (1, 16),
+ *                GRU / ODE-RNN (T + 1, 16), SDE (1 + S, 16), CDE (1, T));
+ *   2 class:     element g -> cls[row] = umulhi(word, C);
+ *   3 selection: select mode only (n_all > 0, sample_images): n rows are picked from R = n_all*T by Floyd's algorithm -- for
+ *                m = 0 .. n-1: j = R - n + m, t = umulhi(word of element m, j + 1), take t if it was not taken before, else
+ *                j -- and sorted ascending, r_0 < ... < r_{n-1}; plan row b is trajectory g_b = traj0 + r_b / T at time
+ *                sel_t[b] = r_b % T.  Two rows may share a trajectory and then carry the same content / motion / class.
+ * Full mode (n_all == 0): g_b = traj0 + b.  The values of a trajectory are a pure function of (seed, stream, call, g): a
+ * select-mode draw is bit for bit the chosen trajectories of the full draw of all n_all.
+ * gode_latent_draw writes exactly x[outer][n][inner], content[n][50] (nullable), sel_t[n] (select mode) and cls[n] (C > 0,
+ * nullable) -- the four sub-blocks of a sampling plan's input block -- in ONE launch, O(n) work (select mode: every workgroup
+ * repeats the selection in LDS), plain stores, independent of the grid.
+ * GODE_E_ARG: a null op or x; n, outer, inner or T below 1; C or n_all below 0; stream outside [0, 2^21); traj0 < 0; select
+ * mode without sel_t.  GODE_E_SHAPE: n * (outer*inner + 52) >= 2^31; select mode with n > 4096, n > n_all*T or
+ * n_all*T >= 2^31.  All are returned before any launch. */
+typedef struct gode_latent_draw_op {
+  float* x; float* content; int32_t* sel_t; int32_t* cls;
+  const int32_t* call_dev;
+  int64_t seed, traj0;
+  int32_t n, outer, inner, T;
+  int32_t n_all;
+  int32_t C, stream, call;
+} gode_latent_draw_op;
+int gode_latent_draw(const gode_latent_draw_op* op, void* stream);
+
 /* ---- ODE-GAN training (GANODETrainer of stage2/ode_training.py: Euler / Heun / RK4 steps in parameter space) ---------
  * One stage update of a whole network in ONE launch, on `count` fp32 tensors described by a DEVICE table:
  *   p += c1*g[0] + c2*g[1] + c3*g[2] + c4*g[3] + cq*(qp - qm)
@@ -968,7 +1003,8 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
   X(CLIP_GATHER,   38, gode_clip_gather_op,   gode_clip_gather)   \
   X(BN_RUNNING,    39, gode_bn_running_op,    gode_bn_running)    \
   X(ROT_CLIPS,     40, gode_rot_clips_op,     gode_rot_clips)     \
-  X(VIDEO_GRID,    41, gode_video_grid_op,    gode_video_grid)
+  X(VIDEO_GRID,    41, gode_video_grid_op,    gode_video_grid)    \
+  X(LATENT_DRAW,   42, gode_latent_draw_op,   gode_latent_draw)
 /* GODE_OP_PACK stays outside the table: it has no (op*, stream) entry point, gode_run sends every run of consecutive pack
  * ops out as batched launches instead. */
 #define GODE_ENUM_ROW_(name, value, op_t, fn) GODE_OP_##name = value,
