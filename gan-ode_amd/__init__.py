@@ -5,9 +5,9 @@ Python host side that mirrors the reference's class surface.  Importing the pack
 anything does, and there is no fallback path.
 """
 from . import _lib
-from .modules import (CategoricalVideoDiscriminator, CDEFunc, Noise, ODEFunc, ODEFuncTanh, PatchImageDiscriminator, SDEFunc, VideoDiscriminator, VideoGenerator,
+from .modules import (CategoricalVideoDiscriminator, CDEFunc, DiffAugment, Noise, ODEFunc, ODEFuncTanh, PatchImageDiscriminator, SDEFunc, VideoDiscriminator, VideoGenerator,
                       VideoGeneratorCDE, VideoGeneratorGRU, VideoGeneratorMNIST, VideoGeneratorMNISTODE, VideoGeneratorMNISTODERNN,
-                      VideoGeneratorMNISTODETanh, VideoGeneratorMNISTTanh, VideoGeneratorSDE, VideoGeneratorTanh)
+                      VideoGeneratorMNISTODETanh, VideoGeneratorMNISTTanh, VideoGeneratorSDE, VideoGeneratorTanh, diffaug_params)
 from .ode_training import GANODETrainer
 from .gres import ConditionalNorm, GResBlock, SpectralNorm
 from . import data, dcgan, fcgan, video_io
@@ -17,7 +17,7 @@ from .train import (FusedAdam, GanTrainer, WassersteinDiscriminatorLoss, Wassers
                     limit_host_threads, train_step, unit_grad, wasserstein_discriminator_loss,
                     wasserstein_discriminator_loss_halves, wasserstein_generator_loss, wasserstein_generator_loss_pair)
 
-__all__ = ["Noise", "ODEFunc", "ODEFuncTanh", "VideoGeneratorTanh", "VideoGeneratorMNISTTanh", "VideoGeneratorMNISTODETanh", "PatchImageDiscriminator", "VideoDiscriminator", "CategoricalVideoDiscriminator", "VideoGenerator",
+__all__ = ["Noise", "DiffAugment", "diffaug_params", "ODEFunc", "ODEFuncTanh", "VideoGeneratorTanh", "VideoGeneratorMNISTTanh", "VideoGeneratorMNISTODETanh", "PatchImageDiscriminator", "VideoDiscriminator", "CategoricalVideoDiscriminator", "VideoGenerator",
            "VideoGeneratorMNIST", "VideoGeneratorMNISTODE", "VideoGeneratorMNISTODERNN", "SDEFunc", "VideoGeneratorSDE", "CDEFunc", "VideoGeneratorCDE", "VideoGeneratorGRU", "FusedAdam", "GanTrainer", "GANODETrainer", "SpectralNorm", "ConditionalNorm", "GResBlock", "bce_with_logits_const",
            "bce_with_logits_pair", "bce_with_logits_halves", "categorical_cross_entropy", "bce_ce_head", "bce_ce_head_pair",
            "bce_ce_head_halves", "bce_ce_heads", "WassersteinGeneratorLoss", "WassersteinDiscriminatorLoss",

@@ -34,6 +34,7 @@ OP_BN_RUNNING = 39
 OP_ROT_CLIPS = 40
 OP_VIDEO_GRID = 41
 OP_LATENT_DRAW = 42
+OP_DIFFAUG = 43
 BN_RUNNING_MAX = 8            # GODE_BN_RUNNING_MAX: the layers one gode_bn_running launch takes
 RESIZE_MAX_TAPS = 32          # GODE_RESIZE_MAX_TAPS: the longest tap row gode_resize_u8 takes
 ROT_MIN_SIZE, ROT_MAX_SIZE = 4, 64   # the image heights and widths gode_rot_clips takes
@@ -360,6 +361,13 @@ class LatentDrawOp(_Op):
     KIND, FN = OP_LATENT_DRAW, "gode_latent_draw"
 
 
+class DiffAugOp(_Op):
+    _fields_ = [("x", ptr), ("out", ptr), ("work", ptr), ("call_dev", ptr), ("xs", i64 * 5), ("seed", i64), ("g0", i64),
+                ("N", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32), ("mask", i32), ("backward", i32), ("stream", i32),
+                ("call", i32), ("pad_", i32)]
+    KIND, FN = OP_DIFFAUG, "gode_diffaug"
+
+
 class AdamNoiseTensor(C.Structure):
     _fields_ = [("p", ptr), ("g", ptr), ("m", ptr), ("v", ptr), ("n", i64), ("noise_off", i64)]
 
@@ -427,6 +435,9 @@ _PROTOS = {
     "gode_adam_noise_multi_dev": ([ptr, i32, i64, f32, f32, f32, f32, f32, ptr, u64, u32, f32, ptr], cint),
     "gode_param_noise": ([ptr, i64, u64, u32, u32, i64, f32, i32, ptr], cint),
     "gode_dnoise_normals": ([ptr, i64, u64, u32, u32, u32, i64, i32, ptr], cint),
+    "gode_diffaug_chunks": ([i32, i32, i32], i32),
+    "gode_diffaug_work_size": ([i32, i32, i32, i32, i32], i64),
+    "gode_diffaug_params": ([ptr, ptr, i64, u64, u32, u32, i64, i32, i32], cint),
     "gode_ode_step_chunks": ([ptr, i64], i64),
     "gode_ode_step": ([ptr, i32, i64, i32, f32, f32, f32, f32, f32, ptr, ptr], cint),
     "gode_axpy_multi": ([ptr, i32, i64, f32, ptr, ptr, f32, ptr, ptr, ptr], cint),

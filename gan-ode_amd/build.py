@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgode.so")
-SOURCES = ["igemm.hip", "conv_patch.hip", "wgrad.hip", "ode.hip", "ode_valu.hip", "odernn.hip", "odernn_valu.hip", "adj_adaptive.hip", "sde_valu.hip", "cde_valu.hip", "gru_valu.hip", "latent_reduce.hip", "elementwise.hip", "dnoise.hip", "categ.hip", "odestep.hip", "gres.hip", "fc.hip", "clips.hip", "rotclips.hip", "vidgrid.hip", "latent_draw.hip", "api.hip"]
+SOURCES = ["igemm.hip", "conv_patch.hip", "wgrad.hip", "ode.hip", "ode_valu.hip", "odernn.hip", "odernn_valu.hip", "adj_adaptive.hip", "sde_valu.hip", "cde_valu.hip", "gru_valu.hip", "latent_reduce.hip", "elementwise.hip", "dnoise.hip", "categ.hip", "odestep.hip", "gres.hip", "fc.hip", "clips.hip", "rotclips.hip", "vidgrid.hip", "latent_draw.hip", "diffaug.hip", "api.hip"]
 HEADERS = ["common.h", "philox.h", "conv_geom.h", "igemm_plan.h", "wgrad_plan.h", "col2im_plan.h", "ode_common.h", "valu_common.h", "dopri5.h", "gif_lzw.h", os.path.join("..", "..", "include", "gode.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"]
 

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import functools
 import math
 import os
 from typing import Optional
@@ -2166,6 +2167,121 @@ class Noise(nn.Module):
         return x + z.view(shape).permute(*inv) * self.sigma      # fp32(x + fp32(sigma * z)): two roundings, as gode.h
 
 
+# -- differentiable augmentation (DiffAugment; gode_diffaug_op) -------------------------------------------
+DIFFAUG_BITS = {"color": 1 | 2 | 4, "translation": 8, "cutout": 16}
+
+
+def diffaug_mask(policy):
+    """'color,translation,cutout' in any order -> the op's mask bits; None or an empty string: 0 (off)."""
+    if policy is None:
+        return 0
+    if not isinstance(policy, str):
+        raise ValueError(f"DiffAugment policy must be a string of comma-separated names or None, got {policy!r}")
+    return _diffaug_mask_of(policy)
+
+
+@functools.lru_cache(maxsize=32)
+def _diffaug_mask_of(policy):
+    mask = 0
+    for name in (s.strip() for s in policy.split(",")):
+        if not name:
+            continue
+        if name not in DIFFAUG_BITS:
+            raise ValueError(f"DiffAugment policy {policy!r}: unknown component {name!r} (known: "
+                             + ", ".join(DIFFAUG_BITS) + ")")
+        mask |= DIFFAUG_BITS[name]
+    return mask
+
+
+def diffaug_params(n, H, W, seed, stream, call, g0=0):
+    """The parameters of samples g0 .. g0 + n - 1 of an H x W map, from the library's host function (no launch, no GPU):
+    (ints int32 [n, 4] = tx, ty, cx, cy; unis float32 [n, 3] = u_b, u_s, u_c)."""
+    ints, unis = np.empty((int(n), 4), dtype=np.int32), np.empty((int(n), 3), dtype=np.float32)
+    L.check(L.lib().gode_diffaug_params(ints.ctypes.data, unis.ctypes.data, int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream),
+                                        int(call) & 0xFFFFFFFF, int(g0), int(H), int(W)), "gode_diffaug_params")
+    return ints, unis
+
+
+# (shape, strides, mask, backward) -> (op struct with the layout filled in, output shape, floats of the output, float offset of
+# the workspace, floats of the workspace).  The discriminators see a handful of layouts; the struct is copied at launch.
+_DIFFAUG_OPS = {}
+
+
+def _diffaug_run(x, backward, mask, seed, stream, call, g0):
+    """One gode_diffaug launch (two with contrast) over x [N, C, H, W] / [N, C, D, H, W] of any strides -> the contiguous
+    channels-last result [N, D, H, W, C].  The result and the sums' workspace behind it are one allocation."""
+    key = (x.shape, x.stride(), mask, backward)
+    ent = _DIFFAUG_OPS.get(key)
+    if ent is None:
+        if len(_DIFFAUG_OPS) >= 64:
+            _DIFFAUG_OPS.clear()
+        N, Cc = x.shape[0], x.shape[1]
+        D, H, W = (x.shape[2], x.shape[3], x.shape[4]) if x.dim() == 5 else (1, x.shape[2], x.shape[3])
+        n = x.numel()
+        op = L.DiffAugOp(xs=(C.c_int64 * 5)(*_strides5(x)), N=N, C=Cc, D=D, H=H, W=W, mask=mask, backward=int(backward))
+        ent = _DIFFAUG_OPS[key] = (op, (N, D, H, W, Cc), n, n + (n & 1), L.lib().gode_diffaug_work_size(N, D, H, W, mask))
+    op, oshape, n, woff, nwork = ent
+    buf = torch.empty(woff + nwork if nwork else n, dtype=torch.float32, device=x.device)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    call = int(call) & 0xFFFFFFFF
+    op.x, op.out = x.data_ptr(), buf.data_ptr()
+    op.work = buf.data_ptr() + 4 * woff if nwork else None          # (8-byte aligned: woff is even)
+    op.seed, op.g0, op.stream = seed - (1 << 64) if seed >= 1 << 63 else seed, int(g0), int(stream)
+    op.call = call - (1 << 32) if call >= 1 << 31 else call
+    L.run_one(op, stream_ptr())
+    return (buf[:n] if nwork else buf).view(oshape)
+
+
+def _from_channels_last(t, ndim):
+    """[N, D, H, W, C] -> the [N, C, D, H, W] (ndim 5) or [N, C, H, W] (ndim 4) permuted view."""
+    return t.permute(0, 4, 1, 2, 3) if ndim == 5 else t.squeeze(1).permute(0, 3, 1, 2)
+
+
+class _DiffAugFn(torch.autograd.Function):
+    """The augmentation as one autograd node; its backward is the same op in its other direction, on the same parameters."""
+
+    @staticmethod
+    def forward(ctx, x, mask, seed, stream, call, g0):
+        ctx.args = (mask, seed, stream, call, g0)
+        return _from_channels_last(_diffaug_run(x, 0, mask, seed, stream, call, g0), x.dim())
+
+    @staticmethod
+    def backward(ctx, g):
+        return _from_channels_last(_diffaug_run(g, 1, *ctx.args), g.dim()), None, None, None, None, None
+
+
+def _diffaug_apply(x, mask, seed, stream, call, g0, what):
+    _require_gpu(x, what)
+    if x.dtype != torch.float32 or x.dim() not in (4, 5):
+        raise RuntimeError(f"{what}: fp32 input [N, C, H, W] or [N, C, D, H, W] expected")
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _DiffAugFn.apply(x, mask, seed, stream, call, g0)
+    return _from_channels_last(_diffaug_run(x, 0, mask, seed, stream, call, g0), x.dim())      # (no node to record)
+
+
+class DiffAugment(nn.Module):
+    """Differentiable augmentation (Zhao et al., NeurIPS 2020) as one HIP op: `policy` is a comma-separated subset of 'color'
+    (brightness, saturation, contrast), 'translation' (up to 1/8 of the map, zero fill) and 'cutout' (half the map), applied to
+    fp32 device tensors [N, C, H, W] or [N, C, D, H, W] of any strides with ONE parameter set per sample (a clip stays
+    temporally consistent).  Returns a permuted view of the channels-last result with the input's shape; gradients flow
+    through it.  The parameters are a pure function of (seed, stream, call, sample_offset + position in the batch) -- see
+    include/gode.h and diffaug_params; `call` advances by one per forward.  Plain attributes, no buffers.  An empty policy
+    returns its input."""
+
+    def __init__(self, policy, seed=None, stream=0):
+        super().__init__()
+        self.policy, self.mask = policy, diffaug_mask(policy)
+        self.seed = (torch.initial_seed() if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
+        self.stream, self.call, self.sample_offset = int(stream), 0, 0
+
+    def forward(self, x):
+        if not self.mask:
+            return x
+        y = _diffaug_apply(x, self.mask, self.seed, self.stream, self.call, self.sample_offset, "DiffAugment input")
+        self.call = (self.call + 1) & 0xFFFFFFFF
+        return y
+
+
 class _DiscFn(torch.autograd.Function):
     """One pass of a discriminator as one autograd node: over x1 alone (x2 None; x1 may want its gradient), or over
     [x1; x2] (real and fake batches of equal shape, detached) with per-group BatchNorm statistics on a groups=2 plan.
@@ -2219,6 +2335,13 @@ class _DiscBase(nn.Module):
         self.noise_seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
         self.noise_stream = stream
         self._noise_call, self._noise_sample_offset = 0, 0
+        # differentiable augmentation, off by default: `diffaug` is a DiffAugment policy string applied to
+        # every input in train mode, in front of the instance noise; plain attributes as above.  diffaug_call counts the
+        # forwards (a paired pass: two), _diffaug_sample_offset is the first global sample of the batch (GanTrainer sets it).
+        self.diffaug = None
+        self.diffaug_seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
+        self.diffaug_stream = stream
+        self.diffaug_call, self._diffaug_sample_offset = 0, 0
 
     def _noise_active(self):
         """sigma 0 adds exact zeros: the plan then stays the noise-free one (the call counter still advances)."""
@@ -2288,6 +2411,13 @@ class _DiscBase(nn.Module):
                 raise RuntimeError("paired pass: both inputs must have the same shape")
             if first.requires_grad or second.requires_grad:
                 raise RuntimeError("paired pass: inputs must be detached (it is the discriminator-update pass)")
+        mask = diffaug_mask(self.diffaug) if self.training and self.diffaug else 0
+        if mask:           # one op per input (call c for `first`, c + 1 for `second`: what two forwards draw)
+            call = self.diffaug_call
+            xs = [_diffaug_apply(t, mask, self.diffaug_seed, self.diffaug_stream, call + i, self._diffaug_sample_offset,
+                                 type(self).__name__ + " input") for i, t in enumerate(xs)]
+            self.diffaug_call = (call + n) & 0xFFFFFFFF
+            first, second = xs[0], (xs[1] if n == 2 else None)
         key = (("pair",) if n == 2 else ()) + shape + (("noise",) if self._noise_active() else ())
         plan = self._pool.get(key, lambda: ConvStack(self._specs((n * shape[0],) + shape[1:]), self._layer_params(),
                                                      self.main[1].weight.device, owns_input=False,

@@ -716,7 +716,8 @@ class GanTrainer:
     def __init__(self, gen, dis_vid, dis_img, lr=2e-4, betas=(0.5, 0.999), weight_decay=1e-5, d_iters=2,
                  process_group=None, freeze_d_in_g_step=True, freeze_gc=False, direct_grads=True, sync_replicas=True,
                  overlap_image_d=True, graph=False, pair_d_passes=True, prefetch_latents=True, overlap_allreduce=True,
-                 joint_generator_passes=True, loss="bce", param_noise=0.0, noise_seed=None):
+                 joint_generator_passes=True, loss="bce", param_noise=0.0, noise_seed=None, diffaug=None,
+                 diffaug_seed=None):
         self.gen, self.dis_vid, self.dis_img = gen, dis_vid, dis_img
         # loss: "bce" (mnist_moco_ode.py) or "wasserstein" (torchgan's losses, mnist_moco_ode_wgan.py: D minimises
         # mean(D(fake) - D(real)), G minimises -mean(D(fake)); no clipping, no gradient penalty)
@@ -759,6 +760,27 @@ class GanTrainer:
             dist.broadcast(t, src=0, group=process_group)
             for m, (lo, hi) in zip(dnoise, t.tolist()):
                 m.noise_seed = int(lo) | (int(hi) << 32)
+        # diffaug: a DiffAugment policy ('color,translation,cutout', any subset) for both discriminators -- every real and
+        # every fake batch passes the same random transform in front of them, and the G step back-propagates through it
+        # (DESIGN section 28).  diffaug_seed, when given, keys both streams (default: each module's torch.initial_seed() at
+        # construction); replicas take rank 0's seeds, and each replica and virtual-replica shard draws the parameters of its
+        # own samples (_noise_shard).  None leaves the discriminators as they are.
+        from .modules import diffaug_mask
+        if diffaug_mask(diffaug) or diffaug_seed is not None:   # (an unknown name is refused here, not in the first step)
+            for m in (dis_vid, dis_img):
+                m.diffaug = diffaug or m.diffaug
+                if diffaug_seed is not None:
+                    m.diffaug_seed = int(diffaug_seed) & 0xFFFFFFFFFFFFFFFF
+        aug = [m for m in (dis_vid, dis_img) if diffaug_mask(getattr(m, "diffaug", None))]
+        if aug and graph:
+            raise NotImplementedError("GanTrainer(graph=True) does not capture a DiffAugment policy: use the eager "
+                                      "schedule (graph=False)")
+        if aug and self.world > 1 and sync_replicas:
+            dev = next(gen.parameters()).device
+            t = torch.tensor([[m.diffaug_seed & 0xFFFFFFFF, m.diffaug_seed >> 32] for m in aug], dtype=torch.int64, device=dev)
+            dist.broadcast(t, src=0, group=process_group)
+            for m, (lo, hi) in zip(aug, t.tolist()):
+                m.diffaug_seed = int(lo) | (int(hi) << 32)
         # param_noise > 0: add_noise(model.parameters(), param_noise) after every optimiser step (mnist_moco_ode_noise.py
         # sigma 1e-5, mnist_moco_ode_wgan.py 1e-4), fused into the Adam launch; streams gen 0, dis_vid 1, dis_img 2 of
         # noise_seed (default torch.initial_seed(): nothing is drawn from the CPU generator, whose stream feeds the latent
@@ -966,10 +988,18 @@ class GanTrainer:
 
     def _noise_shard(self, model, k, B, nsh, call0):
         """Instance noise of shard k of nsh (batch B each): the shards of one step share the call index call0 and draw the
-        noise of their own samples -- the offset is the shard's first sample in the global batch."""
+        noise of their own samples -- the offset is the shard's first sample in the global batch.  call0: the pair
+        (instance-noise call, DiffAugment call) of _calls0; the augmentation's counter and offset follow the same rule."""
         if getattr(model, "use_noise", False):
-            model._noise_call = call0
+            model._noise_call = call0[0]
             model._noise_sample_offset = (self.rank * nsh + k) * B
+        if getattr(model, "diffaug", None):
+            model.diffaug_call = call0[1]
+            model._diffaug_sample_offset = (self.rank * nsh + k) * B
+
+    @staticmethod
+    def _calls0(model):
+        return getattr(model, "_noise_call", 0), getattr(model, "diffaug_call", 0)
 
     def _gen_one_stream(self):
         """The discriminator steps' no-grad generator calls keep the one-stream path (VideoGenerator.one_stream): each
@@ -990,7 +1020,7 @@ class GanTrainer:
         with on_side():
             self._begin(self.dis_img, self.img_opt)
         losses = []
-        call0 = getattr(self.dis_img, "_noise_call", 0)
+        call0 = self._calls0(self.dis_img)
         for k, x in enumerate(shards):
             B = x.shape[0]
             self._noise_shard(self.dis_img, k, B, len(shards), call0)
@@ -1053,7 +1083,7 @@ class GanTrainer:
         labels = self._labels_for(real_labels, shards[0].shape[0], "d_video_step")
         losses = []
         begun = False
-        call0 = getattr(self.dis_vid, "_noise_call", 0)
+        call0 = self._calls0(self.dis_vid)
         for k, x in enumerate(shards):
             B = x.shape[0]
             self._noise_shard(self.dis_vid, k, B, len(shards), call0)
@@ -1117,7 +1147,7 @@ class GanTrainer:
         early_ar = self.world > 1 and self.overlap_ar and id(self.gen) in self.arenas
         try:
             joint = shards == 1 and self._can_pair(B, B, False)
-            calls0 = [getattr(m, "_noise_call", 0) for m in (self.dis_vid, self.dis_img)]
+            calls0 = [self._calls0(m) for m in (self.dis_vid, self.dis_img)]
             for k in range(shards):
                 for m, c0 in zip((self.dis_vid, self.dis_img), calls0):
                     self._noise_shard(m, k, B, shards, c0)

@@ -684,6 +684,50 @@ typedef struct gode_latent_draw_op {
 } gode_latent_draw_op;
 int gode_latent_draw(const gode_latent_draw_op* op, void* stream);
 
+/* ---- differentiable augmentation in front of the discriminators (DiffAugment, Zhao et al., NeurIPS 2020)
+ * A sample is one image [C][H][W] (D = 1) or one clip [C][D][H][W]; all its frames and channels share ONE parameter set.  The
+ * parameters of global sample g = g0 + (position in the batch) come from Philox4x32-10 with key (seed low word, seed high
+ * word) and counter (g low word, call, tag, g high word), tag = 0x20000000 | stream << 8 | field, stream < 2^21: bit 29 set,
+ * bits 30 and 31 clear -- disjoint from the parameter noise (far below 2^29), dropout (0x40000000), the latents (0x60000000)
+ * and the instance noise (0x80000000).  U(w) = ((w >> 9) + 0.5) * 2^-23.  All seven are drawn whatever the mask says:
+ *   field 0: u_b = U(w0), u_s = U(w1), u_c = U(w2)   (w3 unused)
+ *   field 1: tx = umulhi(w0, 2 Sx + 1) - Sx, ty = umulhi(w1, 2 Sy + 1) - Sy, cx = umulhi(w2, W + 1 - cw % 2),
+ *            cy = umulhi(w3, H + 1 - ch % 2), with Sx = (W + 4) / 8, Sy = (H + 4) / 8, cw = (W + 1) / 2, ch = (H + 1) / 2
+ * The components, in this order, selected by the bits of `mask`:
+ *   1  brightness   x <- x + (u_b - 0.5)
+ *   2  saturation   m = mean over the C channels at each (d, h, w); x <- (x - m) * (2 u_s) + m
+ *   4  contrast     M = mean over all C*D*H*W elements of the sample; x <- (x - M) * (u_c + 0.5) + M
+ *   8  translation  y[c][d][h][w] = x[c][d][h - ty][w - tx] where that source lies inside the map, else 0
+ *   16 cutout       y = 0 for cy - ch/2 <= h < cy - ch/2 + ch and cx - cw/2 <= w < cx - cw/2 + cw (clipped to the map)
+ * backward == 1: x is the cotangent of the forward's output and out receives the cotangent of its input -- zero under the
+ * cutout, shifted back (g'[h][w] = g[h + ty][w + tx], 0 outside), g <- s g + (1 - s) mean_sample(g) with s = u_c + 0.5,
+ * g <- s g + (1 - s) mean_channels(g) with s = 2 u_s; brightness is the identity.
+ * x is read through the element strides xs {N, D, H, W, C} (any view, as gode_dnoise_op's gather mode); out is contiguous
+ * channels-last [N][D][H][W][C].  call = (call_dev ? call_dev[0] : 0) + call, as in gode_dnoise_op.  Nothing but (seed,
+ * stream, call, g) enters a sample's parameters: a batch drawn in parts with g0 set equals the whole.
+ * The sample sums that contrast needs (forward: of x; backward: of the masked, shifted cotangent) are fp64, formed in a
+ * fixed order without atomics -- a sample is cut into gode_diffaug_chunks(D, H, W) chunks of positions, one workgroup each,
+ * whose partial sums go to work ([N][chunks] doubles) and are added in index order by the second launch -- so two runs give the
+ * same bits.  work: >= gode_diffaug_work_size(N, D, H, W, mask) floats, 8-byte aligned; 0 for a mask without bit 4, which
+ * launches once and never touches work (it may be NULL).  Masks within 8 | 16 move data only: out holds x's bits or +0.
+ * GODE_E_ARG: a null op / x / out; any of N, C, D, H, W below 1; mask outside [1, 31]; backward not 0 or 1; stream outside
+ * [0, 2^21); g0 < 0; bit 4 with a null or misaligned work.  GODE_E_SHAPE: D*H*W*C >= 2^31 or N * chunks >= 2^31.  All are
+ * returned before any launch. */
+typedef struct gode_diffaug_op {
+  const float* x; float* out; float* work; const int32_t* call_dev;
+  int64_t xs[5];
+  int64_t seed, g0;
+  int32_t N, C, D, H, W;
+  int32_t mask, backward, stream, call, pad_;
+} gode_diffaug_op;
+int gode_diffaug(const gode_diffaug_op* op, void* stream);
+int32_t gode_diffaug_chunks(int32_t D, int32_t H, int32_t W);
+int64_t gode_diffaug_work_size(int32_t N, int32_t D, int32_t H, int32_t W, int32_t mask);
+/* the parameters alone, on the host (no launch): ints[n][4] = tx, ty, cx, cy and unis[n][3] = u_b, u_s, u_c of samples
+ * g0 .. g0 + n - 1.  GODE_E_ARG: a null pointer, n < 0, stream >= 2^21, g0 < 0, H or W below 1. */
+int gode_diffaug_params(int32_t* ints, float* unis, int64_t n, uint64_t seed, uint32_t stream, uint32_t call, int64_t g0,
+                        int32_t H, int32_t W);
+
 /* ---- ODE-GAN training (GANODETrainer of stage2/ode_training.py: Euler / Heun / RK4 steps in parameter space) ---------
  * One stage update of a whole network in ONE launch, on `count` fp32 tensors described by a DEVICE table:
  *   p += c1*g[0] + c2*g[1] + c3*g[2] + c4*g[3] + cq*(qp - qm)
@@ -1004,7 +1048,8 @@ int gode_scale(float* out, const float* a, int64_t n, float alpha, int accumulat
   X(BN_RUNNING,    39, gode_bn_running_op,    gode_bn_running)    \
   X(ROT_CLIPS,     40, gode_rot_clips_op,     gode_rot_clips)     \
   X(VIDEO_GRID,    41, gode_video_grid_op,    gode_video_grid)    \
-  X(LATENT_DRAW,   42, gode_latent_draw_op,   gode_latent_draw)
+  X(LATENT_DRAW,   42, gode_latent_draw_op,   gode_latent_draw)   \
+  X(DIFFAUG,       43, gode_diffaug_op,       gode_diffaug)
 /* GODE_OP_PACK stays outside the table: it has no (op*, stream) entry point, gode_run sends every run of consecutive pack
  * ops out as batched launches instead. */
 #define GODE_ENUM_ROW_(name, value, op_t, fn) GODE_OP_##name = value,
