@@ -138,7 +138,8 @@ class OdeBwdOp(_Op):
     _fields_ = [("p", OdeParams), ("x", ptr), ("traj", ptr), ("dt", ptr), ("sel_t", ptr), ("gz", ptr),
                 ("work", ptr), ("grads", ptr), ("N", i32), ("T", i32), ("substeps", i32), ("prenet", i32),
                 ("accumulate", i32), ("zcols", i32), ("bstep_off", ptr), ("bstep_dt", ptr), ("method", i32),
-                ("rhs", i32), ("rtol", f32), ("atol", f32), ("tout", ptr), ("nsteps", ptr), ("sync", ptr)]
+                ("rhs", i32), ("rtol", f32), ("atol", f32), ("tout", ptr), ("nsteps", ptr), ("sync", ptr),
+                ("backprop", i32), ("G", i32), ("grid_dt", ptr), ("emit_at", ptr), ("emit_w", ptr), ("ysteps", ptr)]
     KIND, FN = OP_ODE_BWD, "gode_ode_bwd"
 
 
@@ -408,6 +409,7 @@ _PROTOS = {
     "gode_wgrad_auto_splits": ([ptr], cint),
     "gode_bn_bwd_work_size": ([i64, i32], i64),
     "gode_ode_bwd_work_size": ([i32], i64),
+    "gode_ode_bwd_steps_size": ([i32, i32, i32, i32], i64),
     "gode_odernn_bwd_work_size": ([i32], i64),
     "gode_odernn_sync_size": ([i32], i64),
     "gode_sde_bwd_work_size": ([i32], i64),

@@ -251,6 +251,12 @@ __global__ void __launch_bounds__(64) ode_bwd_kernel(const gode_ode_bwd_op a) {
 }
 
 extern "C" int64_t gode_ode_bwd_work_size(int32_t N) { return (int64_t)((N + 15) / 16) * GODE_ODE_NPARAM; }
+// floats of `ysteps` (discrete backprop): 16 per trajectory and solver step; 0 where the steps start on traj's rows
+extern "C" int64_t gode_ode_bwd_steps_size(int32_t N, int32_t T, int32_t substeps, int32_t G) {
+  if (N <= 0 || T < 1) return 0;
+  const int64_t S = G > 0 ? G : (substeps > 1 ? (int64_t)(T - 1) * substeps : 0);
+  return (int64_t)N * S * 16;
+}
 
 int gode_launch_ode_dopri5_bwd(const gode_ode_bwd_op* op, hipStream_t st);   // adj_adaptive.hip
 
@@ -273,10 +279,17 @@ extern "C" int gode_ode_bwd(const gode_ode_bwd_op* op, void* stream) {
   if (!op->p.W1 || !op->p.b1 || (op->rhs == 0 && (!op->p.W2 || !op->p.b2))) return GODE_E_ARG;
   if (op->prenet && (!op->x || !op->p.Wa || !op->p.ba || !op->p.Wb || !op->p.bb)) return GODE_E_ARG;
   if ((op->bstep_off == nullptr) != (op->bstep_dt == nullptr)) return GODE_E_ARG;
+  // discrete backprop: fixed-grid methods only, on the forward's grid, with the scratch its forward re-run needs
+  if (op->backprop != 0 && op->backprop != 1) return GODE_E_ARG;
+  if (op->backprop == 1) {
+    if (op->method == 1) return GODE_E_ARG;
+    if (op->grid_dt && (!op->emit_at || !op->emit_w || op->G < 1)) return GODE_E_ARG;
+    if (gode_ode_bwd_steps_size(op->N, op->T, op->substeps, op->grid_dt ? op->G : 0) > 0 && !op->ysteps) return GODE_E_ARG;
+  }
   const int nblk = (op->N + 15) / 16;
   hipStream_t st = (hipStream_t)stream;
   if (adaptive) return gode_ode_bwd_multi(op, 1, stream);      // odernn_valu.hip (reduces into grads itself)
-  if (!ode_use_mfma(op->N, op->method, op->rhs)) {
+  if (op->backprop == 1 || !ode_use_mfma(op->N, op->method, op->rhs)) {   // (discrete backprop: the VALU kernel at every N)
     const int rc = gode_launch_ode_bwd_valu(op, st);
     if (rc) return rc;
   } else {

@@ -41,6 +41,24 @@ struct NoW16 {};                         // stands where an RHS_TANH kernel has 
 template <int RHS> using W16If2 = std::conditional_t<RHS == RHS_MLP, W16, NoW16>;
 template <int RHS> constexpr int rhs_nparam = RHS == RHS_MLP ? GODE_ODE_NPARAM : OFF_W2;
 
+// y(t) -> y(t + dt) with right-hand side f: the ONE step function of a method, called by the forward kernel on every grid
+// mode and by the discrete-backprop kernel's forward re-run
+template <int METHOD, class F>
+__device__ __forceinline__ float fixed_step(F&& f, float y0, float dt) {
+  if constexpr (METHOD == METHOD_EULER) {
+    return y0 + dt * f(y0);
+  } else if constexpr (METHOD == METHOD_MIDPOINT) {
+    return y0 + dt * f(y0 + (0.5f * dt) * f(y0));
+  } else {
+    const float third = 1.0f / 3.0f;
+    const float k1 = f(y0);
+    const float k2 = f(y0 + dt * k1 * third);
+    const float k3 = f(y0 + dt * (k2 - k1 * third));
+    const float k4 = f(y0 + dt * (k1 - k2 + k3));
+    return y0 + (k1 + 3.f * (k2 + k3) + k4) * dt * 0.125f;
+  }
+}
+
 template <int METHOD, int RHS>
 __global__ void __launch_bounds__(256) ode_fwd_valu_kernel(const gode_ode_fwd_op a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -75,21 +93,7 @@ __global__ void __launch_bounds__(256) ode_fwd_valu_kernel(const gode_ode_fwd_op
     else if (t == tsel) a.z[(int64_t)n * a.zcols + i] = y;
   };
   emit(0);
-  // y(t) -> y(t + dt)
-  auto step = [&](float y0, float dt) -> float {
-    if constexpr (METHOD == METHOD_EULER) {
-      return y0 + dt * f(y0);
-    } else if constexpr (METHOD == METHOD_MIDPOINT) {
-      return y0 + dt * f(y0 + (0.5f * dt) * f(y0));
-    } else {
-      const float third = 1.0f / 3.0f;
-      const float k1 = f(y0);
-      const float k2 = f(y0 + dt * k1 * third);
-      const float k3 = f(y0 + dt * (k2 - k1 * third));
-      const float k4 = f(y0 + dt * (k1 - k2 + k3));
-      return y0 + (k1 + 3.f * (k2 + k3) + k4) * dt * 0.125f;
-    }
-  };
+  auto step = [&](float y0, float dt) -> float { return fixed_step<METHOD>(f, y0, dt); };
   if (a.grid_dt != nullptr) {
     int jo = 1;
     for (int s = 0; s < a.G; ++s) {
@@ -113,8 +117,13 @@ __global__ void __launch_bounds__(256) ode_fwd_valu_kernel(const gode_ode_fwd_op
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// adjoint backward
-template <int METHOD, int RHS>
+// backward.  BACKPROP (the `backprop` codes of gode.h): BP_ADJOINT, torchdiffeq's continuous adjoint -- (y, adj, g_theta)
+// re-integrated backwards in time with the method's own steps; BP_DISCRETE, the exact reverse-mode gradient of the forward
+// kernel's steps (autograd through odeint), walked from each step's start state.  The two differ in the time loop only: the
+// lane mapping, the six weight / accumulator arrangements, the upstream reads and everything behind the loop (reduction over
+// trajectories, pre-net backward, the `work` row) are this one body.
+enum { BP_ADJOINT = 0, BP_DISCRETE = 1 };
+template <int METHOD, int RHS, int BACKPROP>
 __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op a) {
   constexpr int NPAR = rhs_nparam<RHS>;       // the block this kernel stages, accumulates and writes out
   __shared__ float R[4][NPAR];                // per-wave image of the gradient vector (combined once, at the end)
@@ -154,7 +163,9 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
     if (a.sel_t == nullptr) return a.gz[((int64_t)n * T + t) * a.zcols + i];
     return t == tsel ? a.gz[(int64_t)n * a.zcols + i] : 0.f;
   };
-  float adj = upstream(T - 1);
+  float adj = 0.f;                        // dL/d(state): the adjoint, or discrete backprop's lambda
+  if constexpr (BACKPROP == BP_ADJOINT) {
+  adj = upstream(T - 1);
   float ky, ka;
   // one stage of the reversed augmented dynamics at (ys, as); c = the stage's b-weight * dt for the parameter integrals
   // (weighted = std::false_type: a stage of weight 0, whose outer products are not formed)
@@ -227,6 +238,107 @@ __global__ void __launch_bounds__(256) ode_bwd_valu_kernel(const gode_ode_bwd_op
     const float dt_eq = a.dt[it - 1] / (float)a.substeps;
     for (int ss = 0; ss < ns; ++ss) step(y, adj, a.bstep_off ? a.bstep_dt[s0 + ss] : dt_eq);
     adj = adj + up;
+  }
+  } else {
+  // ---- discrete backprop: every solver step in reverse order, from its start state y0 and adj = dL/dy1.  The stage inputs
+  // u_s and h_s = tanh(W1 u_s + b1) are recomputed and kept (at most 4 + 4 values per lane), then the stages are walked
+  // backwards; vjp(g, u, h) = J^T g at u, and adds the stage's parameter VJP to the per-lane accumulators
+  auto h_of = [&](float u) { return fast_tanh(mv16(w1, u, b1)); };
+  auto k_of = [&](float h) {
+    if constexpr (RHS == RHS_MLP) return mv16(w2, h, b2);
+    else return h;
+  };
+  auto vjp = [&](float g, float u, float h) -> float {
+    float du;
+    if constexpr (RHS == RHS_MLP) {
+      gb2 += g;
+      outer16(gW2, g, h);
+      du = mv16(w2t, g, 0.f) * (1.f - h * h);
+    } else {
+      du = g * (1.f - h * h);
+    }
+    gb1 += du;
+    outer16(gW1, du, u);
+    return mv16(w1t, du, 0.f);
+  };
+  auto rstep = [&](float y0, float dt) {
+    if constexpr (METHOD == METHOD_EULER) {
+      const float h1 = h_of(y0);
+      adj = adj + vjp(dt * adj, y0, h1);
+    } else if constexpr (METHOD == METHOD_MIDPOINT) {
+      const float half = 0.5f * dt;
+      const float h1 = h_of(y0);
+      const float u2 = y0 + half * k_of(h1);
+      const float h2 = h_of(u2);
+      const float gu2 = vjp(dt * adj, u2, h2);
+      const float gu1 = vjp(half * gu2, y0, h1);
+      adj = adj + gu2 + gu1;
+    } else {
+      const float third = 1.0f / 3.0f;
+      const float h1 = h_of(y0), k1 = k_of(h1);
+      const float u2 = y0 + dt * k1 * third;
+      const float h2 = h_of(u2), k2 = k_of(h2);
+      const float u3 = y0 + dt * (k2 - k1 * third);
+      const float h3 = h_of(u3), k3 = k_of(h3);
+      const float u4 = y0 + dt * (k1 - k2 + k3);
+      const float h4 = h_of(u4);
+      const float l1 = dt * 0.125f * adj, l3 = 3.f * dt * 0.125f * adj;     // the b-weights' share of adj
+      const float gu4 = vjp(l1, u4, h4);
+      const float gu3 = vjp(l3 + dt * gu4, u3, h3);
+      const float gu2 = vjp(l3 + dt * (gu3 - gu4), u2, h2);
+      const float gu1 = vjp(l1 + dt * gu4 + dt * third * (gu2 - gu3), y0, h1);
+      adj = adj + ((gu1 + gu2) + (gu3 + gu4));
+    }
+  };
+#ifdef GODE_ODE_STAMPS
+  st1 = __builtin_amdgcn_s_memtime();
+#endif
+  if (a.grid_dt == nullptr && a.substeps == 1) {
+    // the grid is the output times: the step-start states are traj itself, read as the adjoint loop above reads it
+    adj = upstream(T - 1);
+    float y_next = (valid && T > 1) ? a.traj[((int64_t)n * T + (T - 2)) * 16 + i] : 0.f;
+    for (int it = T - 1; it >= 1; --it) {
+      const float y0 = y_next;
+      const float up = upstream(it - 1);
+      if (it > 1) y_next = valid ? a.traj[((int64_t)n * T + (it - 2)) * 16 + i] : 0.f;
+      rstep(y0, a.dt[it - 1]);
+      adj = adj + up;
+    }
+  } else {
+    // substeps > 1 or a grid_dt grid: the forward is re-run from traj[n][0] (the pre-net output) with the forward kernel's
+    // step, every step's start state goes to ysteps[n][s][:], and the steps are walked backwards.  A lane reads back only
+    // what it wrote itself.
+    const int S = a.grid_dt ? a.G : (T - 1) * a.substeps;
+    float* ys = a.ysteps + (int64_t)n * S * 16 + i;          // (dereferenced by valid lanes only)
+    auto dt_of = [&](int s) { return a.grid_dt ? a.grid_dt[s] : a.dt[s / a.substeps] / (float)a.substeps; };
+    auto f = [&](float yy) { return k_of(h_of(yy)); };
+    float y = valid ? a.traj[(int64_t)n * T * 16 + i] : 0.f;
+    for (int s = 0; s < S; ++s) {
+      if (valid) ys[(int64_t)s * 16] = y;
+      y = fixed_step<METHOD>(f, y, dt_of(s));
+    }
+    int jo = T - 1;                                          // grid_dt: the next output to hand its gradient over
+    float y_next = (valid && S > 0) ? ys[(int64_t)(S - 1) * 16] : 0.f;
+    for (int s = S - 1; s >= 0; --s) {
+      const float y0 = y_next;
+      if (s > 0) y_next = valid ? ys[(int64_t)(s - 1) * 16] : 0.f;
+      float after = 0.f;
+      if (a.grid_dt) {
+        // output jo = y0 + w (y1 - y0) of this step: w gz to dL/dy1 now, (1 - w) gz to dL/dy0 behind the reverse step
+        while (jo >= 1 && a.emit_at[jo] == s) {
+          const float w = a.emit_w[jo], g = upstream(jo);
+          adj = adj + w * g;
+          after = after + (1.f - w) * g;
+          --jo;
+        }
+      } else if ((s + 1) % a.substeps == 0) {
+        adj = adj + upstream((s + 1) / a.substeps);
+      }
+      rstep(y0, dt_of(s));
+      adj = adj + after;
+    }
+    adj = adj + upstream(0);
+  }
   }
 
 #ifdef GODE_ODE_STAMPS
@@ -312,11 +424,11 @@ static void launch_fwd(const gode_ode_fwd_op* op, dim3 grid, dim3 block, hipStre
   else if (op->method == METHOD_MIDPOINT) hipLaunchKernelGGL((ode_fwd_valu_kernel<METHOD_MIDPOINT, RHS>), grid, block, 0, st, *op);
   else hipLaunchKernelGGL((ode_fwd_valu_kernel<METHOD_RK4, RHS>), grid, block, 0, st, *op);
 }
-template <int RHS>
+template <int RHS, int BACKPROP>
 static void launch_bwd(const gode_ode_bwd_op* op, dim3 grid, dim3 block, hipStream_t st) {
-  if (op->method == METHOD_EULER) hipLaunchKernelGGL((ode_bwd_valu_kernel<METHOD_EULER, RHS>), grid, block, 0, st, *op);
-  else if (op->method == METHOD_MIDPOINT) hipLaunchKernelGGL((ode_bwd_valu_kernel<METHOD_MIDPOINT, RHS>), grid, block, 0, st, *op);
-  else hipLaunchKernelGGL((ode_bwd_valu_kernel<METHOD_RK4, RHS>), grid, block, 0, st, *op);
+  if (op->method == METHOD_EULER) hipLaunchKernelGGL((ode_bwd_valu_kernel<METHOD_EULER, RHS, BACKPROP>), grid, block, 0, st, *op);
+  else if (op->method == METHOD_MIDPOINT) hipLaunchKernelGGL((ode_bwd_valu_kernel<METHOD_MIDPOINT, RHS, BACKPROP>), grid, block, 0, st, *op);
+  else hipLaunchKernelGGL((ode_bwd_valu_kernel<METHOD_RK4, RHS, BACKPROP>), grid, block, 0, st, *op);
 }
 int gode_launch_ode_fwd_valu(const gode_ode_fwd_op* op, hipStream_t st) {
   const dim3 grid((op->N + 15) / 16), block(256);
@@ -327,8 +439,12 @@ int gode_launch_ode_fwd_valu(const gode_ode_fwd_op* op, hipStream_t st) {
 }
 int gode_launch_ode_bwd_valu(const gode_ode_bwd_op* op, hipStream_t st) {
   const dim3 grid((op->N + 15) / 16), block(256);
-  if (op->rhs == RHS_TANH) launch_bwd<RHS_TANH>(op, grid, block, st);
-  else launch_bwd<RHS_MLP>(op, grid, block, st);
+  // op->backprop: 1 = discrete backprop (methods 0, 2, 3 only: the caller has refused method 1), else the adjoint
+  if (op->backprop == BP_DISCRETE) {
+    if (op->rhs == RHS_TANH) launch_bwd<RHS_TANH, BP_DISCRETE>(op, grid, block, st);
+    else launch_bwd<RHS_MLP, BP_DISCRETE>(op, grid, block, st);
+  } else if (op->rhs == RHS_TANH) launch_bwd<RHS_TANH, BP_ADJOINT>(op, grid, block, st);
+  else launch_bwd<RHS_MLP, BP_ADJOINT>(op, grid, block, st);
   GODE_LAUNCH_CHECK();
   return 0;
 }

@@ -1112,7 +1112,7 @@ static bool ode5_fwd_ok(const gode_ode_fwd_op* op) {     // (rhs: the adaptive k
 }
 
 static bool ode5_bwd_ok(const gode_ode_bwd_op* op) {
-  if (!op || op->method != 1 || op->rhs != 0 || op->substeps != 0 || !op->traj || !op->gz || !op->work || !op->grads || !op->tout || op->N <= 0 || op->T < 1 ||
+  if (!op || op->method != 1 || op->rhs != 0 || op->backprop != 0 || op->substeps != 0 || !op->traj || !op->gz || !op->work || !op->grads || !op->tout || op->N <= 0 || op->T < 1 ||
       !(op->rtol > 0.f) || !(op->atol >= 0.f) || op->zcols < 16 || op->zcols % 4 != 0)
     return false;
   if (!op->p.W1 || !op->p.b1 || !op->p.W2 || !op->p.b2) return false;

@@ -175,6 +175,30 @@ class ODEFuncTanh(nn.Module):
         raise RuntimeError("ODEFuncTanh is evaluated inside libgode's fused fixed-grid kernels (gode_ode_fwd/bwd, rhs = 1)")
 
 
+ODE_BACKPROPS = {"adjoint": 0, "discrete": 1}      # gen.ode_backprop -> gode_ode_bwd_op.backprop
+_DISCRETE_METHODS = ("rk4", "euler", "midpoint")
+
+
+def ode_backprop_code(gen):
+    """The `backprop` code of gen.ode_backprop (a generator without the attribute: the adjoint).  "discrete" -- the exact
+    gradient of the fixed-grid solve -- is served by the plain Neural-ODE generators with the three fixed-grid methods."""
+    name = getattr(gen, "ode_backprop", "adjoint")
+    try:
+        code = ODE_BACKPROPS[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"ode_backprop {name!r}: " + " or ".join(repr(k) for k in ODE_BACKPROPS)) from None
+    if code:
+        served = ", ".join(repr(k) for k in _DISCRETE_METHODS)
+        if not getattr(gen, "_discrete_ok", True):
+            raise NotImplementedError(f"ode_backprop 'discrete' is implemented for the plain Neural-ODE generators (ode_method "
+                                      f"{served}), not for {type(gen).__name__}: its latent kernels already back-propagate "
+                                      "through their own steps or integrate an adaptive adjoint")
+        if gen.ode_method not in _DISCRETE_METHODS:
+            raise NotImplementedError(f"ode_backprop 'discrete' with ode_method {gen.ode_method!r}: back-propagating through "
+                                      f"adaptive steps is not implemented; the fixed-grid methods {served} are served")
+    return code
+
+
 def _is_one_layer(ode_fn):
     """Is ode_fn (a class or an instance) the one-layer right-hand side?"""
     return issubclass(ode_fn, ODEFuncTanh) if isinstance(ode_fn, type) else isinstance(ode_fn, ODEFuncTanh)
@@ -404,10 +428,14 @@ class _GenPlan:
 
     def _programs(self):
         ps = self._params()
+        discrete = getattr(self.gen, "ode_backprop", "adjoint") != "adjoint"
         ptrs = tuple(dptr(p) for p in ps) + (self.gen.ode_step_size, self.gen.ode_method, self.gen.ode_rtol,
-                                             self.gen.ode_atol, self._draws_on_device())
+                                             self.gen.ode_atol, self._draws_on_device(),
+                                             getattr(self.gen, "ode_backprop", "adjoint"),
+                                             self.gen.ode_substeps if discrete else None)    # (discrete: sizes ysteps)
         if ptrs != self._ode_ptrs:
             method = ode_method_code(self.gen.ode_method)
+            backprop = ode_backprop_code(self.gen)
             rhs = self.rhs
             if rhs and method == ODE_METHODS["dopri5"]:
                 raise NotImplementedError("ode_method 'dopri5' with the one-layer right-hand side (ODEFuncTanh): libgode's "
@@ -449,6 +477,18 @@ class _GenPlan:
                 self.fwd_op.G = gd["G"]
                 self.fwd_op.grid_dt, self.fwd_op.emit_at, self.fwd_op.emit_w = dptr(gd["grid_dt"]), dptr(gd["emit_at"]), dptr(gd["emit_w"])
                 self.bwd_op.bstep_off, self.bwd_op.bstep_dt = dptr(gd["bstep_off"]), dptr(gd["bstep_dt"])
+            self._ysteps = None
+            if backprop:
+                # the exact gradient of the forward's steps, on the forward's grid; off the reference's grid (substeps > 1 or
+                # a step_size grid) the kernel re-runs the forward and keeps every step's start state in ysteps
+                assert not self.multi_ok(self.gen, True)     # (discrete ops never enter the trainer's _adjoint_batch)
+                self.bwd_op.backprop = backprop
+                self.bwd_op.G = self.fwd_op.G
+                self.bwd_op.grid_dt, self.bwd_op.emit_at, self.bwd_op.emit_w = self.fwd_op.grid_dt, self.fwd_op.emit_at, self.fwd_op.emit_w
+                ny = L.lib().gode_ode_bwd_steps_size(self.n, self.T, self.gen.ode_substeps, self.fwd_op.G)
+                if ny:
+                    self._ysteps = torch.empty(ny, dtype=torch.float32, device=self.device)
+                    self.bwd_op.ysteps = dptr(self._ysteps)
             self.categ_op = None
             if self.ncat:
                 # the one-hot columns follow the solve in the same program (the solve's content broadcast zeroes the pad)
@@ -952,6 +992,12 @@ class VideoGenerator(nn.Module):
     # the reference passes method='rk4' (models/mocogan_ode.py:50,144); 'dopri5' is what BASELINE configs[3] words;
     # 'euler' and 'midpoint' are torchdiffeq's other two fixed-grid solvers, on rk4's grid (ODE_METHODS: all served names)
     ode_method = "rk4"
+    # How the fixed-grid solve is back-propagated.  "adjoint": torchdiffeq's odeint_adjoint, the reference's call -- the
+    # continuous adjoint re-integrated backwards, which differs from the gradient of the computed solve by the solver's
+    # truncation error.  "discrete": the exact reverse-mode gradient of the forward's steps (what autograd through
+    # torchdiffeq's odeint gives), for 'rk4', 'euler' and 'midpoint' (DESIGN section 29).  Read at every call.
+    ode_backprop = "adjoint"
+    _discrete_ok = True        # (the SDE / CDE / GRU / ODE-RNN generators switch it off)
     # adjoint_substeps (dopri5 only): 0 = the adjoint is integrated adaptively with the same controller and
     # torchdiffeq's mixed norm, as odeint_adjoint does; k > 0 = k fixed Kutta-3/8 steps per output interval
     ode_rtol, ode_atol, adjoint_substeps = 1e-7, 1e-9, 0
@@ -1174,6 +1220,7 @@ class VideoGenerator(nn.Module):
 
     def _run(self, n_traj, T, select, x, content, sel, cls=None, plan=None):
         # (cls before plan: callers splat _host_inputs' three or four values into x, content, sel[, cls])
+        ode_backprop_code(self)
         _require_gpu(self.main[0].weight, type(self).__name__)
         if plan is None:
             plan = self._pool.get((n_traj, T, select), lambda: self._plan_cls(self, n_traj, T, select))
@@ -1194,6 +1241,7 @@ class VideoGenerator(nn.Module):
         by side (gode_odernn_fwd_multi) instead of six launches back to back.  Results are bit-identical to the calls
         without prefetch.  latent_rng == "device": nothing is drawn on the host; each announced call takes the next index of
         the latent stream, in announcement order, and its plan's draw op runs ahead of the solves."""
+        ode_backprop_code(self)
         _require_gpu(self.main[0].weight, type(self).__name__)
         if self.__dict__.get("_prefetched"):
             raise RuntimeError("prefetch_latents: the previous prefetch has not been consumed "
@@ -1404,6 +1452,7 @@ class VideoGenerator(nn.Module):
         per-call BatchNorm batch statistics (_GenJointPlan): -> ((videos, labels), (images, None)).  Falls back to the two
         calls when the layers' statistics rows do not split at the batch boundary (unusual batch sizes)."""
         T = self.video_length
+        ode_backprop_code(self)
         _require_gpu(self.main[0].weight, type(self).__name__)
         plan = self._take_prefetched("pair_iv" if images_first else "pair_vi", (n_videos, n_images), T)
         host = None
@@ -1470,6 +1519,7 @@ class VideoGenerator(nn.Module):
         surface (and is what sample_z_video calls)."""
         T = video_len if video_len is not None else self.video_length
         self._check_len(T)
+        ode_backprop_code(self)
         _require_gpu(self.main[0].weight, type(self).__name__)
         x = self._draw_motion(num_samples, T)
         return _LatentFn.apply(self, x, num_samples, T, *self._param_list()[1])
@@ -1609,6 +1659,7 @@ class VideoGeneratorMNISTODERNN(VideoGeneratorMNIST):
     _one_layer_ok = False
 
     _plan_cls = _RnnGenPlan
+    _discrete_ok = False
     ode_rtol, ode_atol = 1e-7, 1e-9
     adjoint_substeps = 0      # 0: adaptive adjoint (torchdiffeq's behaviour); 32 was round 1's fixed discretisation
 
@@ -1701,6 +1752,7 @@ class VideoGeneratorGRU(VideoGenerator):
     the device generator on a GPU (models/mocogan.py:297-301), which cannot be reproduced bit for bit."""
 
     _plan_cls = _GruGenPlan
+    _discrete_ok = False
     _gode_graph_capture = False     # GanTrainer(graph=True) refuses this generator (not captured / verified)
 
     def __new__(cls, *args, **kwargs):
@@ -1859,6 +1911,7 @@ class VideoGeneratorSDE(VideoGeneratorMNIST):
     _categorical_ok = False     # dim_z_category > 0 is refused: categorical latents exist for the Neural-ODE generators only
 
     _plan_cls = _SdeGenPlan
+    _discrete_ok = False
     _sde_dt = 2.5e-2
     _gode_graph_capture = False     # GanTrainer(graph=True) refuses this generator (not captured / verified)
 
@@ -2067,6 +2120,7 @@ class VideoGeneratorCDE(VideoGeneratorMNIST):
     _categorical_ok = False     # dim_z_category > 0 is refused: categorical latents exist for the Neural-ODE generators only
 
     _plan_cls = _CdeGenPlan
+    _discrete_ok = False
     _gode_graph_capture = False     # GanTrainer(graph=True) refuses this generator (not captured / verified)
     cde_rtol, cde_atol = 1e-4, 1e-6
     cde_max_steps = 512             # accepted-step capacity of a solve's stored schedule and states

@@ -346,8 +346,33 @@ typedef struct gode_ode_bwd_op {
                         [ceil(N/64)], one per workgroup); a negative entry reports a call that stalled (trial-step limit /
                         step-size underflow: torchdiffeq asserts there) */
   int32_t* sync;     /* adaptive adjoint with N > 32: as in gode_ode_fwd_op */
+  /* backprop: 0 (what a zero-initialised op asks for) = the continuous adjoint above.  1 = DISCRETE backprop: the exact
+   * reverse-mode gradient of the fixed-grid forward solve (what autograd through torchdiffeq's odeint gives), step by step in
+   * reverse order from each step's start state: the stage inputs u_s and h_s = tanh(W1 u_s + b1) are recomputed, then with
+   * J_s^T g the vector-Jacobian product of f at u_s and lambda = dL/dy1
+   *   euler:    g1 = dt lambda;                            lambda += J1^T g1
+   *   midpoint: g2 = dt lambda, gu2 = J2^T g2, g1 = (dt/2) gu2;   lambda += gu2 + J1^T g1
+   *   rk4:      g4 = dt/8 lambda, gu4 = J4^T g4;  g3 = 3dt/8 lambda + dt gu4, gu3 = J3^T g3;
+   *             g2 = 3dt/8 lambda - dt gu4 + dt gu3, gu2 = J2^T g2;
+   *             g1 = dt/8 lambda + dt gu4 - dt/3 gu3 + dt/3 gu2, gu1 = J1^T g1;   lambda += gu1 + gu2 + gu3 + gu4
+   * and every stage adds its parameter VJP with g_s.  Methods 0, 2 and 3, both rhs, on the vector-ALU kernel at every N
+   * (GODE_ODE_MFMA does not apply).  The grid is the FORWARD solve's: dt / substeps, or G / grid_dt / emit_at / emit_w as in
+   * gode_ode_fwd_op, grid_dt != NULL needing emit_at, emit_w and G >= 1; an interpolated output y0 + w (y1 - y0) hands w gz to the
+   * step's lambda before the reverse step and (1 - w) gz after it; bstep_off / bstep_dt are ignored.  With substeps == 1 and
+   * grid_dt == NULL the step-start states are traj itself and ysteps may be NULL; otherwise the launch re-runs the forward
+   * from traj[n][0] and keeps every step's start state in ysteps (>= gode_ode_bwd_steps_size floats, caller-owned
+   * scratch).  grads / work / accumulate / prenet == 0 / rhs == 1 / determinism: exactly as for backprop 0.
+   * GODE_E_ARG before any launch: backprop other than 0 or 1; backprop 1 with method 1; backprop 1 with ysteps needed and
+   * NULL; any op with backprop != 0 in gode_ode_bwd_multi. */
+  int32_t backprop, G;
+  const float* grid_dt; const int32_t* emit_at; const float* emit_w;
+  float* ysteps;
 } gode_ode_bwd_op;
 int gode_ode_bwd(const gode_ode_bwd_op* op, void* stream);
+/* floats of gode_ode_bwd_op.ysteps for a discrete-backprop op: 16 per trajectory and solver step -- N * G * 16 on a grid_dt
+ * grid (G >= 1), N * (T-1) * substeps * 16 with substeps > 1, and 0 where the grid is the output times themselves (G == 0,
+ * substeps <= 1: ysteps may be NULL) */
+int64_t gode_ode_bwd_steps_size(int32_t N, int32_t T, int32_t substeps, int32_t G);
 /* the adaptive adjoints (method 1, substeps 0) of `count` (<= 8) solves in one launch; ops sharing a grads pointer form a
  * group under the group rule stated at gode_odernn_bwd_multi */
 int gode_ode_bwd_multi(const gode_ode_bwd_op* ops, int32_t count, void* stream);
